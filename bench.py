@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the AVLMaps hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload index|build]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload index|build] [--dump-outputs DIR]
 
 Default workload = BASELINE.json configs[1]: landmark indexing of a 2M-voxel x 512-D map with 64 text
 queries on one GPU (voxel rows shard across GPUs for N > 1, no data-path collective -> weak scaling).
@@ -12,7 +12,8 @@ frame (7 776 sampled pixels, 512-D channels-last features) into the voxel map.  
 of one sequence shard across the GPUs, and the merge (one sparse RCCL sum-reduce + chained colour replay) and
 the finalisation on rank 0 are INSIDE the timed region.  Feature extraction (LSeg) is not included.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0; `ms_per_step` is the wall time of one timed step.  --dump-outputs DIR writes what the
+timed path computed in its last step as .npy files (see --help), so that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -265,6 +266,9 @@ def run_index(args, torch, dist, lib, rank, ws):
     dt = max_over_ranks(torch, dist, ws, dt)
     if ws > 1:
         dist.barrier()
+    # --dump-outputs: what the last timed step returned -- the row argmax (query index per voxel) of this rank's rows; the
+    # variants below launch the same kernel into `am` again
+    last = dict(argmax=am.cpu().numpy().astype(np.float32)) if args.dump_outputs and rank == 0 else None
     ms = C.c_float()
     per_step = []
     for i in range(n_ev - 1):
@@ -302,6 +306,8 @@ def run_index(args, torch, dist, lib, rank, ws):
                             if D <= 1024 and Q <= 64 else
                             "sim_stream_f16_kernel (fp16 hi/lo split MFMA, fp32 accumulate, query image streamed through LDS)")),
     )
+    if last is not None:
+        out["dumped_outputs"] = write_outputs(args.dump_outputs, last)
     out["roofline"] = dict(bound="hbm", achieved=achieved, peak=HBM_PEAK_GBS, unit="GB/s", frac=achieved / HBM_PEAK_GBS,
                            kernel_ms=ev_ms, algorithmic_bytes=alg_bytes,
                            **pmc_lookup("index", dict(N=N, D=D, Q=Q, resident=resident)))
@@ -576,6 +582,47 @@ def _json_default(o):
     return str(o)
 
 
+# ---------------------------------------------------------------------------------------- --dump-outputs
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def sample_index(n, k, seed):
+    """all of range(n) when n <= k, else k of them drawn by a generator of fixed seed, ascending"""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, k, replace=False)).astype(np.int64)
+
+
+def build_outputs(torch, fin, max_rows=16384, occupied_samples=1 << 18):
+    """the map the build's timed region ended with (finalize, or this rank's block of the merge) on the host: every row when
+    there are at most max_rows, otherwise the same seeded sample of rows of every per-voxel array (row_index says which)"""
+    rows = {k: fin[k] for k in ("grid_feat", "grid_pos", "weight", "grid_rgb") if fin.get(k) is not None}
+    n = int(rows["grid_pos"].shape[0])
+    idx = sample_index(n, max_rows, seed=0)
+    out = dict(num_rows=np.array([n], np.float64), row_index=idx.astype(np.float64))
+    for k, v in rows.items():
+        t = torch.as_tensor(v)
+        out[k] = t.index_select(0, torch.from_numpy(idx).to(t.device)).cpu().numpy().astype(np.float32)
+    if fin.get("occupied_ids") is not None:
+        t = torch.as_tensor(fin["occupied_ids"]).reshape(-1)
+        j = sample_index(t.numel(), occupied_samples, seed=1)
+        out["occupied_ids_index"] = j.astype(np.float64)
+        out["occupied_ids"] = t.index_select(0, torch.from_numpy(j).to(t.device)).cpu().numpy().astype(np.float64)
+    return out
+
+
+def write_outputs(dirpath, arrays):
+    """DIR/<name>.npy per array, float32 / float64 only, at most DUMP_LIMIT_BYTES in all -> {name: shape}"""
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values()), {k: a.dtype for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, total
+    d = Path(dirpath)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(d / f"{name}.npy", np.ascontiguousarray(a))
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def trajectory(n, kind="loop", radius=8.0):
     """synthetic base poses (x y z qx qy qz qw, dataset/README.md:93).  "loop": a 3 m circle walked every 1 571 frames while the
     camera turns once per 524 frames -- a 10 k-frame sequence revisits the same room six times, so EVERY contiguous frame shard
@@ -653,14 +700,15 @@ def merge_ranks(parallel, acc, mode, exact_rgb, timings=None):
 
 
 def run_build_core(args, torch, dist, lib, rank, ws, total_frames, warmup=8, batch=1, exact_rgb=True, feature_standin=None,
-                   deferred=False, solo=False, merge_mode=None):
+                   deferred=False, solo=False, merge_mode=None, dump=None):
     """STRONG scaling of map creation: `total_frames` frames of one sequence are sharded contiguously over the ranks; the
     timed region is everything between the first fused frame and the finished map resident in HBM:
         fuse own shard (K1/K2/K3 per launch)  ->  [ws > 1: plan + scatter + ONE all_to_all of the ranks' own voxel rows to the
         owners of their final rows (or, --merge-mode reduce, one dense RCCL sum-reduce to rank 0) + chained colour replay]
         -> finalize (first-touch-key order, grid_feat / grid_pos / weight / grid_rgb): every rank its block of rows
     max over ranks.  Per-frame feature extraction (LSeg, 2 ViT-L crops per frame upstream) is NOT included: the pixel features
-    are resident in HBM, as the kernel boundary takes them."""
+    are resident in HBM, as the kernel boundary takes them.  dump: a dict that receives the finished map on the host
+    (build_outputs) once the timed region is over."""
     from avlmaps_amd import ops, parallel
     H, W, Hf, Wf, D, rate = 720, 1080, 347, 520, 512, 100
     nbuf = 4
@@ -771,6 +819,8 @@ def run_build_core(args, torch, dist, lib, rank, ws, total_frames, warmup=8, bat
     fuse_s = max_over_ranks(torch, dist, ws, fuse_ms * 1e-3)
     lib.avl_event_destroy(e0)
     lib.avl_event_destroy(e1)
+    if dump is not None and fin is not None:
+        dump.update(build_outputs(torch, fin))
     nvox, npts, ngroups = acc.num_voxels(), acc.num_points(), acc.num_groups()
     n_final = None if fin is None else int(fin["M"]) if "M" in fin else int(fin["grid_pos"].shape[0])
     if ws > 1 and tim:
@@ -915,8 +965,9 @@ def run_pipeline_probe(torch, frames=300):
 
 
 def run_build(args, torch, dist, lib, rank, ws):
+    last = {} if args.dump_outputs and rank == 0 else None
     r = run_build_core(args, torch, dist, lib, rank, ws, total_frames=args.steps, warmup=args.warmup, batch=args.build_batch,
-                       exact_rgb=not args.no_exact_rgb, feature_standin=args.feature_standin, deferred=args.deferred_fuse)
+                       exact_rgb=not args.no_exact_rgb, feature_standin=args.feature_standin, deferred=args.deferred_fuse, dump=last)
     out = dict(metric="map_build_frames_per_sec", value=r["frames_per_s"], unit="frames/s", n_gpus=ws, steps=args.steps,
                warmup=args.warmup, ms_per_step=r["seconds"] / max(1, args.steps) * 1e3, higher_is_better=True, scaling="strong",
                vs_baseline=None, dtype="f64", data="synthetic",
@@ -936,6 +987,8 @@ def run_build(args, torch, dist, lib, rank, ws):
                            algorithmic_bytes=r["algorithmic_bytes_per_frame"] * max(1, r["frames_per_launch"]),
                            **pmc_lookup("build", dict(frames_per_launch=r["frames_per_launch"])))
     out["extra"] = r
+    if last is not None:
+        out["dumped_outputs"] = write_outputs(args.dump_outputs, last)
     if rank == 0 and ws == 1 and not args.no_cpu:
         out["cpu_baseline"] = cpu_build_baseline()
     return out
@@ -1171,6 +1224,10 @@ def main():
     ap.add_argument("--profile-run", action="store_true",
                     help="only the timed kernel launches (no scores_mat variant, CPU baseline or build extra): used under rocprofv3 "
                          "so that the trace's per-kernel average is the benchmarked launch")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the timed path computed in its last step (rank 0) as DIR/<name>.npy, "
+                         "float32 / float64, at most 64 MB: index = the row argmax; build = the finished map, a fixed seeded "
+                         "sample of rows when it has more than 16384 voxels. The inputs are seeded: the same arguments give the same inputs")
     args = ap.parse_args()
     if args.profile_run:
         args.no_cpu = args.no_build_extra = True

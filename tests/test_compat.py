@@ -1,10 +1,7 @@
 """avlmaps_amd.compat: in-place switch of an upstream-shaped package onto the HIP path (mechanics only, no GPU)."""
 import importlib
-import os
 import sys
 import textwrap
-
-import pytest
 
 
 def _fake_upstream(tmp_path, name):
@@ -79,34 +76,3 @@ def test_install_repoints_every_reference_and_uninstall_restores(tmp_path):
         for m in [m for m in sys.modules if m == name or m.startswith(name + ".")]:
             del sys.modules[m]
 
-
-@pytest.mark.skipif(not os.path.isdir(os.environ.get("AVLMAPS_REFERENCE", "/root/reference")),
-                    reason="the upstream checkout is only present in the build container")
-def test_install_on_the_real_upstream_package():
-    """the real avlmaps modules (imported with their heavy dependencies mocked): the names the patch targets exist there
-    with the call signatures the replacements accept"""
-    import inspect
-    sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "tools"))
-    from ref_import import import_reference
-    from avlmaps_amd import compat
-    from avlmaps_amd.utils import clip_utils
-    m = import_reference()
-    ref_sig = inspect.signature(m["clip_utils"].get_lseg_score)
-    try:
-        counts = compat.install("avlmaps")
-        assert m["clip_utils"].get_lseg_score is clip_utils.get_lseg_score
-        assert m["vlmap"].get_lseg_score is clip_utils.get_lseg_score                 # vlmap.py:24 imported the name
-        assert counts["utils.clip_utils.get_lseg_score"] >= 2
-        assert "map.vlmap_builder.VLMapBuilder.create_mobile_base_map" in counts
-        assert "utils.visualize_utils.get_heatmap_from_mask_3d" in counts
-        mine = inspect.signature(clip_utils.get_lseg_score)
-        assert list(mine.parameters)[:len(ref_sig.parameters)] == list(ref_sig.parameters)   # same positional order
-        for k, p in ref_sig.parameters.items():
-            assert mine.parameters[k].default == p.default, k
-    finally:
-        compat.uninstall("avlmaps")
-    assert m["clip_utils"].get_lseg_score is not clip_utils.get_lseg_score
-    # leave no mocked third-party module (h5py, cv2, ...) or upstream module behind for the other tests
-    from unittest.mock import MagicMock
-    for name in [n for n, mod in sys.modules.items() if isinstance(mod, MagicMock) or n == "avlmaps" or n.startswith("avlmaps.")]:
-        del sys.modules[name]

@@ -14,7 +14,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))
 from avlmaps_amd import merge2, parallel  # noqa: E402
-from test_parallel_gloo import _free_port, expected_merge, make_rank_raw  # noqa: E402
+from test_parallel_gloo import _free_port, cpu_barrier, cpu_rank, expected_merge, make_rank_raw  # noqa: E402
 
 GS, VH = 20, 20          # cells < 400: a 1 x 20 x 20 grid
 
@@ -83,6 +83,7 @@ def check_block(sh, rank, ws, D, cellsets, raws, with_replay=True):
 
 
 def _worker(rank, ws, port, tmpdir):
+    cpu_rank()
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(ws), LOCAL_RANK=str(rank))
     parallel.init_distributed("gloo")
     D, cellsets, raws = make_world(ws)
@@ -109,7 +110,7 @@ def _worker(rank, ws, port, tmpdir):
     _, _, raws_nm = make_world(ws, monotone=False)
     assert merge2.merge_raw_sharded_v2(raws_nm[rank], gs=GS, vh=VH, ncell=400) is None
     Path(tmpdir, f"m2_{rank}").write_text("ok")
-    dist.barrier()
+    cpu_barrier()
     dist.destroy_process_group()
 
 

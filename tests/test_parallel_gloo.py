@@ -23,6 +23,18 @@ def _free_port():
     return p
 
 
+def cpu_rank():
+    """a spawned gloo rank of these CPU tests works on CPU tensors only: it never opens the GPU (on a GPU box torch would
+    otherwise initialise the device in every rank, init_distributed asks torch.cuda.is_available())"""
+    torch.cuda.is_available = lambda: False
+
+
+def cpu_barrier():
+    """dist.barrier() of such a rank: an all_reduce of a CPU tensor (dist.barrier itself asks the HIP runtime which device the
+    machine has, and that opens the GPU)"""
+    dist.all_reduce(torch.zeros(1))
+
+
 def make_rank_raw(seed, D, cells, frame_lo):
     """synthetic raw export of one rank: voxels `cells`, keys inside this rank's frame block"""
     rng = np.random.default_rng(seed)
@@ -57,6 +69,7 @@ def expected_merge(raws):
 
 
 def _worker(rank, ws, port, tmpdir):
+    cpu_rank()
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(ws), LOCAL_RANK=str(rank))
     r, w, _ = parallel.init_distributed("gloo")
     assert (r, w) == (rank, ws)
@@ -128,7 +141,7 @@ def _worker(rank, ws, port, tmpdir):
     assert gi.tolist() == [w.tolist() for w in want], gi
     assert gv[0].tolist() == [3.0, 3.0, 3.0] and gv[1].tolist() == [1.0, 1.0, 1.0]
     Path(tmpdir, f"ok{rank}").write_text("ok")
-    dist.barrier()
+    cpu_barrier()
     dist.destroy_process_group()
 
 
@@ -153,6 +166,7 @@ def _sharded_worker(rank, ws, port, tmpdir, monotone=True):
     result; the plan is the directory plan (nothing O(M) per rank), voxels of one rank alone travel as finished float32 rows,
     shared voxels as float64 partial sums, and the order-dependent replay state reaches the owner through the contributors in
     rank order"""
+    cpu_rank()
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(ws), LOCAL_RANK=str(rank))
     parallel.init_distributed("gloo")
     D = 12
@@ -232,7 +246,7 @@ def _sharded_worker(rank, ws, port, tmpdir, monotone=True):
     else:
         assert fullmap is None
     Path(tmpdir, f"sh{rank}").write_text("ok")
-    dist.barrier()
+    cpu_barrier()
     dist.destroy_process_group()
 
 
