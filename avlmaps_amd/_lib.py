@@ -137,6 +137,11 @@ _SIGS = {
     "avl_heat_plan_destroy": (C.c_int, [_vp]),
     "avl_heatmap_from_mask_planned": (C.c_int, [_vp, _vp, _f64, _f64, _vp, _vp]),
     "avl_lseg_merge_windows": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp]),
+    "avl_field_area": (C.c_int, [_vp, _vp, _i64, C.c_int, _f64, _vp, _vp, _vp]),
+    "avl_field_sound": (C.c_int, [_vp, _vp, _i64, _vp, _i64, C.c_int, _f64, _vp, _vp, _vp]),
+    "avl_field_lift": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _i64, _vp, _vp]),
+    "avl_field_normalize": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp]),
+    "avl_planar_decay": (C.c_int, [_vp, _i64, _i64, _i64, _f64, _vp, _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -20,6 +20,29 @@ DEFAULTS = {
         "potential_obstacle_names": ["chair", "wall", "wall above the door", "table", "window", "floor", "stairs", "other"],
         "obstacle_names": ["wall", "chair", "table", "window", "stairs", "other"],
     },
+    # the sound queries' categories (ESC-50 classes by major category; utils/audio_utils.get_level_categories)
+    "sound_data_collect_params": {"difficulty": "level_3"},
+    "sound_config": {
+        "difficulty": {
+            "level_1": ["Interior/domestic sounds"],
+            "level_2": ["Interior/domestic sounds", "Human, non-speech sounds"],
+            "level_3": ["Interior/domestic sounds", "Human, non-speech sounds", "Animals"],
+            "level_4": ["Interior/domestic sounds", "Human, non-speech sounds", "Animals", "Natural soundscapes"],
+            "level_5": ["Interior/domestic sounds", "Human, non-speech sounds", "Animals", "Natural soundscapes",
+                        "Exterior/urban noises"],
+        },
+        "major_categories": {
+            "Animals": ["dog", "rooster", "pig", "cow", "frog", "cat", "hen", "insects", "sheep", "crow"],
+            "Natural soundscapes": ["rain", "sea_waves", "crackling_fire", "crickets", "chirping_birds", "water_drops", "wind",
+                                    "pouring_water", "toilet_flush", "thunderstorm"],
+            "Human, non-speech sounds": ["crying_baby", "sneezing", "clapping", "breathing", "coughing", "footsteps", "laughing",
+                                         "brushing_teeth", "snoring", "drinking_sipping"],
+            "Interior/domestic sounds": ["door_wood_knock", "mouse_click", "keyboard_typing", "door_wood_creaks", "can_opening",
+                                         "washing_machine", "vacuum_cleaner", "clock_alarm", "clock_tick", "glass_breaking"],
+            "Exterior/urban noises": ["helicopter", "chainsaw", "siren", "car_horn", "engine", "train", "church_bells", "airplane",
+                                      "fireworks", "hand_saw"],
+        },
+    },
 }
 
 
@@ -110,3 +133,51 @@ class HashClip:
             seed = int.from_bytes(hashlib.sha256(self._texts[i].encode()).digest()[:8], "little")
             rows.append(np.random.default_rng(seed).standard_normal(self.D).astype(np.float32))
         return torch.from_numpy(np.stack(rows)).to(ids.device)
+
+
+def _hash_unit(text: str, D: int) -> np.ndarray:
+    seed = int.from_bytes(hashlib.sha256(text.encode()).digest()[:8], "little")
+    v = np.random.default_rng(seed).standard_normal(D).astype(np.float32)
+    return v / np.linalg.norm(v)
+
+
+class HashImageEncoder:
+    """Stand-in for CLIP ViT-L/14's image tower of the area map (demo / smoke runs): a fixed random projection of the image's
+    4 x 4 grid of mean colours to D = 768 channels, L2-normalised, float32."""
+
+    def __init__(self, D=768, seed=0):
+        self.D = D
+        self.proj = np.random.default_rng(seed).standard_normal((48, D)).astype(np.float32)
+
+    def __call__(self, rgb):
+        a = np.asarray(rgb, dtype=np.float32) / 255.0
+        H, W = a.shape[:2]
+        code = np.array([a[i * H // 4:(i + 1) * H // 4 or None, j * W // 4:(j + 1) * W // 4 or None].reshape(-1, 3).mean(0)
+                         for i in range(4) for j in range(4)], dtype=np.float32).reshape(-1) - 0.5
+        f = code @ self.proj
+        return (f / np.linalg.norm(f)).astype(np.float32)
+
+
+class HashAudioText:
+    """Stand-in for AudioCLIP's text side (demo / smoke runs): deterministic 1024-d unit vectors per category name and a fixed
+    logit scale (log 100 -> the clamp's upper end)."""
+
+    def __init__(self, D=1024):
+        self.D = D
+        self.logit_scale_at = float(np.log(100.0))
+
+    def encode_text(self, texts):
+        return np.stack([_hash_unit(t, self.D) for t in texts]) if len(texts) else np.zeros((0, self.D), np.float32)
+
+
+class FixedPoseLocalizer:
+    """Stand-in for HLoc (demo / smoke runs): every query image is 'localised' at one fixed base pose, given as a habitat
+    (px, py, pz, qx, qy, qz, qw) vector (a row of poses.txt).  Returns (camera tf, base tf) like VisualMap.localize_image."""
+
+    def __init__(self, pose_vec, base2cam_tf):
+        from ..utils.mapping_utils import cvt_pose_vec2tf
+        self.base_tf = cvt_pose_vec2tf(np.asarray(pose_vec, dtype=np.float64))
+        self.base2cam_tf = np.asarray(base2cam_tf, dtype=np.float64)
+
+    def __call__(self, img, query_cam_intrinsic_mat=None):
+        return self.base_tf @ self.base2cam_tf, self.base_tf

@@ -1,48 +1,76 @@
-"""Index a saved VLMap with a text query.  Counterpart of branch "1. object" of the reference's
-application/index_map.py:23-38 (the Open3D viewer and the habitat branches are not part of the hot path).
+"""Index a saved AVLMap with a goal query.  Counterpart of the reference's application/index_map.py (the object, area, sound
+and image branches, :23-142; the Open3D viewer and the habitat branches are not part of the hot path).
 
-    python -m avlmaps_amd.apps.index_map --data-dir <scene> --query sofa [--decay-rate 0.01] [--text-model clip|hash]
+    python -m avlmaps_amd.apps.index_map --data-dir <scene> --query sofa [--modality object|area|sound|image]
+                                         [--decay-rate R] [--text-model clip|hash]
 
-Prints the number of voxels assigned to the query, the heat statistics and the voxel the navigator would go to
-(argmax of the heat, habitat_lang_robot.py:427-430); --save writes the (N,) heat vector as .npy."""
+object (default): the VLMap text query; area: the area map's frame embeddings (area_map/clip_sparse_map.h5df); sound: the sound
+map (audio_video/audio_data_<difficulty>.pkl); image: --image (a PNG) localised at row --image-pose of poses.txt (the model-free
+localiser; upstream uses HLoc).  Prints the heat statistics and the voxel the navigator would go to (argmax of the heat,
+habitat_lang_robot.py:427-430); --save writes the (N,) heat vector as .npy."""
 from __future__ import annotations
 
 import argparse
 
 import numpy as np
 
+DEFAULT_DECAY = {"object": 0.01, "area": 0.1, "sound": 0.01, "image": 0.01}
+
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--data-dir", required=True)
-    ap.add_argument("--query", required=True)
+    ap.add_argument("--query", default=None, help="object, area or sound name (not used by --modality image)")
+    ap.add_argument("--modality", choices=["object", "area", "sound", "image"], default="object")
     ap.add_argument("--config", default=None)
-    ap.add_argument("--decay-rate", type=float, default=0.01)
+    ap.add_argument("--decay-rate", type=float, default=None, help="default: 0.01 (object, sound, image), 0.1 (area)")
     ap.add_argument("--text-model", choices=["clip", "hash"], default="clip",
-                    help="clip = OpenAI CLIP ViT-B/32 on PyTorch-ROCm (as upstream); hash = model-free stand-in for smoke runs")
+                    help="clip = OpenAI CLIP on PyTorch-ROCm (as upstream); hash = model-free stand-ins for smoke runs (text towers "
+                         "and the audio-text model)")
     ap.add_argument("--categories", default=None, help="comma separated list: preload scores_mat (VLMap.init_categories)")
+    ap.add_argument("--image", default=None, help="query image (PNG) of --modality image")
+    ap.add_argument("--image-pose", type=int, default=0, help="row of poses.txt the model-free localiser places the image at")
     ap.add_argument("--save", default=None)
     args = ap.parse_args(argv)
+    if args.modality != "image" and not args.query:
+        ap.error(f"--modality {args.modality} needs --query")
+    if args.modality == "image" and not args.image:
+        ap.error("--modality image needs --image")
+    decay = DEFAULT_DECAY[args.modality] if args.decay_rate is None else args.decay_rate
 
     from avlmaps_amd import ops
-    from avlmaps_amd.apps.common import HashClip, load_config
+    from avlmaps_amd.apps.common import FixedPoseLocalizer, HashAudioText, HashClip, load_config
     from avlmaps_amd.map import AVLMap
     cfg = load_config(args.config)
-    avlmap = AVLMap(cfg, data_dir=args.data_dir)
+    hashed = args.text_model == "hash"
+    avlmap = AVLMap(cfg, data_dir=args.data_dir, area_text_model=HashClip(768) if hashed else None,
+                    audio_text_model=HashAudioText() if hashed else None)
     if not avlmap.load_map(args.data_dir):
         raise SystemExit(1)
     vm = avlmap.vlmap
-    if args.text_model == "hash":
-        vm.clip_feat_dim = vm.grid_feat.shape[1]
-        vm.clip_model = HashClip(vm.clip_feat_dim)
+    if args.modality == "object":
+        if hashed:
+            vm.clip_feat_dim = vm.grid_feat.shape[1]
+            vm.clip_model = HashClip(vm.clip_feat_dim)
+        else:
+            vm._init_clip()
+        cats = None
+        if args.categories:
+            cats = ["void"] + [c.strip() for c in args.categories.split(",")] + ["void"]   # upstream passes categories[1:-1]
+        heat = avlmap.index_object(args.query, init_categories=cats, decay_rate=decay)
+        print(f"{int((heat == 1.0).sum())} of {len(heat)} voxels match {args.query!r}; ", end="")
+    elif args.modality == "area":
+        heat = avlmap.index_area(args.query, decay_rate=decay)
+    elif args.modality == "sound":
+        heat = avlmap.index_sound(args.query, decay_rate=decay)
     else:
-        vm._init_clip()
-    cats = None
-    if args.categories:
-        cats = ["void"] + [c.strip() for c in args.categories.split(",")] + ["void"]   # upstream passes categories[1:-1]
-    heat = avlmap.index_object(args.query, init_categories=cats, decay_rate=args.decay_rate)
-    idx, val = ops.argmax_f32(heat)
-    print(f"{int((heat == 1.0).sum())} of {len(heat)} voxels match {args.query!r}; heat>0 on {int((heat > 0).sum())}; "
+        from avlmaps_amd.utils.mapping_utils import load_rgb_png
+        poses = np.loadtxt(vm.pose_path).reshape(-1, 7)
+        avlmap.visual_map.localizer = FixedPoseLocalizer(poses[args.image_pose], vm.base2cam_tf)
+        heat = avlmap.index_image(load_rgb_png(args.image), decay_rate=decay)
+    idx, val = ops.argmax_f32(heat.astype(np.float32, copy=False))
+    what = args.query if args.modality != "image" else args.image
+    print(f"{args.modality} {what!r}: heat>0 on {int((heat > 0).sum())} of {len(heat)} voxels; "
           f"goal voxel id {idx} at grid_pos {vm.grid_pos[idx].tolist()} (heat {val:.3f})")
     if args.save:
         np.save(args.save, heat)

@@ -1,8 +1,21 @@
-"""AVLMap facade restricted to the accelerated path (avlmaps/map/avlmap.py:18-76): the VLMap sub-map,
-create_map / load_map / index_object.  Sound, area and image indexing are separate upstream subsystems
-(AudioCLIP, CLIP ViT-L/14 sparse map, HLoc) that do not touch the voxel hot path."""
+"""AVLMap facade (avlmaps/map/avlmap.py:18-163): the VLMap sub-map with create_map / load_map / index_object, and the area, sound
+and image goal queries.
+
+The four queries end in a per-voxel heat on the GPU.  For area and sound the per-pose / per-segment distance transforms of
+upstream (one full-grid scipy EDT each) are one kernel that builds the 2-D field (csrc/avl_field2d.hip), and the Python loop over
+occupied_ids is one lift kernel reading the map's device-resident grid_pos.  The models around them (CLIP ViT-L/14 frame
+embeddings, AudioCLIP, HLoc) are pluggable, and whatever a query needs that is not loaded or attached raises MissingSubMap, a
+NotImplementedError that says what to provide.
+
+Departures from the reference, all where upstream fails or depends on an online service:
+  * category lookups go through utils/index_utils.find_similar_category_id (KeyError when nothing matches), not an LLM;
+  * a sound location outside the grid raises ValueError (upstream: IndexError, or a silently wrapped negative index);
+  * a degenerate min-max normalisation (max == min, of the scores or of the 2-D field) raises ValueError (upstream: NaN
+    everywhere), as index_object raises where upstream's argmin does;
+  * decay_rate must be finite and >= 0 for area and sound (ValueError)."""
 from __future__ import annotations
 
+from pathlib import Path
 from typing import List
 
 import numpy as np
@@ -12,17 +25,72 @@ from .map import cfg_get
 from .vlmap import VLMap
 
 
+class MissingSubMap(NotImplementedError):
+    """An AVLMap query whose sub-map (area / sound) or image localiser has not been loaded or attached."""
+
+
+def _opt(cfg, key, default=None):
+    try:
+        return cfg_get(cfg, key)
+    except (KeyError, AttributeError):
+        return default
+
+
 class AVLMap:
-    def __init__(self, config, data_dir: str = ""):
+    def __init__(self, config, data_dir: str = "", area_text_model=None, audio_text_model=None, localizer=None):
+        """area_text_model: the CLIP ViT-L/14 text tower (or a stand-in) of the area queries, loaded on demand when None;
+        audio_text_model: AudioCLIP's text side (map/sound_map.py); localizer: the image localiser (map/visual_map.py)."""
+        from .area_map import AreaMap
+        from .visual_map import VisualMap
         self.config = config
         self.vlmap = VLMap(cfg_get(config, "map_config"), data_dir=data_dir)
+        self.area_map = AreaMap(clip_model=area_text_model)
+        self.visual_map = VisualMap(cfg_get(config, "map_config"), data_dir, localizer=localizer)
+        self.sound_map = None
+        sound_cfg, sound_params = _opt(config, "sound_config"), _opt(config, "sound_data_collect_params")
+        if sound_cfg is not None and sound_params is not None:
+            from .sound_map import SoundMap
+            self.sound_map = SoundMap(data_dir, sound_cfg, sound_params, is_ambiguous=False, is_real=False,
+                                      audio_text_model=audio_text_model)
+        self._area_loaded = self._sound_loaded = False
+        self._dataloader = None
+        self._area_cells = self._sound_cells = None
 
-    def create_map(self, data_dir, feat_extractor=None) -> bool:
+    # ------------------------------------------------------------------ build / load
+    def create_map(self, data_dir, feat_extractor=None, area_encoder=None) -> bool:
+        """Reference: avlmap.py:38-46.  area_encoder(rgb) -> (768,): also build the area map (area_map/clip_sparse_map.h5df)."""
         self.vlmap.create_map(data_dir, feat_extractor=feat_extractor)
+        if area_encoder is not None:
+            self.area_map.create_map(data_dir, image_encoder=area_encoder)
         return True
 
     def load_map(self, data_dir: str) -> bool:
-        return self.vlmap.load_map(data_dir)
+        """Reference: avlmap.py:48-54.  The area and sound maps are loaded when their files exist; the poses they refer to are
+        converted to map cells once here, so that a query costs the text tower, one matmul, the field and the lift."""
+        if not self.vlmap.load_map(data_dir):
+            return False
+        from .area_map import AreaMap
+        self._dataloader = None
+        self._area_cells = self._sound_cells = None
+        self._area_loaded = AreaMap.map_exists(data_dir) and self.area_map.load_map(data_dir)
+        self._sound_loaded = False
+        if self.sound_map is not None and self.sound_map.sound_map_path(data_dir).exists():
+            self.sound_map.load_sound_map(data_dir)
+            self._sound_loaded = True
+        return True
+
+    @property
+    def dataloader(self):
+        """VLMapsDataloaderHabitat of the loaded map (avlmap.py:53)"""
+        if self._dataloader is None:
+            from ..dataloader.habitat_dataloader import VLMapsDataloaderHabitat
+            vm = self.vlmap
+            self._dataloader = VLMapsDataloaderHabitat(vm.data_dir, cfg_get(self.config, "map_config"), vm)
+        return self._dataloader
+
+    @dataloader.setter
+    def dataloader(self, value):
+        self._dataloader = value
 
     def index_object(self, object_name: str, init_categories: List[str] = None, decay_rate: float = 0.1) -> np.ndarray:
         """(N,) float32 heat.  Reference: avlmap.py:67-76."""
@@ -48,11 +116,104 @@ class AVLMap:
             raise ValueError("attempt to get argmin of an empty sequence")   # what np.argmin raises upstream (no voxel matched)
         return heat.numpy()
 
-    def index_sound(self, *a, **k):
-        raise NotImplementedError("sound indexing (AudioCLIP segment map) is outside the accelerated voxel path")
+    # ------------------------------------------------------------------ area
+    def _require_area(self):
+        if not self._area_loaded:
+            raise MissingSubMap("AVLMap.index_area needs the area map: create it with create_map(data_dir, area_encoder=...) and "
+                                "load_map(data_dir) (reads area_map/clip_sparse_map.h5df)")
 
-    def index_area(self, *a, **k):
-        raise NotImplementedError("area indexing (sparse CLIP ViT-L/14 frame map) is outside the accelerated voxel path")
+    def _area_field(self, area_name: str, decay_rate: float):
+        from .. import ops
+        self._require_area()
+        scores = self.area_map.index_map(area_name, with_init_cat=False)
+        lo, hi = np.min(scores), np.max(scores)
+        if not hi > lo:
+            raise ValueError(f"area {area_name!r}: every frame has the same score, the min-max normalisation is undefined")
+        peaks = ((scores - lo) / (hi - lo)).astype(np.float64)          # float32 normalisation, as upstream (avlmap.py:81)
+        if self._area_cells is None:
+            cells = self.dataloader.habitat_tfs_to_cells(self.area_map.robot_pose_list)
+            cells = np.clip(cells, -1, np.iinfo(np.int32).max).astype(np.int32)   # (anything negative is outside the grid alike)
+            from ..device import DeviceArray
+            self._area_cells = DeviceArray.from_numpy(cells)
+        return ops.area_field(self._area_cells, peaks, self.vlmap.gs, decay_rate)
 
-    def index_image(self, *a, **k):
-        raise NotImplementedError("image localisation (HLoc) is outside the accelerated voxel path")
+    @staticmethod
+    def _check_bounds(gf, what):
+        lo, hi = gf.bounds()
+        if not hi > lo:
+            raise ValueError(f"{what}: the 2-D map is constant ({lo}), its min-max normalisation is undefined")
+
+    def index_area_2d(self, area_name: str, decay_rate: float = 0.1) -> np.ndarray:
+        """(gs, gs) float64.  Reference: avlmap.py:78-98."""
+        from .. import ops
+        gf = self._area_field(area_name, decay_rate)
+        self._check_bounds(gf, f"area {area_name!r}")
+        return ops.field_normalize(gf).numpy()
+
+    def index_area(self, area_name: str, decay_rate: float = 0.1) -> np.ndarray:
+        """(N,) float32.  Reference: avlmap.py:100-109."""
+        gf = self._area_field(area_name, decay_rate)
+        return self._lift(gf, f"area {area_name!r}")
+
+    def _lift(self, gf, what):
+        from .. import ops
+        vm = self.vlmap
+        vh = vm.occupied_ids.shape[2] if vm.occupied_ids is not None else np.iinfo(np.int32).max
+        heat = ops.field_lift(gf, vm._device_pos(), vh)
+        self._check_bounds(gf, what)
+        return heat.numpy()
+
+    # ------------------------------------------------------------------ sound
+    def _require_sound(self):
+        if self.sound_map is None:
+            raise MissingSubMap("AVLMap.index_sound needs sound_config and sound_data_collect_params in the config")
+        if not self._sound_loaded:
+            raise MissingSubMap("AVLMap.index_sound needs the sound map: load_map(data_dir) reads "
+                                f"audio_video/{self.sound_map.sound_map_path('.').name}")
+        if self.sound_map.aclp is None:
+            raise MissingSubMap("AVLMap.index_sound needs an audio-text model: AVLMap(..., audio_text_model=...) or "
+                                "sound_map.aclp = ...")
+
+    def _sound_field(self, sound_name: str, decay_rate: float):
+        from .. import ops
+        self._require_sound()
+        probabilities, locations = self.sound_map.get_distribution_and_locations(sound_name)
+        if self._sound_cells is None:
+            counts = np.array([len(l) for l in locations], dtype=np.int64)
+            if np.any(counts == 0):
+                raise ValueError("a sound segment without locations")
+            pts = [np.asarray(p, dtype=np.float64).reshape(3) for l in locations for p in l]
+            cells = self.dataloader.habitat_positions_to_cells(pts)
+            gs = self.vlmap.gs
+            if len(cells) and (cells.min() < 0 or cells.max() >= gs):
+                raise ValueError(f"a sound location lies outside the {gs} x {gs} map")
+            self._sound_cells = (np.concatenate([[0], np.cumsum(counts)]), cells.astype(np.int32))
+        offsets, cells = self._sound_cells
+        return ops.sound_field(offsets, cells, probabilities, self.vlmap.gs, decay_rate)
+
+    def index_sound_2d(self, sound_name: str, decay_rate: float = 0.01) -> np.ndarray:
+        """(gs, gs) float32.  Reference: avlmap.py:111-133."""
+        from .. import ops
+        gf = self._sound_field(sound_name, decay_rate)
+        self._check_bounds(gf, f"sound {sound_name!r}")
+        return ops.field_normalize(gf).numpy()
+
+    def index_sound(self, sound_name: str, decay_rate: float = 0.01) -> np.ndarray:
+        """(N,) float32.  Reference: avlmap.py:135-144."""
+        gf = self._sound_field(sound_name, decay_rate)
+        return self._lift(gf, f"sound {sound_name!r}")
+
+    # ------------------------------------------------------------------ image
+    def index_image(self, image: np.ndarray, query_cam_intrinsics: np.ndarray = None, decay_rate: float = 0.01) -> np.ndarray:
+        """(N,) float64.  Reference: avlmap.py:146-163."""
+        from .. import ops
+        if self.visual_map.localizer is None:
+            raise MissingSubMap("AVLMap.index_image needs an image localiser (upstream: HLoc): AVLMap(..., localizer=...) or "
+                                "visual_map.localizer = ...")
+        res = self.visual_map.localize_image(image, query_cam_intrinsic_mat=query_cam_intrinsics)
+        if res is None:
+            raise ValueError("the query image could not be localised in the map")
+        _, query_base_tf = res
+        self.dataloader.from_habitat_tf(query_base_tf)
+        row, col, _ = self.dataloader.to_full_map_pose()
+        return ops.planar_decay(self.vlmap._device_pos(), row, col, decay_rate).numpy()

@@ -912,3 +912,109 @@ def topk_f32(vals, k, stream=None):
     val = np.empty((k,), dtype=np.float32)
     _lib.check(lib.avl_topk_f32(vp, int(np.prod(vshape)), int(k), idx.ctypes.data, val.ctypes.data, stream), "avl_topk_f32")
     return idx, val
+
+
+# ---------------------------------------------------------------------------------------- area / sound / image goal fields
+class GoalField:
+    """A 2-D goal field on the device: `field` (gs, gs) float64 (area) or float32 (sound) and `minmax` (2,) of the same type,
+    [min, max] of the whole grid, both DeviceArrays (csrc/avl_field2d.hip)."""
+
+    def __init__(self, field, minmax):
+        self.field, self.minmax = field, minmax
+        self.gs = field.shape[0]
+        self.is_f64 = field.dtype == np.float64
+
+    def bounds(self, stream=None):
+        """(min, max) on the host (synchronises the stream)"""
+        mm = self.minmax.numpy(stream)
+        return mm[0], mm[1]
+
+
+def _check_decay(decay_rate):
+    d = float(decay_rate)
+    if not (np.isfinite(d) and d >= 0.0):
+        raise ValueError(f"decay_rate must be finite and >= 0, got {decay_rate!r}")
+    return d
+
+
+def area_field(cells, peaks, gs, decay_rate=0.1, stream=None) -> GoalField:
+    """avlmap.py:78-96 (index_area_2d before its normalisation): the float64 maximum of clipped cones
+    clip(peak_i - decay * ||cell - cell_i||, 0, 1) over the poses whose cell lies inside the (gs, gs) grid, on a field of zeros.
+    cells (P, 2) int32 (row, col), peaks (P,) float64 finite: host arrays or device arrays."""
+    lib = _lib.load()
+    _lib.require_gpu()
+    decay = _check_decay(decay_rate)
+    if isinstance(peaks, np.ndarray) and not np.all(np.isfinite(peaks)):
+        raise ValueError("area peaks must be finite")
+    cp, cshape, k1 = as_device(cells, np.int32, stream)
+    pp, pshape, k2 = as_device(peaks, np.float64, stream)
+    P = int(pshape[0]) if len(pshape) else 0
+    if tuple(cshape) != (P, 2):
+        raise ValueError(f"cells must be ({P}, 2), got {tuple(cshape)}")
+    field, mm = DeviceArray((gs, gs), np.float64), DeviceArray((2,), np.float64)
+    _lib.check(lib.avl_field_area(cp, pp, P, int(gs), decay, field.ptr, mm.ptr, stream), "avl_field_area")
+    if isinstance(cells, np.ndarray) or isinstance(peaks, np.ndarray):
+        _lib.check(lib.avl_stream_sync(stream), "avl_stream_sync")      # the uploaded temporaries die here
+    return GoalField(field, mm)
+
+
+def sound_field(offsets, cells, peaks, gs, decay_rate=0.01, stream=None) -> GoalField:
+    """avlmap.py:111-131 (index_sound_2d before its normalisation): for every segment in order, the float64 term
+    max(p - (p * d) * decay, 0), d = distance to the nearest of the segment's locations, added into a float32 field.
+    offsets (S + 1,) int64 CSR offsets into cells (L, 2) int32 (row, col), peaks (S,) float32 >= 0 (host arrays).  Every
+    location must lie inside the grid."""
+    lib = _lib.load()
+    _lib.require_gpu()
+    decay = _check_decay(decay_rate)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    cells = np.ascontiguousarray(cells, dtype=np.int32).reshape(-1, 2)
+    peaks = np.ascontiguousarray(peaks, dtype=np.float32)
+    S, L = len(peaks), len(cells)
+    if offsets.shape != (S + 1,) or offsets[0] != 0 or offsets[-1] != L or np.any(np.diff(offsets) < 1):
+        raise ValueError("offsets must be (S + 1,) CSR offsets from 0 to len(cells), every segment with >= 1 location")
+    if not np.all(np.isfinite(peaks)) or np.any(peaks < 0):
+        raise ValueError("sound peaks must be finite and >= 0")
+    if L and (cells.min() < 0 or cells.max() >= gs):
+        raise ValueError(f"a sound location lies outside the {gs} x {gs} grid")
+    op, _, k1 = as_device(offsets, np.int64, stream)
+    cp, _, k2 = as_device(cells, np.int32, stream)
+    pp, _, k3 = as_device(peaks, np.float32, stream)
+    field, mm = DeviceArray((gs, gs), np.float32), DeviceArray((2,), np.float32)
+    _lib.check(lib.avl_field_sound(op, cp, L, pp, S, int(gs), decay, field.ptr, mm.ptr, stream), "avl_field_sound")
+    _lib.check(lib.avl_stream_sync(stream), "avl_stream_sync")
+    return GoalField(field, mm)
+
+
+def field_lift(gf: GoalField, grid_pos, vh, stream=None):
+    """avlmap.py:97 + 100-109 (area) / :132 + 135-144 (sound): heat[i] = f32(normalised field[row_i, col_i]), 0 for voxels outside
+    the (gs, gs, vh) grid.  grid_pos (N, 3) int32 host or device (VLMap._device_pos()) -> (N,) float32 DeviceArray."""
+    lib = _lib.load()
+    gp, gshape, keep = as_device(grid_pos, np.int32, stream)
+    N = int(gshape[0])
+    heat = DeviceArray((N,), np.float32)
+    _lib.check(lib.avl_field_lift(gf.field.ptr, int(gf.is_f64), gf.minmax.ptr, int(gf.gs), int(vh), gp, N, heat.ptr, stream),
+               "avl_field_lift")
+    if isinstance(grid_pos, np.ndarray):
+        _lib.check(lib.avl_stream_sync(stream), "avl_stream_sync")
+    return heat
+
+
+def field_normalize(gf: GoalField, stream=None):
+    """(field - min) / (max - min) over the whole grid, in the field's precision -> (gs, gs) DeviceArray"""
+    lib = _lib.load()
+    out = DeviceArray((gf.gs, gf.gs), gf.field.dtype)
+    _lib.check(lib.avl_field_normalize(gf.field.ptr, int(gf.is_f64), gf.minmax.ptr, int(gf.gs), out.ptr, stream), "avl_field_normalize")
+    return out
+
+
+def planar_decay(grid_pos, row, col, decay_rate=0.01, stream=None):
+    """avlmap.py:154-161: clip(1 - decay * ||grid_pos[:, :2] - (row, col)||, 0, 1) in float64 -> (N,) float64 DeviceArray"""
+    lib = _lib.load()
+    _lib.require_gpu()
+    gp, gshape, keep = as_device(grid_pos, np.int32, stream)
+    N = int(gshape[0])
+    sim = DeviceArray((N,), np.float64)
+    _lib.check(lib.avl_planar_decay(gp, N, int(row), int(col), float(decay_rate), sim.ptr, stream), "avl_planar_decay")
+    if isinstance(grid_pos, np.ndarray):
+        _lib.check(lib.avl_stream_sync(stream), "avl_stream_sync")
+    return sim

@@ -46,6 +46,11 @@ def base_pos2grid_id_3d(gs: int, cs: float, x_base: float, y_base: float, z_base
     return [int(gs / 2 - int(x_base / cs)), int(gs / 2 - int(y_base / cs)), int(z_base / cs)]
 
 
+def base_rot_mat2theta(rot_mat: np.ndarray) -> float:
+    """Heading (rad) of a base rotation matrix, x forward, y left, z up.  Reference: mapping_utils.py:379-389."""
+    return np.arctan2(rot_mat[1, 0], rot_mat[0, 0])
+
+
 def grid_id2base_pos_3d(row: int, col: int, height: int, cs: float, gs: int):
     """Inverse of base_pos2grid_id_3d (cell origin).  Reference: mapping_utils.py (grid_id2base_pos_3d)."""
     return (gs / 2 - row) * cs, (gs / 2 - col) * cs, height * cs

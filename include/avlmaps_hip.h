@@ -639,6 +639,39 @@ AVL_API int avl_obstacle_scatter(const int32_t* d_grid_pos, const int32_t* d_cla
 AVL_API int avl_lseg_merge_windows(const void* d_win, int is_f16, int G, int D, int crop, const int32_t* h_origin, int height,
                                    int width, float* d_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * (7) 2-D goal fields of the area, sound and image queries, and their lift to the voxels (csrc/avl_field2d.hip)
+ *     Cells are (row, col) int32 pairs of the full (gs, gs) map; the host converts poses to cells (the Habitat dataloader path,
+ *     float64) once per loaded map.  Given the same peaks every result is the reference's bits (correctly rounded sqrt and
+ *     divisions, no FMA contraction).  decay_rate must be finite and >= 0.  All calls are asynchronous.
+ * ------------------------------------------------------------------------------------------------ */
+/* avlmaps/map/avlmap.py:78-96 index_area_2d before its normalisation (one scipy EDT per pose upstream):
+ *   field[r, c] = max(0, max over poses i with 0 <= cell_i < gs of clip(peak_i - decay * ||(r, c) - cell_i||, 0, 1))  (float64)
+ * d_cells (P, 2) int32, d_peaks (P,) float64 (the min-max normalised frame scores); poses outside the grid are skipped.
+ * d_minmax (2,) float64 device receives [min, max] of the whole field. */
+AVL_API int avl_field_area(const int32_t* d_cells, const double* d_peaks, int64_t P, int gs, double decay_rate, double* d_field,
+                           double* d_minmax, void* stream);
+/* avlmaps/map/avlmap.py:111-131 index_sound_2d before its normalisation (one scipy EDT per segment upstream): for every
+ * segment s in order, with d = the distance from the cell to the nearest of its locations,
+ *   field = f32(field + max(p_s - (p_s * d) * decay, 0))   (the term in float64, the sum in float32; field starts at 0)
+ * Locations of segment s are d_cells[d_offsets[s] .. d_offsets[s + 1]) of the (L, 2) int32 array, d_offsets (S + 1,) int64
+ * non-decreasing (clamped to [0, L]); every location must lie inside the grid; d_peaks (S,) float32 >= 0.
+ * d_minmax (2,) float32 device receives [min, max] of the whole field. */
+AVL_API int avl_field_sound(const int64_t* d_offsets, const int32_t* d_cells, int64_t L, const float* d_peaks, int64_t S, int gs,
+                            double decay_rate, float* d_field, float* d_minmax, void* stream);
+/* avlmaps/map/avlmap.py:97,100-109 and :132,135-144 (min-max normalisation + the Python loop over occupied_ids): for every voxel
+ *   heat[i] = f32((field[row_i, col_i] - min) / (max - min)), or 0 when grid_pos[i] lies outside the (gs, gs, vh) grid
+ * is_f64 = 1: a float64 field and d_minmax (avl_field_area), normalised in float64; 0: float32 (avl_field_sound).
+ * max == min gives NaN as upstream; the caller checks d_minmax. */
+AVL_API int avl_field_lift(const void* d_field, int is_f64, const void* d_minmax, int gs, int vh, const int32_t* d_grid_pos, int64_t N,
+                           float* d_heat, void* stream);
+/* the normalised 2-D map itself (the return value of index_area_2d / index_sound_2d): d_out (gs, gs) of the field's type */
+AVL_API int avl_field_normalize(const void* d_field, int is_f64, const void* d_minmax, int gs, void* d_out, void* stream);
+/* avlmaps/map/avlmap.py:154-161 index_image after localisation: sim[i] = clip(1 - decay * ||grid_pos[i, :2] - (row, col)||, 0, 1)
+ * in float64, d_sim (N,) float64 */
+AVL_API int avl_planar_decay(const int32_t* d_grid_pos, int64_t N, int64_t row, int64_t col, double decay_rate, double* d_sim,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif
