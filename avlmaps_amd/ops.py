@@ -252,6 +252,30 @@ def argmax_f32(vals, stream=None):
     return idx.value, val.value
 
 
+def _global_depth(depth, stream):
+    """-> (ptr, shape, keepalive, is_u16) of the depth image of the multi-floor builder: uint16 (metres = value / depth_div) or
+    float32 metres, nothing else.  The kernels read one of these two; converting anything else here would round it quietly (a
+    float64 image in metres, what the reference's PNG / 1000.0 is, would lose bits and move voxel ids at cell edges)."""
+    if _is_torch(depth):
+        dt = str(depth.dtype)
+        is_u16 = dt in ("torch.uint16", "torch.int16")
+        if not (is_u16 or dt == "torch.float32"):
+            raise TypeError(f"depth must be uint16 (value / depth_div metres) or float32 metres, got {dt}")
+        if not depth.is_cuda:
+            raise TypeError("torch tensors passed to avlmaps_amd must live on the GPU")
+        depth = depth.contiguous()
+        return depth.data_ptr(), tuple(depth.shape), depth, is_u16
+    dt = getattr(depth, "dtype", None)
+    dt = np.dtype(object) if dt is None else np.dtype(dt)
+    if dt not in (np.dtype(np.uint16), np.dtype(np.float32)):
+        raise TypeError(f"depth must be uint16 (value / depth_div metres) or float32 metres, got {dt}")
+    if dt == np.uint16:
+        if isinstance(depth, np.ndarray):
+            return (*as_device(depth.view(np.int16), np.int16, stream), True)
+        return depth.ptr, depth.shape, depth, True           # DeviceArray / DeviceView of uint16
+    return (*as_device(depth, np.float32, stream), False)
+
+
 class BatchPlan:
     """resolved device-pointer tables of one batch of frames (VoxelAccumulator.make_batch_plan)"""
     __slots__ = ("B", "H", "W", "Hf", "Wf", "P", "depth", "samples", "feat", "rgb", "keep")
@@ -482,14 +506,10 @@ class VoxelAccumulator:
     def integrate_frame_global(self, depth, calib, transform, sample_idx, feat_hwc, rgb, frame_idx, pcd_min, depth_div=1000.0,
                                calib_inv=None, min_depth=0.1, max_depth=100.0, sigma_sq=0.6, stream=None):
         """Global (multi-floor) fusion, vlmap_builder_multi_floor.py:137-199.  depth: (H,W) uint16 (metres = value /
-        depth_div, like the reference's PNG / 1000.0) or float32 metres; transform = camera_pose_tf @ habitat2cam_rot_tf."""
+        depth_div, like the reference's PNG / 1000.0) or float32 metres (any other dtype raises TypeError);
+        transform = camera_pose_tf @ habitat2cam_rot_tf."""
         lib = _lib.load()
-        depth_np_u16 = isinstance(depth, np.ndarray) and depth.dtype == np.uint16
-        is_u16 = depth_np_u16 or (_is_torch(depth) and str(depth.dtype) in ("torch.uint16", "torch.int16"))
-        if isinstance(depth, np.ndarray):
-            dp, dshape, k1 = as_device(depth.view(np.int16) if depth_np_u16 else depth, np.int16 if is_u16 else np.float32, stream)
-        else:
-            dp, dshape, k1 = depth.data_ptr(), tuple(depth.shape), depth
+        dp, dshape, k1, is_u16 = _global_depth(depth, stream)
         fp_, fshape, k2 = as_device(feat_hwc, np.float32, stream)
         rp, rshape, k3 = as_device(rgb, np.uint8, stream)
         sp, sshape, k4 = as_device(sample_idx, np.int32, stream)
@@ -630,10 +650,10 @@ class VoxelAccumulator:
 
 def points_bbox(minmax, depth, calib, transform, sample_idx, depth_div=1000.0, min_depth=0.1, max_depth=100.0, stream=None):
     """Pass 1 of the global builder (vlmap_builder_multi_floor.py:97-118): fold one frame's transformed sampled points into
-    minmax (6,) float64 [min xyz, max xyz] in place.  depth: uint16 (value / depth_div metres) or float32 metres."""
+    minmax (6,) float64 [min xyz, max xyz] in place.  depth: uint16 (value / depth_div metres) or float32 metres; any other dtype
+    raises TypeError."""
     lib = _lib.load()
-    is_u16 = isinstance(depth, np.ndarray) and depth.dtype == np.uint16
-    dp, dshape, k1 = as_device(depth.view(np.int16) if is_u16 else depth, np.int16 if is_u16 else np.float32, stream)
+    dp, dshape, k1, is_u16 = _global_depth(depth, stream)
     sp, sshape, k2 = as_device(sample_idx, np.int32, stream)
     Kinv = np.ascontiguousarray(np.linalg.inv(np.asarray(calib, dtype=np.float64).reshape(3, 3)))
     T = np.ascontiguousarray(np.asarray(transform, dtype=np.float64).reshape(4, 4))

@@ -210,10 +210,16 @@ class OracleMap:
 HABITAT2CAM_ROT = np.diag([1.0, -1.0, -1.0, 1.0])     # vlmap_builder_multi_floor.py:77-79
 
 
-def points_bbox(minmax, depth_m, calib, transform, sample_idx, min_depth=0.1, max_depth=100.0):
+def _kinv(calib, calib_inv):
+    """inv(K) (mapping_utils.py:237), or the inverse a test injects to place exact camera-frame points (tests/test_geometry_gpu.py)"""
+    m = np.linalg.inv(np.asarray(calib, dtype=np.float64).reshape(3, 3)) if calib_inv is None else calib_inv
+    return np.ascontiguousarray(np.asarray(m, dtype=np.float64).reshape(3, 3))
+
+
+def points_bbox(minmax, depth_m, calib, transform, sample_idx, min_depth=0.1, max_depth=100.0, calib_inv=None):
     """fold one frame into minmax (6,) float64 in place -- pass 1 of create_global_map (:97-118)"""
     d = np.ascontiguousarray(depth_m, dtype=np.float64)
-    Kinv = np.ascontiguousarray(np.linalg.inv(np.asarray(calib, dtype=np.float64).reshape(3, 3)))
+    Kinv = _kinv(calib, calib_inv)
     T = np.ascontiguousarray(transform, dtype=np.float64)
     idx = np.ascontiguousarray(sample_idx, dtype=np.int32)
     lib().avlo_points_bbox(_p(d, C.c_double), d.shape[1], _p(Kinv, C.c_double), _p(T, C.c_double), _p(idx, C.c_int32), len(idx),
@@ -231,11 +237,11 @@ class OracleGlobalMap(OracleMap):
         self.cs, self.D = float(cs), int(D)
         self._h = lib().avlo_map_create_grid(self.n0, self.gs, self.vh, self.cs, self.D)
 
-    def integrate(self, depth_m, calib, transform, sample_idx, feat_chw, rgb, min_depth=0.1, max_depth=100.0):
+    def integrate(self, depth_m, calib, transform, sample_idx, feat_chw, rgb, min_depth=0.1, max_depth=100.0, calib_inv=None):
         d = np.ascontiguousarray(depth_m, dtype=np.float64)
         H, W = d.shape
         K = np.ascontiguousarray(np.asarray(calib, dtype=np.float64).reshape(3, 3))
-        Kinv = np.ascontiguousarray(np.linalg.inv(K))
+        Kinv = _kinv(K, calib_inv)
         feat = np.ascontiguousarray(feat_chw, dtype=np.float32)
         if feat.ndim == 4:
             feat = feat[0]

@@ -152,7 +152,18 @@ def test_heatmap_matches_reference(golden):
 
 def test_multi_floor_builder_matches_reference(golden):
     """vlmap_builder_multi_floor.py:60-199 (two passes: bounding box, then fusion with np.round voxel indices)"""
-    g = golden("g6_multi_floor.npz")
+    check_multi_floor_oracle(golden("g6_multi_floor.npz"))
+
+
+def test_multi_floor_edges_match_reference(golden):
+    """G10, a scene built for exact arithmetic: hundreds of its voxel indices are exact halves k + 1/2 (np.round: to even) on
+    every axis, two floors, the capacity doubling of the reference"""
+    g = golden("g10_multi_floor_edges.npz")
+    assert g["halves"].min() >= 20                                     # (axis, even / odd k) counts of exact halves
+    check_multi_floor_oracle(g)
+
+
+def check_multi_floor_oracle(g):
     nfr = len(g["depths_u16"])
     depth_m = g["depths_u16"] / 1000.0                                   # :105 -- float64 metres
     minmax = np.array([np.inf] * 3 + [-np.inf] * 3)
@@ -171,6 +182,7 @@ def test_multi_floor_builder_matches_reference(golden):
     nz = np.argwhere(occ != -1)
     assert np.array_equal(nz, g["occ_nz"]) and np.array_equal(occ[nz[:, 0], nz[:, 1], nz[:, 2]], g["occ_nz_vals"])
     assert out["weight"].dtype == g["weight"].dtype == np.float64       # capacity doubled (n0*n1 rows < voxels)
+    assert len(set(g["grid_size"].tolist())) == 3                      # (x, y, z) sizes differ: no axis swap goes unnoticed
     np.testing.assert_allclose(out["weight"], g["weight"], rtol=2e-7)
     np.testing.assert_allclose(out["grid_feat"], g["grid_feat"], rtol=1e-6, atol=1e-6)
     np.testing.assert_allclose(out["grid_rgb"], g["grid_rgb"], rtol=1e-5, atol=1e-4)

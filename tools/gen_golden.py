@@ -19,6 +19,9 @@ Reference entry points exercised (file:line in /root/reference):
       (up to the cv2.findContours call, which is stubbed: its input mask is recorded)
   G9  BASELINE config 1 at its stated size (50 000 x 512, one landmark + "other"): clip_utils.py:196-242 get_lseg_score and
       vlmap.py:104-125 VLMap.index_map(with_init_cat=False); the map is regenerated from its seed, outputs only are stored
+  G6  avlmaps/map/vlmap_builder_multi_floor.py:60-199 VLMapBuilderMultiFloor.create_global_map (both passes, real loop)
+  G10 the same on a scene built for exact arithmetic: voxel indices at exact halves, two floors, the capacity doubling
+      (python tools/gen_golden.py --only-g10 writes this fixture alone)
 """
 import os
 import sys
@@ -473,6 +476,10 @@ def main():
     if "--only-g9" in sys.argv:
         gen_g9_config1(import_reference(), np.random.default_rng(99))
         return
+    if "--only-g10" in sys.argv:
+        import_reference()
+        gen_g10_multi_floor_edges(np.random.default_rng(1010))
+        return
     m = import_reference()
     gen_g1(m, np.random.default_rng(11))
     gen_g2(m, np.random.default_rng(22))
@@ -486,6 +493,8 @@ def main():
         gen_g7_wide(import_reference(), np.random.default_rng(77))
     if "--only-g9" in sys.argv or "--all" in sys.argv or not (OUT / "g9_config1.npz").exists():
         gen_g9_config1(import_reference(), np.random.default_rng(99))
+    if "--all" in sys.argv or not (OUT / "g10_multi_floor_edges.npz").exists():
+        gen_g10_multi_floor_edges(np.random.default_rng(1010))
     os.system(f"ls -la {OUT}")
 
 
@@ -633,29 +642,13 @@ class _FakePCD:
         return self
 
 
-def gen_g6_multi_floor(rng):
-    """avlmaps/map/vlmap_builder_multi_floor.py:60-199 VLMapBuilderMultiFloor.create_global_map (real loop, fake I/O)"""
+def run_reference_multi_floor(cfg, poses, rgbs, depths, feats, D):
+    """VLMapBuilderMultiFloor.create_global_map of the reference on in-memory frames (only image / model / file I/O and the
+    point-cloud container are stubbed).  -> (arrays save_3d_map received, poses as read back from the pose files, the sample
+    list of every shuffle: pass 1 of all frames, then pass 2)"""
     import importlib
     vbm = importlib.import_module("avlmaps.map.vlmap_builder_multi_floor")
-    H, W, Hf, Wf, D, nfr = 24, 32, 11, 15, 8, 6
-    calib = [W / 2, 0, W / 2, 0, W / 2, H / 2, 0, 0, 1]
-    cfg = make_map_config(gs=1000, cs=0.1, cam_h=1.5, calib=calib, rate=1)
-    cfg["skip_frame"] = 1
-    cfg.pose_info["building_init_height"] = 0.0
-    yy, xx = np.meshgrid(np.linspace(-1, 1, H), np.linspace(-1, 1, W), indexing="ij")
-    depths, rgbs, feats, poses = [], [], [], []
-    from scipy.spatial.transform import Rotation as R
-    for i in range(nfr):
-        d = 2.0 + 0.8 * np.sin(2 * xx + 0.4 * i) * np.cos(yy) + 0.3 * yy
-        d[rng.random(d.shape) < 0.05] = 0.0
-        depths.append(np.round(d * 1000).astype(np.uint16))
-        rgbs.append(rng.integers(0, 256, (H, W, 3), dtype=np.uint8))
-        f = rng.standard_normal((1, D, Hf, Wf)).astype(np.float32)
-        feats.append((f / np.linalg.norm(f, axis=1, keepdims=True) * 14.2857).astype(np.float16).astype(np.float32))
-        T = np.eye(4)
-        T[:3, :3] = R.from_euler("yxz", [0.3 * i, 0.05 * i, 0.02 * i]).as_matrix()
-        T[:3, 3] = [0.3 * i, 0.1 + 0.6 * (i // 3), -0.2 * i]          # second "floor" after 3 frames
-        poses.append(T)
+    nfr = len(depths)
     tmp = Path(tempfile.mkdtemp(prefix="avl_golden_mf_"))
     pose_paths = []
     for i, T in enumerate(poses):
@@ -706,6 +699,40 @@ def gen_g6_multi_floor(rng):
         builder.create_global_map()
     finally:
         np.random.shuffle = orig_shuffle
+    return captured, poses_rt, samples
+
+
+def gen_g6_multi_floor(rng):
+    """avlmaps/map/vlmap_builder_multi_floor.py:60-199 VLMapBuilderMultiFloor.create_global_map (real loop, fake I/O)"""
+    H, W, Hf, Wf, D, nfr = 24, 32, 11, 15, 8, 6
+    calib = [W / 2, 0, W / 2, 0, W / 2, H / 2, 0, 0, 1]
+    cfg = make_map_config(gs=1000, cs=0.1, cam_h=1.5, calib=calib, rate=1)
+    cfg["skip_frame"] = 1
+    cfg.pose_info["building_init_height"] = 0.0
+    yy, xx = np.meshgrid(np.linspace(-1, 1, H), np.linspace(-1, 1, W), indexing="ij")
+    depths, rgbs, feats, poses = [], [], [], []
+    from scipy.spatial.transform import Rotation as R
+    for i in range(nfr):
+        d = 2.0 + 0.8 * np.sin(2 * xx + 0.4 * i) * np.cos(yy) + 0.3 * yy
+        d[rng.random(d.shape) < 0.05] = 0.0
+        depths.append(np.round(d * 1000).astype(np.uint16))
+        rgbs.append(rng.integers(0, 256, (H, W, 3), dtype=np.uint8))
+        f = rng.standard_normal((1, D, Hf, Wf)).astype(np.float32)
+        feats.append((f / np.linalg.norm(f, axis=1, keepdims=True) * 14.2857).astype(np.float16).astype(np.float32))
+        T = np.eye(4)
+        T[:3, :3] = R.from_euler("yxz", [0.3 * i, 0.05 * i, 0.02 * i]).as_matrix()
+        T[:3, 3] = [0.3 * i, 0.1 + 0.6 * (i // 3), -0.2 * i]          # second "floor" after 3 frames
+        poses.append(T)
+    captured, poses_rt, samples = run_reference_multi_floor(cfg, poses, rgbs, depths, feats, D)
+    out = multi_floor_fixture(cfg, calib, depths, rgbs, feats, captured, poses_rt, samples)
+    np.savez_compressed(OUT / "g6_multi_floor.npz", **out)
+    print("G6 written: voxels", captured["max_id"], "grid", captured["grid_size"], "occ", captured["occupied_ids"].shape,
+          "weight", captured["weight"].dtype)
+
+
+def multi_floor_fixture(cfg, calib, depths, rgbs, feats, captured, poses_rt, samples):
+    """inputs and the reference's outputs of one create_global_map run, occupied_ids stored sparsely"""
+    nfr = len(depths)
     occ = captured["occupied_ids"]
     nz = np.argwhere(occ != -1).astype(np.int32)
     out = dict(cs=cfg.cell_size, rate=cfg.depth_sample_rate, calib=np.array(calib, dtype=np.float64), depths_u16=np.stack(depths),
@@ -715,8 +742,84 @@ def gen_g6_multi_floor(rng):
                grid_feat=captured["grid_feat"], grid_pos=captured["grid_pos"], weight=captured["weight"],
                grid_rgb=captured["grid_rgb"], occ_shape=np.array(occ.shape), occ_nz=nz,
                occ_nz_vals=occ[nz[:, 0], nz[:, 1], nz[:, 2]].astype(np.int32), max_id=captured["max_id"])
-    np.savez_compressed(OUT / "g6_multi_floor.npz", **out)
-    print("G6 written: voxels", captured["max_id"], "grid", captured["grid_size"], "occ", occ.shape, "weight", captured["weight"].dtype)
+    return out
+
+
+def _rot90(axis, k):
+    """exact rotation by k * 90 degrees about axis 0 / 1 / 2 (integer entries: no cos(pi / 2) = 6e-17 residue)"""
+    c, s = [1, 0, -1, 0][k % 4], [0, 1, 0, -1][k % 4]
+    i, j = [(1, 2), (2, 0), (0, 1)][axis]
+    m = np.eye(3)
+    m[i, i], m[i, j], m[j, i], m[j, j] = c, -s, s, c
+    return m
+
+
+def gen_g10_multi_floor_edges(rng):
+    """create_global_map (vlmap_builder_multi_floor.py:60-199, real loop, fake I/O like G6) on a scene built for exact
+    arithmetic, so that the voxel index np.round((p - pcd_min) / cs) meets many exact halves k + 1/2 (even and odd k, on all
+    three axes): focal length 16 with integer principal point (inv(K) exact), depths in multiples of 125 mm (/ 1000.0 exact),
+    rotations by multiples of 90 degrees and translations in eighths, cs = 0.25.  Four frames with generic rotations, two floors
+    2.75 m apart, a grid whose three sizes differ, more voxels than the grid_size[0] * grid_size[2] rows the reference reserves
+    (weight / grid_rgb switch dtype).  depth_sample_rate = 1: both passes see the same points, none falls outside the box."""
+    H, W, Hf, Wf, D = 24, 32, 9, 13, 8
+    calib = [16, 0, 16, 0, 16, 12, 0, 0, 1]
+    cfg = make_map_config(gs=1000, cs=0.25, cam_h=1.5, calib=calib, rate=1)
+    cfg["skip_frame"] = 1
+    cfg.pose_info["building_init_height"] = 0.0
+    from scipy.spatial.transform import Rotation as R
+    yy, xx = np.meshgrid(np.linspace(-1, 1, H), np.linspace(-1, 1, W), indexing="ij")
+    # (yaw quarter turns, pitch quarter turns, x, floor height, z): x / z in eighths of a metre
+    exact = [(0, 0, 0.0, 1.5, 0.0), (1, 0, 0.375, 1.5, -0.625), (2, 0, 1.125, 1.5, 0.25), (3, 0, -0.5, 1.5, 1.875),
+             (0, 1, 0.625, 1.5, -1.0), (2, 3, 2.0, 1.5, 0.125), (1, 0, -1.25, 4.25, 0.5), (3, 0, 0.875, 4.25, -2.125),
+             (0, 3, -0.375, 4.25, 1.0), (2, 1, 1.5, 4.25, -0.75)]
+    generic = [([0.7, 0.1, 0.05], [0.31, 1.62, -0.47]), ([2.2, -0.15, 0.02], [-0.83, 1.41, 0.66]),
+               ([-1.1, 0.2, -0.1], [0.52, 4.37, -0.79]), ([3.9, 0.05, 0.12], [1.07, 4.11, 0.94])]
+    depths, rgbs, feats, poses = [], [], [], []
+    for i in range(len(exact) + len(generic)):
+        T = np.eye(4)
+        if i < len(exact):
+            yaw, pitch, x, y, z = exact[i]
+            T[:3, :3] = _rot90(1, yaw) @ _rot90(0, pitch)
+            T[:3, 3] = [x, y, z]
+            base = 1.5 if pitch else 2.75          # (pitched: looking at the floor / ceiling)
+        else:
+            T[:3, :3] = R.from_euler("yxz", generic[i - len(exact)][0]).as_matrix()
+            T[:3, 3] = generic[i - len(exact)][1]
+            base = 2.5
+        d = base + 1.1 * np.sin(2.3 * xx + 0.7 * i) * np.cos(1.3 * yy) + 0.4 * yy
+        d = 125 * np.clip(np.round(d / 0.125), 2, 48)
+        d[rng.random(d.shape) < 0.04] = 0
+        depths.append(d.astype(np.uint16))
+        rgbs.append(rng.integers(0, 256, (H, W, 3), dtype=np.uint8))
+        f = rng.standard_normal((1, D, Hf, Wf)).astype(np.float32)
+        feats.append((f / np.linalg.norm(f, axis=1, keepdims=True) * 14.2857).astype(np.float16).astype(np.float32))
+        poses.append(T)
+    captured, poses_rt, samples = run_reference_multi_floor(cfg, poses, rgbs, depths, feats, D)
+    out = multi_floor_fixture(cfg, calib, depths, rgbs, feats, captured, poses_rt, samples)
+    # what the scene is for: exact halves on every axis, for even and odd k, and the reference's dtype switch
+    Kinv = np.linalg.inv(np.array(calib, dtype=np.float64).reshape(3, 3))
+    v, u = np.divmod(np.arange(H * W), W)
+    halves = np.zeros((3, 2), dtype=np.int64)
+    for i in range(len(depths)):
+        z = depths[i].reshape(-1) / 1000.0
+        pc = (Kinv @ np.stack([u + 0.5, v + 0.5, np.ones(H * W)])) * z
+        pc = pc[:, (pc[2] > 0.1) & (pc[2] < 100)]
+        pg = (poses_rt[i] @ HABITAT2CAM @ np.vstack([pc, np.ones(pc.shape[1])]))[:3]
+        q = (pg - captured["pcd_min"][:, None]) / cfg.cell_size
+        half = q - np.floor(q) == 0.5
+        for a in range(3):
+            k = np.floor(q[a][half[a]]).astype(np.int64)
+            halves[a] += [(k % 2 == 0).sum(), (k % 2 == 1).sum()]
+    assert halves.min() >= 20, halves
+    gsz = captured["grid_size"]
+    assert len(set(gsz.tolist())) == 3 and captured["max_id"] > gsz[0] * gsz[2] and captured["weight"].dtype == np.float64
+    out["halves"] = halves
+    np.savez_compressed(OUT / "g10_multi_floor_edges.npz", **out)
+    print("G10 written: voxels", captured["max_id"], "grid", gsz, "rows reserved", gsz[0] * gsz[2], "exact halves (axis, even/odd k)",
+          halves.tolist())
+
+
+HABITAT2CAM = np.diag([1.0, -1.0, -1.0, 1.0])        # vlmap_builder_multi_floor.py:77-79
 
 
 if __name__ == "__main__":
