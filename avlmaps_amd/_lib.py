@@ -142,6 +142,13 @@ _SIGS = {
     "avl_field_lift": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _i64, _vp, _vp]),
     "avl_field_normalize": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp]),
     "avl_planar_decay": (C.c_int, [_vp, _i64, _i64, _i64, _f64, _vp, _vp]),
+    "avl_nav_create": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.POINTER(_vp)]),
+    "avl_nav_destroy": (C.c_int, [_vp]),
+    "avl_nav_num_vertices": (C.c_int, [_vp, C.POINTER(_i64)]),
+    "avl_nav_vertices": (C.c_int, [_vp, _vp, _vp]),
+    "avl_nav_export_visibility": (C.c_int, [_vp, _vp, _vp]),
+    "avl_nav_plan": (C.c_int, [_vp, _f64, _f64, _f64, _f64, C.POINTER(_f64), _vp, C.POINTER(C.c_int), C.c_int, _vp]),
+    "avl_nav_last_plan": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

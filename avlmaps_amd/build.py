@@ -25,6 +25,7 @@ SOURCES = {
     "avl_merge.hip": [],
     "avl_merge2.hip": [],
     "avl_field2d.hip": ["-ffp-contract=off"],      # the goal fields reproduce NumPy's float64 / float32 rounding step by step
+    "avl_nav.hip": ["-ffp-contract=off"],          # the query predicates and path lengths round like the float64 oracle
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fvisibility=hidden", "-Wall",
           "-Wno-unused-function", "-munsafe-fp-atomics"]

@@ -110,6 +110,59 @@ class Map:
         m = binary_dilation(m, structure=np.ones((3, 3)), iterations=dilate_iter * 2)
         return cv2.resize(m.astype(float), (w, h))
 
+    # ------------------------------------------------------------------------ goal helpers of the planner (map.py:183-240)
+    def get_nearest_pos(self, curr_pos: List[float], name: str) -> List[float]:
+        """the point of the nearest sizeable `name` object's contour closest to curr_pos (full-map (row, col)); curr_pos itself
+        when there is none"""
+        contours, centers, bbox_list = self.get_pos(name)
+        keep = self.filter_small_objects(bbox_list, area_thres=10)
+        contours = [contours[i] for i in keep]
+        centers = [centers[i] for i in keep]
+        bbox_list = [bbox_list[i] for i in keep]
+        if not centers:
+            return curr_pos
+        k = self.select_nearest_obj(centers, bbox_list, curr_pos)
+        return self.nearest_point_on_polygon(curr_pos, contours[k])
+
+    @staticmethod
+    def nearest_point_on_polygon(coord: List[float], polygon) -> List[int]:
+        """The exact nearest point to `coord` on the closed ring through `polygon`'s points (no shapely): among equally near points
+        the one with the smallest arc length from the first point, then int() truncation of both coordinates as upstream."""
+        pts = np.asarray(polygon, dtype=np.float64).reshape(-1, 2)
+        x = np.asarray(coord, dtype=np.float64)
+        if len(pts) == 0:
+            raise ValueError("empty polygon")
+        best, best_d2 = pts[0], float(np.sum((x - pts[0]) ** 2))
+        for k in range(len(pts)):
+            a, b = pts[k], pts[(k + 1) % len(pts)]
+            ab = b - a
+            L2 = float(ab @ ab)
+            if L2 == 0.0:
+                continue
+            t = min(1.0, max(0.0, float((x - a) @ ab) / L2))
+            q = a + t * ab
+            d2 = float(np.sum((x - q) ** 2))
+            if d2 < best_d2:
+                best, best_d2 = q, d2
+        return [int(best[0]), int(best[1])]
+
+    def get_forward_pos(self, curr_pos: List[float], curr_angle_deg: float, meters: float) -> List[float]:
+        """the cell `meters` ahead of curr_pos (row, col) at heading curr_angle_deg (0 = towards smaller rows)"""
+        rad = np.deg2rad(curr_angle_deg)
+        pix = meters / self.cs
+        return [curr_pos[0] - pix * np.cos(rad), curr_pos[1] + pix * np.sin(rad)]
+
+    def filter_small_objects(self, bbox_list: List[List[int]], area_thres: int = 50) -> List[int]:
+        """indices of the boxes [rmin, rmax, cmin, cmax] whose (rmax - rmin) * (cmax - cmin) exceeds area_thres"""
+        return [i for i, b in enumerate(bbox_list) if (b[1] - b[0]) * (b[3] - b[2]) > area_thres]
+
+    def select_nearest_obj(self, centers: List[List[float]], bbox_list: List[List[float]], curr_pos) -> int:
+        """index of the box nearest to curr_pos (utils.navigation_utils.get_dist_to_bbox_2d), the first on ties"""
+        from ..utils.navigation_utils import get_dist_to_bbox_2d
+        d = [get_dist_to_bbox_2d(np.array(c), np.array([b[1] - b[0], b[3] - b[2]]), np.array(curr_pos))
+             for c, b in zip(centers, bbox_list)]
+        return int(np.argmin(d))
+
     @staticmethod
     def create(map_config) -> "Map":
         """Reference: map.py:120-129."""

@@ -1,0 +1,56 @@
+"""Navigator with the reference's surface (avlmaps/navigator/navigator.py:7-65), planning on the GPU.
+
+build_visgraph uploads the cropped obstacle map and builds the visibility graph on the device (ops.NavGraph); the graph stays
+there between plan_to calls, which only compute the start and goal visibility rows and the shortest path.  A start inside a
+walled room needs no corridor carving (upstream _check_if_start_in_graph_obstacle / _rebuild_visgraph), see DESIGN.md."""
+from __future__ import annotations
+
+from typing import List, Tuple
+
+import numpy as np
+
+from ..utils.navigation_utils import NoPathError, build_visgraph_with_obs_map, plan_to_pos_v2  # noqa: F401
+
+
+class Navigator:
+    def __init__(self):
+        self.visgraph = None
+        self.obs_map = None
+        self.rowmin = 0
+        self.colmin = 0
+
+    def build_visgraph(self, obstacle_map: np.ndarray, rowmin: float, colmin: float, vis: bool = False):
+        """obstacle_map: the cropped map (nonzero / True = free); rowmin, colmin: its offset in the full map"""
+        self.close()
+        self.obs_map = np.asarray(obstacle_map)
+        self.visgraph = build_visgraph_with_obs_map(self.obs_map, vis=vis)
+        self.rowmin = rowmin
+        self.colmin = colmin
+
+    def plan_to(self, start_full_map: Tuple[float, float], goal_full_map: Tuple[float, float], vis: bool = False) -> List[List[float]]:
+        """full-map (row, col) start and goal -> the path as full-map [row, col] points, first the start.  NoPathError when the goal
+        cannot be reached."""
+        if self.visgraph is None:
+            raise RuntimeError("build_visgraph first")
+        start = self._convert_full_map_pos_to_cropped_map_pos(start_full_map)
+        goal = self._convert_full_map_pos_to_cropped_map_pos(goal_full_map)
+        paths = plan_to_pos_v2(start, goal, self.obs_map, self.visgraph, vis)
+        return self.shift_path(paths, self.rowmin, self.colmin)
+
+    def shift_path(self, paths: List[List[float]], row_shift: float, col_shift: float) -> List[List[float]]:
+        return [[p[0] + row_shift, p[1] + col_shift] for p in paths]
+
+    def _convert_full_map_pos_to_cropped_map_pos(self, full_map_pos: Tuple[float, float]) -> List[float]:
+        return [full_map_pos[0] - self.rowmin, full_map_pos[1] - self.colmin]
+
+    def _convert_cropped_map_pos_to_full_map_pos(self, cropped_map_pos: Tuple[float, float]) -> List[float]:
+        return [cropped_map_pos[0] + self.rowmin, cropped_map_pos[1] + self.colmin]
+
+    def close(self):
+        """release the graph's device memory"""
+        if getattr(self, "visgraph", None) is not None:
+            self.visgraph.close()
+            self.visgraph = None
+
+    def __del__(self):
+        self.close()

@@ -1038,3 +1038,112 @@ def planar_decay(grid_pos, row, col, decay_rate=0.01, stream=None):
     if isinstance(grid_pos, np.ndarray):
         _lib.check(lib.avl_stream_sync(stream), "avl_stream_sync")
     return sim
+
+
+# ---------------------------------------------------------------------------------------- visibility-graph navigation
+NAV_MAX_VERTICES = 65536
+NAV_MAX_SIDE = 32768
+
+
+class NavGraph:
+    """The navigation graph of one obstacle map, resident on the device (csrc/avl_nav.hip): the padded obstacle raster, the path
+    vertices and their V x V visibility bitset.  Node ids of a plan: vertices 0 .. V-1 (raster order), V = start, V + 1 = goal.
+    Release the device memory with close() (also on garbage collection)."""
+
+    def __init__(self, handle, shape, V):
+        self._h = handle
+        self.shape = shape
+        self.V = V
+        self.W64 = (V + 63) // 64
+        self._verts = None
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("the navigation graph has been closed")
+        return self._h
+
+    def vertices(self) -> np.ndarray:
+        """(V, 2) int32 (row, col) of the path vertices, raster order (cached on the host)"""
+        if self._verts is None:
+            out = np.zeros((self.V, 2), np.int32)
+            if self.V:
+                _lib.check(_lib.load().avl_nav_vertices(self._handle(), out.ctypes.data, None), "avl_nav_vertices")
+            self._verts = out
+        return self._verts
+
+    def visibility_words(self) -> np.ndarray:
+        """(V, ceil(V / 64)) uint64: bit b % 64 of word (a, b // 64) = a and b see each other"""
+        out = np.zeros((self.V, self.W64), np.uint64)
+        if self.V:
+            _lib.check(_lib.load().avl_nav_export_visibility(self._handle(), out.ctypes.data, None), "avl_nav_export_visibility")
+        return out
+
+    def visibility(self) -> np.ndarray:
+        """(V, V) bool, symmetric, False on the diagonal"""
+        return unpack_rows(self.visibility_words(), self.V)
+
+    def plan(self, start, goal):
+        """float64 shortest path from start (row, col) to goal over the graph -> (distance, node ids start .. goal); (inf, [])
+        when the goal is unreachable.  Both points must lie inside the map."""
+        s = [float(start[0]), float(start[1])]
+        t = [float(goal[0]), float(goal[1])]
+        H, W = self.shape
+        for r, c in (s, t):
+            if not (np.isfinite(r) and np.isfinite(c) and 0.0 <= r <= H - 1 and 0.0 <= c <= W - 1):
+                raise ValueError(f"point ({r}, {c}) lies outside the {H} x {W} map")
+        cap = self.V + 2
+        ids = np.zeros(cap, np.int32)
+        dist, n = C.c_double(0.0), C.c_int(0)
+        _lib.check(_lib.load().avl_nav_plan(self._handle(), s[0], s[1], t[0], t[1], C.byref(dist), ids.ctypes.data, C.byref(n), cap,
+                                            None), "avl_nav_plan")
+        return dist.value, ids[:n.value].tolist()
+
+    def last_plan(self) -> dict:
+        """the last plan's internals: dist (V + 2,) float64, pred (V + 2,) int32, qvis (2, V) bool (start row, goal row), sg bool"""
+        N = self.V + 2
+        dist, pred = np.zeros(N, np.float64), np.zeros(N, np.int32)
+        q = np.zeros((2, max(self.W64, 1)), np.uint64)
+        sg = np.zeros(1, np.int32)
+        _lib.check(_lib.load().avl_nav_last_plan(self._handle(), dist.ctypes.data, pred.ctypes.data, q.ctypes.data, sg.ctypes.data,
+                                                 None), "avl_nav_last_plan")
+        return dict(dist=dist, pred=pred, qvis=unpack_rows(q[:, :self.W64], self.V), sg=bool(sg[0]))
+
+    def close(self):
+        if self._h is not None:
+            h, self._h = self._h, None
+            try:
+                _lib.load().avl_nav_destroy(h)
+            except Exception:
+                pass
+
+    def __del__(self):
+        self.close()
+
+
+def unpack_rows(words: np.ndarray, n: int) -> np.ndarray:
+    """(R, ceil(n / 64)) uint64 bit rows -> (R, n) bool (bit b % 64 of word b // 64)"""
+    words = np.ascontiguousarray(words, dtype=np.uint64)
+    bits = np.unpackbits(words.view(np.uint8).reshape(words.shape[0], -1), axis=1, bitorder="little")
+    return bits[:, :n].astype(bool)
+
+
+def nav_graph(obstacle_map) -> NavGraph:
+    """navigation_utils.py:77-127 build_visgraph_with_obs_map on the GPU: obstacle_map (H, W), nonzero / True = free, 0 = obstacle
+    (Map.obstacles_cropped).  Raises AvlError above NAV_MAX_VERTICES path vertices."""
+    obs = np.asarray(obstacle_map)
+    if obs.ndim != 2 or obs.shape[0] < 1 or obs.shape[1] < 1:
+        raise ValueError(f"the obstacle map must be a non-empty 2-D array, got shape {obs.shape}")
+    if max(obs.shape) > NAV_MAX_SIDE:
+        raise ValueError(f"the obstacle map is {obs.shape[0]} x {obs.shape[1]}; at most {NAV_MAX_SIDE} per side")
+    if obs.dtype.kind not in "biuf":
+        raise TypeError(f"the obstacle map must be boolean or numeric, got {obs.dtype}")
+    free = np.ascontiguousarray(obs != 0, dtype=np.uint8)
+    lib = _lib.load()
+    _lib.require_gpu()
+    h = C.c_void_p()
+    _lib.check(lib.avl_nav_create(free.ctypes.data, free.shape[0], free.shape[1], None, C.byref(h)), "avl_nav_create")
+    V = C.c_int64(0)
+    rc = lib.avl_nav_num_vertices(h, C.byref(V))
+    g = NavGraph(h, free.shape, int(V.value))
+    _lib.check(rc, "avl_nav_num_vertices")
+    return g

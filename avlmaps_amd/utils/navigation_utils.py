@@ -6,6 +6,8 @@ component extents -- are identical; the contour itself is the component's full o
 OpenCV's corner-compressed polyline, and components are listed bottom-up like OpenCV lists them."""
 from __future__ import annotations
 
+import math
+
 import numpy as np
 
 
@@ -62,3 +64,120 @@ def get_segment_islands_pos(segment_map, label_id, detect_internal_contours=Fals
         bbox_list.append([xmin, xmax, ymin, ymax])
         centers_list.append([(xmin + xmax) / 2, (ymin + ymax) / 2])
     return contours_list, centers_list, bbox_list, hierarchy
+
+
+# ---------------------------------------------------------------------------------------- planning on the obstacle map
+# The reference builds a pyvisgraph visibility graph over the cv2 contours of the obstacles (navigation_utils.py:77-127) and runs
+# pyvisgraph's Dijkstra (:130-197).  Here the graph is built and searched on the GPU (csrc/avl_nav.hip, ops.NavGraph) over the
+# raster model of DESIGN.md "Navigation"; neither pyvisgraph nor OpenCV is needed.
+
+
+class NoPathError(ValueError):
+    """the goal cannot be reached from the start on the obstacle map"""
+
+
+def build_visgraph_with_obs_map(obs_map, vis=False):
+    """-> ops.NavGraph of the obstacle map (nonzero / True = free).  `vis` (cv2 windows upstream) is accepted and ignored.
+    The reference's use_internal_contour / internal_point corridor carving is not needed: a start inside a walled room is
+    planned from as it is."""
+    from .. import ops
+    return ops.nav_graph(obs_map)
+
+
+def _nearest_free(obstacles, pos):
+    """the free cell with the smallest squared distance to the float point `pos`, first in np.where order (as upstream)"""
+    rows, cols = np.where(np.asarray(obstacles) != 0)
+    if len(rows) == 0:
+        raise NoPathError("the obstacle map has no free cell")
+    d2 = (rows - pos[0]) ** 2 + (cols - pos[1]) ** 2
+    k = int(np.argmin(d2))
+    return [float(rows[k]), float(cols[k])]
+
+
+def _in_obstacle(obstacles, pos):
+    """Is the float point inside the obstacle set of the raster model, where every segment from it is
+    blocked?  Upstream's test is its int() cell.  With that cell free, the point can only be inside the triangle fill of the 2 x 2
+    window with top-left at that cell (the free corner) when it lies strictly beyond the hypotenuse; on a grid line it lies on no
+    bond, since the cell is the line segment's first end."""
+    obs = np.asarray(obstacles) == 0
+    H, W = obs.shape
+    r, c = float(pos[0]), float(pos[1])
+    fr, fc = int(r), int(c)
+    if obs[fr, fc]:
+        return True
+    if r == fr or c == fc or fr + 1 >= H or fc + 1 >= W or obs[fr:fr + 2, fc:fc + 2].sum() < 3:
+        return False
+    return (r - fr) + (c - fc) > 1                     # the free corner is (fr, fc): the hypotenuse is u + v = 1
+
+
+def _inside(obstacles, pos):
+    H, W = np.shape(obstacles)
+    r, c = float(pos[0]), float(pos[1])
+    if not (np.isfinite(r) and np.isfinite(c) and 0.0 <= r <= H - 1 and 0.0 <= c <= W - 1):
+        raise ValueError(f"point ({pos[0]}, {pos[1]}) lies outside the {H} x {W} obstacle map")
+    return r, c
+
+
+def plan_to_pos_v2(start, goal, obstacles, G=None, vis=False):
+    """Shortest path on a cropped obstacle map (nonzero = free) from start to goal, both (row, col), as a list of [row, col] floats
+    starting at the start.  G is the map's NavGraph (built here when None).  As upstream, a start on an obstacle cell snaps to the
+    nearest free cell and that cell is listed twice at the head of the path.  A goal on an obstacle cell snaps by the same rule
+    (upstream: pyvisgraph's closest_point).  Besides upstream's obstacle cell (int() of the point), a point that lies inside the
+    obstacle set -- in a fill of the raster model, where no segment could leave it -- snaps too.  An unreachable goal raises
+    NoPathError.  `vis` is accepted and ignored."""
+    obstacles = np.asarray(obstacles)
+    s = list(_inside(obstacles, start))
+    g = list(_inside(obstacles, goal))
+    path = []
+    if _in_obstacle(obstacles, s):           # upstream: obstacles[int(row), int(col)] == 0; also a point inside a fill
+        s = _nearest_free(obstacles, s)
+        path.append(list(s))
+    if _in_obstacle(obstacles, g):
+        g = _nearest_free(obstacles, g)
+    if s == g:                                   # pyvisgraph's shortest_path returns its origin alone
+        path.append(list(s))
+        return path
+    own = G is None
+    if own:
+        G = build_visgraph_with_obs_map(obstacles)
+    try:
+        dist, ids = G.plan(s, g)
+        if not ids:
+            raise NoPathError(f"no path from {s} to {g} on the obstacle map")
+        verts = G.vertices()
+        for k in ids:
+            if k == G.V:
+                path.append(list(s))
+            elif k == G.V + 1:
+                path.append(list(g))
+            else:
+                path.append([float(verts[k, 0]), float(verts[k, 1])])
+    finally:
+        if own:
+            G.close()
+    return path
+
+
+def get_bbox(center, size):
+    """(min corner, max corner) of the box of `size` centred at `center` (navigation_utils.py:200-206)"""
+    center, size = np.asarray(center), np.asarray(size)
+    half = size / 2
+    return center - half, center + half
+
+
+def get_dist_to_bbox_2d(center, size, pos):
+    """distance from `pos` to the 2-D box (navigation_utils.py:209-266): 0 inside, the excess along the one axis on which `pos`
+    lies outside, the Euclidean corner distance when it lies outside on both"""
+    center, size, pos = np.asarray(center), np.asarray(size), np.asarray(pos)
+    lo, hi = get_bbox(center, size)
+    out_r = pos[0] < lo[0] or pos[0] > hi[0]
+    out_c = pos[1] < lo[1] or pos[1] > hi[1]
+    er = np.abs(pos[0] - center[0]) - size[0] / 2
+    ec = np.abs(pos[1] - center[1]) - size[1] / 2
+    if out_r and out_c:
+        return np.sqrt(er * er + ec * ec)
+    if out_r:
+        return er
+    if out_c:
+        return ec
+    return 0

@@ -672,6 +672,39 @@ AVL_API int avl_field_normalize(const void* d_field, int is_f64, const void* d_m
 AVL_API int avl_planar_decay(const int32_t* d_grid_pos, int64_t N, int64_t row, int64_t col, double decay_rate, double* d_sim,
                              void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * (8) visibility-graph navigation on the 2-D obstacle map (csrc/avl_nav.hip)
+ *     The obstacle map is (H, W) uint8, nonzero = free, 0 = obstacle (Map.obstacles_cropped).  Obstacle pixel (r, c) is the point
+ *     (r, c); the obstacle set is the union of the segments between 8-adjacent obstacle pixels and the convex hulls of the obstacle
+ *     corners of every 2 x 2 window holding 3 or 4 (DESIGN.md "Navigation").  Path vertices are the obstacle pixels whose obstacle
+ *     8-neighbours (at least one) lie within 135 degrees, in raster order; their ids are their positions in that list.
+ *     The graph stays on the device behind the opaque handle until avl_nav_destroy.  H, W <= 32768; at most 65 536 vertices.
+ * ------------------------------------------------------------------------------------------------ */
+/* avlmaps/utils/navigation_utils.py:77-127 build_visgraph_with_obs_map (cv2.findContours + pyvisgraph's VisGraph.build) and
+ * avlmaps/navigator/navigator.py:11-15 Navigator.build_visgraph: uploads h_obs, finds the vertices and fills the symmetric
+ * V x V visibility bitset.  Synchronous.  More than 65 536 vertices: AVL_ERR_CAPACITY and no handle. */
+AVL_API int avl_nav_create(const uint8_t* h_obs, int H, int W, void* stream, void** h_graph);
+AVL_API int avl_nav_destroy(void* graph);
+AVL_API int avl_nav_num_vertices(void* graph, int64_t* h_V);
+/* the vertex list, (V, 2) int32 (row, col) on the host (synchronous) */
+AVL_API int avl_nav_vertices(void* graph, int32_t* h_verts, void* stream);
+/* the visibility bitset on the host, (V, ceil(V / 64)) uint64 words: bit b % 64 of word (a, b / 64) = vertices a and b see each
+ * other (the diagonal is 0); synchronous */
+AVL_API int avl_nav_export_visibility(void* graph, uint64_t* h_bits, void* stream);
+/* avlmaps/utils/navigation_utils.py:130-197 plan_to_pos_v2 from the pyvisgraph shortest_path call on, and navigator.py:17-30
+ * Navigator.plan_to: the visibility of the start (sr, sc) and the goal (gr, gc) -- float64 points inside the map -- to every vertex
+ * and to each other, then the float64 shortest path from the start over the graph (edge length sqrt(dr * dr + dc * dc)).
+ * Node ids in h_path: vertices 0 .. V-1, V = the start, V + 1 = the goal; the path runs start -> goal, ties between predecessors
+ * go to the smallest id.  A visible edge is used only where it leaves each vertex end outside the angular span of that vertex's
+ * obstacle neighbours and not along a wall whose neighbours lie on both sides of it.  *h_dist = the path length, +inf and *h_len = 0 when the goal is unreachable.  cap = the capacity of
+ * h_path (V + 2 always suffices).  Synchronous. */
+AVL_API int avl_nav_plan(void* graph, double sr, double sc, double gr, double gc, double* h_dist, int32_t* h_path, int* h_len,
+                         int cap, void* stream);
+/* the last plan's internals, for tests and tools (each pointer may be NULL): h_dist (V + 2,) float64 distances from the start,
+ * h_pred (V + 2,) int32 predecessors (-1 for the start and unreached nodes), h_qbits (2, ceil(V / 64)) uint64 vertex visibility
+ * of the start and of the goal, h_sg the start-goal visibility.  Synchronous. */
+AVL_API int avl_nav_last_plan(void* graph, double* h_dist, int32_t* h_pred, uint64_t* h_qbits, int32_t* h_sg, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

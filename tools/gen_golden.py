@@ -465,6 +465,52 @@ def gen_g8(m, rng):
     print("G8 written: N =", N, "obstacle cells", int((~out["obstacles_default"]).sum()), "dyn free", int(new_obs.sum()))
 
 
+
+def gen_g11_nav_helpers(m, rng):
+    """G11: the planner's goal helpers run through the reference -- Map.filter_small_objects, Map.select_nearest_obj,
+    Map.get_forward_pos (avlmaps/map/map.py:183-240) and get_dist_to_bbox_2d (avlmaps/utils/navigation_utils.py:209-266) -- on
+    random boxes, with corner, edge and inside positions and ties."""
+    import importlib.util
+    import types
+    spec = importlib.util.spec_from_file_location("ref_navigation_utils", os.path.join(os.environ.get("AVLMAPS_REFERENCE", "/root/reference"),
+                                                                                        "avlmaps", "utils", "navigation_utils.py"))
+    nav = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(nav)                        # cv2 / pyvisgraph are stubbed by import_reference; these helpers are NumPy
+    Map = m["map"].Map
+    m["map"].get_dist_to_bbox_2d = nav.get_dist_to_bbox_2d
+    self_ = types.SimpleNamespace(cs=0.05)
+    n_sets, n_boxes = 24, 7
+    boxes = np.zeros((n_sets, n_boxes, 4), np.int64)
+    centers = np.zeros((n_sets, n_boxes, 2), np.float64)
+    pos = np.zeros((n_sets, 2), np.float64)
+    keep = np.zeros((n_sets, n_boxes), bool)
+    nearest = np.zeros(n_sets, np.int64)
+    for k in range(n_sets):
+        r0, c0 = rng.integers(0, 80, n_boxes), rng.integers(0, 80, n_boxes)
+        h, w = rng.integers(0, 15, n_boxes), rng.integers(0, 15, n_boxes)
+        if k % 4 == 0:
+            h[1], w[1], r0[1], c0[1] = h[0], w[0], r0[0], c0[0] + 40        # a second box at the same size: ties in area
+        boxes[k] = np.stack([r0, r0 + h, c0, c0 + w], 1)
+        centers[k] = np.stack([(2 * r0 + h) / 2, (2 * c0 + w) / 2], 1)
+        b = boxes[k][rng.integers(0, n_boxes)]
+        choice = k % 3                                  # inside, on an edge line, anywhere
+        pos[k] = ([rng.uniform(b[0], b[1]), rng.uniform(b[2], b[3])] if choice == 0 else
+                  [float(b[1]), rng.uniform(-10, 100)] if choice == 1 else rng.uniform(-10, 100, 2))
+        ids = Map.filter_small_objects(self_, boxes[k].tolist(), area_thres=10)
+        keep[k, ids] = True
+        nearest[k] = Map.select_nearest_obj(self_, centers[k].tolist(), boxes[k].tolist(), pos[k].tolist())
+    d_c = rng.uniform(-50, 150, (64, 2))
+    d_s = rng.integers(0, 20, (64, 2)).astype(np.float64)
+    d_p = np.concatenate([rng.uniform(-60, 160, (48, 2)), d_c[48:] + d_s[48:] / 2 * rng.choice([-1, 0, 1], (16, 2))])
+    dist = np.array([float(nav.get_dist_to_bbox_2d(c, s, p)) for c, s, p in zip(d_c, d_s, d_p)])
+    f_pos = rng.uniform(0, 500, (16, 2))
+    f_ang = np.concatenate([[0.0, 90.0, 180.0, 270.0], rng.uniform(-360, 360, 12)])
+    f_m = rng.uniform(0, 5, 16)
+    fwd = np.array([Map.get_forward_pos(self_, list(p), a, mm) for p, a, mm in zip(f_pos, f_ang, f_m)], np.float64)
+    np.savez_compressed(OUT / "g11_nav_helpers.npz", boxes=boxes, centers=centers, pos=pos, keep10=keep, nearest=nearest,
+                        dist_center=d_c, dist_size=d_s, dist_pos=d_p, dist=dist, fwd_pos=f_pos, fwd_angle=f_ang, fwd_meters=f_m,
+                        fwd=fwd, cs=np.float64(0.05))
+
 def main():
     OUT.mkdir(parents=True, exist_ok=True)
     if "--only-g8" in sys.argv:
@@ -475,6 +521,9 @@ def main():
         return
     if "--only-g9" in sys.argv:
         gen_g9_config1(import_reference(), np.random.default_rng(99))
+        return
+    if "--only-g11" in sys.argv:
+        gen_g11_nav_helpers(import_reference(), np.random.default_rng(1111))
         return
     if "--only-g10" in sys.argv:
         import_reference()
@@ -495,6 +544,8 @@ def main():
         gen_g9_config1(import_reference(), np.random.default_rng(99))
     if "--all" in sys.argv or not (OUT / "g10_multi_floor_edges.npz").exists():
         gen_g10_multi_floor_edges(np.random.default_rng(1010))
+    if "--all" in sys.argv or not (OUT / "g11_nav_helpers.npz").exists():
+        gen_g11_nav_helpers(import_reference(), np.random.default_rng(1111))
     os.system(f"ls -la {OUT}")
 
 
