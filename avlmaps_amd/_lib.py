@@ -142,6 +142,7 @@ _SIGS = {
     "avl_field_lift": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _i64, _vp, _vp]),
     "avl_field_normalize": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp]),
     "avl_planar_decay": (C.c_int, [_vp, _i64, _i64, _i64, _f64, _vp, _vp]),
+    "avl_goal_fuse": (C.c_int, [_vp, C.c_int, _vp, _i64, _vp, C.POINTER(_i64), C.POINTER(_f64), _vp, _vp]),
     "avl_nav_create": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.POINTER(_vp)]),
     "avl_nav_destroy": (C.c_int, [_vp]),
     "avl_nav_num_vertices": (C.c_int, [_vp, C.POINTER(_i64)]),

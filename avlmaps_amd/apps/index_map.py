@@ -3,11 +3,14 @@ and image branches, :23-142; the Open3D viewer and the habitat branches are not 
 
     python -m avlmaps_amd.apps.index_map --data-dir <scene> --query sofa [--modality object|area|sound|image]
                                          [--decay-rate R] [--text-model clip|hash]
+    python -m avlmaps_amd.apps.index_map --data-dir <scene> --modality fused [--object NAME]... [--area NAME]... [--sound NAME]...
+                                         [--image PNG] [--object-decay R] [--area-decay R] [--sound-decay R] [--image-decay R]
 
 object (default): the VLMap text query; area: the area map's frame embeddings (area_map/clip_sparse_map.h5df); sound: the sound
 map (audio_video/audio_data_<difficulty>.pkl); image: --image (a PNG) localised at row --image-pose of poses.txt (the model-free
-localiser; upstream uses HLoc).  Prints the heat statistics and the voxel the navigator would go to (argmax of the heat,
-habitat_lang_robot.py:427-430); --save writes the (N,) heat vector as .npy."""
+localiser; upstream uses HLoc); fused: the cross-modal goal, the product of every --object, --area, --sound and --image heat
+(AVLMap.index_goal; at least one of them, decay rates default to the stand-alone queries' 0.1, 0.1, 0.01, 0.01).  Prints the heat statistics and the voxel the navigator would go to (argmax of the heat,
+habitat_lang_robot.py:427-430); --save writes the (N,) heat vector as .npy (float64 for fused)."""
 from __future__ import annotations
 
 import argparse
@@ -17,26 +20,49 @@ import numpy as np
 DEFAULT_DECAY = {"object": 0.01, "area": 0.1, "sound": 0.01, "image": 0.01}
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--data-dir", required=True)
-    ap.add_argument("--query", default=None, help="object, area or sound name (not used by --modality image)")
-    ap.add_argument("--modality", choices=["object", "area", "sound", "image"], default="object")
+    ap.add_argument("--query", default=None, help="object, area or sound name (not used by --modality image and fused)")
+    ap.add_argument("--modality", choices=["object", "area", "sound", "image", "fused"], default="object")
     ap.add_argument("--config", default=None)
     ap.add_argument("--decay-rate", type=float, default=None, help="default: 0.01 (object, sound, image), 0.1 (area)")
     ap.add_argument("--text-model", choices=["clip", "hash"], default="clip",
                     help="clip = OpenAI CLIP on PyTorch-ROCm (as upstream); hash = model-free stand-ins for smoke runs (text towers "
                          "and the audio-text model)")
     ap.add_argument("--categories", default=None, help="comma separated list: preload scores_mat (VLMap.init_categories)")
-    ap.add_argument("--image", default=None, help="query image (PNG) of --modality image")
+    ap.add_argument("--image", default=None, help="query image (PNG) of --modality image and fused")
     ap.add_argument("--image-pose", type=int, default=0, help="row of poses.txt the model-free localiser places the image at")
+    ap.add_argument("--object", action="append", default=[], help="fused: an object name (repeatable)")
+    ap.add_argument("--area", action="append", default=[], help="fused: an area name (repeatable)")
+    ap.add_argument("--sound", action="append", default=[], help="fused: a sound name (repeatable)")
+    ap.add_argument("--object-decay", type=float, default=None, help="fused: decay rate of the object heats (default 0.1)")
+    ap.add_argument("--area-decay", type=float, default=None, help="fused: decay rate of the area heats (default 0.1)")
+    ap.add_argument("--sound-decay", type=float, default=None, help="fused: decay rate of the sound heats (default 0.01)")
+    ap.add_argument("--image-decay", type=float, default=None, help="fused: decay rate of the image heat (default 0.01)")
     ap.add_argument("--save", default=None)
     args = ap.parse_args(argv)
-    if args.modality != "image" and not args.query:
+    if args.modality == "fused":
+        if not (args.object or args.area or args.sound or args.image):
+            ap.error("--modality fused needs at least one of --object, --area, --sound, --image")
+    elif args.object or args.area or args.sound:
+        ap.error("--object, --area and --sound belong to --modality fused")
+    elif args.modality != "image" and not args.query:
         ap.error(f"--modality {args.modality} needs --query")
-    if args.modality == "image" and not args.image:
+    elif args.modality == "image" and not args.image:
         ap.error("--modality image needs --image")
-    decay = DEFAULT_DECAY[args.modality] if args.decay_rate is None else args.decay_rate
+    return args
+
+
+def fused_decay_rates(args) -> dict:
+    """the decay_rates argument of AVLMap.index_goal from the per-flag overrides"""
+    given = {"obj": args.object_decay, "area": args.area_decay, "sound": args.sound_decay, "img": args.image_decay}
+    return {k: v for k, v in given.items() if v is not None}
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    decay = DEFAULT_DECAY.get(args.modality) if args.decay_rate is None else args.decay_rate
 
     from avlmaps_amd import ops
     from avlmaps_amd.apps.common import FixedPoseLocalizer, HashAudioText, HashClip, load_config
@@ -48,12 +74,29 @@ def main(argv=None):
     if not avlmap.load_map(args.data_dir):
         raise SystemExit(1)
     vm = avlmap.vlmap
-    if args.modality == "object":
+    if args.modality == "object" or args.object:
         if hashed:
             vm.clip_feat_dim = vm.grid_feat.shape[1]
             vm.clip_model = HashClip(vm.clip_feat_dim)
         else:
             vm._init_clip()
+    if args.modality == "fused":
+        img = None
+        if args.image:
+            from avlmaps_amd.utils.mapping_utils import load_rgb_png
+            poses = np.loadtxt(vm.pose_path).reshape(-1, 7)
+            avlmap.visual_map.localizer = FixedPoseLocalizer(poses[args.image_pose], vm.base2cam_tf)
+            img = load_rgb_png(args.image)
+        goal = avlmap.index_goal(obj=args.object or None, area=args.area or None, sound=args.sound or None, img=img,
+                                 decay_rates=fused_decay_rates(args))
+        heat = goal.heat
+        what = " * ".join(args.object + args.area + args.sound + ([args.image] if args.image else []))
+        print(f"fused {what!r}: heat>0 on {int((heat > 0).sum())} of {len(heat)} voxels; "
+              f"goal voxel id {goal.voxel} at grid_pos {goal.pos.tolist()} (heat {goal.value:.3f})")
+        if args.save:
+            np.save(args.save, heat)
+        return heat
+    if args.modality == "object":
         cats = None
         if args.categories:
             cats = ["void"] + [c.strip() for c in args.categories.split(",")] + ["void"]   # upstream passes categories[1:-1]

@@ -2,18 +2,26 @@
 setup_scene + move_to (robot/habitat_lang_robot.py:88-104, 432-461) without the simulator.
 
     python -m avlmaps_amd.apps.plan_path --data-dir <scene> --query sofa --start ROW COL [--text-model clip|hash]
+                                        [--area NAME]... [--sound NAME]... [--image PNG]
 
 Loads <scene>/vlmap/vlmaps.h5df (with --text-model hash a missing map is first created with the model-free feature stand-in, as
 apps.create_map --features hash does), builds the obstacle map (Map.generate_obstacle_map), takes the goal from
 Map.get_nearest_pos, plans with Navigator on the GPU and prints one JSON line: the query, the start, the goal and the path, all
-in full-map (row, col) cells."""
+in full-map (row, col) cells.
+
+With --area, --sound or --image the goal is cross-modal (habitat_lang_robot.py:377-430): the cell of
+AVLMap.index_goal(obj=--query, area=.., sound=.., img=..), handed to Navigator.plan_to as it is -- a goal voxel is an occupied
+voxel, and the planner snaps a goal on an obstacle cell to the nearest free cell.  The JSON line then also has "goal_voxel",
+"goal_value" (0.0: the modalities do not overlap anywhere) and "goal_cell", the voxel's own cell; "goal" is that cell clamped into
+the cropped obstacle map, which differs only when the voxel's height is outside --h-min / --h-max and nothing in the band reaches
+that far."""
 from __future__ import annotations
 
 import argparse
 import json
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--data-dir", required=True)
     ap.add_argument("--query", required=True)
@@ -24,21 +32,47 @@ def main(argv=None):
     ap.add_argument("--categories", default=None, help="comma separated category list of get_pos (default: the query and 'other')")
     ap.add_argument("--h-min", type=float, default=0.0)
     ap.add_argument("--h-max", type=float, default=1.5)
-    args = ap.parse_args(argv)
+    ap.add_argument("--area", action="append", default=[], help="cross-modal goal: an area name (repeatable)")
+    ap.add_argument("--sound", action="append", default=[], help="cross-modal goal: a sound name (repeatable)")
+    ap.add_argument("--image", default=None, help="cross-modal goal: a query image (PNG)")
+    ap.add_argument("--image-pose", type=int, default=0, help="row of poses.txt the model-free localiser places the image at")
+    return ap.parse_args(argv)
+
+
+def is_cross_modal(args) -> bool:
+    return bool(args.area or args.sound or args.image)
+
+
+def clamp_cell(cell, rmin, cmin, shape):
+    """the full-map cell moved into the (H, W) crop that starts at (rmin, cmin)"""
+    return [min(max(int(cell[0]), int(rmin)), int(rmin) + int(shape[0]) - 1),
+            min(max(int(cell[1]), int(cmin)), int(cmin) + int(shape[1]) - 1)]
+
+
+def main(argv=None):
+    args = parse_args(argv)
 
     from avlmaps_amd.apps.common import HashClip, load_config
     from avlmaps_amd.map import VLMap
     from avlmaps_amd.navigator import Navigator
     cfg = load_config(args.config)
     hashed = args.text_model == "hash"
-    vm = VLMap(cfg.map_config, data_dir=args.data_dir)
-    if not vm.load_map(args.data_dir):
+    avlmap = None
+    if is_cross_modal(args):
+        from avlmaps_amd.apps.common import HashAudioText
+        from avlmaps_amd.map import AVLMap
+        avlmap = AVLMap(cfg, data_dir=args.data_dir, area_text_model=HashClip(768) if hashed else None,
+                        audio_text_model=HashAudioText() if hashed else None)
+        vm, loader = avlmap.vlmap, avlmap
+    else:
+        vm = loader = VLMap(cfg.map_config, data_dir=args.data_dir)
+    if not loader.load_map(args.data_dir):
         if not hashed:
             raise SystemExit(f"no map under {args.data_dir}: run apps.create_map first")
         from avlmaps_amd.apps import create_map
         create_map.main(["--data-dir", args.data_dir, "--features", "hash", "--feat-dim", "64"]
                         + (["--config", args.config] if args.config else []))
-        if not vm.load_map(args.data_dir):
+        if not loader.load_map(args.data_dir):
             raise SystemExit(1)
     if hashed:
         vm.clip_feat_dim = vm.grid_feat.shape[1]
@@ -49,7 +83,21 @@ def main(argv=None):
     vm.init_categories(cats)
     vm.generate_obstacle_map(args.h_min, args.h_max)
     start = [float(args.start[0]), float(args.start[1])]
-    goal = vm.get_nearest_pos(start, args.query)
+    extra = {}
+    if avlmap is None:
+        goal = vm.get_nearest_pos(start, args.query)
+    else:
+        img = None
+        if args.image:
+            import numpy as np
+            from avlmaps_amd.apps.common import FixedPoseLocalizer
+            from avlmaps_amd.utils.mapping_utils import load_rgb_png
+            poses = np.loadtxt(vm.pose_path).reshape(-1, 7)
+            avlmap.visual_map.localizer = FixedPoseLocalizer(poses[args.image_pose], vm.base2cam_tf)
+            img = load_rgb_png(args.image)
+        g = avlmap.index_goal(obj=args.query, area=args.area or None, sound=args.sound or None, img=img, want_heat=False)
+        goal = clamp_cell(g.cell, vm.rmin, vm.cmin, vm.obstacles_cropped.shape)
+        extra = {"goal_voxel": g.voxel, "goal_value": g.value, "goal_cell": [float(g.cell[0]), float(g.cell[1])]}
     nav = Navigator()
     try:
         nav.build_visgraph(vm.obstacles_cropped, vm.rmin, vm.cmin)
@@ -58,6 +106,7 @@ def main(argv=None):
         nav.close()
     out = {"query": args.query, "start": start, "goal": [float(goal[0]), float(goal[1])],
            "path": [[float(p[0]), float(p[1])] for p in path]}
+    out.update(extra)
     print(json.dumps(out))
     return out
 

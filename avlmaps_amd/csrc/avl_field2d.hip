@@ -27,13 +27,12 @@
 #include <cmath>
 
 #include "avl_common.h"
+#include "avl_field_math.h"
 
 namespace avl {
 
 constexpr int kFieldTile = 16;                    // tile edge in cells; the workgroup is kFieldTile^2 = 256 threads
 constexpr int kFieldThreads = kFieldTile * kFieldTile;
-
-__device__ __forceinline__ double clip01(double v) { return v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v); }
 
 // squared distance from (r, c) to the nearest cell of the tile [r0, r1] x [c0, c1]
 __device__ __forceinline__ long long tile_d2(int r, int c, int r0, int r1, int c0, int c1) {
@@ -182,14 +181,14 @@ __global__ __launch_bounds__(256) void field_lift_kernel(const void* __restrict_
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
         const int r = pos[3 * i], c = pos[3 * i + 1], h = pos[3 * i + 2];
         float v = 0.0f;
-        if (r >= 0 && r < gs && c >= 0 && c < gs && h >= 0 && h < vh) {
+        if (in_grid(r, c, h, gs, vh)) {
             const size_t cell = (size_t)r * gs + c;
             if (F64) {
                 const double* mm = static_cast<const double*>(minmax);
-                v = (float)__ddiv_rn(static_cast<const double*>(field)[cell] - mm[0], mm[1] - mm[0]);
+                v = lift_norm(static_cast<const double*>(field)[cell], mm[0], mm[1]);
             } else {
                 const float* mm = static_cast<const float*>(minmax);
-                v = __fdiv_rn(static_cast<const float*>(field)[cell] - mm[0], mm[1] - mm[0]);
+                v = lift_norm(static_cast<const float*>(field)[cell], mm[0], mm[1]);
             }
         }
         heat[i] = v;
@@ -214,8 +213,7 @@ __global__ __launch_bounds__(256) void field_normalize_kernel(const void* __rest
 __global__ __launch_bounds__(256) void planar_decay_kernel(const int32_t* __restrict__ pos, int64_t N, double row, double col, double decay,
                                                            double* __restrict__ sim) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
-        const double dx = (double)pos[3 * i] - row, dy = (double)pos[3 * i + 1] - col;
-        sim[i] = clip01(1.0 - decay * sqrt(dx * dx + dy * dy));
+        sim[i] = planar_cone(1.0, decay, pos[3 * i], pos[3 * i + 1], row, col);
     }
 }
 

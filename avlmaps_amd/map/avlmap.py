@@ -100,7 +100,12 @@ class AVLMap:
             mask = self.vlmap.index_map(object_name, with_init_cat=True)
             return get_heatmap_from_mask_3d(self.vlmap.grid_pos, mask, cell_size=cs, decay_rate=decay_rate)
         # query -> argmax -> mask -> heat without leaving the GPU: only the (N,) float32 heat comes back
+        return self._object_heat(object_name, decay_rate).numpy()
+
+    def _object_heat(self, object_name: str, decay_rate: float):
+        """index_object's heat while it is still on the device: (N,) float32.  ValueError when no voxel matches."""
         from .. import ops
+        cs = cfg_get(cfg_get(self.config, "params"), "cs")
         vm = self.vlmap
         q = vm._text_feats([object_name])            # cached per string: the text tower costs more than the kernels below
         feat = vm._device_feat()
@@ -108,13 +113,13 @@ class AVLMap:
             mask = vm._score(q, want_scores=False)[1] == 0
             if not mask.any():
                 raise ValueError("attempt to get argmin of an empty sequence")
-            return vm.heatmap_from_mask(mask.astype(np.uint8), cs, decay_rate).numpy()
+            return vm.heatmap_from_mask(mask.astype(np.uint8), cs, decay_rate)
         _, am, _ = ops.sim_scores(feat, q, want_scores=False, want_argmax=True, precision=vm._sim_precision)
         mask = ops.mask_from_argmax(am, 0)
         heat = vm.heatmap_from_mask(mask, cs, decay_rate)
         if vm.grid_pos.shape[0] and ops.argmax_f32(heat)[1] < 1.0:      # a target voxel has heat exactly 1
             raise ValueError("attempt to get argmin of an empty sequence")   # what np.argmin raises upstream (no voxel matched)
-        return heat.numpy()
+        return heat
 
     # ------------------------------------------------------------------ area
     def _require_area(self):
@@ -155,11 +160,13 @@ class AVLMap:
         gf = self._area_field(area_name, decay_rate)
         return self._lift(gf, f"area {area_name!r}")
 
+    def _vh(self) -> int:
+        vm = self.vlmap
+        return vm.occupied_ids.shape[2] if vm.occupied_ids is not None else np.iinfo(np.int32).max
+
     def _lift(self, gf, what):
         from .. import ops
-        vm = self.vlmap
-        vh = vm.occupied_ids.shape[2] if vm.occupied_ids is not None else np.iinfo(np.int32).max
-        heat = ops.field_lift(gf, vm._device_pos(), vh)
+        heat = ops.field_lift(gf, self.vlmap._device_pos(), self._vh())
         self._check_bounds(gf, what)
         return heat.numpy()
 
@@ -207,6 +214,11 @@ class AVLMap:
     def index_image(self, image: np.ndarray, query_cam_intrinsics: np.ndarray = None, decay_rate: float = 0.01) -> np.ndarray:
         """(N,) float64.  Reference: avlmap.py:146-163."""
         from .. import ops
+        row, col = self._image_cell(image, query_cam_intrinsics)
+        return ops.planar_decay(self.vlmap._device_pos(), row, col, decay_rate).numpy()
+
+    def _image_cell(self, image, query_cam_intrinsics=None):
+        """(row, col) of the full map where the query image was taken (avlmap.py:146-153)"""
         if self.visual_map.localizer is None:
             raise MissingSubMap("AVLMap.index_image needs an image localiser (upstream: HLoc): AVLMap(..., localizer=...) or "
                                 "visual_map.localizer = ...")
@@ -216,4 +228,105 @@ class AVLMap:
         _, query_base_tf = res
         self.dataloader.from_habitat_tf(query_base_tf)
         row, col, _ = self.dataloader.to_full_map_pose()
-        return ops.planar_decay(self.vlmap._device_pos(), row, col, decay_rate).numpy()
+        return int(row), int(col)
+
+    # ------------------------------------------------------------------ cross-modal goals
+    DEFAULT_DECAY = {"obj": 0.1, "area": 0.1, "sound": 0.01, "img": 0.01}     # those of the stand-alone queries
+
+    @staticmethod
+    def _goal_specs(obj=None, area=None, sound=None, img=None, extra=(), decay_rates=None):
+        """The ordered factor list of a goal: [(modality, what, decay_rate)], objects, areas, sounds, image, extras, each in the
+        order given (the float64 product depends on it).  obj / area / sound: a name, a (name, decay_rate) pair, or a list of those."""
+        rates = dict(AVLMap.DEFAULT_DECAY)
+        for k, v in (decay_rates or {}).items():
+            if k not in rates:
+                raise ValueError(f"decay_rates: unknown modality {k!r} (one of {sorted(rates)})")
+            rates[k] = float(v)
+
+        def is_pair(x):
+            return (isinstance(x, tuple) and len(x) == 2 and isinstance(x[0], str)
+                    and isinstance(x[1], (int, float, np.integer, np.floating)) and not isinstance(x[1], bool))
+
+        def one(kind, x):
+            if isinstance(x, str):
+                return (kind, x, rates[kind])
+            if is_pair(x):
+                return (kind, x[0], float(x[1]))
+            raise TypeError(f"{kind}: expected a name or a (name, decay_rate) pair, got {x!r}")
+
+        specs = []
+        for kind, arg in (("obj", obj), ("area", area), ("sound", sound)):
+            if arg is None:
+                continue
+            items = [arg] if isinstance(arg, str) or is_pair(arg) else list(arg)
+            specs += [one(kind, x) for x in items]
+        if img is not None:
+            specs.append(("img", img, rates["img"]))
+        specs += [("extra", h, None) for h in extra]
+        return specs
+
+    def _goal_terms(self, specs, intr_mat=None):
+        """ops.GoalTerms of a spec list, built from what the stand-alone queries compute, without their host copies"""
+        from .. import ops
+        terms = []
+        for kind, what, rate in specs:
+            if kind == "obj":
+                terms.append(ops.GoalTerm.dense(self._object_heat(what, rate)))
+            elif kind in ("area", "sound"):
+                gf = self._area_field(what, rate) if kind == "area" else self._sound_field(what, rate)
+                self._check_bounds(gf, f"{kind} {what!r}")
+                terms.append(ops.GoalTerm.field(gf, self._vh()))
+            elif kind == "img":
+                row, col = self._image_cell(what, intr_mat)
+                terms.append(ops.GoalTerm.cones(np.array([[row, col]], dtype=np.int32), np.ones(1), rate))
+            else:
+                terms.append(ops.GoalTerm.dense(what))
+        return terms
+
+    def index_goal(self, obj=None, area=None, sound=None, img=None, intr_mat=None, extra=(), decay_rates=None,
+                   want_heat: bool = True) -> "Goal":
+        """The cross-modal goal of habitat_lang_robot.py:377-430: the float64 product of the per-voxel heats of every modality
+        given, and the first voxel of its maximum, in one pass on the GPU (csrc/avl_goal.hip).
+
+        obj, area, sound: a name, a (name, decay_rate) pair, or a list of those (two objects multiply); img (with intr_mat) as in
+        index_image; extra: a sequence of caller-made (N,) heats.  decay_rates={"obj": .., "area": .., "sound": .., "img": ..}
+        overrides the stand-alone queries' defaults per modality.  The factors are multiplied in a fixed order: objects, areas,
+        sounds, image, extras.  Every factor is the stand-alone query's value bit for bit, so
+        goal.heat == float64(index_object(..)) * float64(index_sound(..)) * ... exactly.
+
+        Raises what the stand-alone queries raise; ValueError without any term or on an empty map.  Modalities that do not overlap
+        give a product that is 0 everywhere: the goal is then voxel 0 with value 0.0, as np.argmax returns it -- check `value`."""
+        specs = self._goal_specs(obj, area, sound, img, extra, decay_rates)
+        if not specs:
+            raise ValueError("index_goal needs at least one of obj, area, sound, img, extra")
+        from .. import ops
+        if self.vlmap.grid_pos is None or len(self.vlmap.grid_pos) == 0:
+            raise ValueError("an empty map has no goal")
+        terms = self._goal_terms(specs, intr_mat)
+        res = ops.goal_fuse(terms, self.vlmap._device_pos(), want_heat=want_heat)
+        return Goal(res.heat.numpy() if want_heat else None, res.index, res.value, res.pos)
+
+    def get_max_pos_3d(self, heat: np.ndarray) -> np.ndarray:
+        """grid_pos of the first maximum of a host (N,) float32 / float64 heat.  Reference: habitat_lang_robot.py:427-430."""
+        from .. import ops
+        heat = np.asarray(heat)
+        if heat.dtype not in (np.float32, np.float64):
+            raise TypeError(f"heat must be float32 or float64, got {heat.dtype}")
+        if heat.shape != (len(self.vlmap.grid_pos),):
+            raise ValueError(f"heat must be ({len(self.vlmap.grid_pos)},), got {heat.shape}")
+        return ops.goal_fuse([ops.GoalTerm.dense(heat)], self.vlmap._device_pos(), want_heat=False).pos
+
+
+class Goal:
+    """AVLMap.index_goal's answer: heat (N,) float64 (None with want_heat=False), voxel = the first index of its maximum, value =
+    the product there (0.0: the modalities do not overlap), pos = grid_pos[voxel] (row, col, height), cell = pos[:2], what
+    Navigator.plan_to takes."""
+    __slots__ = ("heat", "voxel", "value", "pos")
+
+    def __init__(self, heat, voxel, value, pos):
+        self.heat, self.voxel, self.value = heat, int(voxel), float(value)
+        self.pos = np.asarray(pos, dtype=np.int32)
+
+    @property
+    def cell(self) -> np.ndarray:
+        return self.pos[:2]

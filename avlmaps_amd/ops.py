@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .device import DeviceArray, as_device, _is_torch
+from .device import DeviceArray, DeviceView, as_device, _is_torch
 
 PRECISION = {"auto": _lib.SIM_AUTO, "exact": _lib.SIM_EXACT, "split_f16": _lib.SIM_SPLIT_F16, "exact_valu": _lib.SIM_EXACT_VALU,
              "prepared": _lib.SIM_PREPARED}
@@ -1038,6 +1038,117 @@ def planar_decay(grid_pos, row, col, decay_rate=0.01, stream=None):
     if isinstance(grid_pos, np.ndarray):
         _lib.check(lib.avl_stream_sync(stream), "avl_stream_sync")
     return sim
+
+
+# ---------------------------------------------------------------------------------------- cross-modal goals
+GOAL_DENSE_F32, GOAL_DENSE_F64, GOAL_FIELD_F32, GOAL_FIELD_F64, GOAL_CONES = 0, 1, 2, 3, 4
+GOAL_MAX_TERMS = 8
+
+
+def _on_device(x):
+    return isinstance(x, (DeviceArray, DeviceView)) or _is_torch(x)
+
+
+class _GoalTermC(C.Structure):
+    """avl_goal_term of include/avlmaps_hip.h"""
+    _fields_ = [("kind", C.c_int32), ("gs", C.c_int32), ("vh", C.c_int32), ("reserved", C.c_int32), ("d_data", C.c_void_p),
+                ("d_aux", C.c_void_p), ("n_points", C.c_int64), ("decay", C.c_double)]
+
+
+class GoalTerm:
+    """One factor of a fused goal (csrc/avl_goal.hip): build it with dense(), field() or cones().  `n` is the number of voxels a
+    dense term covers (None for the other kinds); `keep` holds the device buffers the term points into."""
+
+    def __init__(self, kind, data=0, aux=0, gs=0, vh=0, n_points=0, decay=0.0, n=None, keep=()):
+        self.kind, self.data, self.aux, self.gs, self.vh = int(kind), data, aux, int(gs), int(vh)
+        self.n_points, self.decay, self.n, self.keep = int(n_points), float(decay), n, keep
+
+    @classmethod
+    def dense(cls, heat, stream=None):
+        """an (N,) float32 or float64 heat: a device array (DeviceArray, torch CUDA tensor) is used in place, a host array is
+        uploaded in its own type (anything but float32 / float64 is converted to float64 first)"""
+        if isinstance(heat, (DeviceArray, DeviceView)):
+            dt = heat.dtype
+        elif _is_torch(heat):
+            dt = np.dtype(str(heat.dtype).split(".")[-1])
+        else:
+            heat = np.asarray(heat)
+            dt = heat.dtype if heat.dtype in (np.float32, np.float64) else np.dtype(np.float64)
+        if dt not in (np.float32, np.float64):
+            raise TypeError(f"a dense goal term is float32 or float64, got {dt}")
+        ptr, shape, keep = as_device(heat, dt, stream)
+        if len(shape) != 1:
+            raise ValueError(f"a dense goal term is an (N,) vector, got shape {tuple(shape)}")
+        return cls(GOAL_DENSE_F64 if dt == np.float64 else GOAL_DENSE_F32, data=ptr, n=int(shape[0]), keep=(keep,))
+
+    @classmethod
+    def field(cls, gf: "GoalField", vh):
+        """the lift of a GoalField (area_field / sound_field) to the voxels of a (gs, gs, vh) grid: field_lift's value"""
+        vh = int(vh)
+        if vh < 0:
+            raise ValueError(f"vh must be >= 0, got {vh}")
+        return cls(GOAL_FIELD_F64 if gf.is_f64 else GOAL_FIELD_F32, data=gf.field.ptr, aux=gf.minmax.ptr, gs=gf.gs, vh=vh, keep=(gf,))
+
+    @classmethod
+    def cones(cls, cells, peaks, decay_rate, stream=None):
+        """max over the points of clip(peak - decay_rate * ||(row, col) - cell||, 0, 1): cells (P, 2) int32, peaks (P,) float64
+        finite, P >= 1 (host or device arrays).  One point with peak 1 is planar_decay."""
+        decay = _check_decay(decay_rate)
+        if not _on_device(peaks):
+            peaks = np.ascontiguousarray(peaks, dtype=np.float64).reshape(-1)
+            if not np.all(np.isfinite(peaks)):
+                raise ValueError("cone peaks must be finite")
+        if not _on_device(cells):
+            cells = np.ascontiguousarray(cells, dtype=np.int32).reshape(-1, 2)
+        P = int(peaks.shape[0])
+        if P < 1 or tuple(cells.shape) != (P, 2):
+            raise ValueError(f"cones need P >= 1 points: cells (P, 2) and peaks (P,), got {tuple(cells.shape)} and {tuple(peaks.shape)}")
+        cp, _, k1 = as_device(cells, np.int32, stream)
+        pp, _, k2 = as_device(peaks, np.float64, stream)
+        return cls(GOAL_CONES, data=cp, aux=pp, n_points=P, decay=decay, keep=(k1, k2))
+
+    def _c(self):
+        return _GoalTermC(self.kind, self.gs, self.vh, 0, self.data or None, self.aux or None, self.n_points, self.decay)
+
+
+class GoalResult:
+    """goal_fuse's result: heat (N,) float64 DeviceArray or None, index of the first maximum, the product there, grid_pos there"""
+    __slots__ = ("heat", "index", "value", "pos")
+
+    def __init__(self, heat, index, value, pos):
+        self.heat, self.index, self.value, self.pos = heat, index, value, pos
+
+
+def goal_terms_array(terms):
+    """the C array of avl_goal_term that avl_goal_fuse reads (host side only)"""
+    terms = list(terms)
+    if not 1 <= len(terms) <= GOAL_MAX_TERMS:
+        raise ValueError(f"a goal is the product of 1 to {GOAL_MAX_TERMS} terms, got {len(terms)}")
+    return (_GoalTermC * len(terms))(*[t._c() for t in terms])
+
+
+def goal_fuse(terms, grid_pos, want_heat=True, stream=None) -> GoalResult:
+    """habitat_lang_robot.py:377-430: heat = ((t0 * t1) * t2) ... in float64 over the voxels, and the first voxel of its maximum
+    (np.argmax), in one pass (csrc/avl_goal.hip).  terms: 1 to 8 GoalTerms, multiplied in the order given; grid_pos (N, 3) int32
+    host or device.  Only index / value / pos come back to the host; want_heat=False stores nothing of size N."""
+    lib = _lib.load()
+    arr = goal_terms_array(terms)
+    _lib.require_gpu()
+    gp, gshape, keep = as_device(grid_pos, np.int32, stream)
+    if len(gshape) != 2 or gshape[1] != 3:
+        raise ValueError(f"grid_pos must be (N, 3), got {tuple(gshape)}")
+    N = int(gshape[0])
+    for t in terms:
+        if t.n is not None and t.n != N:
+            raise ValueError(f"a dense term has {t.n} values, the map {N} voxels")
+    if N == 0:
+        raise ValueError("an empty map has no goal")
+    heat = DeviceArray((N,), np.float64) if want_heat else None
+    idx, val = C.c_int64(), C.c_double()
+    pos = np.empty((3,), dtype=np.int32)
+    _lib.check(lib.avl_goal_fuse(arr, len(arr), gp, N, heat.ptr if want_heat else None, C.byref(idx), C.byref(val), pos.ctypes.data,
+                                 stream), "avl_goal_fuse")
+    return GoalResult(heat, int(idx.value), float(val.value), pos)
 
 
 # ---------------------------------------------------------------------------------------- visibility-graph navigation

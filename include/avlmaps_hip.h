@@ -673,6 +673,47 @@ AVL_API int avl_planar_decay(const int32_t* d_grid_pos, int64_t N, int64_t row, 
                              void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * (7b) cross-modal goals: the product of per-voxel heats and its first maximum in one pass (csrc/avl_goal.hip)
+ *     replaces  avlmaps/robot/habitat_lang_robot.py:377-430 as generated robot code uses them: get_map_3d(..) * get_major_map_3d(..)
+ *               * ... on (N,) host arrays (:377-425), then get_max_pos_3d = grid_pos[np.argmax(heat)] (:427-430)
+ *     A term is one factor of the product, evaluated at voxel i with grid_pos[i] = (r, c, h) and widened to float64 exactly:
+ *       AVL_GOAL_DENSE_F32 / _F64  d_data[i], (N,) float32 / float64: the object heat, or any heat the caller made
+ *       AVL_GOAL_FIELD_F32 / _F64  the value avl_field_lift gives this voxel, bit for bit: d_data the (gs, gs) field, d_aux its
+ *                                  (2,) [min, max], both float32 / float64 (avl_field_sound / avl_field_area); 0 outside (gs, gs, vh)
+ *       AVL_GOAL_CONES             max over the n_points points j of clip(peak_j - decay * ||(r, c) - cell_j||, 0, 1) in float64:
+ *                                  d_data (n_points, 2) int32 cells, d_aux (n_points,) float64 peaks.  One point with peak 1 is
+ *                                  avl_planar_decay bit for bit (avlmap.py:154-161); several are get_distribution_map_3d
+ *                                  (habitat_lang_robot.py:207-227, distances in cells)
+ *     heat[i] = ((t_0 * t_1) * t_2) * ... in float64, left to right (the order NumPy multiplies the arrays in).
+ * ------------------------------------------------------------------------------------------------ */
+enum {
+    AVL_GOAL_DENSE_F32 = 0,
+    AVL_GOAL_DENSE_F64 = 1,
+    AVL_GOAL_FIELD_F32 = 2,
+    AVL_GOAL_FIELD_F64 = 3,
+    AVL_GOAL_CONES = 4
+};
+#define AVL_GOAL_MAX_TERMS 8
+typedef struct avl_goal_term {
+    int32_t kind;         /* AVL_GOAL_* */
+    int32_t gs;           /* field: the grid size, >= 1 */
+    int32_t vh;           /* field: the grid height, >= 0 */
+    int32_t reserved;     /* 0 */
+    const void* d_data;   /* dense: the values; field: the field; cones: the cells */
+    const void* d_aux;    /* field: [min, max]; cones: the peaks; dense: unused */
+    int64_t n_points;     /* cones: the number of points, >= 1 */
+    double decay;         /* cones: the decay per cell, finite and >= 0 */
+} avl_goal_term;
+/* h_terms: K terms on the host, 1 <= K <= AVL_GOAL_MAX_TERMS.  d_out (N,) float64 receives the product, or NULL: then nothing
+ * of size N is written.  h_index / h_value / h_pos3 (each may be NULL) receive the first index of the maximum product, the product
+ * there and grid_pos of that voxel: what np.argmax and habitat_lang_robot.py:427-430 return.  The order is (product descending,
+ * index ascending); a NaN product never wins, and when every product is NaN the call fails with AVL_ERR_INVALID.  With any of the
+ * three host outputs the call is synchronous and N == 0 is AVL_ERR_INVALID (there is no goal); with none of them it only enqueues
+ * the product.  Arguments are checked before any device work. */
+AVL_API int avl_goal_fuse(const avl_goal_term* h_terms, int K, const int32_t* d_grid_pos, int64_t N, double* d_out, int64_t* h_index,
+                          double* h_value, int32_t* h_pos3, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * (8) visibility-graph navigation on the 2-D obstacle map (csrc/avl_nav.hip)
  *     The obstacle map is (H, W) uint8, nonzero = free, 0 = obstacle (Map.obstacles_cropped).  Obstacle pixel (r, c) is the point
  *     (r, c); the obstacle set is the union of the segments between 8-adjacent obstacle pixels and the convex hulls of the obstacle
