@@ -11,6 +11,7 @@ _PKG = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("AVLMAPS_HIP_LIB") or _PKG / "lib" / "libavlmaps_hip.so")       # (an empty variable = the stock library)
 
 AVL_OK = 0
+MORPH_DILATE, MORPH_ERODE, MORPH_CROSS, MORPH_BOX = 0, 1, 0, 1
 SIM_AUTO, SIM_EXACT, SIM_SPLIT_F16, SIM_EXACT_VALU, SIM_PREPARED, SIM_PREPARED24 = 0, 1, 2, 3, 4, 5
 
 
@@ -150,6 +151,14 @@ _SIGS = {
     "avl_nav_export_visibility": (C.c_int, [_vp, _vp, _vp]),
     "avl_nav_plan": (C.c_int, [_vp, _f64, _f64, _f64, _f64, C.POINTER(_f64), _vp, C.POINTER(C.c_int), C.c_int, _vp]),
     "avl_nav_last_plan": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "avl_morph_binary": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "avl_gauss2d_f64": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _f64, _vp, _vp]),
+    "avl_resize2x_up_f64": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "avl_resize2x_down_f64": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "avl_dilate_map_work_bytes": (C.c_int, [C.c_int, C.c_int, C.POINTER(_sz)]),
+    "avl_dilate_map": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _f64, _vp, _vp, _vp, _sz, _vp]),
+    "avl_mask_foreground_work_bytes": (C.c_int, [C.c_int, C.c_int, C.POINTER(_sz)]),
+    "avl_mask_foreground": (C.c_int, [_vp, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _sz, _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -1,0 +1,72 @@
+"""Write a saved VLMap's obstacle map and its customised version as images.  Counterpart of the reference's
+application/generate_obstacle_map.py (:19-33), with PNG files where upstream opens cv2 windows.
+
+    python -m avlmaps_amd.apps.generate_obstacle_map --data-dir <scene> [--out-dir DIR] [--text-model clip|hash]
+                                                     [--potential-obstacles a,b,c --obstacles a,b] [--dilate-iter N] [--gaussian-sigma S]
+
+Loads <scene>/vlmap/vlmaps.h5df, builds the obstacle map from the occupancy between --h-min and --h-max
+(Map.generate_obstacle_map), then keeps only the obstacles of the classes --obstacles and smooths the map
+(VLMap.customize_obstacle_map; the class lists and the smoothing parameters default to the map config's).  Writes obstacles.png
+and obstacles_customized.png (white = free, the cropped maps) under --out-dir (default <scene>/vlmap) and prints one JSON line with
+the crop and the number of obstacle cells of both maps."""
+from __future__ import annotations
+
+import argparse
+import json
+from pathlib import Path
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--data-dir", required=True)
+    ap.add_argument("--out-dir", default=None)
+    ap.add_argument("--config", default=None)
+    ap.add_argument("--text-model", choices=["clip", "hash"], default="clip",
+                    help="clip = OpenAI CLIP on PyTorch-ROCm (as upstream); hash = model-free stand-in for smoke runs")
+    ap.add_argument("--h-min", type=float, default=0.0)
+    ap.add_argument("--h-max", type=float, default=1.5)
+    ap.add_argument("--potential-obstacles", default=None, help="comma separated class list the voxels are scored against")
+    ap.add_argument("--obstacles", default=None, help="comma separated classes (of --potential-obstacles) that stay obstacles")
+    ap.add_argument("--dilate-iter", type=int, default=None)
+    ap.add_argument("--gaussian-sigma", type=float, default=None)
+    return ap.parse_args(argv)
+
+
+def save_mask_png(path, mask) -> None:
+    """bool (H, W) -> 8-bit grey PNG, True = 255 (what upstream shows: obs_map.astype(np.uint8) * 255)"""
+    import numpy as np
+    from PIL import Image
+    Image.fromarray(np.asarray(mask).astype(np.uint8) * 255).save(str(path))
+
+
+def main(argv=None):
+    args = parse_args(argv)
+
+    from avlmaps_amd.apps.common import HashClip, load_config
+    from avlmaps_amd.apps.plan_path import obstacle_overrides
+    from avlmaps_amd.map import VLMap
+    cfg = load_config(args.config, overrides={f"map_config.{k}": v for k, v in obstacle_overrides(args).items()})
+    vm = VLMap(cfg.map_config, data_dir=args.data_dir)
+    if not vm.load_map(args.data_dir):
+        raise SystemExit(f"no map under {args.data_dir}: run apps.create_map first")
+    if args.text_model == "hash":
+        vm.clip_feat_dim = vm.grid_feat.shape[1]
+        vm.clip_model = HashClip(vm.clip_feat_dim)
+    else:
+        vm._init_clip()
+    vm.generate_obstacle_map(args.h_min, args.h_max)
+    vm.customize_obstacle_map(cfg.map_config.potential_obstacle_names, cfg.map_config.obstacle_names)
+    raw, custom = vm.get_obstacle_cropped(), vm.get_customized_obstacle_cropped()
+    out_dir = Path(args.out_dir) if args.out_dir else Path(args.data_dir) / "vlmap"
+    out_dir.mkdir(parents=True, exist_ok=True)
+    save_mask_png(out_dir / "obstacles.png", raw)
+    save_mask_png(out_dir / "obstacles_customized.png", custom)
+    out = {"crop": [int(vm.rmin), int(vm.rmax), int(vm.cmin), int(vm.cmax)], "shape": [int(raw.shape[0]), int(raw.shape[1])],
+           "obstacle_cells": int((raw == 0).sum()), "customized_obstacle_cells": int((custom == 0).sum()),
+           "files": [str(out_dir / "obstacles.png"), str(out_dir / "obstacles_customized.png")]}
+    print(json.dumps(out))
+    return out
+
+
+if __name__ == "__main__":
+    main()

@@ -3,6 +3,8 @@ setup_scene + move_to (robot/habitat_lang_robot.py:88-104, 432-461) without the 
 
     python -m avlmaps_amd.apps.plan_path --data-dir <scene> --query sofa --start ROW COL [--text-model clip|hash]
                                         [--area NAME]... [--sound NAME]... [--image PNG]
+                                        [--customize-obstacles [--potential-obstacles a,b,c --obstacles a,b]
+                                         [--dilate-iter N] [--gaussian-sigma S]]
 
 Loads <scene>/vlmap/vlmaps.h5df (with --text-model hash a missing map is first created with the model-free feature stand-in, as
 apps.create_map --features hash does), builds the obstacle map (Map.generate_obstacle_map), takes the goal from
@@ -14,7 +16,12 @@ AVLMap.index_goal(obj=--query, area=.., sound=.., img=..), handed to Navigator.p
 voxel, and the planner snaps a goal on an obstacle cell to the nearest free cell.  The JSON line then also has "goal_voxel",
 "goal_value" (0.0: the modalities do not overlap anywhere) and "goal_cell", the voxel's own cell; "goal" is that cell clamped into
 the cropped obstacle map, which differs only when the voxel's height is outside --h-min / --h-max and nothing in the band reaches
-that far."""
+that far.
+
+With --customize-obstacles the path is planned on Map.get_customized_obstacle_cropped() as upstream's robot does
+(habitat_lang_robot.py:89-104): VLMap.customize_obstacle_map keeps only the obstacles whose class is one of --obstacles among
+--potential-obstacles and smooths the map (Map._dilate_map with --dilate-iter and --gaussian-sigma).  The four values default to
+the map config's (config/map_config/vlmaps.yaml:14-15 upstream)."""
 from __future__ import annotations
 
 import argparse
@@ -36,7 +43,26 @@ def parse_args(argv=None):
     ap.add_argument("--sound", action="append", default=[], help="cross-modal goal: a sound name (repeatable)")
     ap.add_argument("--image", default=None, help="cross-modal goal: a query image (PNG)")
     ap.add_argument("--image-pose", type=int, default=0, help="row of poses.txt the model-free localiser places the image at")
-    return ap.parse_args(argv)
+    ap.add_argument("--customize-obstacles", action="store_true",
+                    help="plan on the customised obstacle map (VLMap.customize_obstacle_map) instead of the raw one")
+    ap.add_argument("--potential-obstacles", default=None, help="comma separated class list the voxels are scored against")
+    ap.add_argument("--obstacles", default=None, help="comma separated classes (of --potential-obstacles) that stay obstacles")
+    ap.add_argument("--dilate-iter", type=int, default=None)
+    ap.add_argument("--gaussian-sigma", type=float, default=None)
+    args = ap.parse_args(argv)
+    if not args.customize_obstacles and any(v is not None for v in (args.potential_obstacles, args.obstacles, args.dilate_iter,
+                                                                    args.gaussian_sigma)):
+        ap.error("--potential-obstacles, --obstacles, --dilate-iter and --gaussian-sigma belong to --customize-obstacles")
+    return args
+
+
+def obstacle_overrides(args) -> dict:
+    """the map_config entries VLMap.customize_obstacle_map reads, for the flags that were given"""
+    names = lambda v: [c.strip() for c in v.split(",") if c.strip()]       # noqa: E731
+    given = {"potential_obstacle_names": None if args.potential_obstacles is None else names(args.potential_obstacles),
+             "obstacle_names": None if args.obstacles is None else names(args.obstacles),
+             "dilate_iter": args.dilate_iter, "gaussian_sigma": args.gaussian_sigma}
+    return {k: v for k, v in given.items() if v is not None}
 
 
 def is_cross_modal(args) -> bool:
@@ -55,7 +81,7 @@ def main(argv=None):
     from avlmaps_amd.apps.common import HashClip, load_config
     from avlmaps_amd.map import VLMap
     from avlmaps_amd.navigator import Navigator
-    cfg = load_config(args.config)
+    cfg = load_config(args.config, overrides={f"map_config.{k}": v for k, v in obstacle_overrides(args).items()})
     hashed = args.text_model == "hash"
     avlmap = None
     if is_cross_modal(args):
@@ -82,6 +108,10 @@ def main(argv=None):
     cats = [c.strip() for c in args.categories.split(",")] if args.categories else [args.query, "other"]
     vm.init_categories(cats)
     vm.generate_obstacle_map(args.h_min, args.h_max)
+    obstacles = vm.get_obstacle_cropped()
+    if args.customize_obstacles:
+        vm.customize_obstacle_map(cfg.map_config.potential_obstacle_names, cfg.map_config.obstacle_names)
+        obstacles = vm.get_customized_obstacle_cropped()
     start = [float(args.start[0]), float(args.start[1])]
     extra = {}
     if avlmap is None:
@@ -100,7 +130,7 @@ def main(argv=None):
         extra = {"goal_voxel": g.voxel, "goal_value": g.value, "goal_cell": [float(g.cell[0]), float(g.cell[1])]}
     nav = Navigator()
     try:
-        nav.build_visgraph(vm.obstacles_cropped, vm.rmin, vm.cmin)
+        nav.build_visgraph(obstacles, vm.rmin, vm.cmin)
         path = nav.plan_to(start, goal)
     finally:
         nav.close()

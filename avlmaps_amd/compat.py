@@ -13,6 +13,7 @@ so `from avlmaps.utils.clip_utils import get_lseg_score` in avlmaps/map/vlmap.py
   avlmaps.utils.visualize_utils.pool_3d_label_to_2d      (visualize_utils.py:77-83)
   avlmaps.map.vlmap_builder.VLMapBuilder.create_mobile_base_map (vlmap_builder.py:54-185) -> builder kernels
   avlmaps.map.map.Map.generate_obstacle_map / generate_rgb_topdown_map (map.py:79-95, :106-113) -> top-down scatter kernels
+  avlmaps.map.map.Map._dilate_map                  (map.py:169-181)          -> 2-D morphology kernels (avl_dilate_map)
   avlmaps.robot.habitat_lang_robot.HabitatLanguageRobot.get_vl_distribution_map_3d (habitat_lang_robot.py:242-265) -> heat kernels
       (only if that module is already imported -- it needs habitat_sim -- and only for a robot whose map holds grid_pos: the
       navigator's own decay loop never calls get_heatmap_from_mask_3d; upstream it indexes a Python list -- global_pc comes
@@ -72,7 +73,14 @@ def _map_adapters():
         assert self.grid_rgb is not None, "map not loaded"
         assert self.grid_pos is not None
         return ops.rgb_topdown(self.grid_pos, self.grid_rgb, self.gs)
-    return dict(generate_obstacle_map=generate_obstacle_map, generate_rgb_topdown_map=generate_rgb_topdown_map)
+
+    def _dilate_map(binary_map, dilate_iter: int = 0, gaussian_sigma: float = 1.0):
+        """avlmaps.map.map.Map._dilate_map on avl_dilate_map (no cv2.resize, no SciPy): the same (h, w) float64 image"""
+        import numpy as np
+        from . import ops
+        return ops.dilate_map(np.asarray(binary_map) != 0, dilate_iter, gaussian_sigma, want_zero=False)[0]
+    return dict(generate_obstacle_map=generate_obstacle_map, generate_rgb_topdown_map=generate_rgb_topdown_map,
+                _dilate_map=staticmethod(_dilate_map))
 
 
 def _navigator_adapter(module):

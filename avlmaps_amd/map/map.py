@@ -97,18 +97,20 @@ class Map:
     def init_categories(self, categories: List[str]) -> np.ndarray:
         return NotImplementedError
 
+    def get_obstacle_cropped(self) -> np.ndarray:
+        """Reference: map.py:159-160."""
+        return self.obstacles_cropped
+
+    def get_customized_obstacle_cropped(self) -> np.ndarray:
+        """the map VLMap.customize_obstacle_map left behind.  Reference: map.py:162-163."""
+        return self.obstacles_new_cropped
+
     @staticmethod
     def _dilate_map(binary_map: np.ndarray, dilate_iter: int = 0, gaussian_sigma: float = 1.0):
-        """2x bilinear upsample -> gaussian -> threshold -> dilation -> downsample.  Reference: map.py:169-181.
-        Navigator-side image processing (not on the accelerated path); needs OpenCV exactly like upstream."""
-        import cv2
-        from scipy.ndimage import binary_dilation, gaussian_filter
-        h, w = binary_map.shape
-        m = cv2.resize(binary_map.astype(float), (w * 2, h * 2))
-        m = gaussian_filter(m.astype(float), sigma=gaussian_sigma, truncate=3)
-        m = (m > 0.5).astype(np.uint8)
-        m = binary_dilation(m, structure=np.ones((3, 3)), iterations=dilate_iter * 2)
-        return cv2.resize(m.astype(float), (w, h))
+        """2x bilinear upsample -> gaussian -> threshold -> dilation -> downsample, (h, w) float64.  Reference: map.py:169-181
+        (cv2.resize, scipy.ndimage); here one composite of csrc/avl_morph2d.hip (avl_dilate_map)."""
+        from .. import ops
+        return ops.dilate_map(np.asarray(binary_map) != 0, dilate_iter, gaussian_sigma, want_zero=False)[0]
 
     # ------------------------------------------------------------------------ goal helpers of the planner (map.py:183-240)
     def get_nearest_pos(self, curr_pos: List[float], name: str) -> List[float]:

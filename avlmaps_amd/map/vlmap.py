@@ -300,8 +300,10 @@ class VLMap(Map):
         return am == 0
 
     def customize_obstacle_map(self, potential_obstacle_names: List[str], obstacle_names: List[str], vis: bool = False):
-        """Reference: vlmap.py:127-156.  The class scoring runs on the GPU; the 2-D smoothing (Map._dilate_map,
-        map.py:169-181: cv2 resize + gaussian + dilation) is navigator-side image processing and needs OpenCV."""
+        """Reference: vlmap.py:127-156 (like upstream the class lists and the smoothing parameters come from map_config, not from
+        the arguments).  The class scoring and the scatter run on the GPU (avl_obstacle_scatter), and so does the 2-D smoothing
+        (Map._dilate_map's chain, avl_dilate_map); the (H, W) byte map takes one host hop in between, where upstream negates it."""
+        from .. import ops
         from ..utils.index_utils import get_dynamic_obstacles_map_3d
         if self.obstacles_cropped is None and self.obstacles_map is None:
             self.generate_obstacle_map()
@@ -316,25 +318,21 @@ class VLMap(Map):
         self.obstacles_new_cropped = get_dynamic_obstacles_map_3d(
             self.clip_model, self.obstacles_cropped, potential, list(cfg_get(self.map_config, "obstacle_names")), feat,
             self.grid_pos, self.rmin, self.cmin, self.clip_feat_dim, vis=vis, precision=self._sim_precision, predict=predict)
-        self.obstacles_new_cropped = Map._dilate_map(self.obstacles_new_cropped == 0, cfg_get(self.map_config, "dilate_iter"),
-                                                     cfg_get(self.map_config, "gaussian_sigma"))
-        self.obstacles_new_cropped = self.obstacles_new_cropped == 0
+        # Map._dilate_map(...) == 0 (vlmap.py:151-156): the comparison is the composite's second output, the float64 image stays unbuilt
+        self.obstacles_new_cropped = ops.dilate_map(self.obstacles_new_cropped == 0, cfg_get(self.map_config, "dilate_iter"),
+                                                    cfg_get(self.map_config, "gaussian_sigma"), want_values=False)[1]
 
     def get_pos(self, name: str):
         """Contours, centres and bounding boxes of a category on the full map.  Reference: vlmap.py:158-187.  The per-voxel
-        work (argmax mask, top-down pooling) runs on the GPU; the 2-D morphology is the same SciPy calls as upstream; the
-        island extraction is utils/navigation_utils.get_segment_islands_pos (OpenCV when installed)."""
-        from scipy.ndimage import binary_closing, binary_dilation, gaussian_filter
+        work (argmax mask, top-down pooling) and the 2-D morphology (closing, gaussian, threshold, dilation: avl_mask_foreground,
+        SciPy's results bit for bit) run on the GPU and only the finished foreground mask is copied back; the island extraction
+        is utils/navigation_utils.get_segment_islands_pos (OpenCV when installed)."""
+        from .. import ops
         from ..utils.navigation_utils import get_segment_islands_pos
-        from ..utils.visualize_utils import pool_3d_label_to_2d
         assert self.categories
         pc_mask = self.index_map(name, with_init_cat=True)
-        mask_2d = pool_3d_label_to_2d(pc_mask, self._device_pos(), self.gs)
-        mask_2d = mask_2d[self.rmin:self.rmax + 1, self.cmin:self.cmax + 1]
-        foreground = binary_closing(mask_2d, iterations=3)
-        foreground = gaussian_filter(foreground.astype(float), sigma=0.8, truncate=3)
-        foreground = foreground > 0.5
-        foreground = binary_dilation(foreground)
+        mask_2d = ops.pool_label_2d(pc_mask, self._device_pos(), int(self.gs), device=True)
+        foreground = ops.mask_foreground(mask_2d, self.rmin, self.rmax + 1, self.cmin, self.cmax + 1)
         self._last_foreground = foreground
         contours, centers, bbox_list, _ = get_segment_islands_pos(foreground, 1)
         for i in range(len(contours)):          # whole-map positions (upstream adds rmin to both row bounds: kept)

@@ -852,14 +852,17 @@ def _dev_u8(x, stream):
     return as_device(x, np.uint8, stream)
 
 
-def pool_label_2d(mask_3d, grid_pos, gs, stream=None):
-    """(gs, gs) bool: mask_2d[row, col] |= mask_3d[i]  (visualize_utils.py:77-83).  Inputs host or device-resident."""
+def pool_label_2d(mask_3d, grid_pos, gs, stream=None, device=False):
+    """(gs, gs) bool: mask_2d[row, col] |= mask_3d[i]  (visualize_utils.py:77-83).  Inputs host or device-resident.
+    device=True: the (gs, gs) uint8 DeviceArray instead (nothing crosses PCIe)."""
     lib = _lib.load()
     _lib.require_gpu()
     pp, pshape, k1 = as_device(grid_pos, np.int32, stream)
     mp, mshape, k2 = _dev_u8(mask_3d, stream)
     out = DeviceArray((gs, gs), np.uint8)
     _lib.check(lib.avl_pool_label_2d(pp, mp, pshape[0], int(gs), out.ptr, stream), "avl_pool_label_2d")
+    if device:
+        return out
     return out.numpy(stream).astype(bool)
 
 
@@ -905,6 +908,150 @@ def obstacle_scatter(grid_pos, predict, obs_inds, n_classes, obstacles_cropped, 
     _lib.check(lib.avl_obstacle_scatter(pp, cp, pshape[0], table.ctypes.data, int(n_classes), int(rmin), int(cmin), H, W, fp_, out.ptr,
                                         stream), "avl_obstacle_scatter")
     return out.numpy(stream).astype(bool)
+
+
+# ---------------------------------------------------------------------------------------- 2-D image morphology (csrc/avl_morph2d.hip)
+_MORPH_OPS = {"dilate": _lib.MORPH_DILATE, "erode": _lib.MORPH_ERODE}
+_MORPH_STRUCTURES = {"cross": _lib.MORPH_CROSS, "box": _lib.MORPH_BOX}
+
+
+def _image_u8(x, stream):
+    """2-D bool / uint8 image, host or device -> (ptr, (H, W), keepalive)"""
+    ptr, shape, keep = _dev_u8(x, stream)
+    if len(shape) != 2 or shape[0] < 1 or shape[1] < 1:
+        raise ValueError(f"expected a non-empty 2-D image, got shape {tuple(shape)}")
+    return ptr, (int(shape[0]), int(shape[1])), keep
+
+
+def _image_any(x, stream):
+    """2-D image -> (ptr, (H, W), is_u8, keepalive): float64 stays float64, everything else becomes uint8 (nonzero = true)"""
+    dt = np.dtype(x.dtype) if isinstance(x, (np.ndarray, DeviceArray, DeviceView)) else None
+    if dt is None and not _is_torch(x):
+        x = np.asarray(x)
+        dt = x.dtype
+    if dt is not None and dt == np.float64:
+        ptr, shape, keep = as_device(x, np.float64, stream)
+        if len(shape) != 2 or shape[0] < 1 or shape[1] < 1:
+            raise ValueError(f"expected a non-empty 2-D image, got shape {tuple(shape)}")
+        return ptr, (int(shape[0]), int(shape[1])), 0, keep
+    if _is_torch(x):
+        import torch
+        if x.dtype == torch.float64:
+            ptr, shape, keep = as_device(x, np.float64, stream)
+            return ptr, (int(shape[0]), int(shape[1])), 0, keep
+    if isinstance(x, np.ndarray) and x.dtype not in (np.dtype(bool), np.dtype(np.uint8)):
+        x = x != 0
+    ptr, shape, keep = _image_u8(x, stream)
+    return ptr, shape, 1, keep
+
+
+def _result(out, device, stream, as_bool=False, keep=()):
+    if device:
+        out._keep = keep          # inputs and workspaces of the queued launches live as long as their result
+        return out
+    a = out.numpy(stream)
+    return a.astype(bool) if as_bool else a
+
+
+def gaussian_weights(sigma, truncate=4.0):
+    """(weights (2 * radius + 1,) float64, radius): scipy.ndimage._filters._gaussian_kernel1d(sigma, 0, radius) with
+    gaussian_filter1d's radius = int(truncate * sigma + 0.5), operation for operation"""
+    sd = float(sigma)
+    radius = int(float(truncate) * sd + 0.5)
+    sigma2 = sd * sd
+    x = np.arange(-radius, radius + 1)
+    phi_x = np.exp(-0.5 / sigma2 * x ** 2)
+    return phi_x / phi_x.sum(), radius
+
+
+def binary_morph(image, op, structure="cross", iterations=1, device=False, stream=None):
+    """scipy.ndimage.binary_dilation / binary_erosion(image, structure, iterations) with border_value 0: op 'dilate' | 'erode',
+    structure 'cross' (SciPy's default) | 'box' (np.ones((3, 3))).  -> (H, W) bool, or the uint8 DeviceArray (device=True)."""
+    lib = _lib.load()
+    _lib.require_gpu()
+    ip, (H, W), keep = _image_u8(image, stream)
+    out = DeviceArray((H, W), np.uint8)
+    tmp = DeviceArray((H, W), np.uint8) if iterations > 4 else None
+    _lib.check(lib.avl_morph_binary(ip, H, W, _MORPH_OPS[op], _MORPH_STRUCTURES[structure], int(iterations), out.ptr,
+                                    tmp.ptr if tmp is not None else None, stream), "avl_morph_binary")
+    return _result(out, device, stream, as_bool=True, keep=(keep, tmp))
+
+
+def gaussian_filter2d(image, sigma, truncate=4.0, threshold=None, device=False, stream=None):
+    """scipy.ndimage.gaussian_filter(image.astype(float), sigma, truncate=truncate) (mode 'reflect'), SciPy's bits: (H, W) float64.
+    With `threshold` the mask `value > threshold` is returned as well: (values, mask)."""
+    lib = _lib.load()
+    _lib.require_gpu()
+    ip, (H, W), is_u8, keep = _image_any(image, stream)
+    w, radius = gaussian_weights(sigma, truncate)
+    out = DeviceArray((H, W), np.float64)
+    tmp = DeviceArray((H, W), np.float64)
+    gt = DeviceArray((H, W), np.uint8) if threshold is not None else None
+    _lib.check(lib.avl_gauss2d_f64(ip, is_u8, H, W, w.ctypes.data, radius, out.ptr, gt.ptr if gt is not None else None,
+                                   float(threshold if threshold is not None else 0.0), tmp.ptr, stream), "avl_gauss2d_f64")
+    vals = _result(out, device, stream, keep=(keep, tmp))
+    if gt is None:
+        return vals
+    return vals, _result(gt, device, stream, as_bool=True, keep=(keep, tmp))
+
+
+def resize2x_up(image, device=False, stream=None):
+    """cv2.resize(image.astype(float), (2 * W, 2 * H)) with the default INTER_LINEAR: (2 * H, 2 * W) float64"""
+    lib = _lib.load()
+    _lib.require_gpu()
+    ip, (H, W), is_u8, keep = _image_any(image, stream)
+    out = DeviceArray((2 * H, 2 * W), np.float64)
+    _lib.check(lib.avl_resize2x_up_f64(ip, is_u8, H, W, out.ptr, stream), "avl_resize2x_up_f64")
+    return _result(out, device, stream, keep=(keep,))
+
+
+def resize2x_down(image, device=False, stream=None):
+    """cv2.resize(image.astype(float), (W // 2, H // 2)) of an image with even sides: the 2 x 2 block means, float64"""
+    lib = _lib.load()
+    _lib.require_gpu()
+    ip, (H2, W2), is_u8, keep = _image_any(image, stream)
+    if H2 % 2 or W2 % 2:
+        raise ValueError(f"resize2x_down needs even sides, got {(H2, W2)}")
+    out = DeviceArray((H2 // 2, W2 // 2), np.float64)
+    _lib.check(lib.avl_resize2x_down_f64(ip, is_u8, H2 // 2, W2 // 2, out.ptr, stream), "avl_resize2x_down_f64")
+    return _result(out, device, stream, keep=(keep,))
+
+
+def dilate_map(binary_map, dilate_iter=0, gaussian_sigma=1.0, want_values=True, want_zero=True, device=False, stream=None):
+    """Map._dilate_map (map.py:169-181) on the GPU -> (values (H, W) float64, zero (H, W) bool = values == 0); an output that is
+    not wanted is None.  binary_map: bool / uint8 image, host or device."""
+    lib = _lib.load()
+    _lib.require_gpu()
+    ip, (H, W), keep = _image_u8(binary_map, stream)
+    n = C.c_size_t(0)
+    _lib.check(lib.avl_dilate_map_work_bytes(H, W, C.byref(n)), "avl_dilate_map_work_bytes")
+    ws = DeviceArray((n.value,), np.uint8)
+    vals = DeviceArray((H, W), np.float64) if want_values else None
+    zero = DeviceArray((H, W), np.uint8) if want_zero else None
+    _lib.check(lib.avl_dilate_map(ip, H, W, int(dilate_iter), float(gaussian_sigma), vals.ptr if vals is not None else None,
+                                  zero.ptr if zero is not None else None, ws.ptr, n.value, stream), "avl_dilate_map")
+    return (None if vals is None else _result(vals, device, stream, keep=(keep, ws)),
+            None if zero is None else _result(zero, device, stream, as_bool=True, keep=(keep, ws)))
+
+
+def mask_foreground(mask_2d, r0=0, r1=None, c0=0, c1=None, device=False, stream=None):
+    """The mask chain of VLMap.get_pos (vlmap.py:166-171) on the crop [r0:r1, c0:c1] of mask_2d: binary_closing(iterations=3),
+    gaussian_filter(0.8, truncate=3), > 0.5, binary_dilation -> (r1 - r0, c1 - c0) bool, or the uint8 DeviceArray."""
+    lib = _lib.load()
+    _lib.require_gpu()
+    ip, (Hf, Wf), keep = _image_u8(mask_2d, stream)
+    r1 = Hf if r1 is None else int(r1)
+    c1 = Wf if c1 is None else int(c1)
+    r0, c0 = int(r0), int(c0)
+    if not (0 <= r0 < r1 <= Hf and 0 <= c0 < c1 <= Wf):
+        raise ValueError(f"crop [{r0}:{r1}, {c0}:{c1}] is not inside the {(Hf, Wf)} mask")
+    H, W = r1 - r0, c1 - c0
+    n = C.c_size_t(0)
+    _lib.check(lib.avl_mask_foreground_work_bytes(H, W, C.byref(n)), "avl_mask_foreground_work_bytes")
+    ws = DeviceArray((n.value,), np.uint8)
+    out = DeviceArray((H, W), np.uint8)
+    _lib.check(lib.avl_mask_foreground(ip, Wf, r0, r1, c0, c1, out.ptr, ws.ptr, n.value, stream), "avl_mask_foreground")
+    return _result(out, device, stream, as_bool=True, keep=(keep, ws))
 
 
 def export_raw_torch(acc: "VoxelAccumulator", device=None, stream=None):

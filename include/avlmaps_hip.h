@@ -746,6 +746,47 @@ AVL_API int avl_nav_plan(void* graph, double sr, double sc, double gr, double gc
  * of the start and of the goal, h_sg the start-goal visibility.  Synchronous. */
 AVL_API int avl_nav_last_plan(void* graph, double* h_dist, int32_t* h_pred, uint64_t* h_qbits, int32_t* h_sg, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * (9) 2-D image morphology on top-down masks (csrc/avl_morph2d.hip): the SciPy / OpenCV calls of the planner's map smoothing.
+ *     All pointers are device pointers unless named h_*; images are row-major, uint8 (nonzero = true on input, 0 / 1 on output)
+ *     or float64.  All calls are asynchronous on `stream`; no call works in place.
+ * ------------------------------------------------------------------------------------------------ */
+enum { AVL_MORPH_DILATE = 0, AVL_MORPH_ERODE = 1 };
+enum { AVL_MORPH_CROSS = 0, AVL_MORPH_BOX = 1 };
+/* scipy.ndimage.binary_dilation / binary_erosion(x, structure, iterations) with border_value = 0 and no mask, as called in
+ * avlmaps/map/vlmap.py:168,171 (cross = generate_binary_structure(2, 1), the default) and avlmaps/map/map.py:175-179
+ * (box = np.ones((3, 3))).  k iterations = one pass with the L1 diamond / the Chebyshev square of radius k; cells outside the image
+ * count as 0 for both ops, so erosion eats k cells inwards from every edge.  1 <= iterations <= 127, else AVL_ERR_INVALID.
+ * d_tmp (H * W bytes) is needed for iterations > 4 only. */
+AVL_API int avl_morph_binary(const uint8_t* d_in, int H, int W, int op, int structure, int iterations, uint8_t* d_out, uint8_t* d_tmp,
+                             void* stream);
+/* scipy.ndimage.gaussian_filter(x.astype(float), sigma, truncate=t) (vlmap.py:169, map.py:173): mode 'reflect', axis 0 first, then
+ * axis 1, float64, SciPy's summation order for a symmetric kernel -- the result has SciPy's bits.  h_weights: the 2 * radius + 1
+ * weights of _gaussian_kernel1d on the host (radius = int(t * sigma + 0.5) <= 32).  d_in is uint8 (in_is_u8 != 0) or float64.
+ * d_out_f64 (H, W) and d_out_gt_u8 (H, W) = value > threshold may each be NULL, not both; d_tmp: H * W float64. */
+AVL_API int avl_gauss2d_f64(const void* d_in, int in_is_u8, int H, int W, const double* h_weights, int radius, double* d_out_f64,
+                            uint8_t* d_out_gt_u8, double threshold, double* d_tmp, void* stream);
+/* cv2.resize(x, (2 * W, 2 * H)) with the default INTER_LINEAR (map.py:172): destination index i samples the source at
+ * (i + 0.5) / 2 - 0.5 -- fraction 0.75 for even i, 0.25 for odd i -- with source indices clamped at both ends.
+ * d_in (H, W) uint8 or float64 -> d_out (2 * H, 2 * W) float64. */
+AVL_API int avl_resize2x_up_f64(const void* d_in, int in_is_u8, int H, int W, double* d_out, void* stream);
+/* cv2.resize(x, (W, H)) of a (2 * H, 2 * W) image (map.py:180): the mean of every 2 x 2 block.  -> d_out (H, W) float64. */
+AVL_API int avl_resize2x_down_f64(const void* d_in, int in_is_u8, int H, int W, double* d_out, void* stream);
+/* avlmaps/map/map.py:169-181 Map._dilate_map on a (H, W) binary image: x2 up-sampling, gaussian(sigma, truncate 3), > 0.5, 3 x 3 box
+ * dilation with 2 * dilate_iter iterations, x1/2 down-sampling.  d_out_f64 (H, W) is upstream's return value, d_out_zero_u8 (H, W)
+ * is `result == 0`, what VLMap.customize_obstacle_map keeps (vlmap.py:156); each may be NULL, not both.  dilate_iter = 0 is SciPy's
+ * "repeat until nothing changes": one set cell after the threshold fills the image.  0 <= dilate_iter <= 63, radius
+ * int(3 * sigma + 0.5) <= 32.  ws: avl_dilate_map_work_bytes(H, W) bytes of device memory. */
+AVL_API int avl_dilate_map_work_bytes(int H, int W, size_t* bytes);
+AVL_API int avl_dilate_map(const uint8_t* d_binary_u8, int H, int W, int dilate_iter, double sigma, double* d_out_f64,
+                           uint8_t* d_out_zero_u8, void* ws, size_t ws_bytes, void* stream);
+/* avlmaps/map/vlmap.py:166-171 VLMap.get_pos: the crop [r0:r1, c0:c1] of a mask with rows of ld cells (the pooled (gs, gs) mask of
+ * avl_pool_label_2d), then binary_closing(iterations=3), gaussian_filter(sigma=0.8, truncate=3), > 0.5, binary_dilation -- all with
+ * the crop's borders.  d_out_u8 (r1 - r0, c1 - c0).  ws: avl_mask_foreground_work_bytes(r1 - r0, c1 - c0) bytes of device memory. */
+AVL_API int avl_mask_foreground_work_bytes(int H, int W, size_t* bytes);
+AVL_API int avl_mask_foreground(const uint8_t* d_mask2d_u8, int64_t ld, int r0, int r1, int c0, int c1, uint8_t* d_out_u8, void* ws,
+                                size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
