@@ -18,7 +18,10 @@ ARCH = "gfx950"
 SOURCES = {
     "avl_api.hip": [],
     "avl_sim.hip": [],
-    "avl_builder.hip": ["-ffp-contract=off"],
+    "avl_builder.hip": ["-ffp-contract=off"],      # the frame path: the only fused multiply-adds of K1 are the explicit fma() of the reference's BLAS order
+    "avl_finalize.hip": ["-ffp-contract=off"],     # finished rows and merge payloads are the reference's float64 expressions, operation for operation
+    "avl_replay.hip": ["-ffp-contract=off"],       # the replay rounds weight / grid_rgb like the reference's running mean, step by step
+    "avl_rows.hip": ["-ffp-contract=off"],         # rows_div_f32 is finalize_kernel's division; the sums it divides are plain adds
     "avl_heat.hip": [],
     "avl_map2d.hip": [],
     "avl_lseg.hip": [],

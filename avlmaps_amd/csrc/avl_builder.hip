@@ -41,18 +41,14 @@
 // voxelize_link_next_kernel / pipe_kernel), so that a frame's dependent chain starts at the voxel-hash lookup.
 // K1 and K3 are written as STRAIGHT-LINE code around their loads (flags and selects, full-width rows): a load inside a branch makes
 // the compiler wait for everything outstanding where the branches merge, and these kernels live on having several loads in flight.
-// Slots are handed out in arrival order, so finalisation sorts the first-touch keys (rocPRIM radix sort) to emit
-// rows in the reference's voxel-id order; the sort is a once-per-save cost.
+// This file is the frame path only.  Finalisation and map I/O: avl_finalize.hip; the exact-colour replay: avl_replay.hip; the state
+// all three share (struct avl_builder, the per-sample records): avl_builder_state.h.
 #include <algorithm>
 #include <climits>
 #include <cstring>
 #include <vector>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_select.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
-
-#include "avl_common.h"
+#include "avl_builder_state.h"
 
 namespace avl {
 
@@ -72,78 +68,6 @@ constexpr int kProbeK12Row0 = 16384;
 #define AVL_RESTAMP(var)
 #endif
 
-// one frame of a batch (avl_builder_integrate_batch): what differs between the frames of one launch
-struct BatchEntry {
-    double t[16];                 // pc_transform of the frame
-    const float* depth;
-    const int32_t* samples;
-    const uint8_t* rgb;
-    const float* feat;
-    unsigned long long frame_key; // key_bias | frame_idx << 32
-};
-
-struct FrameParams {
-    double kinv[9];   // inv(calib)            (mapping_utils.py:237)
-    double k[9];      // calib                 (vlmap_builder.py:98)
-    double kf[9];     // get_sim_cam_mat(Hf,Wf)(mapping_utils.py:591-596)
-    double t[16];     // pc_transform          (vlmap_builder.py:133)
-    double min_depth, max_depth, two_sigma_sq;
-    double cs, half_gs;
-    double pcd_min[3];   // global mode: lower corner of the pass-1 bounding box (vlmap_builder_multi_floor.py:117)
-    double depth_div;    // uint16 depth images: metres = value / depth_div (multi-floor: / 1000.0, :105)
-    int H, W, Hf, Wf, n0, n1, n2, P;   // grid: n0 rows x n1 cols x n2 heights (mobile-base mode: gs, gs, vh)
-    const BatchEntry* batch;   // nullptr: single frame (pointers / transform passed directly); else P = B * P_frame samples
-    int P_frame;
-    int mode;            // 0 = mobile-base map (vlmap_builder.py), 1 = global multi-floor map (vlmap_builder_multi_floor.py)
-    int depth_u16;
-    long long capacity;
-    const struct PreRec* pre;   // the stateless half of K1 for THIS frame, computed by the previous launch (PreGather); nullptr: compute here
-};
-
-// The frame loop in C (avl_builder_integrate_frames) knows frame i + 1 while it launches frame i, and the first half of K1 --
-// sample index -> depth -> back-projection, pose, cell, the two pinhole projections, the colour gather, the weight -- depends on
-// nothing the builder holds: only from the cell's slot onwards does a sample touch the map.  A few workgroups in FRONT of frame
-// i's launch run that half for frame i + 1 (bp_voxelize_body<.., 2>) and leave 24 bytes per sample; K1 of frame i + 1
-// (bp_voxelize_body<.., 1>) then starts its chain with one coalesced load and goes straight to the slot: four of the chain's
-// hops (sample index, depth, geometry, colour) move out of the dependent path into the shadow of the previous frame.
-// Single float32-depth frames of one avl_builder_integrate_frames call; the same arithmetic, operation for operation.
-struct PreRec {
-    double alpha;     // 0 if the sample dropped out
-    int32_t cell;     // -1 if the sample dropped out
-    int32_t fpix;
-    uint32_t rgbv;
-    uint32_t flags;   // bit 0: outside the pass-1 bounding box (global mode), bit 1: projected outside the RGB image
-};
-static_assert(sizeof(PreRec) == 24, "PreRec");
-
-struct PreGather {
-    PreRec* out;              // nullptr: nothing to prepare
-    const float* depth;
-    const int32_t* samples;
-    const uint8_t* rgb;
-};
-
-// per-frame sample records (structure of arrays, sized for the largest P seen)
-struct Recs {
-    double* alpha;
-    int32_t* slot;    // -1 = the sample updates no voxel
-    int32_t* fpix;    // py*Wf + px into the (Hf, Wf, D) feature map
-    uint32_t* rgb;    // r | g<<8 | b<<16
-    int32_t* next;    // next sample of the same voxel in this frame, -1 = end
-    uint8_t* owner;   // 1 = this sample found its voxel's list empty: it is the list's TAIL and its wave fuses the list
-};
-// The owners of a BATCHED launch compacted per K2 workgroup (no atomics: a ballot and four LDS words): entry 256 b + k is owner k of
-// workgroup b, ocnt[b] of them.  K3 then runs kFuseWaves waves per K2 workgroup over them instead of one wave per SAMPLE, most of
-// which load a flag and leave: half the workgroups to dispatch, +3 % / +6 % at 16 / 64 frames per launch.  Single-frame launches keep
-// the wave-per-sample form (the compacted one measured 11.2 -> 12.0 us there), and these pointers stay out of their kernel arguments.
-struct OwnerList {
-    double* o_alpha;
-    int32_t* o_s;
-    int32_t* o_slot;
-    int32_t* o_fpix;
-    uint32_t* o_rgb;
-    int32_t* ocnt;
-};
 #ifndef AVL_K3_THREADS
 #define AVL_K3_THREADS 256      // wave-per-sample K3 launches (single frames): threads per workgroup
 #endif
@@ -151,7 +75,6 @@ constexpr int kFuseWaves = 128;   // K3 waves per K2 workgroup of 256 samples (m
 
 constexpr int kEmpty = -1, kPending = -2;
 constexpr int kAggregateSamples = 32768;   // launches at least this large allocate slots per workgroup instead of per wave
-constexpr unsigned long long kNoKey = ~0ull;
 constexpr int kMaxPendingSpins = 1 << 18;   // link step of a deferred-fuse launch: polls of a cell that is being created
 
 // The kernel-argument block of these kernels is 450-1 040 bytes (FrameParams alone: three 3 x 3 matrices and the pose), the
@@ -416,22 +339,6 @@ __device__ __forceinline__ SampleRec bp_voxelize_body(int blk, const FrameParams
 #endif
     return SampleRec{alpha, cell, fpix, rgbv, known};
 }
-
-// optional per-sample log for the exact sequential replay of weight / grid_rgb at finalisation (position = key order)
-// One 32-byte record per sample = one memory sector: the replay walks a voxel's samples through an index list, i.e. every entry is
-// a random access -- with alpha / key / colour in three arrays that was three sectors per entry (replay_chain_kernel 1.63 ms for the
-// 27 M active samples of a 10 000-frame build).  The slots stay in an array of their own: the compaction and the sort read only them.
-struct alignas(32) LogRec {
-    double alpha;
-    unsigned long long key;
-    uint32_t rgb;
-    uint32_t pad[3];
-};
-static_assert(sizeof(LogRec) == 32, "one sector per replay-log record");
-struct ReplayLog {
-    uint32_t* slot;            // 0xFFFFFFFF = sample did not update a voxel
-    LogRec* rec;
-};
 
 // K2 body.  Runs right behind K1 in the same kernel: the sample comes in registers, and a cell another workgroup is still
 // creating (kPending) is waited for.  That cannot deadlock: a creator publishes its slot without waiting for anybody but
@@ -999,488 +906,9 @@ __global__ __launch_bounds__(256) void fuse_generic_kernel(int P, int D, unsigne
     }
 }
 
-// wave per output row r; the accumulators of row r live in slot perm[r] (perm == nullptr: identity).  sum_feat rows have
-// stride ld_sf, the [sum alpha, sum alpha*rgb] quadruple of a row sits at sum_w4 + row * ld_w4.  first_feat == nullptr: the
-// first-touch correction has already been folded into sum_feat (merged accumulators, scatter_merge_kernel).  Output row r
-// is voxel id row0 + r (row0 != 0: one rank finalises one block of a reduce-scattered map).
-__global__ __launch_bounds__(256) void finalize_kernel(int64_t n, int D, int gs, int vh, int64_t row0, const int32_t* __restrict__ perm,
-                                                       const int32_t* __restrict__ cell, const double* __restrict__ sum_feat,
-                                                       int64_t ld_sf, const double* __restrict__ sum_w4, int64_t ld_w4,
-                                                       const float* __restrict__ first_feat, const double* __restrict__ first_alpha,
-                                                       float* __restrict__ grid_feat, int32_t* __restrict__ grid_pos,
-                                                       float* __restrict__ weight, uint8_t* __restrict__ grid_rgb,
-                                                       int32_t* __restrict__ occupied) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    for (int64_t r = wave0; r < n; r += nwaves) {
-        const int64_t sl = perm ? perm[r] : r;
-        const double w = sum_w4[sl * ld_w4];
-        if (grid_feat) {
-            const double* s = sum_feat + sl * ld_sf;
-            float* o = grid_feat + r * D;
-            if (first_feat) {
-                // reference closed form (a1^2 f1 + sum_{i >= 2} alpha_i f_i) / sum alpha; sum_feat excludes the first touch
-                const double a1 = first_alpha[sl];
-                const double a1sq = a1 * a1;
-                const float* f1 = first_feat + sl * D;
-                for (int c = lane; c < D; c += 64) o[c] = (float)((a1sq * (double)f1[c] + s[c]) / w);
-            } else {
-                for (int c = lane; c < D; c += 64) o[c] = (float)(s[c] / w);
-            }
-        }
-        if (lane == 0) {
-            const int32_t cl = cell[sl];
-            if (grid_pos) {
-                grid_pos[r * 3 + 0] = cl / (gs * vh);
-                grid_pos[r * 3 + 1] = (cl / vh) % gs;
-                grid_pos[r * 3 + 2] = cl % vh;
-            }
-            if (weight) weight[r] = (float)w;
-            if (occupied) occupied[cl] = (int32_t)(row0 + r);
-        }
-        if (grid_rgb && lane < 3) {
-            // running mean stored into a uint8 array (truncating cast); we truncate the exact weighted mean.  (sum alpha c) / (sum
-            // alpha) of samples that all have the colour c is c or c - 1 ulp: the 1e-9 keeps that from truncating to c - 1 (a voxel
-            // touched once stores its pixel's colour exactly, vlmap_builder.py:167)
-            double m = sum_w4[sl * ld_w4 + 1 + lane] / w + 1e-9;
-            m = fmin(fmax(m, 0.0), 255.0);
-            grid_rgb[r * 3 + lane] = (uint8_t)m;
-        }
-    }
-}
-
-// Multi-GPU merge, step "scatter" (avlmaps_amd/parallel.py): wave per local slot s.  The slot's accumulators go to row
-// row_of_slot[s] of the dense (M, D + 4) float64 buffer every rank reduces -- straight from the builder's own arrays, no
-// export copy.  The rank that OWNS the voxel's global first touch (its slot_key equals the all-reduced MIN key) subtracts the
-// first touch with the reference's weight a1^2 (every other rank: a1; vlmap_builder.py:166-174 closed form), so that the
-// reduced rows only need dividing by sum alpha: ONE sum-reduce carries the whole merge.
-__global__ __launch_bounds__(256) void scatter_merge_kernel(int64_t n, int D, const int64_t* __restrict__ row_of_slot,
-                                                            const unsigned long long* __restrict__ global_key,
-                                                            const unsigned long long* __restrict__ slot_key,
-                                                            const double* __restrict__ sum_feat, const double* __restrict__ sum_w4,
-                                                            const float* __restrict__ first_feat, const double* __restrict__ first_alpha,
-                                                            double* __restrict__ acc, int64_t ld) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    for (int64_t s = wave0; s < n; s += nwaves) {
-        const int64_t row = row_of_slot[s];
-        const bool owner = slot_key[s] == global_key[row];
-        // sum_feat leaves the slot's LOCAL first touch out (fuse_body): the rank that holds the GLOBAL first touch contributes it
-        // with the reference's a1^2, every other rank with its plain weight a1
-        const double a1 = first_alpha[s];
-        const double wf = owner ? a1 * a1 : a1;
-        const double* sf = sum_feat + s * D;
-        const float* f1 = first_feat + s * D;
-        double* o = acc + row * ld;
-        for (int c = lane; c < D; c += 64) o[c] = wf * (double)f1[c] + sf[c];
-        if (lane < 4) o[D + lane] = sum_w4[s * 4 + lane];
-    }
-}
-
-// Row-sharded merge with the mixed payload (avlmaps_amd/parallel.py, round 4).  A voxel that only ONE rank ever touched needs no
-// float64 exchange: its finished float32 feature row (a1^2 f1 + sum) / sum alpha is computed where the accumulators live --
-// the same float64 expression finalize_kernel evaluates, so the row is bit-identical to the single-process map -- and travels as
-// 4 B per element.  Only voxels that several ranks touched ship float64 partial sums (own != 0: this rank holds the global first
-// touch and folds the reference's first-touch term in).  Wave per listed slot; output row i belongs to slot slots[i].
-__global__ __launch_bounds__(256) void export_rows_f32_kernel(int64_t k, int D, const int32_t* __restrict__ slots,
-                                                              const double* __restrict__ sum_feat, const double* __restrict__ sum_w4,
-                                                              const float* __restrict__ first_feat, const double* __restrict__ first_alpha,
-                                                              float* __restrict__ out, int64_t ld) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    for (int64_t i = wave0; i < k; i += nwaves) {
-        const int64_t sl = slots[i];
-        const double w = sum_w4[sl * 4];
-        const double a1 = first_alpha[sl];
-        const double a1sq = a1 * a1;
-        const double* s = sum_feat + sl * D;
-        const float* f1 = first_feat + sl * D;
-        float* o = out + i * ld;
-        for (int c = lane; c < D; c += 64) o[c] = (float)((a1sq * (double)f1[c] + s[c]) / w);   // finalize_kernel's expression
-    }
-}
-
-__global__ __launch_bounds__(256) void export_rows_f64_kernel(int64_t k, int D, const int32_t* __restrict__ slots,
-                                                              const uint8_t* __restrict__ own, const double* __restrict__ sum_feat,
-                                                              const float* __restrict__ first_feat, const double* __restrict__ first_alpha,
-                                                              double* __restrict__ out, int64_t ld) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    for (int64_t i = wave0; i < k; i += nwaves) {
-        const int64_t sl = slots[i];
-        const double a1 = first_alpha[sl];
-        const double wf = own[i] ? a1 * a1 : a1;   // global first touch: a1^2 f1 (reference closed form); else the sample's plain weight
-        const double* s = sum_feat + sl * D;
-        const float* f1 = first_feat + sl * D;
-        double* o = out + i * ld;
-        for (int c = lane; c < D; c += 64) o[c] = wf * (double)f1[c] + s[c];
-    }
-}
-
-// Sender side of the gather-plan merge (avl_merge2.hip, avlmaps_amd/merge2.py): the rank's voxels in final-row order, straight from
-// the accumulators into the send buffer of the ONE payload all_to_all.  Destination q's segment = [side records | finished float32
-// rows | float64 partial rows].  Wave per voxel i: its 64-byte side record [row - first row of q's block | index in q's done / part
-// list << 32 | flags, sum_w4 (4 x f64), 3 words of replay state (avl_merge2_side_state fills them after the replay)], and its
-// feature row: export_rows_f32_kernel's expression for a voxel of this rank alone (straight into this rank's own block when it owns
-// the row), export_rows_f64_kernel's for a voxel several ranks touched.
-struct M2PackSeg {
-    long long cum[65];        // cum[q] = voxels of this call for ranks < q (cum[ws] = all of them): wave w serves rank q with cum[q] <= w < cum[q + 1]
-    long long lo[64];         // ... and is voxel lo[q] + (w - cum[q]) of the rank's final-row order
-    long long dlo[64];        // single-rank voxels of that order before lo[q]
-    long long row0[64];       // first final row this call covers at rank q (a chunk of q's block): side records carry row - row0[q]
-    long long side_off[64], done_off[64], part_off[64];   // word (8 B) offsets of q's three lists in the send buffer
-};
-
-__global__ __launch_bounds__(256) void m2_pack_kernel(long long n, int ws, int rank, int D, long long own_r0, M2PackSeg sg,
-                                                      const int32_t* __restrict__ order, const int32_t* __restrict__ row_s,
-                                                      const int32_t* __restrict__ prev_s, const int32_t* __restrict__ next_s,
-                                                      const int32_t* __restrict__ sidx, const double* __restrict__ sum_feat,
-                                                      const double* __restrict__ sum_w4, const float* __restrict__ first_feat,
-                                                      const double* __restrict__ first_alpha, long long* __restrict__ send,
-                                                      float* __restrict__ own_feat) {
-    const int lane = threadIdx.x & 63;
-    const long long wave0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const long long nwaves = ((long long)gridDim.x * blockDim.x) >> 6;
-    const long long ldf = (D + 1) / 2 * 2;
-    for (long long w = wave0; w < n; w += nwaves) {
-        int q = 0;
-        while (q + 1 < ws && w >= sg.cum[q + 1]) ++q;
-        const long long j = w - sg.cum[q];
-        const long long i = sg.lo[q] + j;
-        const long long sl = order[i];
-        const bool is_new = prev_s[sl] < 0, single = is_new && next_s[sl] < 0;
-        const long long didx = (long long)sidx[i] - sg.dlo[q], pidx = j - didx;
-        const bool direct = single && q == rank && own_feat != nullptr;
-        const long long row = row_s[sl];
-        const long long row_rel = row - sg.row0[q];
-        const double a1 = first_alpha[sl];
-        const double* s = sum_feat + sl * D;
-        const float* f1 = first_feat + sl * D;
-        if (single) {
-            const double wsum = sum_w4[sl * 4];
-            const double a1sq = a1 * a1;
-            float* o = direct ? own_feat + (row - own_r0) * D : reinterpret_cast<float*>(send + sg.done_off[q]) + didx * ldf;
-            for (int c = lane; c < D; c += 64) o[c] = (float)((a1sq * (double)f1[c] + s[c]) / wsum);     // finalize_kernel's expression
-        } else {
-            const double wf = is_new ? a1 * a1 : a1;   // global first touch: a1^2 f1 (reference closed form); else the sample's plain weight
-            double* o = reinterpret_cast<double*>(send + sg.part_off[q]) + pidx * D;
-            for (int c = lane; c < D; c += 64) o[c] = wf * (double)f1[c] + s[c];
-        }
-        long long* rec = send + sg.side_off[q] + 8 * j;
-        if (lane == 0)
-            rec[0] = (long long)((unsigned long long)row_rel | ((unsigned long long)(single ? didx : pidx) << 32) |
-                                 (single ? (1ull << 63) : 0ull) | (direct ? (1ull << 62) : 0ull));
-        else if (lane < 5)
-            rec[lane] = __double_as_longlong(sum_w4[sl * 4 + lane - 1]);
-        else if (lane < 8)
-            rec[lane] = 0;
-    }
-}
-
-// grid_pos / weight / grid_rgb / occupied_ids of n merged rows from their cells and [sum alpha, sum alpha rgb] quadruples alone
-// (the feature rows of the mixed payload are finished elsewhere); same arithmetic as finalize_kernel's lane-0 part
-__global__ __launch_bounds__(256) void finalize_side_kernel(int64_t n, int gs, int vh, int64_t row0, const int32_t* __restrict__ cell,
-                                                            const double* __restrict__ w4, int32_t* __restrict__ grid_pos,
-                                                            float* __restrict__ weight, uint8_t* __restrict__ grid_rgb,
-                                                            int32_t* __restrict__ occupied) {
-    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x) {
-        const int32_t cl = cell[r];
-        const double w = w4[r * 4];
-        if (grid_pos) {
-            grid_pos[r * 3 + 0] = cl / (gs * vh);
-            grid_pos[r * 3 + 1] = (cl / vh) % gs;
-            grid_pos[r * 3 + 2] = cl % vh;
-        }
-        if (weight) weight[r] = (float)w;
-        if (occupied) occupied[cl] = (int32_t)(row0 + r);
-        if (grid_rgb)
-            for (int k = 0; k < 3; ++k) {
-                double m = w4[r * 4 + 1 + k] / w + 1e-9;   // as finalize_kernel
-                m = fmin(fmax(m, 0.0), 255.0);
-                grid_rgb[r * 3 + k] = (uint8_t)m;
-            }
-    }
-}
-
-// first / one-past-last position of every slot's run in the slot-sorted log
-__global__ void log_segments_kernel(const uint32_t* __restrict__ sorted_slot, long long L, long long nslots,
-                                    long long* __restrict__ seg_start, long long* __restrict__ seg_end) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < L; i += (long long)gridDim.x * blockDim.x) {
-        const uint32_t sl = sorted_slot[i];
-        if (sl >= (uint32_t)nslots) continue;
-        if (i == 0 || sorted_slot[i - 1] != sl) seg_start[sl] = i;
-        if (i == L - 1 || sorted_slot[i + 1] != sl) seg_end[sl] = i + 1;
-    }
-}
-
-// One update of the reference's running weight / colour with the reference's dtypes (vlmap_builder.py:164-178; NumPy >= 2
-// promotion, see oracle/avl_oracle.c avlo_integrate_frame):
-//   until the first capacity doubling (_reserve_map_space, :286-311) weight is float32 and grid_rgb uint8 (truncating
-//   store at every update); afterwards weight is float64 and grid_rgb float32.  The doubling happens right after the
-//   voxel with id gs*gs - 1 was created, i.e. for every update whose key is greater than that voxel's first-touch key
-//   (`grown`).  c[] holds uint8 or float32 values exactly.
-__device__ __forceinline__ void replay_step(double& w, double (&c)[3], bool& started, double alpha, uint32_t rgbv, bool grown) {
-    const double v[3] = {(double)(rgbv & 0xffu), (double)((rgbv >> 8) & 0xffu), (double)((rgbv >> 16) & 0xffu)};
-    if (!started) {
-        started = true;
-        for (int k = 0; k < 3; ++k) c[k] = v[k];
-        const double ww = 0.0 + alpha;
-        w = grown ? ww : (double)(float)ww;
-    } else {
-        const double denom = w + alpha;
-        if (!grown) {
-            const float wf = (float)w;
-            for (int k = 0; k < 3; ++k) {
-                const float prod = (float)c[k] * wf;
-                const double q = ((double)prod + v[k] * alpha) / denom;
-                c[k] = (double)(uint8_t)q;
-            }
-            w = (double)(float)denom;
-        } else {
-            for (int k = 0; k < 3; ++k) c[k] = (double)(float)((c[k] * w + v[k] * alpha) / denom);
-            w = denom;
-        }
-    }
-}
-
-// The updates [i0, i1) of one voxel, in order.  The state is a serial chain, the loads are not: kReplayAhead entries' index ->
-// {alpha, rgb, key} gathers are requested together (unconditionally: positions past the end re-read the last entry), so a long
-// segment pays one memory round trip per kReplayAhead entries instead of two per entry.
-#ifndef AVL_REPLAY_AHEAD
-#define AVL_REPLAY_AHEAD 4
-#endif
-constexpr int kReplayAhead = AVL_REPLAY_AHEAD;
-__device__ __forceinline__ void replay_walk(double& w, double (&c)[3], bool& started, long long i0, long long i1, const int32_t* __restrict__ order,
-                                            const ReplayLog& log, unsigned long long gkey) {
-    for (long long i = i0; i < i1; i += kReplayAhead) {
-        int32_t e[kReplayAhead];
-#pragma unroll
-        for (int k = 0; k < kReplayAhead; ++k) e[k] = order[i + k < i1 ? i + k : i1 - 1];
-        double a[kReplayAhead];
-        uint32_t v[kReplayAhead];
-        unsigned long long ky[kReplayAhead];
-#pragma unroll
-        for (int k = 0; k < kReplayAhead; ++k) {
-            using u64x2 = __attribute__((ext_vector_type(2))) unsigned long long;
-            const u64x2* r = reinterpret_cast<const u64x2*>(log.rec + e[k]);
-            const u64x2 r0 = r[0];
-            a[k] = __longlong_as_double((long long)r0.x);
-            ky[k] = r0.y;
-            v[k] = (uint32_t)r[1].x;
-        }
-#pragma unroll
-        for (int k = 0; k < kReplayAhead; ++k)
-            if (i + k < i1) replay_step(w, c, started, a[k], v[k], ky[k] > gkey);
-    }
-}
-
-// Thread per output row: replay the voxel's updates in the reference's order (the log is in key order, `order` is its stable
-// sort by slot).
-__global__ __launch_bounds__(256) void replay_rgb_kernel(int64_t n, long long gs2, const int32_t* __restrict__ perm,
-                                                         const unsigned long long* __restrict__ keys_sorted,
-                                                         const int32_t* __restrict__ order, const long long* __restrict__ seg_start,
-                                                         const long long* __restrict__ seg_end, ReplayLog log,
-                                                         float* __restrict__ weight, uint8_t* __restrict__ grid_rgb) {
-    const unsigned long long gkey = n >= gs2 ? keys_sorted[gs2 - 1] : kNoKey;
-    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x) {
-        const int32_t sl = perm[r];
-        double w = 0.0, c[3] = {0.0, 0.0, 0.0};
-        bool started = false;
-        replay_walk(w, c, started, seg_start[sl], seg_end[sl], order, log, gkey);
-        if (started) {
-            if (weight) weight[r] = (float)w;
-            if (grid_rgb)
-                for (int k = 0; k < 3; ++k) grid_rgb[r * 3 + k] = (uint8_t)fmin(fmax(c[k], 0.0), 255.0);
-        }
-    }
-}
-
-// Multi-GPU: the sequential replay is a CHAIN over ranks (frames are sharded contiguously, so every update of rank r comes
-// before every update of rank r + 1): a rank receives the per-voxel state left by its predecessors, continues it with its own
-// log and passes it on -- 24 bytes per voxel per hop instead of shipping the logs (avlmaps_amd/parallel.py).
-struct ReplayState {
-    double w;
-    float c[3];
-    uint32_t started;
-};
-static_assert(sizeof(ReplayState) == 24, "ReplayState is exchanged between ranks as 3 x int64");
-
-__global__ __launch_bounds__(256) void replay_chain_kernel(int64_t n, unsigned long long gkey, const int64_t* __restrict__ row_of_slot,
-                                                           const int32_t* __restrict__ order, const long long* __restrict__ seg_start,
-                                                           const long long* __restrict__ seg_end, ReplayLog log,
-                                                           ReplayState* __restrict__ state) {
-    for (int64_t sl = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; sl < n; sl += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t si = row_of_slot[sl];
-        if (si < 0 || seg_start[sl] >= seg_end[sl]) continue;          // negative index: slot not part of this call
-        ReplayState& st = state[si];
-        double w = st.w, c[3] = {(double)st.c[0], (double)st.c[1], (double)st.c[2]};
-        bool started = st.started != 0;
-        replay_walk(w, c, started, seg_start[sl], seg_end[sl], order, log, gkey);
-        st.w = w;
-        for (int k = 0; k < 3; ++k) st.c[k] = (float)c[k];
-        st.started = started ? 1u : 0u;
-    }
-}
-
-__global__ __launch_bounds__(256) void replay_apply_kernel(int64_t n, const ReplayState* __restrict__ state, float* __restrict__ weight,
-                                                           uint8_t* __restrict__ grid_rgb) {
-    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x) {
-        const ReplayState st = state[r];
-        if (!st.started) continue;
-        if (weight) weight[r] = (float)st.w;
-        if (grid_rgb)
-            for (int k = 0; k < 3; ++k) grid_rgb[r * 3 + k] = (uint8_t)fminf(fmaxf(st.c[k], 0.f), 255.f);
-    }
-}
-
-// row_dirty[r] = the voxel in output row r was fused since the flags were last cleared
-__global__ void row_dirty_kernel(int64_t n, const int32_t* __restrict__ perm, uint8_t* __restrict__ dirty, uint8_t* __restrict__ row_dirty,
-                                 int clear) {
-    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x) {
-        const int32_t sl = perm[r];
-        row_dirty[r] = dirty[sl];
-        if (clear) dirty[sl] = 0;
-    }
-}
-
-__global__ void iota_kernel(int32_t* __restrict__ v, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) v[i] = (int32_t)i;
-}
-
-// wave per imported voxel row: rebuild accumulators from a finalised map (resume, vlmap_builder.py:212-222)
-__global__ __launch_bounds__(256) void import_map_kernel(int64_t n, int D, int n0, int gs, int vh, const float* __restrict__ grid_feat,
-                                                         const int32_t* __restrict__ grid_pos, const float* __restrict__ weight,
-                                                         const uint8_t* __restrict__ grid_rgb, int32_t* __restrict__ cell_slot,
-                                                         int32_t* __restrict__ slot_cell, unsigned long long* __restrict__ slot_key,
-                                                         double* __restrict__ sum_feat, double* __restrict__ sum_w4,
-                                                         float* __restrict__ first_feat, double* __restrict__ first_alpha,
-                                                         int* __restrict__ err_flags) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    for (int64_t r = wave0; r < n; r += nwaves) {
-        const double w = (double)weight[r];
-        for (int c = lane; c < D; c += 64) {
-            sum_feat[r * D + c] = (double)grid_feat[r * D + c] * w;   // first-touch weighting is already baked in
-            first_feat[r * D + c] = 0.f;
-        }
-        if (lane == 0) {
-            const int row = grid_pos[r * 3], col = grid_pos[r * 3 + 1], h = grid_pos[r * 3 + 2];
-            if (row < 0 || row >= n0 || col < 0 || col >= gs || h < 0 || h >= vh) {
-                atomicOr(err_flags, 4);
-            } else {
-                const int32_t cell = (row * gs + col) * vh + h;
-                cell_slot[cell] = (int32_t)r;
-                slot_cell[r] = cell;
-            }
-            slot_key[r] = (unsigned long long)r;                        // imported voxels order before any new one
-            first_alpha[r] = 0.0;                                       // no first-touch term: it is baked into the imported row
-            sum_w4[r * 4] = w;
-            for (int c = 0; c < 3; ++c) sum_w4[r * 4 + 1 + c] = (grid_rgb ? (double)grid_rgb[r * 3 + c] : 0.0) * w;
-        }
-    }
-}
-
-// pass 1 of the global (multi-floor) builder: bounding box of the transformed sampled points
-// (vlmap_builder_multi_floor.py:97-118).  minmax = [min xyz, max xyz] as order-preserving uint64 keys of the doubles.
-__device__ __forceinline__ unsigned long long f64_key(double v) {
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    return (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
-}
-
-__global__ __launch_bounds__(256) void bbox_kernel(FrameParams fp, const float* __restrict__ depth,
-                                                   const int32_t* __restrict__ sample_idx, unsigned long long* __restrict__ minmax) {
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= fp.P) return;
-    const int pix = sample_idx[s];
-    if (pix < 0 || pix >= fp.H * fp.W) return;
-    const double x = (double)(pix % fp.W) + 0.5, y = (double)(pix / fp.W) + 0.5;
-    const double z = fp.depth_u16 ? (double)reinterpret_cast<const uint16_t*>(depth)[pix] / fp.depth_div : (double)depth[pix];
-    const double pl0 = fma(fp.kinv[2], 1.0, fma(fp.kinv[1], y, fp.kinv[0] * x)) * z;
-    const double pl1 = fma(fp.kinv[5], 1.0, fma(fp.kinv[4], y, fp.kinv[3] * x)) * z;
-    const double pl2 = fma(fp.kinv[8], 1.0, fma(fp.kinv[7], y, fp.kinv[6] * x)) * z;
-    if (!((pl2 > fp.min_depth) && (pl2 < fp.max_depth))) return;
-    const double g[3] = {fma(fp.t[3], 1.0, fma(fp.t[2], pl2, fma(fp.t[1], pl1, fp.t[0] * pl0))),
-                         fma(fp.t[7], 1.0, fma(fp.t[6], pl2, fma(fp.t[5], pl1, fp.t[4] * pl0))),
-                         fma(fp.t[11], 1.0, fma(fp.t[10], pl2, fma(fp.t[9], pl1, fp.t[8] * pl0)))};
-    for (int c = 0; c < 3; ++c) {
-        const unsigned long long k = f64_key(g[c]);
-        atomicMin(&minmax[c], k);
-        atomicMax(&minmax[3 + c], k);
-    }
-}
-
 }  // namespace avl
 
 using namespace avl;
-
-struct LogSegments;
-struct avl_builder {
-    int n0, gs, vh, D;   // grid n0 x gs x vh (n0 == gs for the square mobile-base map)
-    double cs;
-    int64_t capacity;
-    size_t ncell;
-    int32_t* cell_slot = nullptr;
-    int32_t* slot_cell = nullptr;
-    unsigned long long* slot_key = nullptr;
-    double* sum_feat = nullptr;
-    double* sum_w4 = nullptr;
-    float* first_feat = nullptr;
-    double* first_alpha = nullptr;
-    int32_t* head = nullptr;                 // lists of the launch being linked
-    int32_t* head_alt = nullptr;             // deferred fuse: lists of the frame whose K3 is still pending (the two swap per frame)
-    uint8_t* dirty = nullptr;                // slot fused since the last clearing finalize (incremental checkpoints)
-    unsigned long long* counters = nullptr;  // [0] slots handed out, [1] samples fused, [2] per-frame voxel groups fused
-    int* err_flags = nullptr;
-    char* recs_mem = nullptr;
-    OwnerList owners{};                      // batched launches only (see struct OwnerList)
-    Recs recs{}, recs_alt{};                 // recs_alt: records of the pending frame (deferred fuse), swapped like head
-    int recs_cap = 0;
-    // deferred fuse (avl_builder_set_deferred_fuse): K3 of a frame runs inside the NEXT frame's launch
-    int deferred = 0;
-    struct Pending {
-        int P = 0;                           // 0: nothing pending
-        unsigned long long frame_key = 0;
-        const float* feat = nullptr;
-    } pend;
-    unsigned long long key_bias = 0;  // set after import_map so that imported voxels order before new ones
-    ReplayLog log{};
-    long long log_cap = 0, log_used = 0;
-    char* rs_mem = nullptr;     // scratch of the log's slot-sorted form (LogSegments), allocated WITH the log: the first finalisation /
-    size_t rs_bytes = 0;        // merge of a build does not grow a pool by a GB inside its timed path (22 ms at 78 M samples)
-    size_t rs_tmp_bytes = 0;
-    BatchEntry* d_table = nullptr;
-    int table_cap = 0;
-    int64_t vox_bound = 0;       // host-side upper bound on the voxel counter (every fused sample may create one voxel)
-    int64_t max_capacity = 0;    // 0: the capacity is fixed; else the accumulators double up to this many voxels
-    // the slot-sorted replay log of the last avl_builder_replay_chain call: the round-4 merge calls it twice per merge (voxels that
-    // depend on no other rank, then the ones whose predecessor's state had to arrive first) and sorts the log once
-    LogSegments* ls_cache = nullptr;
-    long long ls_log_used = -1;
-    int64_t ls_n = -1;
-
-    // next frame's stateless half of K1 in the C frame loop (PreGather): two buffers of recs_cap records, the one K1 reads and the one
-    // being written
-    PreRec* pre_buf[2] = {nullptr, nullptr};
-    struct PreHeld {           // what pre_buf[buf] holds: the frame with exactly these inputs and parameters
-        FrameParams fp{};
-        const int32_t* samples = nullptr;
-        const void* depth = nullptr;
-        const uint8_t* rgb = nullptr;
-        int buf = 0;
-        bool valid = false;
-    } pre_held;
-    struct PreNext {           // set by avl_builder_integrate_frames for the launch being issued: the frame after it
-        const int32_t* samples = nullptr;
-        const float* depth = nullptr;
-        const uint8_t* rgb = nullptr;
-        const double* h_pc_transform = nullptr;
-    } pre_next;
-};
 
 // the parameters the stateless half of K1 reads (everything of FrameParams up to the grid shape, the mode; not pre / capacity / batch)
 static bool same_geometry(const FrameParams& a, const FrameParams& b) {
@@ -1513,8 +941,6 @@ static int read_counter(avl_builder* b, int which, int64_t* h_n, hipStream_t st)
     *h_n = (int64_t)v;
     return AVL_OK;
 }
-
-static int flush_pending(avl_builder* b, hipStream_t st);
 
 static int ensure_recs(avl_builder* b, int P, hipStream_t st) {
     if (P <= b->recs_cap) return AVL_OK;
@@ -1558,7 +984,7 @@ static int ensure_recs(avl_builder* b, int P, hipStream_t st) {
 // The reference doubles its arrays when max_id reaches their length (_reserve_map_space, vlmap_builder.py:286-311).  Here the
 // per-slot arrays are reallocated at (at least) twice the size and copied device-to-device; cell_slot is indexed by cell and
 // does not change.  Called between launches only (stream drained first).
-static int grow_builder(avl_builder* b, int64_t want, hipStream_t st) {
+int avl::grow_builder(avl_builder* b, int64_t want, hipStream_t st) {
     // `want` is a worst-case bound (every sample of the next launch creates a voxel): grow as far as allowed; if the map
     // really outgrows max_capacity the kernel's own overflow flag reports it (AVL_ERR_CAPACITY at the next counter read)
     int64_t cap = b->capacity;
@@ -1599,157 +1025,6 @@ static int grow_builder(avl_builder* b, int64_t want, hipStream_t st) {
     return AVL_OK;
 }
 
-// Compaction of the replay log to the entries that updated a voxel (slot != 0xFFFFFFFF), order kept: kLogParts contiguous parts,
-// one workgroup each -- count, one-workgroup scan of the counts, then every part writes its survivors' log position and slot behind
-// its offset (ballot ranks inside a wave, LDS across the four waves).  rocprim::select with a predicate over a counting iterator
-// took 0.92 ms for 78 M entries (0.43 GB of traffic); these three kernels read the slots twice and write 2 x 4 B per survivor.
-constexpr int kLogParts = 2048;
-
-__global__ __launch_bounds__(256) void log_count_kernel(const uint32_t* __restrict__ slot, long long L, long long chunk, int* __restrict__ counts) {
-    __shared__ int wsum[4];
-    const long long lo = (long long)blockIdx.x * chunk, hi = lo + chunk < L ? lo + chunk : L;
-    int c = 0;
-    for (long long i = lo + threadIdx.x; i < hi; i += 256) c += slot[i] != 0xFFFFFFFFu;
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-}
-
-__global__ __launch_bounds__(1024) void log_offsets_kernel(const int* __restrict__ counts, long long* __restrict__ offsets, long long* __restrict__ total) {
-    __shared__ long long part[1024];
-    static_assert(kLogParts == 2048, "two parts per thread");
-    const int t = threadIdx.x;
-    const long long a = counts[2 * t], b = counts[2 * t + 1];
-    part[t] = a + b;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        const long long v = t >= off ? part[t - off] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    const long long before = part[t] - (a + b);
-    offsets[2 * t] = before;
-    offsets[2 * t + 1] = before + a;
-    if (t == 1023) *total = part[t];
-}
-
-__global__ __launch_bounds__(256) void log_compact_kernel(const uint32_t* __restrict__ slot, long long L, long long chunk,
-                                                          const long long* __restrict__ offsets, int32_t* __restrict__ active,
-                                                          uint32_t* __restrict__ active_slot) {
-    __shared__ int wsum[4];
-    const long long lo = (long long)blockIdx.x * chunk, hi = lo + chunk < L ? lo + chunk : L;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    long long base = offsets[blockIdx.x];
-    for (long long i0 = lo; i0 < hi; i0 += 256) {                 // (chunk is a multiple of 256: a uniform trip count per workgroup)
-        const long long i = i0 + threadIdx.x;
-        const uint32_t sl = i < hi ? slot[i] : 0xFFFFFFFFu;
-        const bool keep = sl != 0xFFFFFFFFu;
-        const unsigned long long m = __ballot(keep);
-        const int rank = __popcll(m & ((1ull << lane) - 1ull));
-        if (lane == 0) wsum[wave] = __popcll(m);
-        __syncthreads();
-        int before = 0, all = 0;
-        for (int w = 0; w < 4; ++w) {
-            before += w < wave ? wsum[w] : 0;
-            all += wsum[w];
-        }
-        if (keep) {
-            active[base + before + rank] = (int32_t)i;
-            active_slot[base + before + rank] = sl;
-        }
-        base += all;
-        __syncthreads();
-    }
-}
-
-// The replay log sorted by voxel: `order` = the positions of the entries that updated a voxel, stably sorted by slot (the log is
-// in key order, so every voxel's run is in the reference's update order), [seg_start[s], seg_end[s]) = the run of slot s.
-// Only ~35 % of the sampled pixels update a voxel (depth mask, feature-image bounds): the log is first compacted to those
-// entries, and the radix sort only looks at the bits a slot index can have -- a third of the entries and three of the four
-// passes (sorting all 78 M entries of a 10 000-frame log instead: 0.58 ms per pass against 0.22).
-struct LogSegments {
-    uint32_t *active_slot = nullptr, *sorted_slot = nullptr;
-    int32_t *active = nullptr, *order = nullptr;
-    long long *seg_start = nullptr, *seg_end = nullptr, *d_count = nullptr;
-    void* tmp = nullptr;
-    char *block1 = nullptr, *block2 = nullptr;   // TWO pool allocations hold all of the above (a hipMallocAsync / hipFreeAsync pair costs
-                                                 // ~90 us of host time: nine of them were most of a small rank's replay)
-    static size_t al(size_t bytes) { return (bytes + 255) / 256 * 256; }
-    int build(avl_builder* b, int64_t n, hipStream_t st) {
-        const long long L = b->log_used;
-        const long long chunk = ((L + kLogParts - 1) / kLogParts + 255) / 256 * 256;
-        size_t tmp_bytes = 0;
-        const size_t b_active = al((size_t)L * sizeof(int32_t)), b_seg = al((size_t)n * sizeof(long long));
-        const size_t b_counts = al(kLogParts * sizeof(int)), b_off = al(kLogParts * sizeof(long long));
-        // the two L-sized arrays (and, below, the two La-sized ones + the sort's storage) come from the scratch allocated with the log
-        // when it is there and large enough; the small per-voxel arrays always from the pool
-        const bool own = b->rs_mem && b->rs_bytes >= 4 * b_active + b->rs_tmp_bytes + 256;
-        AVL_HIP_CHECK(hipMallocAsync((void**)&block1, (own ? 0 : 2 * b_active) + 256 + 2 * b_seg + b_counts + b_off, st));
-        char* p1 = block1;
-        if (own) {
-            active = reinterpret_cast<int32_t*>(b->rs_mem);
-            active_slot = reinterpret_cast<uint32_t*>(b->rs_mem + b_active);
-        } else {
-            active = reinterpret_cast<int32_t*>(p1);
-            active_slot = reinterpret_cast<uint32_t*>(p1 + b_active);
-            p1 += 2 * b_active;
-        }
-        d_count = reinterpret_cast<long long*>(p1);
-        seg_start = reinterpret_cast<long long*>(p1 + 256);
-        seg_end = reinterpret_cast<long long*>(p1 + 256 + b_seg);
-        int* counts = reinterpret_cast<int*>(p1 + 256 + 2 * b_seg);
-        long long* offsets = reinterpret_cast<long long*>(p1 + 256 + 2 * b_seg + b_counts);
-        AVL_HIP_CHECK(hipMemsetAsync(seg_start, 0, 2 * b_seg, st));
-        hipLaunchKernelGGL(log_count_kernel, dim3(kLogParts), dim3(256), 0, st, b->log.slot, L, chunk, counts);
-        hipLaunchKernelGGL(log_offsets_kernel, dim3(1), dim3(1024), 0, st, counts, offsets, d_count);
-        hipLaunchKernelGGL(log_compact_kernel, dim3(kLogParts), dim3(256), 0, st, b->log.slot, L, chunk, offsets, active, active_slot);
-        long long La = 0;
-        AVL_HIP_CHECK(hipMemcpyAsync(&La, d_count, sizeof(La), hipMemcpyDeviceToHost, st));
-        AVL_HIP_CHECK(hipStreamSynchronize(st));
-        const size_t Ls = (size_t)(La > 0 ? La : 1);
-        int bits = 1;
-        while (bits < 32 && (1ll << bits) <= (long long)n) ++bits;      // slots are < n
-        if (La > 0)
-            AVL_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr,
-                                                    (size_t)La, 0, bits, st));
-        const size_t b_ls = al(Ls * sizeof(uint32_t));
-        if (own && tmp_bytes <= b->rs_tmp_bytes) {
-            char* p2 = b->rs_mem + 2 * b_active;
-            sorted_slot = reinterpret_cast<uint32_t*>(p2);
-            order = reinterpret_cast<int32_t*>(p2 + b_ls);
-            tmp = p2 + 2 * b_active;                   // (behind the four L-sized words: La <= L)
-        } else {
-            AVL_HIP_CHECK(hipMallocAsync((void**)&block2, 2 * b_ls + al(tmp_bytes ? tmp_bytes : 16), st));
-            sorted_slot = reinterpret_cast<uint32_t*>(block2);
-            order = reinterpret_cast<int32_t*>(block2 + b_ls);
-            tmp = block2 + 2 * b_ls;
-        }
-        if (La > 0) {
-            AVL_HIP_CHECK(rocprim::radix_sort_pairs(tmp, tmp_bytes, active_slot, sorted_slot, active, order, (size_t)La, 0, bits, st));
-            hipLaunchKernelGGL(log_segments_kernel, dim3((unsigned)std::min<long long>((La + 255) / 256, 8192)), dim3(256), 0, st, sorted_slot,
-                               La, (long long)n, seg_start, seg_end);
-        }
-        AVL_HIP_CHECK(hipGetLastError());
-        return AVL_OK;
-    }
-    void release(hipStream_t st) {
-        if (block2) (void)hipFreeAsync(block2, st);
-        if (block1) (void)hipFreeAsync(block1, st);
-        block1 = block2 = nullptr;
-    }
-};
-
-static void drop_log_segments(avl_builder* b, hipStream_t st) {
-    if (!b->ls_cache) return;
-    b->ls_cache->release(st);
-    delete b->ls_cache;
-    b->ls_cache = nullptr;
-    b->ls_log_used = -1;
-    b->ls_n = -1;
-}
-
 // K3 over one launch's records (CH = 256-float register chunks of a feature row)
 // `owners_compacted`: the K2 that produced `recs` was voxelize_link_kernel with b->owners (it compacts iff P >= kAggregateSamples);
 // pipe_kernel's and voxelize_link_next_kernel's K2 never write the OwnerList, so their K3 is always wave-per-sample
@@ -1759,6 +1034,7 @@ static int launch_fuse(avl_builder* b, int P, unsigned long long frame_key, cons
     const bool compact = owners_compacted && b->D <= 1536 && P >= kAggregateSamples;
     constexpr int kWaves = AVL_K3_THREADS / 64;
     const unsigned wb = compact ? (unsigned)((P + 255) / 256) * (kFuseWaves / 4) : (unsigned)((P + kWaves - 1) / kWaves);
+    const unsigned wb_generic = (unsigned)((P + 256 / 64 - 1) / (256 / 64));     // (fuse_generic_kernel has 256 threads whatever AVL_K3_THREADS is)
 #define AVL_FUSE_LAUNCH(CH)                                                                                                              \
     do {                                                                                                                                 \
         if (compact)                                                                                                                     \
@@ -1774,7 +1050,7 @@ static int launch_fuse(avl_builder* b, int P, unsigned long long frame_key, cons
     else if (b->D <= 1024) AVL_FUSE_LAUNCH(4);
     else if (b->D <= 1536) AVL_FUSE_LAUNCH(6);     // a fused visual | audio map (512 + 1024 columns, BASELINE config 5)
     else
-        hipLaunchKernelGGL(fuse_generic_kernel, dim3(wb), dim3(256), 0, st, P, b->D, frame_key, batch, P_frame, recs, head, d_feat,
+        hipLaunchKernelGGL(fuse_generic_kernel, dim3(wb_generic), dim3(256), 0, st, P, b->D, frame_key, batch, P_frame, recs, head, d_feat,
                            b->sum_feat, b->sum_w4, b->first_feat, b->first_alpha, b->slot_key, b->dirty);
 #undef AVL_FUSE_LAUNCH
     AVL_HIP_CHECK(hipGetLastError());
@@ -1782,7 +1058,7 @@ static int launch_fuse(avl_builder* b, int P, unsigned long long frame_key, cons
 }
 
 // deferred fuse: run the K3 that is still owed (on `st`, which must be the stream the frame was integrated on)
-static int flush_pending(avl_builder* b, hipStream_t st) {
+int avl::flush_pending(avl_builder* b, hipStream_t st) {
     if (b->pend.P == 0) return AVL_OK;
     const int P = b->pend.P;
     b->pend.P = 0;
@@ -1914,20 +1190,16 @@ int avl_builder_enable_replay_log(avl_builder* b, int64_t max_samples) {
     (void)hipFree(b->rs_mem);
     b->rs_mem = nullptr;
     b->rs_bytes = b->rs_tmp_bytes = 0;
-    {
-        size_t tb = 0;
-        if (rocprim::radix_sort_pairs(nullptr, tb, (uint32_t*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, (size_t)max_samples, 0, 32,
-                                      nullptr) == hipSuccess) {
-            const size_t w = ((size_t)max_samples * 4 + 255) / 256 * 256;
-            const size_t total = 4 * w + (tb + 255) / 256 * 256 + 256;
-            if (hipMalloc((void**)&b->rs_mem, total) == hipSuccess) {
-                b->rs_bytes = total;
-                b->rs_tmp_bytes = (tb + 255) / 256 * 256;
-            } else {
-                b->rs_mem = nullptr;      // (not fatal: LogSegments falls back to the stream-ordered pool)
-            }
+    if (const size_t tb = replay_sort_tmp_bytes(max_samples)) {
+        const size_t w = ((size_t)max_samples * 4 + 255) / 256 * 256;
+        const size_t total = 4 * w + (tb + 255) / 256 * 256 + 256;
+        if (hipMalloc((void**)&b->rs_mem, total) == hipSuccess) {
+            b->rs_bytes = total;
+            b->rs_tmp_bytes = (tb + 255) / 256 * 256;
+        } else {
+            b->rs_mem = nullptr;      // (not fatal: LogSegments falls back to the stream-ordered pool)
+            (void)hipGetLastError();
         }
-        (void)hipGetLastError();
     }
     return AVL_OK;
 }
@@ -2200,547 +1472,6 @@ int avl_builder_num_groups(avl_builder* b, int64_t* h_n, void* stream) {
     AVL_REQUIRE(b && h_n, "avl_builder_num_groups: null argument");
     if (int rc = flush_pending(b, as_stream(stream)); rc != AVL_OK) return rc;
     return read_counter(b, 2, h_n, as_stream(stream));
-}
-
-static int launch_finalize(int64_t n, int D, int gs, int vh, int64_t row0, const int32_t* perm, const int32_t* d_cell,
-                           const double* d_sum_feat, int64_t ld_sf, const double* d_sum_w4, int64_t ld_w4, const float* d_first_feat,
-                           const double* d_first_alpha, float* d_grid_feat, int32_t* d_grid_pos, float* d_weight,
-                           uint8_t* d_grid_rgb, int32_t* d_occupied_ids, hipStream_t st) {
-    int64_t blocks = (n + 3) / 4;
-    const int64_t maxb = (int64_t)num_cus() * 16;
-    if (blocks > maxb) blocks = maxb;
-    hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)blocks), dim3(256), 0, st, n, D, gs, vh, row0, perm, d_cell, d_sum_feat, ld_sf,
-                       d_sum_w4, ld_w4, d_first_feat, d_first_alpha, d_grid_feat, d_grid_pos, d_weight, d_grid_rgb, d_occupied_ids);
-    AVL_HIP_CHECK(hipGetLastError());
-    return AVL_OK;
-}
-
-int avl_finalize_raw(int64_t n, int D, int gs, int vh, const int32_t* d_cell, const double* d_sum_feat,
-                     const double* d_sum_w4, const float* d_first_feat, const double* d_first_alpha, float* d_grid_feat,
-                     int32_t* d_grid_pos, float* d_weight, uint8_t* d_grid_rgb, int32_t* d_occupied_ids, void* stream) {
-    AVL_REQUIRE(n >= 0 && D > 0 && gs > 0 && vh > 0, "avl_finalize_raw: bad shape");
-    if (n == 0) return AVL_OK;
-    AVL_REQUIRE(d_cell && d_sum_w4 && d_first_alpha, "avl_finalize_raw: null input");
-    AVL_REQUIRE(!d_grid_feat || (d_sum_feat && d_first_feat), "avl_finalize_raw: grid_feat needs sum_feat and first_feat");
-    return launch_finalize(n, D, gs, vh, 0, nullptr, d_cell, d_sum_feat, D, d_sum_w4, 4, d_first_feat, d_first_alpha, d_grid_feat,
-                           d_grid_pos, d_weight, d_grid_rgb, d_occupied_ids, as_stream(stream));
-}
-
-int avl_finalize_merged(int64_t n, int64_t row0, int D, int gs, int vh, const int32_t* d_cell, const double* d_acc,
-                        int64_t ld_acc, float* d_grid_feat, int32_t* d_grid_pos, float* d_weight, uint8_t* d_grid_rgb,
-                        int32_t* d_occupied_ids, void* stream) {
-    AVL_REQUIRE(n >= 0 && row0 >= 0 && D > 0 && gs > 0 && vh > 0 && ld_acc >= D + 4, "avl_finalize_merged: bad shape");
-    AVL_REQUIRE(row0 + n < (1ll << 31), "avl_finalize_merged: voxel ids must fit int32");
-    if (n == 0) return AVL_OK;
-    AVL_REQUIRE(d_cell && d_acc, "avl_finalize_merged: null input");
-    return launch_finalize(n, D, gs, vh, row0, nullptr, d_cell, d_acc, ld_acc, d_acc + D, ld_acc, nullptr, nullptr, d_grid_feat,
-                           d_grid_pos, d_weight, d_grid_rgb, d_occupied_ids, as_stream(stream));
-}
-
-int avl_builder_scatter_merge(avl_builder* b, int64_t n, const int64_t* d_row_of_slot, const uint64_t* d_global_key,
-                              double* d_acc, int64_t ld_acc, void* stream) {
-    AVL_REQUIRE(b, "avl_builder_scatter_merge: null handle");
-    hipStream_t st = as_stream(stream);
-    int64_t have = 0;
-    int rc = avl_builder_num_voxels(b, &have, stream);
-    if (rc != AVL_OK) return rc;
-    AVL_REQUIRE(n == have, "avl_builder_scatter_merge: n=%lld but the map holds %lld voxels", (long long)n, (long long)have);
-    AVL_REQUIRE(ld_acc >= b->D + 4, "avl_builder_scatter_merge: ld_acc must be >= D + 4");
-    if (n == 0) return AVL_OK;
-    AVL_REQUIRE(d_row_of_slot && d_global_key && d_acc, "avl_builder_scatter_merge: null pointer");
-    int64_t blocks = (n + 3) / 4;
-    const int64_t maxb = (int64_t)num_cus() * 16;
-    if (blocks > maxb) blocks = maxb;
-    hipLaunchKernelGGL(scatter_merge_kernel, dim3((unsigned)blocks), dim3(256), 0, st, n, b->D, d_row_of_slot,
-                       reinterpret_cast<const unsigned long long*>(d_global_key), b->slot_key, b->sum_feat, b->sum_w4, b->first_feat,
-                       b->first_alpha, d_acc, ld_acc);
-    AVL_HIP_CHECK(hipGetLastError());
-    return AVL_OK;
-}
-
-static int check_slot_list(avl_builder* b, int64_t k, const void* slots, const void* out, int64_t ld, const char* who, void* stream) {
-    AVL_REQUIRE(b, "%s: null handle", who);
-    AVL_REQUIRE(k >= 0 && ld >= b->D, "%s: bad shape", who);
-    int64_t have = 0;
-    int rc = avl_builder_num_voxels(b, &have, stream);
-    if (rc != AVL_OK) return rc;
-    AVL_REQUIRE(k <= have, "%s: %lld slots listed but the map holds %lld voxels", who, (long long)k, (long long)have);
-    AVL_REQUIRE(k == 0 || (slots && out), "%s: null pointer", who);
-    return AVL_OK;
-}
-
-int avl_builder_export_rows_f32(avl_builder* b, int64_t k, const int32_t* d_slots, float* d_out, int64_t ld, void* stream) {
-    int rc = check_slot_list(b, k, d_slots, d_out, ld, "avl_builder_export_rows_f32", stream);
-    if (rc != AVL_OK || k == 0) return rc;
-    const int64_t blocks = std::min<int64_t>((k + 3) / 4, (int64_t)num_cus() * 16);
-    hipLaunchKernelGGL(export_rows_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), k, b->D, d_slots, b->sum_feat,
-                       b->sum_w4, b->first_feat, b->first_alpha, d_out, ld);
-    AVL_HIP_CHECK(hipGetLastError());
-    return AVL_OK;
-}
-
-int avl_builder_export_rows_f64(avl_builder* b, int64_t k, const int32_t* d_slots, const uint8_t* d_own, double* d_out, int64_t ld,
-                                void* stream) {
-    int rc = check_slot_list(b, k, d_slots, d_out, ld, "avl_builder_export_rows_f64", stream);
-    if (rc != AVL_OK || k == 0) return rc;
-    AVL_REQUIRE(d_own, "avl_builder_export_rows_f64: null ownership flags");
-    const int64_t blocks = std::min<int64_t>((k + 3) / 4, (int64_t)num_cus() * 16);
-    hipLaunchKernelGGL(export_rows_f64_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), k, b->D, d_slots, d_own, b->sum_feat,
-                       b->first_feat, b->first_alpha, d_out, ld);
-    AVL_HIP_CHECK(hipGetLastError());
-    return AVL_OK;
-}
-
-int avl_builder_m2_pack(avl_builder* b, int64_t n, int ws, int rank, int64_t own_r0, const int64_t* h_cum, const int64_t* h_lo,
-                        const int64_t* h_dlo, const int64_t* h_row0, const int64_t* h_side_off, const int64_t* h_done_off,
-                        const int64_t* h_part_off, const int32_t* d_order, const int32_t* d_row, const int32_t* d_prev, const int32_t* d_next,
-                        const int32_t* d_sidx, int64_t* d_send, float* d_own_feat, void* stream) {
-    AVL_REQUIRE(b, "avl_builder_m2_pack: null handle");
-    AVL_REQUIRE(n >= 0 && ws >= 1 && ws <= 64 && rank >= 0 && rank < ws && own_r0 >= 0, "avl_builder_m2_pack: bad arguments");
-    hipStream_t st = as_stream(stream);
-    int rc = flush_pending(b, st);
-    if (rc != AVL_OK) return rc;
-    if (n == 0) return AVL_OK;
-    AVL_REQUIRE(n <= b->capacity, "avl_builder_m2_pack: n=%lld exceeds the capacity %lld", (long long)n, (long long)b->capacity);
-    AVL_REQUIRE(h_cum && h_lo && h_dlo && h_row0 && h_side_off && h_done_off && h_part_off && d_order && d_row && d_prev && d_next && d_sidx && d_send,
-                "avl_builder_m2_pack: null pointer");
-    M2PackSeg sg{};
-    for (int q = 0; q <= 64; ++q) sg.cum[q] = h_cum[q < ws ? q : ws];
-    for (int q = 0; q < ws; ++q) {
-        sg.lo[q] = h_lo[q];
-        sg.dlo[q] = h_dlo[q];
-        sg.row0[q] = h_row0[q];
-        sg.side_off[q] = h_side_off[q];
-        sg.done_off[q] = h_done_off[q];
-        sg.part_off[q] = h_part_off[q];
-    }
-    AVL_REQUIRE(sg.cum[0] == 0 && sg.cum[ws] == n, "avl_builder_m2_pack: the destination ranges cover %lld voxels, n = %lld", sg.cum[ws], (long long)n);
-    int64_t blocks = (n + 3) / 4;
-    const int64_t maxb = (int64_t)num_cus() * 16;
-    if (blocks > maxb) blocks = maxb;
-    hipLaunchKernelGGL(m2_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (long long)n, ws, rank, b->D, (long long)own_r0, sg, d_order, d_row,
-                       d_prev, d_next, d_sidx, b->sum_feat, b->sum_w4, b->first_feat, b->first_alpha, reinterpret_cast<long long*>(d_send),
-                       d_own_feat);
-    AVL_HIP_CHECK(hipGetLastError());
-    return AVL_OK;
-}
-
-int avl_finalize_side(int64_t n, int64_t row0, int gs, int vh, const int32_t* d_cell, const double* d_w4, int32_t* d_grid_pos,
-                      float* d_weight, uint8_t* d_grid_rgb, int32_t* d_occupied_ids, void* stream) {
-    AVL_REQUIRE(n >= 0 && row0 >= 0 && gs > 0 && vh > 0, "avl_finalize_side: bad shape");
-    AVL_REQUIRE(row0 + n < (1ll << 31), "avl_finalize_side: voxel ids must fit int32");
-    if (n == 0) return AVL_OK;
-    AVL_REQUIRE(d_cell && d_w4, "avl_finalize_side: null input");
-    hipLaunchKernelGGL(finalize_side_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 8192)), dim3(256), 0, as_stream(stream), n, gs,
-                       vh, row0, d_cell, d_w4, d_grid_pos, d_weight, d_grid_rgb, d_occupied_ids);
-    AVL_HIP_CHECK(hipGetLastError());
-    return AVL_OK;
-}
-
-int avl_builder_finalize(avl_builder* b, int64_t n, float* d_grid_feat, int32_t* d_grid_pos, float* d_weight,
-                         uint8_t* d_grid_rgb, int32_t* d_occupied_ids, void* stream) {
-    return avl_builder_finalize_ex(b, n, d_grid_feat, d_grid_pos, d_weight, d_grid_rgb, d_occupied_ids, nullptr, 0, stream);
-}
-
-static int ensure_log_segments(avl_builder* b, int64_t n, hipStream_t st);
-
-int avl_builder_finalize_ex(avl_builder* b, int64_t n, float* d_grid_feat, int32_t* d_grid_pos, float* d_weight,
-                            uint8_t* d_grid_rgb, int32_t* d_occupied_ids, uint8_t* d_row_dirty, int clear_dirty, void* stream) {
-    AVL_REQUIRE(b, "avl_builder_finalize: null handle");
-    hipStream_t st = as_stream(stream);
-    int64_t have = 0;
-    int rc = avl_builder_num_voxels(b, &have, stream);
-    if (rc != AVL_OK) return rc;
-    AVL_REQUIRE(n == have, "avl_builder_finalize: n=%lld but the map holds %lld voxels", (long long)n, (long long)have);
-    if (d_occupied_ids) AVL_HIP_CHECK(hipMemsetAsync(d_occupied_ids, 0xFF, b->ncell * sizeof(int32_t), st));
-    if (n == 0) {
-        AVL_HIP_CHECK(hipStreamSynchronize(st));
-        return AVL_OK;
-    }
-    // rows in the reference's voxel-id order = slots sorted by first-touch key
-    unsigned long long* keys_out = nullptr;
-    int32_t *iota = nullptr, *perm = nullptr;
-    void* tmp = nullptr;
-    size_t tmp_bytes = 0;
-    // one pool allocation for the four temporaries (each hipMallocAsync / hipFreeAsync pair is ~90 us of host time)
-    AVL_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, b->slot_key, keys_out, iota, perm, (size_t)n, 0, 64, st));
-    const size_t b_keys = ((size_t)n * sizeof(unsigned long long) + 255) / 256 * 256, b_idx = ((size_t)n * sizeof(int32_t) + 255) / 256 * 256;
-    char* block = nullptr;
-    AVL_HIP_CHECK(hipMallocAsync((void**)&block, b_keys + 2 * b_idx + (tmp_bytes ? tmp_bytes : 16), st));
-    keys_out = reinterpret_cast<unsigned long long*>(block);
-    iota = reinterpret_cast<int32_t*>(block + b_keys);
-    perm = reinterpret_cast<int32_t*>(block + b_keys + b_idx);
-    tmp = block + b_keys + 2 * b_idx;
-    hipLaunchKernelGGL(iota_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, st, iota, n);
-    AVL_HIP_CHECK(rocprim::radix_sort_pairs(tmp, tmp_bytes, b->slot_key, keys_out, iota, perm, (size_t)n, 0, 64, st));
-    rc = launch_finalize(n, b->D, b->gs, b->vh, 0, perm, b->slot_cell, b->sum_feat, b->D, b->sum_w4, 4, b->first_feat, b->first_alpha,
-                         d_grid_feat, d_grid_pos, d_weight, d_grid_rgb, d_occupied_ids, st);
-    if (rc == AVL_OK && b->log.slot && b->key_bias == 0 && b->log_used > 0 && (d_weight || d_grid_rgb)) {
-        // exact sequential weight / grid_rgb: stable sort of the key-ordered log by slot, then replay per voxel
-        // (the builder's ONE voxel-sorted form of the log, shared with the merge's replay: it lives in the scratch allocated with the log,
-        // so a private second build here would overwrite a cached one; it stays valid until the next frame is fused)
-        rc = ensure_log_segments(b, n, st);
-        if (rc == AVL_OK) {
-            const LogSegments& ls = *b->ls_cache;
-            hipLaunchKernelGGL(replay_rgb_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 8192)), dim3(256), 0, st, n,
-                               (long long)b->n0 * b->gs, perm, keys_out, ls.order, ls.seg_start, ls.seg_end, b->log, d_weight, d_grid_rgb);
-            if (hipGetLastError() != hipSuccess) rc = AVL_ERR_HIP;
-        }
-    }
-    if (rc == AVL_OK && d_row_dirty) {
-        hipLaunchKernelGGL(row_dirty_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 8192)), dim3(256), 0, st, n, perm, b->dirty,
-                           d_row_dirty, clear_dirty);
-        if (hipGetLastError() != hipSuccess) rc = AVL_ERR_HIP;
-    }
-    (void)hipFreeAsync(block, st);
-    if (rc != AVL_OK) return rc;
-    AVL_HIP_CHECK(hipStreamSynchronize(st));
-    return AVL_OK;
-}
-
-int avl_builder_drop_replay_cache(avl_builder* b, void* stream) {
-    AVL_REQUIRE(b, "avl_builder_drop_replay_cache: null handle");
-    drop_log_segments(b, as_stream(stream));
-    return AVL_OK;
-}
-
-// the log sorted by voxel (LogSegments), built if it is not there: a merge asks for it FIRST, so that the compaction, the sort and the one
-// host synchronisation in between run under the plan's host work and collectives instead of in front of the replay
-static int ensure_log_segments(avl_builder* b, int64_t n, hipStream_t st) {
-    if (b->ls_cache && b->ls_log_used == b->log_used && b->ls_n == n) return AVL_OK;
-    drop_log_segments(b, st);
-    b->ls_cache = new LogSegments();
-    int rc = b->ls_cache->build(b, n, st);
-    if (rc != AVL_OK) {
-        drop_log_segments(b, st);
-        return rc;
-    }
-    b->ls_log_used = b->log_used;
-    b->ls_n = n;
-    return AVL_OK;
-}
-
-int avl_builder_replay_prepare(avl_builder* b, int64_t n, void* stream) {
-    AVL_REQUIRE(b, "avl_builder_replay_prepare: null handle");
-    int64_t have = 0;
-    int rc = avl_builder_num_voxels(b, &have, stream);
-    if (rc != AVL_OK) return rc;
-    AVL_REQUIRE(n == have, "avl_builder_replay_prepare: n=%lld but the map holds %lld voxels", (long long)n, (long long)have);
-    if (!b->log.slot || b->key_bias != 0 || n == 0 || b->log_used == 0) return AVL_OK;      // (nothing to prepare: replay_chain reports a missing log)
-    // (a build on a stream of the builder's own, overlapping the merge plan's host work, was measured in round 6: nothing in the 8-rank
-    // rehearsal, +10 ms on the first merge of a process for the stream and its events -- the form is built on the caller's stream)
-    return ensure_log_segments(b, n, as_stream(stream));
-}
-
-int avl_builder_replay_chain(avl_builder* b, int64_t n, const int64_t* d_row_of_slot, uint64_t grow_key, void* d_state,
-                             void* stream) {
-    AVL_REQUIRE(b, "avl_builder_replay_chain: null handle");
-    hipStream_t st = as_stream(stream);
-    int64_t have = 0;
-    int rc = avl_builder_num_voxels(b, &have, stream);
-    if (rc != AVL_OK) return rc;
-    AVL_REQUIRE(n == have, "avl_builder_replay_chain: n=%lld but the map holds %lld voxels", (long long)n, (long long)have);
-    if (!b->log.slot || b->key_bias != 0) {
-        set_error("avl_builder_replay_chain: the builder has no replay log (avl_builder_enable_replay_log on a fresh builder)");
-        return AVL_ERR_STATE;
-    }
-    if (n == 0 || b->log_used == 0) return AVL_OK;
-    AVL_REQUIRE(d_row_of_slot && d_state, "avl_builder_replay_chain: null pointer");
-    rc = ensure_log_segments(b, n, st);
-    if (rc != AVL_OK) return rc;
-    const LogSegments& ls = *b->ls_cache;
-    hipLaunchKernelGGL(replay_chain_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 8192)), dim3(256), 0, st, n,
-                       (unsigned long long)grow_key, d_row_of_slot, ls.order, ls.seg_start, ls.seg_end, b->log,
-                       reinterpret_cast<ReplayState*>(d_state));
-    if (hipGetLastError() != hipSuccess) rc = AVL_ERR_HIP;
-    return rc;
-}
-
-// dst[d_rows[i] - row0, 0:cols] += src[i, 0:cols]  (float64): folds the contributions one rank received from ONE peer into its
-// block of final rows.  A peer holds a voxel at most once, so the rows of a call are distinct: plain read-modify-write, and the
-// caller's peer-by-peer order of the calls fixes the summation order (reproducible merges).  Wave per row.
-__global__ __launch_bounds__(256) void rows_add_f64_kernel(int64_t n, int cols, const int64_t* __restrict__ rows, int64_t row0, int64_t nrows,
-                                                           const double* __restrict__ src, int64_t ld_src, double* __restrict__ dst,
-                                                           int64_t ld_dst, int* __restrict__ err_flag) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    for (int64_t i = wave0; i < n; i += nwaves) {
-        const int64_t r = rows[i] - row0;
-        if (r < 0 || r >= nrows) {
-            if (lane == 0 && err_flag) atomicOr(err_flag, 1);
-            continue;
-        }
-        const double* a = src + i * ld_src;
-        double* o = dst + r * ld_dst;
-        for (int c = lane; c < cols; c += 64) o[c] += a[c];
-    }
-}
-
-// the same for rows of a few columns (the four [alpha, alpha rgb] sums of a side record): a lane per element, not a wave per row
-__global__ __launch_bounds__(256) void rows_add_f64_narrow_kernel(int64_t n, int cols, const int64_t* __restrict__ rows, int64_t row0, int64_t nrows,
-                                                                  const double* __restrict__ src, int64_t ld_src, double* __restrict__ dst,
-                                                                  int64_t ld_dst, int* __restrict__ err_flag) {
-    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n * cols; t += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t i = t / cols;
-        const int c = (int)(t - i * cols);
-        const int64_t r = rows[i] - row0;
-        if (r < 0 || r >= nrows) {
-            if (c == 0 && err_flag) atomicOr(err_flag, 1);
-            continue;
-        }
-        dst[r * ld_dst + c] += src[i * ld_src + c];
-    }
-}
-
-static void launch_rows_add(int64_t n, int cols, const int64_t* d_rows, int64_t row0, int64_t nrows, const double* d_src, int64_t ld_src,
-                            double* d_dst, int64_t ld_dst, int* flag, hipStream_t st) {
-    const int64_t maxb = (int64_t)num_cus() * 16;
-    if (cols <= 16) {
-        const int64_t blocks = std::min<int64_t>((n * cols + 255) / 256, maxb);
-        hipLaunchKernelGGL(rows_add_f64_narrow_kernel, dim3((unsigned)blocks), dim3(256), 0, st, n, cols, d_rows, row0, nrows, d_src, ld_src, d_dst,
-                           ld_dst, flag);
-    } else {
-        const int64_t blocks = std::min<int64_t>((n + 3) / 4, maxb);
-        hipLaunchKernelGGL(rows_add_f64_kernel, dim3((unsigned)blocks), dim3(256), 0, st, n, cols, d_rows, row0, nrows, d_src, ld_src, d_dst, ld_dst,
-                           flag);
-    }
-}
-
-int avl_rows_add_f64(int64_t n, int cols, const int64_t* d_rows, int64_t row0, int64_t nrows, const double* d_src, int64_t ld_src,
-                     double* d_dst, int64_t ld_dst, void* stream) {
-    AVL_REQUIRE(n >= 0 && cols > 0 && nrows >= 0 && ld_src >= cols && ld_dst >= cols, "avl_rows_add_f64: bad shape");
-    if (n == 0) return AVL_OK;
-    AVL_REQUIRE(d_rows && d_src && d_dst, "avl_rows_add_f64: null pointer");
-    hipStream_t st = as_stream(stream);
-    int* flag = static_cast<int*>(avl::scratch(64));
-    if (!flag) return AVL_ERR_HIP;
-    AVL_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(int), st));
-    launch_rows_add(n, cols, d_rows, row0, nrows, d_src, ld_src, d_dst, ld_dst, flag, st);
-    int h = 0;
-    AVL_HIP_CHECK(hipMemcpyAsync(&h, flag, sizeof(int), hipMemcpyDeviceToHost, st));
-    AVL_HIP_CHECK(hipStreamSynchronize(st));
-    AVL_REQUIRE(h == 0, "avl_rows_add_f64: a row index lies outside [row0, row0 + nrows)");
-    return AVL_OK;
-}
-
-int avl_rows_add_f64_async(int64_t n, int cols, const int64_t* d_rows, int64_t row0, int64_t nrows, const double* d_src, int64_t ld_src,
-                           double* d_dst, int64_t ld_dst, int32_t* d_err_flag, void* stream) {
-    AVL_REQUIRE(n >= 0 && cols > 0 && nrows >= 0 && ld_src >= cols && ld_dst >= cols, "avl_rows_add_f64_async: bad shape");
-    if (n == 0) return AVL_OK;
-    AVL_REQUIRE(d_rows && d_src && d_dst && d_err_flag, "avl_rows_add_f64_async: null pointer");
-    launch_rows_add(n, cols, d_rows, row0, nrows, d_src, ld_src, d_dst, ld_dst, reinterpret_cast<int*>(d_err_flag), as_stream(stream));
-    AVL_HIP_CHECK(hipGetLastError());
-    return AVL_OK;
-}
-
-// out[rows[i], :] = (float)(acc[i, :] / w[rows[i]]): the shared rows of a rank's block from their float64 sums -- finalize_kernel's
-// division -- without the (k, D) float64 and float32 temporaries of the tensor expression.  Wave per row.
-__global__ __launch_bounds__(256) void rows_div_f32_kernel(int64_t k, int D, const double* __restrict__ acc, const int64_t* __restrict__ rows,
-                                                           const double* __restrict__ w4, float* __restrict__ out, int64_t n_out,
-                                                           int* __restrict__ err_flag) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    for (int64_t i = wave0; i < k; i += nwaves) {
-        const int64_t r = rows[i];
-        if (r < 0 || r >= n_out) {
-            if (lane == 0 && err_flag) atomicOr(err_flag, 1);
-            continue;
-        }
-        const double w = w4[r * 4];
-        const double* a = acc + i * D;
-        float* o = out + r * D;
-        for (int c = lane; c < D; c += 64) o[c] = (float)(a[c] / w);
-    }
-}
-
-int avl_rows_div_f32(int64_t k, int D, const double* d_acc, const int64_t* d_rows, const double* d_w4, float* d_out, int64_t n_out,
-                     int32_t* d_err_flag, void* stream) {
-    AVL_REQUIRE(k >= 0 && D > 0 && n_out >= 0, "avl_rows_div_f32: bad shape");
-    if (k == 0) return AVL_OK;
-    AVL_REQUIRE(d_acc && d_rows && d_w4 && d_out, "avl_rows_div_f32: null pointer");
-    int64_t blocks = (k + 3) / 4;
-    const int64_t maxb = (int64_t)num_cus() * 16;
-    if (blocks > maxb) blocks = maxb;
-    hipLaunchKernelGGL(rows_div_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), k, D, d_acc, d_rows, d_w4, d_out, n_out,
-                       reinterpret_cast<int*>(d_err_flag));
-    AVL_HIP_CHECK(hipGetLastError());
-    return AVL_OK;
-}
-
-int avl_replay_state_apply(int64_t n, const void* d_state, float* d_weight, uint8_t* d_grid_rgb, void* stream) {
-    AVL_REQUIRE(n >= 0, "avl_replay_state_apply: bad n");
-    if (n == 0) return AVL_OK;
-    AVL_REQUIRE(d_state, "avl_replay_state_apply: null state");
-    hipLaunchKernelGGL(replay_apply_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 8192)), dim3(256), 0, as_stream(stream), n,
-                       reinterpret_cast<const ReplayState*>(d_state), d_weight, d_grid_rgb);
-    AVL_HIP_CHECK(hipGetLastError());
-    return AVL_OK;
-}
-
-int avl_builder_import_map(avl_builder* b, int64_t n, const float* d_grid_feat, const int32_t* d_grid_pos,
-                           const float* d_weight, const uint8_t* d_grid_rgb, void* stream) {
-    AVL_REQUIRE(b, "avl_builder_import_map: null handle");
-    AVL_REQUIRE(n >= 0, "avl_builder_import_map: bad n");
-    hipStream_t st = as_stream(stream);
-    // a map that grew past the initial capacity (the reference doubles its arrays, _reserve_map_space vlmap_builder.py:286-311,
-    // and resumes such a map): grow like a frame launch would, if the handle is allowed to
-    if (n > b->capacity && b->max_capacity > b->capacity) {
-        const int rcg = grow_builder(b, n, st);
-        if (rcg != AVL_OK) return rcg;
-    }
-    AVL_REQUIRE(n <= b->capacity, "avl_builder_import_map: %lld voxels exceed the capacity %lld (avl_builder_set_max_capacity lets it grow)",
-                (long long)n, (long long)b->capacity);
-    int64_t have = 0;
-    int rc = avl_builder_num_voxels(b, &have, stream);
-    if (rc != AVL_OK) return rc;
-    if (have != 0) {
-        set_error("avl_builder_import_map: the map already holds %lld voxels (import into an empty builder)", (long long)have);
-        return AVL_ERR_STATE;
-    }
-    if (n == 0) {
-        b->key_bias = 1ull << 62;   // continuing a map: the voxels of new frames order after every imported one (none here: the
-        return AVL_OK;              // other ranks of a resumed multi-GPU build import nothing but must use the same key space)
-    }
-    AVL_REQUIRE(d_grid_feat && d_grid_pos && d_weight, "avl_builder_import_map: null input");
-    int64_t blocks = (n + 3) / 4;
-    const int64_t maxb = (int64_t)num_cus() * 16;
-    if (blocks > maxb) blocks = maxb;
-    hipLaunchKernelGGL(import_map_kernel, dim3((unsigned)blocks), dim3(256), 0, st, n, b->D, b->n0, b->gs, b->vh, d_grid_feat, d_grid_pos,
-                       d_weight, d_grid_rgb, b->cell_slot, b->slot_cell, b->slot_key, b->sum_feat, b->sum_w4, b->first_feat,
-                       b->first_alpha, b->err_flags);
-    const unsigned long long nn = (unsigned long long)n;
-    AVL_HIP_CHECK(hipMemcpyAsync(b->counters, &nn, sizeof(nn), hipMemcpyHostToDevice, st));
-    int flags = 0;
-    AVL_HIP_CHECK(hipMemcpyAsync(&flags, b->err_flags, sizeof(int), hipMemcpyDeviceToHost, st));
-    AVL_HIP_CHECK(hipStreamSynchronize(st));
-    if (flags & 4) {
-        set_error("avl_builder_import_map: a grid_pos row lies outside the (gs, gs, vh) grid");
-        return AVL_ERR_INVALID;
-    }
-    b->key_bias = 1ull << 62;
-    b->vox_bound = n;
-    return AVL_OK;
-}
-
-int avl_builder_export_raw(avl_builder* b, int64_t n, int32_t* d_cell, uint64_t* d_first_key, double* d_sum_feat,
-                           double* d_sum_w4, float* d_first_feat, double* d_first_alpha, void* stream) {
-    AVL_REQUIRE(b, "avl_builder_export_raw: null handle");
-    hipStream_t st = as_stream(stream);
-    int64_t have = 0;
-    int rc = avl_builder_num_voxels(b, &have, stream);
-    if (rc != AVL_OK) return rc;
-    AVL_REQUIRE(n >= 0 && n <= have, "avl_builder_export_raw: n=%lld but the map holds %lld voxels", (long long)n, (long long)have);
-    if (n == 0) return AVL_OK;
-    const size_t D = (size_t)b->D;
-    auto cp = [&](void* dst, const void* src, size_t bytes) {
-        return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st) : hipSuccess;
-    };
-    AVL_HIP_CHECK(cp(d_cell, b->slot_cell, (size_t)n * sizeof(int32_t)));
-    AVL_HIP_CHECK(cp(d_first_key, b->slot_key, (size_t)n * sizeof(uint64_t)));
-    AVL_HIP_CHECK(cp(d_sum_feat, b->sum_feat, (size_t)n * D * sizeof(double)));
-    AVL_HIP_CHECK(cp(d_sum_w4, b->sum_w4, (size_t)n * 4 * sizeof(double)));
-    AVL_HIP_CHECK(cp(d_first_feat, b->first_feat, (size_t)n * D * sizeof(float)));
-    AVL_HIP_CHECK(cp(d_first_alpha, b->first_alpha, (size_t)n * sizeof(double)));
-    return AVL_OK;
-}
-
-// values of the sort below: 0, 1, 2, ...
-__global__ void iota64_kernel(int64_t* __restrict__ v, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) v[i] = i;
-}
-
-}  // extern "C"
-
-template <typename K>
-static hipError_t argsort_bits_impl(void* tmp, size_t& tmp_bytes, const void* keys, void* keys_out, const int64_t* iota, int64_t* perm,
-                                    int64_t n, int bits, hipStream_t st) {
-    // LSD radix sort over the low `bits` bits only (the keys are non-negative and smaller than 2^bits): stable
-    return rocprim::radix_sort_pairs(tmp, tmp_bytes, reinterpret_cast<const K*>(keys), reinterpret_cast<K*>(keys_out), iota, perm,
-                                     (size_t)n, 0, bits, st);
-}
-
-static size_t argsort_align(size_t b) { return (b + 255) / 256 * 256; }
-
-extern "C" {
-
-int avl_argsort_bits_work_bytes(int64_t n, int key_bytes, int bits, size_t* h_bytes) {
-    AVL_REQUIRE(h_bytes && n >= 0 && n < (1ll << 31) && (key_bytes == 4 || key_bytes == 8) && bits >= 1 && bits <= 8 * key_bytes - 1,
-                "avl_argsort_bits_work_bytes: bad arguments");
-    size_t tmp_bytes = 0;
-    const hipError_t e = key_bytes == 8 ? argsort_bits_impl<uint64_t>(nullptr, tmp_bytes, nullptr, nullptr, nullptr, nullptr, n ? n : 1, bits, nullptr)
-                                        : argsort_bits_impl<uint32_t>(nullptr, tmp_bytes, nullptr, nullptr, nullptr, nullptr, n ? n : 1, bits, nullptr);
-    AVL_HIP_CHECK(e);
-    // [values 0..n-1 | sorted keys | rocPRIM's own storage (its size depends on the bit range: rocPRIM picks the passes by it)]
-    *h_bytes = argsort_align((size_t)n * 8) + argsort_align((size_t)n * key_bytes) + argsort_align(tmp_bytes) + 256;
-    return AVL_OK;
-}
-
-int avl_argsort_bits(int64_t n, const void* d_keys, int key_bytes, int bits, int64_t* d_perm, void* d_work, size_t work_bytes,
-                     void* stream) {
-    AVL_REQUIRE(n >= 0 && n < (1ll << 31), "avl_argsort_bits: bad n");
-    AVL_REQUIRE(key_bytes == 4 || key_bytes == 8, "avl_argsort_bits: keys are int32 or int64");
-    AVL_REQUIRE(bits >= 1 && bits <= 8 * key_bytes - 1, "avl_argsort_bits: bits must be in [1, %d]", 8 * key_bytes - 1);
-    if (n == 0) return AVL_OK;
-    AVL_REQUIRE(d_keys && d_perm && d_work, "avl_argsort_bits: null pointer");
-    size_t need = 0;
-    int rc = avl_argsort_bits_work_bytes(n, key_bytes, bits, &need);
-    if (rc != AVL_OK) return rc;
-    AVL_REQUIRE(work_bytes >= need, "avl_argsort_bits: work buffer of %zu bytes, %zu needed (avl_argsort_bits_work_bytes)", work_bytes, need);
-    hipStream_t st = as_stream(stream);
-    char* w = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(d_work) + 255) / 256 * 256);
-    int64_t* iota = reinterpret_cast<int64_t*>(w);
-    void* keys_out = w + argsort_align((size_t)n * 8);
-    void* tmp = reinterpret_cast<char*>(keys_out) + argsort_align((size_t)n * key_bytes);
-    size_t tmp_bytes = need - 256 - argsort_align((size_t)n * 8) - argsort_align((size_t)n * key_bytes);
-    hipLaunchKernelGGL(iota64_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, st, iota, n);
-    const hipError_t e = key_bytes == 8 ? argsort_bits_impl<uint64_t>(tmp, tmp_bytes, d_keys, keys_out, iota, d_perm, n, bits, st)
-                                        : argsort_bits_impl<uint32_t>(tmp, tmp_bytes, d_keys, keys_out, iota, d_perm, n, bits, st);
-    if (e != hipSuccess) {
-        set_error("avl_argsort_bits: %s", hipGetErrorString(e));
-        return AVL_ERR_HIP;
-    }
-    return AVL_OK;
-}
-
-int avl_points_bbox(const void* d_depth, int depth_is_u16, double depth_div, int H, int W, const double* h_calib_inv,
-                    const double* h_transform, const int32_t* d_sample_idx, int P, double min_depth, double max_depth,
-                    double* h_minmax, void* stream) {
-    AVL_REQUIRE(H > 0 && W > 0 && P >= 0 && h_calib_inv && h_transform && h_minmax, "avl_points_bbox: bad arguments");
-    if (P == 0) return AVL_OK;
-    AVL_REQUIRE(d_depth && d_sample_idx, "avl_points_bbox: null pointer");
-    hipStream_t st = as_stream(stream);
-    auto key = [](double v) {
-        unsigned long long u;
-        memcpy(&u, &v, 8);
-        return (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
-    };
-    auto unkey = [](unsigned long long k) {
-        unsigned long long u = (k & 0x8000000000000000ull) ? (k & 0x7fffffffffffffffull) : ~k;
-        double v;
-        memcpy(&v, &u, 8);
-        return v;
-    };
-    unsigned long long h_keys[6];
-    for (int i = 0; i < 6; ++i) h_keys[i] = key(h_minmax[i]);
-    unsigned long long* d_keys = nullptr;
-    AVL_HIP_CHECK(hipMallocAsync((void**)&d_keys, sizeof(h_keys), st));
-    AVL_HIP_CHECK(hipMemcpyAsync(d_keys, h_keys, sizeof(h_keys), hipMemcpyHostToDevice, st));
-    FrameParams fp{};
-    for (int i = 0; i < 9; ++i) fp.kinv[i] = h_calib_inv[i];
-    for (int i = 0; i < 16; ++i) fp.t[i] = h_transform[i];
-    fp.min_depth = min_depth; fp.max_depth = max_depth;
-    fp.H = H; fp.W = W; fp.P = P;
-    fp.depth_u16 = depth_is_u16 ? 1 : 0;
-    fp.depth_div = depth_div;
-    hipLaunchKernelGGL(bbox_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, fp, reinterpret_cast<const float*>(d_depth),
-                       d_sample_idx, d_keys);
-    AVL_HIP_CHECK(hipMemcpyAsync(h_keys, d_keys, sizeof(h_keys), hipMemcpyDeviceToHost, st));
-    AVL_HIP_CHECK(hipStreamSynchronize(st));
-    (void)hipFreeAsync(d_keys, st);
-    for (int i = 0; i < 6; ++i) h_minmax[i] = unkey(h_keys[i]);
-    return AVL_OK;
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // The multi-GPU merge of the map build, second form ("gather plan"): everything a rank computes between two collectives is ONE
-// entry point of this file (or avl_builder_m2_pack in avl_builder.hip, which needs the accumulators), with no host
+// entry point of this file (or avl_builder_m2_pack in avl_finalize.hip, which needs the accumulators), with no host
 // synchronisation inside except the single read-back of the plan's sizes.
 //
 // What is merged: the ranks' voxel maps of the reference's builder loop (avlmaps/map/vlmap_builder.py:102-183), frames sharded
@@ -218,7 +218,7 @@ __global__ void m2_state_scatter_kernel(long long k, const int32_t* __restrict__
 }
 
 struct M2Seg {
-    long long cum[kM2MaxRanks + 1];     // as M2PackSeg (avl_builder.hip): record t serves rank q with cum[q] <= t < cum[q + 1]
+    long long cum[kM2MaxRanks + 1];     // as M2PackSeg (avl_finalize.hip): record t serves rank q with cum[q] <= t < cum[q + 1]
     long long lo[kM2MaxRanks];          // ... and is voxel lo[q] + (t - cum[q]) of the rank's final-row order
     long long side_off[kM2MaxRanks];    // word offset of destination q's side records in the send buffer
 };
@@ -330,7 +330,7 @@ __global__ __launch_bounds__(256) void m2_fold_scalar_kernel(long long n_own, lo
 
 // Owner side, step 3.  Wave per group of 16 rows, the rows that still need their features one after the other: a single-rank voxel's
 // finished float32 row is copied, a voxel several ranks touched gets (sum over the contributors, in rank order, of their float64
-// partial rows) / sum alpha -- finalize_kernel's expression (avl_builder.hip).
+// partial rows) / sum alpha -- finalize_kernel's expression (avl_finalize.hip).
 __global__ __launch_bounds__(256) void m2_fold_feat_kernel(long long n_own, int ws, int D, long long ldf, long long ldp, M2Peers pe,
                                                            const int32_t* __restrict__ table, const double* __restrict__ wsum,
                                                            const uint8_t* __restrict__ need, float* __restrict__ grid_feat) {
