@@ -144,6 +144,7 @@ _SIGS = {
     "avl_field_normalize": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp]),
     "avl_planar_decay": (C.c_int, [_vp, _i64, _i64, _i64, _f64, _vp, _vp]),
     "avl_goal_fuse": (C.c_int, [_vp, C.c_int, _vp, _i64, _vp, C.POINTER(_i64), C.POINTER(_f64), _vp, _vp]),
+    "avl_product_argmax_2d": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, C.POINTER(_i64), C.POINTER(_f64), _vp]),
     "avl_nav_create": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.POINTER(_vp)]),
     "avl_nav_destroy": (C.c_int, [_vp]),
     "avl_nav_num_vertices": (C.c_int, [_vp, C.POINTER(_i64)]),
@@ -159,6 +160,10 @@ _SIGS = {
     "avl_dilate_map": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _f64, _vp, _vp, _vp, _sz, _vp]),
     "avl_mask_foreground_work_bytes": (C.c_int, [C.c_int, C.c_int, C.POINTER(_sz)]),
     "avl_mask_foreground": (C.c_int, [_vp, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _sz, _vp]),
+    "avl_gauss2d_f32": (C.c_int, [_vp, C.c_int, _i64, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _f64, _vp, _vp]),
+    "avl_edt2d_work_bytes": (C.c_int, [C.c_int, C.c_int, C.POINTER(_sz)]),
+    "avl_edt2d": (C.c_int, [_vp, _i64, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _sz, _vp]),
+    "avl_mask_decay_2d": (C.c_int, [_vp, _i64, C.c_int, C.c_int, _f64, _f64, C.c_int, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

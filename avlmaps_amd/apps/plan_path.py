@@ -2,7 +2,7 @@
 setup_scene + move_to (robot/habitat_lang_robot.py:88-104, 432-461) without the simulator.
 
     python -m avlmaps_amd.apps.plan_path --data-dir <scene> --query sofa --start ROW COL [--text-model clip|hash]
-                                        [--area NAME]... [--sound NAME]... [--image PNG]
+                                        [--area NAME]... [--sound NAME]... [--image PNG] [--goal-2d]
                                         [--customize-obstacles [--potential-obstacles a,b,c --obstacles a,b]
                                          [--dilate-iter N] [--gaussian-sigma S]]
 
@@ -17,6 +17,11 @@ voxel, and the planner snaps a goal on an obstacle cell to the nearest free cell
 "goal_value" (0.0: the modalities do not overlap anywhere) and "goal_cell", the voxel's own cell; "goal" is that cell clamped into
 the cropped obstacle map, which differs only when the voxel's height is outside --h-min / --h-max and nothing in the band reaches
 that far.
+
+With --goal-2d the goal is taken on the planner's own grid instead: the cell of AVLMap.index_goal_2d(obj=--query, area=..,
+sound=..), the first maximum of the product of the 2-D distribution maps over the obstacle crop (habitat_lang_robot.py:357-375,
+419-425).  The JSON line then has "goal_value" and "goal_cell"; the cell lies inside the crop, so "goal" equals it.  --image has no
+2-D map and is rejected.
 
 With --customize-obstacles the path is planned on Map.get_customized_obstacle_cropped() as upstream's robot does
 (habitat_lang_robot.py:89-104): VLMap.customize_obstacle_map keeps only the obstacles whose class is one of --obstacles among
@@ -43,6 +48,8 @@ def parse_args(argv=None):
     ap.add_argument("--sound", action="append", default=[], help="cross-modal goal: a sound name (repeatable)")
     ap.add_argument("--image", default=None, help="cross-modal goal: a query image (PNG)")
     ap.add_argument("--image-pose", type=int, default=0, help="row of poses.txt the model-free localiser places the image at")
+    ap.add_argument("--goal-2d", action="store_true",
+                    help="take the goal from the 2-D distribution maps over the obstacle crop (AVLMap.index_goal_2d)")
     ap.add_argument("--customize-obstacles", action="store_true",
                     help="plan on the customised obstacle map (VLMap.customize_obstacle_map) instead of the raw one")
     ap.add_argument("--potential-obstacles", default=None, help="comma separated class list the voxels are scored against")
@@ -53,6 +60,8 @@ def parse_args(argv=None):
     if not args.customize_obstacles and any(v is not None for v in (args.potential_obstacles, args.obstacles, args.dilate_iter,
                                                                     args.gaussian_sigma)):
         ap.error("--potential-obstacles, --obstacles, --dilate-iter and --gaussian-sigma belong to --customize-obstacles")
+    if args.goal_2d and args.image:
+        ap.error("--goal-2d takes --query, --area and --sound: an image query has no 2-D map")
     return args
 
 
@@ -66,7 +75,7 @@ def obstacle_overrides(args) -> dict:
 
 
 def is_cross_modal(args) -> bool:
-    return bool(args.area or args.sound or args.image)
+    return bool(args.area or args.sound or args.image or args.goal_2d)
 
 
 def clamp_cell(cell, rmin, cmin, shape):
@@ -116,6 +125,10 @@ def main(argv=None):
     extra = {}
     if avlmap is None:
         goal = vm.get_nearest_pos(start, args.query)
+    elif args.goal_2d:
+        g = avlmap.index_goal_2d(obj=args.query, area=args.area or None, sound=args.sound or None, want_heat=False)
+        goal = [int(g.cell[0]), int(g.cell[1])]
+        extra = {"goal_value": g.value, "goal_cell": [float(g.cell[0]), float(g.cell[1])]}
     else:
         img = None
         if args.image:

@@ -31,6 +31,7 @@ SOURCES = {
     "avl_nav.hip": ["-ffp-contract=off"],          # the query predicates and path lengths round like the float64 oracle
     "avl_goal.hip": ["-ffp-contract=off"],         # every term of the fused goal is the stand-alone query's value bit for bit
     "avl_morph2d.hip": ["-ffp-contract=off"],      # the gaussian multiplies and adds in SciPy's order, without fused multiply-adds
+    "avl_edt2d.hip": ["-ffp-contract=off"],        # the decay and the normalisation round like NumPy's float64 expressions
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fvisibility=hidden", "-Wall",
           "-Wno-unused-function", "-munsafe-fp-atomics"]

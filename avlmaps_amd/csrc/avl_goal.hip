@@ -146,14 +146,90 @@ __global__ __launch_bounds__(kWave) void goal_finish_kernel(const double* __rest
     if (threadIdx.x == 0) {
         res->index = bi;
         res->value = bv;
-        for (int k = 0; k < 3; ++k) res->pos[k] = bi == LLONG_MAX ? 0 : pos[3 * bi + k];   // (LLONG_MAX: every product is NaN)
+        for (int k = 0; k < 3; ++k) res->pos[k] = (bi == LLONG_MAX || !pos) ? 0 : pos[3 * bi + k];   // (LLONG_MAX: every product is NaN)
         res->pad = 0;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- 2-D windows
+struct WindowTerms {
+    avl_window_term t[AVL_GOAL_MAX_TERMS];
+    int K;
+};
+
+// the product of K (h, w) windows, left to right in float64, and its first maximum in raster order: index = row * w + col
+__global__ __launch_bounds__(kGoalThreads) void window_product_kernel(const WindowTerms a, int h, int w, double* __restrict__ out,
+                                                                     double* __restrict__ part_v, long long* __restrict__ part_i) {
+    __shared__ double s_bv[kGoalWaves];
+    __shared__ long long s_bi[kGoalWaves];
+    double bv = -INFINITY;
+    long long bi = LLONG_MAX;
+    const int64_t n = (int64_t)h * w;
+    for (int64_t i = (int64_t)blockIdx.x * kGoalThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kGoalThreads) {
+        const int64_t r = i / w, c = i - r * w;
+        double acc = 0.0;
+        for (int k = 0; k < a.K; ++k) {
+            const avl_window_term& t = a.t[k];
+            const int64_t at = r * t.ld + c;
+            const double v = t.is_f64 ? static_cast<const double*>(t.d_data)[at] : (double)static_cast<const float*>(t.d_data)[at];
+            acc = k == 0 ? v : acc * v;
+        }
+        if (out) out[i] = acc;
+        if (goal_better(acc, i, bv, bi)) { bv = acc; bi = i; }
+    }
+    wave_best(bv, bi);
+    const int wv = threadIdx.x / kWave;
+    if ((threadIdx.x & (kWave - 1)) == 0) { s_bv[wv] = bv; s_bi[wv] = bi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < kGoalWaves; ++k)
+            if (goal_better(s_bv[k], s_bi[k], bv, bi)) { bv = s_bv[k]; bi = s_bi[k]; }
+        part_v[blockIdx.x] = bv;
+        part_i[blockIdx.x] = bi;
     }
 }
 
 }  // namespace avl
 
 using namespace avl;
+
+extern "C" int avl_product_argmax_2d(const avl_window_term* h_terms, int K, int h, int w, double* d_out, int64_t* h_index, double* h_value,
+                                     void* stream) {
+    AVL_REQUIRE(h_terms, "avl_product_argmax_2d: null terms");
+    AVL_REQUIRE(K >= 1 && K <= AVL_GOAL_MAX_TERMS, "avl_product_argmax_2d: K = %d terms, need 1 .. %d", K, AVL_GOAL_MAX_TERMS);
+    AVL_REQUIRE(h >= 1 && w >= 1 && h <= 32768 && w <= 32768, "avl_product_argmax_2d: bad window %d x %d", h, w);
+    WindowTerms a;
+    a.K = K;
+    for (int k = 0; k < AVL_GOAL_MAX_TERMS; ++k) a.t[k] = avl_window_term{};
+    for (int k = 0; k < K; ++k) {
+        AVL_REQUIRE(h_terms[k].d_data, "avl_product_argmax_2d: term %d: null data pointer", k);
+        AVL_REQUIRE(h_terms[k].ld >= w, "avl_product_argmax_2d: term %d: rows of %lld values cannot hold %d columns", k,
+                    (long long)h_terms[k].ld, w);
+        a.t[k] = h_terms[k];
+    }
+    AVL_REQUIRE(d_out || h_index || h_value, "avl_product_argmax_2d: no output requested");
+    hipStream_t st = as_stream(stream);
+    const int64_t n = (int64_t)h * w;
+    const int nb = (int)std::max<int64_t>(1, std::min<int64_t>((n + kGoalThreads - 1) / kGoalThreads, (int64_t)num_cus() * 8));
+    const size_t off_i = (size_t)nb * sizeof(double), off_res = off_i + (size_t)nb * sizeof(long long);
+    char* sc = static_cast<char*>(avl::scratch(off_res + sizeof(GoalResult)));
+    if (!sc) return AVL_ERR_HIP;
+    double* d_pv = reinterpret_cast<double*>(sc);
+    long long* d_pi = reinterpret_cast<long long*>(sc + off_i);
+    GoalResult* d_res = reinterpret_cast<GoalResult*>(sc + off_res);
+    hipLaunchKernelGGL(window_product_kernel, dim3((unsigned)nb), dim3(kGoalThreads), 0, st, a, h, w, d_out, d_pv, d_pi);
+    AVL_HIP_CHECK(hipGetLastError());
+    if (!h_index && !h_value) return AVL_OK;
+    hipLaunchKernelGGL(goal_finish_kernel, dim3(1), dim3(kWave), 0, st, d_pv, d_pi, nb, (const int32_t*)nullptr, d_res);
+    AVL_HIP_CHECK(hipGetLastError());
+    GoalResult res;
+    AVL_HIP_CHECK(hipMemcpyAsync(&res, d_res, sizeof(res), hipMemcpyDeviceToHost, st));
+    AVL_HIP_CHECK(hipStreamSynchronize(st));
+    AVL_REQUIRE(res.index != LLONG_MAX, "avl_product_argmax_2d: every product is NaN");
+    if (h_index) *h_index = res.index;
+    if (h_value) *h_value = res.value;
+    return AVL_OK;
+}
 
 extern "C" int avl_goal_fuse(const avl_goal_term* h_terms, int K, const int32_t* d_grid_pos, int64_t N, double* d_out, int64_t* h_index,
                              double* h_value, int32_t* h_pos3, void* stream) {

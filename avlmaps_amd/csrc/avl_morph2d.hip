@@ -119,6 +119,11 @@ struct SrcF64 {
     int64_t ld;
     __device__ __forceinline__ double at(int r, int c) const { return p[(int64_t)r * ld + c]; }
 };
+struct SrcF32 {
+    const float* p;
+    int64_t ld;
+    __device__ __forceinline__ double at(int r, int c) const { return (double)p[(int64_t)r * ld + c]; }
+};
 // the (2h, 2w) bilinear x2 up-sampling of an (h, w) 0/1 image, never stored (cv2.resize, INTER_LINEAR, half-pixel centres,
 // replicated border): every value is a multiple of 1/16, exact in any evaluation order
 struct SrcUp2 {
@@ -137,31 +142,35 @@ struct SrcUp2 {
     }
 };
 
-// axis 0 (down the columns): out[r, c] = sum_j w[j] src[reflect(r + j), c] in SciPy's symmetric order
-template <class Src>
-__global__ __launch_bounds__(256) void gauss_axis0_kernel(Src src, int H, int W, GaussW gw, int radius, double* __restrict__ out) {
+// axis 0 (down the columns): out[r, c] = sum_j w[j] src[reflect(r + j), c] in SciPy's symmetric order.  T = the array type SciPy
+// filters in: double, or float for a float32 image -- SciPy then still accumulates every line in double and rounds what it stores
+template <class Src, class T = double>
+__global__ __launch_bounds__(256) void gauss_axis0_kernel(Src src, int H, int W, GaussW gw, int radius, T* __restrict__ out) {
     const int c = blockIdx.x * 64 + (threadIdx.x & 63);
     const int r = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (r >= H || c >= W) return;
     double tmp = src.at(r, c) * gw.w[radius];
     for (int j = -radius; j < 0; ++j) tmp += (src.at(reflect_index(r + j, H), c) + src.at(reflect_index(r - j, H), c)) * gw.w[j + radius];
-    out[(int64_t)r * W + c] = tmp;
+    out[(int64_t)r * W + c] = (T)tmp;
 }
 
-// axis 1 (along the rows) of the float64 intermediate; optional value output, optional `> threshold` output, and (any != nullptr)
-// a flag that is set when one cell passes the threshold
-__global__ __launch_bounds__(256) void gauss_axis1_kernel(const double* __restrict__ in, int H, int W, GaussW gw, int radius,
-                                                          double* __restrict__ out, uint8_t* __restrict__ gt, double threshold,
+// axis 1 (along the rows) of the intermediate (float64, or float32 rounded as SciPy stores it); optional value output, optional
+// `> threshold` output of the stored value, and (any != nullptr) a flag that is set when one cell passes the threshold
+template <class T = double>
+__global__ __launch_bounds__(256) void gauss_axis1_kernel(const T* __restrict__ in, int H, int W, GaussW gw, int radius,
+                                                          T* __restrict__ out, uint8_t* __restrict__ gt, double threshold,
                                                           int* __restrict__ any) {
     const int c = blockIdx.x * 64 + (threadIdx.x & 63);
     const int r = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (r >= H || c >= W) return;
-    const double* row = in + (int64_t)r * W;
-    double tmp = row[c] * gw.w[radius];
-    for (int j = -radius; j < 0; ++j) tmp += (row[reflect_index(c + j, W)] + row[reflect_index(c - j, W)]) * gw.w[j + radius];
-    if (out) out[(int64_t)r * W + c] = tmp;
+    const T* row = in + (int64_t)r * W;
+    double tmp = (double)row[c] * gw.w[radius];
+    for (int j = -radius; j < 0; ++j)
+        tmp += ((double)row[reflect_index(c + j, W)] + (double)row[reflect_index(c - j, W)]) * gw.w[j + radius];
+    const T val = (T)tmp;
+    if (out) out[(int64_t)r * W + c] = val;
     if (gt) {
-        const bool on = tmp > threshold;
+        const bool on = (double)val > threshold;
         gt[(int64_t)r * W + c] = on;
         if (any && on) atomicOr(any, 1);
     }
@@ -284,7 +293,27 @@ int avl_gauss2d_f64(const void* d_in, int in_is_u8, int H, int W, const double* 
         hipLaunchKernelGGL(gauss_axis0_kernel<SrcU8>, grid2d(H, W), dim3(256), 0, st, SrcU8{(const uint8_t*)d_in, W}, H, W, gw, radius, d_tmp);
     else
         hipLaunchKernelGGL(gauss_axis0_kernel<SrcF64>, grid2d(H, W), dim3(256), 0, st, SrcF64{(const double*)d_in, W}, H, W, gw, radius, d_tmp);
-    hipLaunchKernelGGL(gauss_axis1_kernel, grid2d(H, W), dim3(256), 0, st, (const double*)d_tmp, H, W, gw, radius, d_out_f64, d_out_gt_u8,
+    hipLaunchKernelGGL(gauss_axis1_kernel<double>, grid2d(H, W), dim3(256), 0, st, (const double*)d_tmp, H, W, gw, radius, d_out_f64, d_out_gt_u8,
+                       threshold, (int*)nullptr);
+    AVL_HIP_CHECK(hipGetLastError());
+    return AVL_OK;
+}
+
+int avl_gauss2d_f32(const void* d_in, int in_is_u8, int64_t ld, int H, int W, const double* h_weights, int radius, float* d_out_f32,
+                    uint8_t* d_out_gt_u8, double threshold, float* d_tmp, void* stream) {
+    AVL_REQUIRE(H > 0 && W > 0 && H <= kMaxSide && W <= kMaxSide && d_in && d_tmp && ld >= W, "avl_gauss2d_f32: bad image arguments");
+    AVL_REQUIRE(d_out_f32 || d_out_gt_u8, "avl_gauss2d_f32: no output requested");
+    GaussW gw;
+    int rc = make_weights(h_weights, radius, &gw, "avl_gauss2d_f32");
+    if (rc != AVL_OK) return rc;
+    hipStream_t st = as_stream(stream);
+    if (in_is_u8)
+        hipLaunchKernelGGL((gauss_axis0_kernel<SrcU8, float>), grid2d(H, W), dim3(256), 0, st, SrcU8{(const uint8_t*)d_in, ld}, H, W, gw, radius,
+                           d_tmp);
+    else
+        hipLaunchKernelGGL((gauss_axis0_kernel<SrcF32, float>), grid2d(H, W), dim3(256), 0, st, SrcF32{(const float*)d_in, ld}, H, W, gw, radius,
+                           d_tmp);
+    hipLaunchKernelGGL(gauss_axis1_kernel<float>, grid2d(H, W), dim3(256), 0, st, (const float*)d_tmp, H, W, gw, radius, d_out_f32, d_out_gt_u8,
                        threshold, (int*)nullptr);
     AVL_HIP_CHECK(hipGetLastError());
     return AVL_OK;
@@ -345,7 +374,7 @@ int avl_dilate_map(const uint8_t* d_binary_u8, int H, int W, int dilate_iter, do
     uint8_t* dist = thr + align256(up);
     if (dilate_iter == 0) AVL_HIP_CHECK(hipMemsetAsync(any, 0, sizeof(int), st));
     hipLaunchKernelGGL(gauss_axis0_kernel<SrcUp2>, grid2d(H2, W2), dim3(256), 0, st, SrcUp2{d_binary_u8, H, W}, H2, W2, gw, radius, tmp);
-    hipLaunchKernelGGL(gauss_axis1_kernel, grid2d(H2, W2), dim3(256), 0, st, (const double*)tmp, H2, W2, gw, radius, (double*)nullptr, thr, 0.5,
+    hipLaunchKernelGGL(gauss_axis1_kernel<double>, grid2d(H2, W2), dim3(256), 0, st, (const double*)tmp, H2, W2, gw, radius, (double*)nullptr, thr, 0.5,
                        dilate_iter == 0 ? any : (int*)nullptr);
     if (dilate_iter == 0) {
         const int64_t cells = (int64_t)H * W;
@@ -393,7 +422,7 @@ int avl_mask_foreground(const uint8_t* d_mask2d_u8, int64_t ld, int r0, int r1, 
     rc = launch_morph(a, W, H, W, 1, 0, 3, b, nullptr, st);
     if (rc != AVL_OK) return rc;
     hipLaunchKernelGGL(gauss_axis0_kernel<SrcU8>, grid2d(H, W), dim3(256), 0, st, SrcU8{b, W}, H, W, gw, radius, tmp);
-    hipLaunchKernelGGL(gauss_axis1_kernel, grid2d(H, W), dim3(256), 0, st, (const double*)tmp, H, W, gw, radius, (double*)nullptr, a, 0.5,
+    hipLaunchKernelGGL(gauss_axis1_kernel<double>, grid2d(H, W), dim3(256), 0, st, (const double*)tmp, H, W, gw, radius, (double*)nullptr, a, 0.5,
                        (int*)nullptr);
     AVL_HIP_CHECK(hipGetLastError());
     return launch_morph(a, W, H, W, 0, 0, 1, d_out_u8, nullptr, st);

@@ -306,6 +306,37 @@ class AVLMap:
         res = ops.goal_fuse(terms, self.vlmap._device_pos(), want_heat=want_heat)
         return Goal(res.heat.numpy() if want_heat else None, res.index, res.value, res.pos)
 
+    def index_goal_2d(self, obj=None, area=None, sound=None, decay_rates=None, want_heat: bool = True) -> "Goal2D":
+        """The cross-modal goal on the planner's grid: the float64 product of 2-D maps over the obstacle crop
+        [rmin:rmax + 1, cmin:cmax + 1] and the cell of its first maximum (habitat_lang_robot.py:357-375 get_map / get_major_map
+        and :419-425 get_max_pos), on the GPU (csrc/avl_edt2d.hip, csrc/avl_goal.hip).
+
+        obj, area, sound, decay_rates: as in index_goal, same factor order (objects, areas, sounds).  An object factor is
+        vlmap.get_distribution_map(name, rate); an area / sound factor is the crop window of index_area_2d / index_sound_2d as this
+        class returns them, i.e. normalised over the FULL map.  The definition is the NumPy product of those stand-alone public
+        calls, bit for bit; it makes no claim to equal upstream's region maps, which are built and normalised on the crop.
+
+        Raises what the stand-alone queries raise; ValueError without any term.  goal.cell is a full-map (row, col), what
+        Navigator.plan_to takes; goal.value == 0.0 means the modalities do not overlap anywhere on the crop."""
+        from .. import ops
+        specs = self._goal_specs(obj, area, sound, None, (), decay_rates)
+        if not specs:
+            raise ValueError("index_goal_2d needs at least one of obj, area, sound")
+        if len(specs) > ops.GOAL_MAX_TERMS:
+            raise ValueError(f"a goal is the product of 1 to {ops.GOAL_MAX_TERMS} terms, got {len(specs)}")
+        vm = self.vlmap
+        r0, r1, c0, c1 = vm._crop_window()
+        terms = []
+        for kind, what, rate in specs:
+            if kind == "obj":
+                terms.append(vm._distribution_map_device(what, rate))
+            else:
+                gf = self._area_field(what, rate) if kind == "area" else self._sound_field(what, rate)
+                self._check_bounds(gf, f"{kind} {what!r}")
+                terms.append(ops.Window(ops.field_normalize(gf), r0, r1, c0, c1))
+        res = ops.product_argmax_2d(terms, want_heat=want_heat)
+        return Goal2D(res.heat.numpy() if want_heat else None, res.value, (res.cell[0] + r0, res.cell[1] + c0))
+
     def get_max_pos_3d(self, heat: np.ndarray) -> np.ndarray:
         """grid_pos of the first maximum of a host (N,) float32 / float64 heat.  Reference: habitat_lang_robot.py:427-430."""
         from .. import ops
@@ -330,3 +361,14 @@ class Goal:
     @property
     def cell(self) -> np.ndarray:
         return self.pos[:2]
+
+
+class Goal2D:
+    """AVLMap.index_goal_2d's answer: heat (h, w) float64 over the obstacle crop (None with want_heat=False), value = its maximum
+    (0.0: the modalities do not overlap), cell = the full-map (row, col) of the first maximum in raster order, what
+    Navigator.plan_to takes."""
+    __slots__ = ("heat", "value", "cell")
+
+    def __init__(self, heat, value, cell):
+        self.heat, self.value = heat, float(value)
+        self.cell = np.asarray(cell, dtype=np.int64)

@@ -97,6 +97,26 @@ class Map:
     def init_categories(self, categories: List[str]) -> np.ndarray:
         return NotImplementedError
 
+    def get_distribution_map(self, name: str, decay_rate: float = 0.1) -> np.ndarray:
+        """Abstract upstream (map.py:153-154); VLMap implements it."""
+        raise NotImplementedError(f"{type(self).__name__} has no 2-D distribution map")
+
+    def get_predict_mask(self, name: str) -> np.ndarray:
+        """Abstract upstream (map.py:156-157); VLMap implements it."""
+        raise NotImplementedError(f"{type(self).__name__} has no predicted mask")
+
+    def get_max_pos(self, map_2d: np.ndarray):
+        """(row + rmin, col + cmin) of the first maximum of a map over the obstacle crop: np.argmax + np.unravel_index plus the crop
+        offset, found on the GPU (ops.product_argmax_2d).  Reference: habitat_lang_robot.py:419-425."""
+        from .. import ops
+        m = np.asarray(map_2d)
+        if m.ndim != 2 or m.size == 0:
+            raise ValueError(f"expected a non-empty 2-D map, got shape {m.shape}")
+        if m.dtype not in (np.float32, np.float64):
+            m = m.astype(np.float64)
+        row, col = ops.product_argmax_2d([m], want_heat=False).cell
+        return row + self.rmin, col + self.cmin
+
     def get_obstacle_cropped(self) -> np.ndarray:
         """Reference: map.py:159-160."""
         return self.obstacles_cropped

@@ -299,6 +299,52 @@ class VLMap(Map):
         _, am = self._score(q, want_scores=False)          # rows sharded over ranks: the argmax blocks are all-gathered
         return am == 0
 
+    # ------------------------------------------------------------------ 2-D goal maps
+    def _crop_window(self):
+        """(r0, r1, c0, c1) of the obstacle crop on the full map; the obstacle map is generated on first use"""
+        if self.obstacles_cropped is None:
+            self.generate_obstacle_map()
+        return int(self.rmin), int(self.rmax) + 1, int(self.cmin), int(self.cmax) + 1
+
+    def _predict_mask_device(self, name: str):
+        """the (gs, gs) uint8 top-down mask of the voxels whose argmax is `name`'s category, on the device"""
+        from .. import ops
+        from ..device import DeviceArray
+        from ..utils.index_utils import find_similar_category_id
+        if self.scores_mat is None or self.categories is None:
+            raise Exception("Categories are not preloaded. Call init_categories(categories: List[str]) to initialize categories.")
+        cat_id = find_similar_category_id(name, self.categories)
+        if getattr(self, "_argmax_src", None) is not self.scores_mat:       # scores_mat was replaced from outside
+            self._argmax, self._argmax_src = np.argmax(self.scores_mat, axis=1), self.scores_mat
+        if getattr(self, "_dev_argmax_src", None) is not self._argmax:      # the argmax goes up once per init_categories
+            self._dev_argmax = DeviceArray.from_numpy(np.ascontiguousarray(self._argmax, dtype=np.int32))
+            self._dev_argmax_src = self._argmax
+        mask = ops.mask_from_argmax(self._dev_argmax, cat_id)
+        return ops.pool_label_2d(mask, self._device_pos(), int(self.gs), device=True)
+
+    def get_predict_mask(self, name: str) -> np.ndarray:
+        """The top-down mask of a category over the obstacle crop: 1 where a voxel whose argmax over scores_mat is the category
+        lies in the column, in obstacles_cropped's shape and dtype.  Reference: vlmap_3d.py:75-81.  The comparison and the pooling
+        run on the GPU (avl_mask_from_argmax, avl_pool_label_2d) and the pooled mask is cut to [rmin:rmax + 1, cmin:cmax + 1]:
+        voxels outside the crop are dropped, where upstream's fancy index would wrap around (negative offsets) or raise IndexError."""
+        r0, r1, c0, c1 = self._crop_window()
+        pooled = self._predict_mask_device(name).numpy()
+        return pooled[r0:r1, c0:c1].astype(np.asarray(self.obstacles_cropped).dtype)
+
+    def _distribution_map_device(self, name: str, decay_rate: float = 0.1):
+        from .. import ops
+        window = self._crop_window()
+        return ops.mask_decay_2d(self._predict_mask_device(name), decay_rate, normalize=True, smooth_sigma=1, device=True, window=window)
+
+    def get_distribution_map(self, name: str, decay_rate: float = 0.1) -> np.ndarray:
+        """The 2-D distribution map of a category over the obstacle crop, (h, w) float64.  Reference:
+        habitat_lang_robot.py:229-240 get_vl_distribution_map: predicted mask -> gaussian_filter(float32, sigma=1) > 0.5 ->
+        distance_transform_edt(mask == 0) -> 1 - d * decay_rate, negative values 0 -> min-max normalisation.  The whole chain runs on
+        the GPU (avl_gauss2d_f32, avl_mask_decay_2d) with SciPy's and NumPy's bits; between the voxel argmax and the finished map
+        only status flags come back to the host.  ValueError when no cell survives the smoothing (a category without a voxel) or the
+        map is constant."""
+        return self._distribution_map_device(name, decay_rate).numpy()
+
     def customize_obstacle_map(self, potential_obstacle_names: List[str], obstacle_names: List[str], vis: bool = False):
         """Reference: vlmap.py:127-156 (like upstream the class lists and the smoothing parameters come from map_config, not from
         the arguments).  The class scoring and the scatter run on the GPU (avl_obstacle_scatter), and so does the 2-D smoothing

@@ -22,3 +22,12 @@ def pool_3d_label_to_2d(mask_3d: np.ndarray, grid_pos: np.ndarray, gs: int) -> n
     voxels upstream; here one scatter kernel, avl_pool_label_2d).  grid_pos / mask_3d may be device-resident."""
     from .. import ops
     return ops.pool_label_2d(mask_3d, grid_pos, int(gs))
+
+
+def get_heatmap_from_mask_2d(mask: np.ndarray, cell_size: float = 0.05, decay_rate: float = 0.01) -> np.ndarray:
+    """Distance-decay heat of a 2-D mask, (H, W) float64: 1 - distance_transform_edt(mask == 0) / cell_size * decay_rate, negative
+    values 0.  Reference: visualize_utils.py:97-102 (scipy's EDT upstream; here the exact transform of csrc/avl_edt2d.hip and the
+    decay in one chain on the GPU, NumPy's bits).  A mask without a set cell raises ValueError (upstream: distances to an imaginary
+    cell outside the image)."""
+    from .. import ops
+    return ops.mask_decay_2d(np.asarray(mask) != 0, decay_rate, cell_size=cell_size)

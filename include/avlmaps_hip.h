@@ -713,6 +713,22 @@ typedef struct avl_goal_term {
 AVL_API int avl_goal_fuse(const avl_goal_term* h_terms, int K, const int32_t* d_grid_pos, int64_t N, double* d_out, int64_t* h_index,
                           double* h_value, int32_t* h_pos3, void* stream);
 
+/* The same product over 2-D windows: avlmaps/robot/habitat_lang_robot.py:357-375 get_map(..) * get_major_map(..) * ... on (h, w)
+ * host arrays, then get_max_pos (:419-425), np.argmax + np.unravel_index.  A term is an (h, w) window of a row-major float32 or
+ * float64 device image: d_data points at the window's first value, ld is the image's row length in values. */
+typedef struct avl_window_term {
+    const void* d_data;   /* the window's first value */
+    int64_t ld;           /* values per image row, >= w */
+    int32_t is_f64;       /* 1: float64, 0: float32 (widened exactly) */
+    int32_t reserved;     /* 0 */
+} avl_window_term;
+/* h_terms: K windows on the host, 1 <= K <= AVL_GOAL_MAX_TERMS, multiplied left to right in float64.  d_out (h, w) float64 receives
+ * the product, or NULL.  h_index / h_value (each may be NULL) receive row * w + col of the first maximum in raster order and the
+ * product there; with either of them the call is synchronous.  A NaN product never wins; all NaN is AVL_ERR_INVALID.  Arguments are
+ * checked before any device work. */
+AVL_API int avl_product_argmax_2d(const avl_window_term* h_terms, int K, int h, int w, double* d_out, int64_t* h_index, double* h_value,
+                                  void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * (8) visibility-graph navigation on the 2-D obstacle map (csrc/avl_nav.hip)
  *     The obstacle map is (H, W) uint8, nonzero = free, 0 = obstacle (Map.obstacles_cropped).  Obstacle pixel (r, c) is the point
@@ -786,6 +802,38 @@ AVL_API int avl_dilate_map(const uint8_t* d_binary_u8, int H, int W, int dilate_
 AVL_API int avl_mask_foreground_work_bytes(int H, int W, size_t* bytes);
 AVL_API int avl_mask_foreground(const uint8_t* d_mask2d_u8, int64_t ld, int r0, int r1, int c0, int c1, uint8_t* d_out_u8, void* ws,
                                 size_t ws_bytes, void* stream);
+
+/* scipy.ndimage.gaussian_filter(x.astype(np.float32), sigma, truncate=t) as avlmaps/robot/habitat_lang_robot.py:231-232 calls it
+ * on the predicted mask: SciPy filters a float32 array in float32 storage -- every line is accumulated in double in the order of
+ * avl_gauss2d_f64, and the intermediate (after axis 0) and the result are rounded to float32.  The result has SciPy's float32 bits.
+ * d_in: uint8 (in_is_u8 != 0, nonzero = 1.0f) or float32, rows of ld values (a window of a larger image: ld > W); h_weights as for
+ * avl_gauss2d_f64.  d_out_f32 (H, W) and d_out_gt_u8 (H, W) = stored value > threshold may each be NULL, not both; d_tmp: H * W
+ * float32. */
+AVL_API int avl_gauss2d_f32(const void* d_in, int in_is_u8, int64_t ld, int H, int W, const double* h_weights, int radius, float* d_out_f32,
+                            uint8_t* d_out_gt_u8, double threshold, float* d_tmp, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * (10) exact 2-D Euclidean distance transform and the decay maps of the 2-D goal queries (csrc/avl_edt2d.hip)
+ *     Images are row-major uint8 with rows of ld cells (a window of a larger image: ld > W), 1 <= H, W <= 16384 -- beyond that the
+ *     squared distance leaves 32 bits: AVL_ERR_INVALID before any device work.  Results are float64 (H, W), contiguous.  All calls
+ *     are asynchronous.  d_found (1 int32, device) receives 1 when the image has a cell to measure to and 0 when it has none; the
+ *     result is then meaningless and the caller reports it (SciPy measures to an imaginary cell outside the image there).
+ *     ws: avl_edt2d_work_bytes(H, W) bytes of device memory.
+ * ------------------------------------------------------------------------------------------------ */
+AVL_API int avl_edt2d_work_bytes(int H, int W, size_t* bytes);
+/* scipy.ndimage.distance_transform_edt(image) (habitat_lang_robot.py:233, visualize_utils.py:98): per cell the distance to the
+ * nearest zero cell, 0 on zero cells, SciPy's bits (the minimum of the exact integer squared distances, one correctly rounded
+ * sqrt).  invert != 0 measures to the nearest NON-zero cell instead: distance_transform_edt(image == 0). */
+AVL_API int avl_edt2d(const uint8_t* d_image_u8, int64_t ld, int H, int W, int invert, double* d_out_f64, int32_t* d_found, void* ws,
+                      size_t ws_bytes, void* stream);
+/* habitat_lang_robot.py:233-236 (and :284-287, :298-301, :315-318) and visualize_utils.py:98-100 on a mask (nonzero = target):
+ *   d = distance_transform_edt(mask == 0);  t = 1 - (d / cell_size) * decay_rate;  t < 0 -> 0;
+ *   normalize != 0:  (t - min t) / (max t - min t)
+ * in NumPy's float64 operation order.  cell_size = 1 is the robot's expression (a division by 1.0 is the identity), cell_size = cs
+ * is get_heatmap_from_mask_2d.  d_minmax (2 float64, device; required with normalize, else optional) receives [min t, max t]:
+ * max == min gives NaN as upstream, the caller checks.  decay_rate finite and >= 0, cell_size finite and > 0. */
+AVL_API int avl_mask_decay_2d(const uint8_t* d_mask_u8, int64_t ld, int H, int W, double cell_size, double decay_rate, int normalize,
+                              double* d_out_f64, double* d_minmax, int32_t* d_found, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
