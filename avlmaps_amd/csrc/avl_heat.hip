@@ -505,9 +505,6 @@ extern "C" int avl_heatmap_from_mask_planned(avl_heat_plan* p, const uint8_t* d_
 }
 
 namespace avl {
-__global__ void iota64_kernel(int64_t* __restrict__ v, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) v[i] = i;
-}
 
 // ---- wave-level top-k (k <= 64) ------------------------------------------------------------------------------------------
 // Order: value descending, equal values by ascending index, NaN last -- the order of np.argsort(-v, kind="stable").
@@ -582,12 +579,27 @@ __global__ __launch_bounds__(64) void topk_merge_kernel(const float* __restrict_
         out_val[lane] = t.idx != INT_MAX ? v[t.idx] : 0.f;
     }
 }
+
+// ---- full sort (k > 64) --------------------------------------------------------------------------------------------------
+// The same order from a stable descending radix sort of the SAME keys: sorting the raw floats would put a NaN without the sign
+// bit above +inf -- first, not last -- and one with the sign bit below -inf, apart from each other.
+__global__ void topk_sort_keys_kernel(const float* __restrict__ v, int64_t n, uint32_t* __restrict__ key, int64_t* __restrict__ iota) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        key[i] = topk_key(v[i]);
+        iota[i] = i;
+    }
+}
+
+// the values are read back through the sorted indices: the elements themselves (a key does not tell -0 from +0 or one NaN from another)
+__global__ void topk_take_kernel(const float* __restrict__ v, const int64_t* __restrict__ order, int k, float* __restrict__ out_val) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < k; i += gridDim.x * blockDim.x) out_val[i] = v[order[i]];
+}
 }  // namespace avl
 
 // k largest values of a float32 vector with their indices, descending; equal values keep ascending index order and NaN comes
 // last (the order np.argsort(-v, kind="stable") gives).  The k = 1 case is the navigator's goal voxel
 // (habitat_lang_robot.py:427-430).  k <= 64: wave-level selection, two small launches, no allocation (library scratch);
-// larger k: a full radix sort.
+// larger k: a full stable radix sort of the same order-preserving keys, values read back through the sorted indices.
 extern "C" int avl_topk_f32(const float* d_vals, int64_t N, int k, int64_t* h_index, float* h_value, void* stream) {
     AVL_REQUIRE(d_vals && N > 0 && k > 0 && k <= N, "avl_topk_f32: bad arguments (N=%lld k=%d)", (long long)N, k);
     AVL_REQUIRE(N < (1ll << 31), "avl_topk_f32: N must fit 31 bits");
@@ -611,20 +623,28 @@ extern "C" int avl_topk_f32(const float* d_vals, int64_t N, int k, int64_t* h_in
         AVL_HIP_CHECK(hipStreamSynchronize(st));
         return AVL_OK;
     }
-    float* keys_out = nullptr;
+    uint32_t *keys = nullptr, *keys_out = nullptr;
+    float* vals = nullptr;
     int64_t *iota = nullptr, *order = nullptr;
     void* tmp = nullptr;
     size_t tmp_bytes = 0;
-    AVL_HIP_CHECK(hipMallocAsync((void**)&keys_out, (size_t)N * sizeof(float), st));
+    AVL_HIP_CHECK(hipMallocAsync((void**)&keys, (size_t)N * sizeof(uint32_t), st));
+    AVL_HIP_CHECK(hipMallocAsync((void**)&keys_out, (size_t)N * sizeof(uint32_t), st));
+    AVL_HIP_CHECK(hipMallocAsync((void**)&vals, (size_t)k * sizeof(float), st));
     AVL_HIP_CHECK(hipMallocAsync((void**)&iota, (size_t)N * sizeof(int64_t), st));
     AVL_HIP_CHECK(hipMallocAsync((void**)&order, (size_t)N * sizeof(int64_t), st));
-    hipLaunchKernelGGL(avl::iota64_kernel, dim3((unsigned)((N + 255) / 256 > 4096 ? 4096 : (N + 255) / 256)), dim3(256), 0, st, iota, N);
-    AVL_HIP_CHECK(rocprim::radix_sort_pairs_desc(nullptr, tmp_bytes, d_vals, keys_out, iota, order, (size_t)N, 0, 32, st));
+    hipLaunchKernelGGL(avl::topk_sort_keys_kernel, dim3((unsigned)((N + 255) / 256 > 4096 ? 4096 : (N + 255) / 256)), dim3(256), 0, st, d_vals, N,
+                       keys, iota);
+    AVL_HIP_CHECK(rocprim::radix_sort_pairs_desc(nullptr, tmp_bytes, keys, keys_out, iota, order, (size_t)N, 0, 32, st));
     AVL_HIP_CHECK(hipMallocAsync(&tmp, tmp_bytes ? tmp_bytes : 16, st));
-    AVL_HIP_CHECK(rocprim::radix_sort_pairs_desc(tmp, tmp_bytes, d_vals, keys_out, iota, order, (size_t)N, 0, 32, st));
+    AVL_HIP_CHECK(rocprim::radix_sort_pairs_desc(tmp, tmp_bytes, keys, keys_out, iota, order, (size_t)N, 0, 32, st));
+    hipLaunchKernelGGL(avl::topk_take_kernel, dim3((unsigned)((k + 255) / 256 > 1024 ? 1024 : (k + 255) / 256)), dim3(256), 0, st, d_vals, order, k,
+                       vals);
+    AVL_HIP_CHECK(hipGetLastError());
     if (h_index) AVL_HIP_CHECK(hipMemcpyAsync(h_index, order, (size_t)k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    if (h_value) AVL_HIP_CHECK(hipMemcpyAsync(h_value, keys_out, (size_t)k * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (h_value) AVL_HIP_CHECK(hipMemcpyAsync(h_value, vals, (size_t)k * sizeof(float), hipMemcpyDeviceToHost, st));
     AVL_HIP_CHECK(hipStreamSynchronize(st));
-    (void)hipFreeAsync(tmp, st); (void)hipFreeAsync(order, st); (void)hipFreeAsync(iota, st); (void)hipFreeAsync(keys_out, st);
+    (void)hipFreeAsync(tmp, st); (void)hipFreeAsync(order, st); (void)hipFreeAsync(iota, st); (void)hipFreeAsync(vals, st);
+    (void)hipFreeAsync(keys_out, st); (void)hipFreeAsync(keys, st);
     return AVL_OK;
 }

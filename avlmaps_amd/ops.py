@@ -244,7 +244,9 @@ def mask_bool_from_argmax(argmax, cat_id, stream=None) -> np.ndarray:
 
 
 def argmax_f32(vals, stream=None):
-    """(index, value) of the first maximum of a float32 vector (habitat_lang_robot.py:427-430)."""
+    """(index, value) of the first maximum of a float32 vector (habitat_lang_robot.py:427-430).  NaN is ignored: with at least
+    one value that is not NaN the index is np.nanargmax's (not np.argmax's, which returns the first NaN); an all-NaN vector
+    returns index 0."""
     lib = _lib.load()
     vp, vshape, vk = as_device(vals, np.float32, stream)
     idx, val = C.c_int64(), C.c_float()

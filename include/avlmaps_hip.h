@@ -210,11 +210,14 @@ AVL_API int avl_mask_from_argmax(const int32_t* d_argmax, int64_t N, int32_t cat
 AVL_API int avl_mask_bits_from_argmax(const int32_t* d_argmax, int64_t N, int32_t cat_id, uint64_t* d_bits, void* stream);
 
 /* index and value of the maximum of a float32 vector, first maximum wins -- the navigator's
- * heatmap argmax, avlmaps/robot/habitat_lang_robot.py:427-430.  Synchronous (returns host scalars). */
+ * heatmap argmax, avlmaps/robot/habitat_lang_robot.py:427-430.  Synchronous (returns host scalars).
+ * NaN is ignored: with at least one value that is not NaN the index is np.nanargmax's (not np.argmax's, which returns the first
+ * NaN); an all-NaN vector returns index 0. */
 AVL_API int avl_argmax_f32(const float* d_vals, int64_t N, int64_t* h_index, float* h_value, void* stream);
 
-/* the k largest values with their indices, descending, ties in ascending index order (np.argsort(-v, kind="stable")[:k]);
- * h_index (k,) int64 and h_value (k,) float32 are host buffers.  Synchronous. */
+/* the k largest values with their indices, descending, ties in ascending index order (np.argsort(-v, kind="stable")[:k]): for
+ * every k, +0 and -0 tie and NaN of either sign comes last.  h_index (k,) int64 and h_value (k,) float32 are host buffers.
+ * Synchronous. */
 AVL_API int avl_topk_f32(const float* d_vals, int64_t N, int k, int64_t* h_index, float* h_value, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
