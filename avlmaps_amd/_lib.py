@@ -164,6 +164,12 @@ _SIGS = {
     "avl_edt2d_work_bytes": (C.c_int, [C.c_int, C.c_int, C.POINTER(_sz)]),
     "avl_edt2d": (C.c_int, [_vp, _i64, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _sz, _vp]),
     "avl_mask_decay_2d": (C.c_int, [_vp, _i64, C.c_int, C.c_int, _f64, _f64, C.c_int, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "avl_label_islands_work_bytes": (C.c_int, [C.c_int, C.c_int, C.POINTER(_sz)]),
+    "avl_label_islands": (C.c_int, [_vp, _i64, C.c_int, C.c_int, _vp, _vp, _vp, _sz, _vp]),
+    "avl_island_table": (C.c_int, [_vp, C.c_int, C.c_int, _i32, _vp, _vp]),
+    "avl_trace_islands": (C.c_int, [_vp, C.c_int, C.c_int, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "avl_nearest_pair_work_bytes": (C.c_int, [_i64, _i64, C.POINTER(_sz)]),
+    "avl_nearest_pair_i32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

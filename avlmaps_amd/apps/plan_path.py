@@ -5,6 +5,7 @@ setup_scene + move_to (robot/habitat_lang_robot.py:88-104, 432-461) without the 
                                         [--area NAME]... [--sound NAME]... [--image PNG] [--goal-2d]
                                         [--customize-obstacles [--potential-obstacles a,b,c --obstacles a,b]
                                          [--dilate-iter N] [--gaussian-sigma S]]
+                                        [--relation left|right|between|north|south|east|west|face --heading DEG [--query-b NAME]]
 
 Loads <scene>/vlmap/vlmaps.h5df (with --text-model hash a missing map is first created with the model-free feature stand-in, as
 apps.create_map --features hash does), builds the obstacle map (Map.generate_obstacle_map), takes the goal from
@@ -26,11 +27,21 @@ sound=..), the first maximum of the product of the 2-D distribution maps over th
 With --customize-obstacles the path is planned on Map.get_customized_obstacle_cropped() as upstream's robot does
 (habitat_lang_robot.py:89-104): VLMap.customize_obstacle_map keeps only the obstacles whose class is one of --obstacles among
 --potential-obstacles and smooths the map (Map._dilate_map with --dilate-iter and --gaussian-sigma).  The four values default to
-the map config's (config/map_config/vlmaps.yaml:14-15 upstream)."""
+the map config's (config/map_config/vlmaps.yaml:14-15 upstream).
+
+With --relation the goal is one of the robot's spatial-relation goals (Map.get_left_pos, get_right_pos, get_pos_in_between,
+get_north_pos / get_south_pos / get_east_pos / get_west_pos; map.py:366-485 upstream) for a robot at --start heading --heading
+degrees (0 = towards smaller rows, clockwise positive).  `between` takes the second object from --query-b.  The JSON line then has
+"relation", "heading" and "goal_cell", the method's own result; "goal" is that point clamped into the cropped obstacle map.
+`face` plans nothing: it prints the angle to turn right to face the nearest --query object (Map.get_delta_angle_to) as
+"turn_right_deg".  A relation with nothing in front of the robot ends with a message and exit status 1."""
 from __future__ import annotations
 
 import argparse
 import json
+
+
+RELATIONS = ("left", "right", "between", "north", "south", "east", "west", "face")
 
 
 def parse_args(argv=None):
@@ -56,13 +67,45 @@ def parse_args(argv=None):
     ap.add_argument("--obstacles", default=None, help="comma separated classes (of --potential-obstacles) that stay obstacles")
     ap.add_argument("--dilate-iter", type=int, default=None)
     ap.add_argument("--gaussian-sigma", type=float, default=None)
+    ap.add_argument("--relation", choices=RELATIONS, default=None, help="take the goal from a spatial relation to --query")
+    ap.add_argument("--heading", type=float, default=None, metavar="DEG", help="the robot's heading for --relation (0 = up, clockwise)")
+    ap.add_argument("--query-b", default=None, metavar="NAME", help="the second object of --relation between")
     args = ap.parse_args(argv)
+    if args.relation is None and (args.heading is not None or args.query_b is not None):
+        ap.error("--heading and --query-b belong to --relation")
+    if args.relation is not None:
+        if args.area or args.sound or args.image or args.goal_2d:
+            ap.error("--relation takes its goal from --query alone: no --area, --sound, --image or --goal-2d")
+        if (args.relation == "between") != (args.query_b is not None):
+            ap.error("--query-b goes with --relation between, and only with it")
+        if args.heading is None:
+            ap.error("--relation needs the robot's --heading")
     if not args.customize_obstacles and any(v is not None for v in (args.potential_obstacles, args.obstacles, args.dilate_iter,
                                                                     args.gaussian_sigma)):
         ap.error("--potential-obstacles, --obstacles, --dilate-iter and --gaussian-sigma belong to --customize-obstacles")
     if args.goal_2d and args.image:
         ap.error("--goal-2d takes --query, --area and --sound: an image query has no 2-D map")
     return args
+
+
+def relation_goal(vm, args, start):
+    """the goal point of --relation (left, right, between and the compass four), SystemExit when nothing is in front"""
+    if args.relation == "between":
+        goal = vm.get_pos_in_between(start, args.heading, args.query, args.query_b)
+        missing = goal is None
+        what = f"{args.query!r} and {args.query_b!r}"
+    else:
+        goal = getattr(vm, f"get_{args.relation}_pos")(start, args.heading, args.query)
+        missing = goal[0] is None or goal[0] == "stop"
+        what = repr(args.query)
+    if missing:
+        raise SystemExit(f"--relation {args.relation}: no sizeable {what} in front of a robot at {start} heading {args.heading} degrees")
+    return [float(goal[0]), float(goal[1])]
+
+
+def clamp_point(point, rmin, cmin, shape):
+    """the full-map point moved into the (H, W) crop that starts at (rmin, cmin)"""
+    return [min(max(float(point[0]), float(rmin)), float(rmin) + shape[0] - 1), min(max(float(point[1]), float(cmin)), float(cmin) + shape[1] - 1)]
 
 
 def obstacle_overrides(args) -> dict:
@@ -114,7 +157,8 @@ def main(argv=None):
         vm.clip_model = HashClip(vm.clip_feat_dim)
     else:
         vm._init_clip()
-    cats = [c.strip() for c in args.categories.split(",")] if args.categories else [args.query, "other"]
+    cats = ([c.strip() for c in args.categories.split(",")] if args.categories
+            else [args.query] + ([args.query_b] if args.query_b else []) + ["other"])
     vm.init_categories(cats)
     vm.generate_obstacle_map(args.h_min, args.h_max)
     obstacles = vm.get_obstacle_cropped()
@@ -123,7 +167,21 @@ def main(argv=None):
         obstacles = vm.get_customized_obstacle_cropped()
     start = [float(args.start[0]), float(args.start[1])]
     extra = {}
-    if avlmap is None:
+    if args.relation == "face":
+        try:
+            turn = float(vm.get_delta_angle_to(start, args.heading, args.query))
+        except ValueError:
+            raise SystemExit(f"--relation face: the map has no {args.query!r} to face") from None
+        out = {"query": args.query, "start": start, "relation": "face", "heading": args.heading, "turn_right_deg": turn}
+        print(json.dumps(out))
+        return out
+    if args.relation is not None:
+        cell = relation_goal(vm, args, start)
+        goal = clamp_point(cell, vm.rmin, vm.cmin, obstacles.shape)
+        extra = {"relation": args.relation, "heading": args.heading, "goal_cell": cell}
+        if args.query_b:
+            extra["query_b"] = args.query_b
+    elif avlmap is None:
         goal = vm.get_nearest_pos(start, args.query)
     elif args.goal_2d:
         g = avlmap.index_goal_2d(obj=args.query, area=args.area or None, sound=args.sound or None, want_heat=False)

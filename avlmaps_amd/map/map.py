@@ -185,6 +185,150 @@ class Map:
              for c, b in zip(centers, bbox_list)]
         return int(np.argmin(d))
 
+    # ------------------------------------------------------------------- spatial-relation goals of the robot (map.py:243-485)
+    # Angles: 0 = towards smaller rows ("up"), clockwise positive, like get_forward_pos.  Positions are full-map (row, col).
+    # Upstream's conventions are kept as they are, the odd ones included; each is named where it happens.
+    @staticmethod
+    def _side_pos(curr_pos, tar_pos, tar_bbox, sign: float, margin: float) -> List[float]:
+        """the point beside the target as seen from curr_pos: half the box diagonal (+ margin) away from its centre, at a right angle
+        to the line of sight; sign +1 = left, -1 = right"""
+        angle = np.arctan2(-(tar_pos[1] - curr_pos[1]), -(tar_pos[0] - curr_pos[0]))
+        h = tar_bbox[1] - tar_bbox[0]
+        w = tar_bbox[3] - tar_bbox[2]
+        d = 0.5 * np.sqrt(h * h + w * w) + margin
+        return [tar_pos[0] + sign * (np.sin(angle) * d), tar_pos[1] - sign * (np.cos(angle) * d)]
+
+    def _get_left_pos(self, curr_pos: List[float], tar_pos: List[float], tar_bbox: List[float]) -> List[float]:
+        """Reference: map.py:243-260.  Upstream first derives a distance from the box's extent along the line of sight and then
+        overwrites it with half the diagonal + 2; only the latter reaches the result, so only it is computed."""
+        return self._side_pos(curr_pos, tar_pos, tar_bbox, 1.0, 2)
+
+    def _get_right_pos(self, curr_pos: List[float], tar_pos: List[float], tar_bbox: List[float]) -> List[float]:
+        """Reference: map.py:262-276: half the diagonal, without the left side's + 2."""
+        return self._side_pos(curr_pos, tar_pos, tar_bbox, -1.0, 0)
+
+    def select_front_objs(self, centers: List[List[float]], curr_pos: List[float], curr_angle_deg: float, fov_deg: float = 90) -> List[int]:
+        """indices of the centres inside the field of view of a robot at curr_pos heading curr_angle_deg.  Reference: map.py:308-349,
+        with its two wrap-around branches for headings beyond +-90 degrees."""
+        theta = curr_angle_deg * np.pi / 180
+        half_fov = fov_deg * np.pi / 360
+        quarter = np.pi / 2
+        row0, col0 = curr_pos
+        keep = []
+        for k, (row, col) in enumerate(centers):
+            a = np.arctan2(-col + col0, -row + row0)
+            if (np.abs(a - theta) < half_fov
+                    or (theta > quarter and a < -quarter and np.abs(2 * np.pi - theta + a) < half_fov)
+                    or (theta < -quarter and a > quarter and np.abs(2 * np.pi - a + theta) < half_fov)):
+                keep.append(k)
+        return keep
+
+    def get_front_nearest_obj_pos(self, curr_pos: List[float], curr_angle_deg: float, name: str):
+        """centre of the nearest `name` object in front, None when there is none.  Reference: map.py:278-287 -- the front centres
+        are paired with the UNFILTERED box list there (box k of all objects goes with front centre k); kept."""
+        _, centers, bbox_list = self.get_pos(name)
+        front = self.select_front_objs(centers, curr_pos, curr_angle_deg)
+        if not front:
+            return None
+        front_centers = [centers[i] for i in front]
+        return front_centers[self.select_nearest_obj(front_centers, bbox_list, curr_pos)]
+
+    def get_front_nearest_obj_pos_box(self, curr_pos: List[float], curr_angle_deg: float, name: str):
+        """(centre, box) of the nearest `name` object in front, (None, None) when there is none.  Reference: map.py:289-306."""
+        _, centers, bbox_list = self.get_pos(name)
+        front = self.select_front_objs(centers, curr_pos, curr_angle_deg)
+        if not front:
+            return None, None
+        front_centers = [centers[i] for i in front]
+        front_boxes = [bbox_list[i] for i in front]
+        k = self.select_nearest_obj(front_centers, front_boxes, curr_pos)
+        return front_centers[k], front_boxes[k]
+
+    def find_middle_bewteen_contours(self, cona, conb):
+        """midpoint of the nearest pair of points of two contours (upstream's spelling).  Reference: map.py:351-364 builds the
+        |A| x |B| float64 distance matrix for its argmin; here the pair comes from the GPU (ops.contour_nearest_pair: the same first
+        minimum, the matrix never built)."""
+        from .. import ops
+        i, j, _ = ops.contour_nearest_pair(cona, conb)
+        return (cona[i] + conb[j]) / 2
+
+    def get_pos_in_between(self, curr_pos: List[float], curr_angle_deg: float, obj_a_name: str, obj_b_name: str):
+        """the point between the pair of sizeable front objects a, b whose centre midpoint is nearest to curr_pos; None when either
+        has nothing in front.  Reference: map.py:366-413.  Upstream filters the FRONT boxes by size and then uses the surviving
+        indices on the front contours but on the FULL centre lists; kept, so the chosen pair of centres need not belong to the
+        contours the midpoint is taken between."""
+        contours_a, centers_a, bbox_a = self.get_pos(obj_a_name)
+        contours_b, centers_b, bbox_b = self.get_pos(obj_b_name)
+        front_a = self.select_front_objs(centers_a, curr_pos, curr_angle_deg)
+        front_b = self.select_front_objs(centers_b, curr_pos, curr_angle_deg)
+        if not front_a or not front_b:
+            return None
+        contours_a = [contours_a[i] for i in front_a]
+        contours_b = [contours_b[i] for i in front_b]
+        big_a = self.filter_small_objects([bbox_a[i] for i in front_a])
+        big_b = self.filter_small_objects([bbox_b[i] for i in front_b])
+        if not big_a or not big_b:
+            return None
+        ca = np.array([centers_a[i] for i in big_a]).reshape((-1, 1, 2))
+        cb = np.array([centers_b[i] for i in big_b]).reshape((1, -1, 2))
+        cona = [contours_a[i] for i in big_a]
+        conb = [contours_b[i] for i in big_b]
+        to_curr = np.linalg.norm((ca + cb) / 2 - np.array(curr_pos).reshape((1, 1, 2)), axis=-1)
+        row, col = np.unravel_index(np.argmin(to_curr), to_curr.shape)
+        return self.find_middle_bewteen_contours(cona[row], conb[col])
+
+    def get_left_pos(self, curr_pos: List[float], curr_angle_deg: float, name: str) -> List[float]:
+        """Reference: map.py:415-422; [None, None] with nothing in front."""
+        center, box = self.get_front_nearest_obj_pos_box(curr_pos, curr_angle_deg, name)
+        if center is None:
+            return [None, None]
+        return self._get_left_pos(curr_pos, center, box)
+
+    def get_right_pos(self, curr_pos: List[float], curr_angle_deg: float, name: str) -> List[float]:
+        """Reference: map.py:424-430; [None, None] with nothing in front."""
+        center, box = self.get_front_nearest_obj_pos_box(curr_pos, curr_angle_deg, name)
+        if center is None:
+            return [None, None]
+        return self._get_right_pos(curr_pos, center, box)
+
+    def get_delta_angle_to(self, curr_pos: List[float], curr_angle_deg: float, name: str):
+        """degrees to turn right to face the nearest `name` object (front or not).  Reference: map.py:432-449: np.mod brings the
+        turn into [0, 360) and values above 180 come back as negative turns."""
+        _, centers, bbox_list = self.get_pos(name)
+        center = centers[self.select_nearest_obj(centers, bbox_list, curr_pos)]
+        down = center[0] - curr_pos[0]
+        right = center[1] - curr_pos[1]
+        turn = np.mod(np.arctan2(right, -down) * 180.0 / np.pi - curr_angle_deg, 360)
+        if turn < -180:
+            turn += 360
+        elif turn > 180:
+            turn -= 360
+        return turn
+
+    def _compass_pos(self, curr_pos, curr_angle_deg, name, side: int, sign: int):
+        """10 cells beyond side `side` of the nearest front object's box, level with its centre; ["stop"] with nothing in front"""
+        center, box = self.get_front_nearest_obj_pos_box(curr_pos, curr_angle_deg, name)
+        if center is None:
+            return ["stop"]
+        edge = box[side] + sign * 10
+        return [edge, center[1]] if side < 2 else [center[0], edge]
+
+    def get_north_pos(self, curr_pos: List[float], curr_angle_deg: float, name: str):
+        """Reference: map.py:451-458."""
+        return self._compass_pos(curr_pos, curr_angle_deg, name, 0, -1)
+
+    def get_south_pos(self, curr_pos: List[float], curr_angle_deg: float, name: str):
+        """Reference: map.py:460-467."""
+        return self._compass_pos(curr_pos, curr_angle_deg, name, 1, 1)
+
+    def get_west_pos(self, curr_pos: List[float], curr_angle_deg: float, name: str):
+        """Reference: map.py:469-476."""
+        return self._compass_pos(curr_pos, curr_angle_deg, name, 2, -1)
+
+    def get_east_pos(self, curr_pos: List[float], curr_angle_deg: float, name: str):
+        """Reference: map.py:478-485."""
+        return self._compass_pos(curr_pos, curr_angle_deg, name, 3, 1)
+
     @staticmethod
     def create(map_config) -> "Map":
         """Reference: map.py:120-129."""

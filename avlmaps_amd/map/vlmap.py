@@ -368,19 +368,49 @@ class VLMap(Map):
         self.obstacles_new_cropped = ops.dilate_map(self.obstacles_new_cropped == 0, cfg_get(self.map_config, "dilate_iter"),
                                                     cfg_get(self.map_config, "gaussian_sigma"), want_values=False)[1]
 
+    island_path = None          # "host" / "device" forces get_pos's island step; None: host with OpenCV installed, else device
+
+    def _island_path(self) -> str:
+        if self.island_path is not None:
+            return self.island_path
+        try:
+            import cv2  # noqa: F401
+            return "host"
+        except Exception:
+            return "device"
+
+    @property
+    def _last_foreground(self):
+        """the (h, w) bool foreground mask of the last get_pos call (None before the first)"""
+        fg = self.__dict__.get("_foreground")
+        if fg is not None and not isinstance(fg, np.ndarray):
+            fg = self.__dict__["_foreground"] = fg.numpy().astype(bool)
+        return fg
+
+    @_last_foreground.setter
+    def _last_foreground(self, value):
+        self.__dict__["_foreground"] = value
+
     def get_pos(self, name: str):
         """Contours, centres and bounding boxes of a category on the full map.  Reference: vlmap.py:158-187.  The per-voxel
         work (argmax mask, top-down pooling) and the 2-D morphology (closing, gaussian, threshold, dilation: avl_mask_foreground,
-        SciPy's results bit for bit) run on the GPU and only the finished foreground mask is copied back; the island extraction
-        is utils/navigation_utils.get_segment_islands_pos (OpenCV when installed)."""
+        SciPy's results bit for bit) run on the GPU.  With OpenCV installed the finished foreground mask is copied back and
+        utils/navigation_utils.get_segment_islands_pos calls cv2.findContours as upstream does; without it the islands are
+        labelled and traced on the GPU too (get_segment_islands_pos_device: the same result as the host function's SciPy path)
+        and only the island table and the contour points are copied back."""
         from .. import ops
-        from ..utils.navigation_utils import get_segment_islands_pos
+        from ..utils.navigation_utils import get_segment_islands_pos, get_segment_islands_pos_device
         assert self.categories
         pc_mask = self.index_map(name, with_init_cat=True)
         mask_2d = ops.pool_label_2d(pc_mask, self._device_pos(), int(self.gs), device=True)
-        foreground = ops.mask_foreground(mask_2d, self.rmin, self.rmax + 1, self.cmin, self.cmax + 1)
-        self._last_foreground = foreground
-        contours, centers, bbox_list, _ = get_segment_islands_pos(foreground, 1)
+        if self._island_path() == "host":
+            foreground = ops.mask_foreground(mask_2d, self.rmin, self.rmax + 1, self.cmin, self.cmax + 1)
+            self._last_foreground = foreground
+            contours, centers, bbox_list, _ = get_segment_islands_pos(foreground, 1)
+        else:
+            foreground = ops.mask_foreground(mask_2d, self.rmin, self.rmax + 1, self.cmin, self.cmax + 1, device=True)
+            self._last_foreground = foreground                  # stays on the device; reading the attribute copies it back
+            contours, centers, bbox_list, _ = get_segment_islands_pos_device(foreground, 1)
         for i in range(len(contours)):          # whole-map positions (upstream adds rmin to both row bounds: kept)
             centers[i][0] += self.rmin
             centers[i][1] += self.cmin

@@ -66,6 +66,31 @@ def get_segment_islands_pos(segment_map, label_id, detect_internal_contours=Fals
     return contours_list, centers_list, bbox_list, hierarchy
 
 
+def get_segment_islands_pos_device(foreground, label_id=1):
+    """get_segment_islands_pos without OpenCV, on the GPU: the same (contours, centers, bbox_list, None) -- the same arrays, dtypes and
+    bottom-up order (label n first) -- from ops.label_islands and ops.trace_islands (csrc/avl_islands.hip).  `foreground` is the
+    0 / 1 uint8 DeviceArray ops.mask_foreground(..., device=True) leaves on the device (label_id must then be 1), or a host segment
+    map; only the island table (for the contour lengths) and the contour points come back to the host.  Internal contours are not
+    supported."""
+    from .. import ops
+    from ..device import DeviceArray, DeviceView
+    if isinstance(foreground, (DeviceArray, DeviceView)):
+        if label_id != 1:
+            raise ValueError("a device foreground mask holds 0 / 1: label_id must be 1")
+        mask = foreground
+    else:
+        mask = (np.asarray(foreground) == label_id).astype(np.uint8)
+    with ops.label_islands(mask, device=True) as isl:
+        traced = ops.trace_islands(isl)
+    contours_list = [traced[k].astype(np.int64) for k in range(isl.n - 1, -1, -1)]
+    centers_list, bbox_list = [], []
+    for c in contours_list:         # the extents of the CONTOUR, as above: a trace that meets its start early covers less than the island
+        xmin, xmax, ymin, ymax = np.min(c[:, 0]), np.max(c[:, 0]), np.min(c[:, 1]), np.max(c[:, 1])
+        bbox_list.append([xmin, xmax, ymin, ymax])
+        centers_list.append([(xmin + xmax) / 2, (ymin + ymax) / 2])
+    return contours_list, centers_list, bbox_list, None
+
+
 # ---------------------------------------------------------------------------------------- planning on the obstacle map
 # The reference builds a pyvisgraph visibility graph over the cv2 contours of the obstacles (navigation_utils.py:77-127) and runs
 # pyvisgraph's Dijkstra (:130-197).  Here the graph is built and searched on the GPU (csrc/avl_nav.hip, ops.NavGraph) over the

@@ -838,6 +838,34 @@ AVL_API int avl_edt2d(const uint8_t* d_image_u8, int64_t ld, int H, int W, int i
 AVL_API int avl_mask_decay_2d(const uint8_t* d_mask_u8, int64_t ld, int H, int W, double cell_size, double decay_rate, int normalize,
                               double* d_out_f64, double* d_minmax, int32_t* d_found, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * (11) object islands of a 2-D mask: labels, table, outer contours, nearest pair of two contours (csrc/avl_islands.hip)
+ *     The island step of navigation_utils.py:10-36 (get_segment_islands_pos) and the distance matrix of map.py:351-364
+ *     (find_middle_bewteen_contours).  Images are row-major (H, W), 1 <= H, W <= 16384 and H * W <= 2^28: AVL_ERR_INVALID before
+ *     any device work otherwise.  All calls are asynchronous; every result is unique (the bytes do not depend on scheduling).
+ * ------------------------------------------------------------------------------------------------ */
+AVL_API int avl_label_islands_work_bytes(int H, int W, size_t* bytes);
+/* 8-connected components of the non-zero cells of a uint8 mask with rows of ld cells: d_labels (H, W) int32, background 0, islands
+ * 1 .. n in raster order of their first pixel = scipy.ndimage.label(mask, np.ones((3, 3))); *d_n (1 int32, device) = n. */
+AVL_API int avl_label_islands(const uint8_t* d_mask_u8, int64_t ld, int H, int W, int32_t* d_labels, int32_t* d_n, void* ws, size_t ws_bytes,
+                              void* stream);
+/* d_table (n, 8) int32, row k - 1 for label k: area, rmin, rmax, cmin, cmax, first_row, first_col, 0.  n is avl_label_islands' count
+ * (at most ceil(H / 2) * ceil(W / 2)); n = 0 does nothing. */
+AVL_API int avl_island_table(const int32_t* d_labels, int H, int W, int32_t n, int32_t* d_table, void* stream);
+/* The outer boundary of every island by Moore tracing from (first_row, first_col): neighbour order W NW N NE E SE S SW, the scan
+ * restarting at (d + 5) % 8, stop at the first return to the start or when no neighbour is found, at most 4 * H * W + 8 steps.
+ * d_points == NULL (and d_offsets == NULL): the count pass, the number of points of island k goes to d_table[k - 1][7].
+ * Otherwise the write pass: island k's (row, col) int32 pairs go to d_points[d_offsets[k - 1] ...]; d_points holds n_points pairs
+ * and nothing is written past an island's counted length or past n_points. */
+AVL_API int avl_trace_islands(const int32_t* d_labels, int H, int W, int32_t n, int32_t* d_table, const int64_t* d_offsets, int32_t* d_points,
+                              int64_t n_points, void* stream);
+AVL_API int avl_nearest_pair_work_bytes(int64_t na, int64_t nb, size_t* bytes);
+/* d_a (na, 2), d_b (nb, 2) int32 points, 1 <= na, nb <= 2^24, |coordinate| <= 2^15.  d_out3 (3 int64, device) = i, j, d2: the pair
+ * with the smallest squared distance, among equals the smallest i * nb + j =
+ * np.unravel_index(np.argmin(np.linalg.norm(a[:, None] - b[None], axis=2)), (na, nb)).  The matrix is never built. */
+AVL_API int avl_nearest_pair_i32(const int32_t* d_a, int64_t na, const int32_t* d_b, int64_t nb, int64_t* d_out3, void* ws, size_t ws_bytes,
+                                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif
