@@ -152,6 +152,11 @@ _SIGS = {
     "avl_nav_export_visibility": (C.c_int, [_vp, _vp, _vp]),
     "avl_nav_plan": (C.c_int, [_vp, _f64, _f64, _f64, _f64, C.POINTER(_f64), _vp, C.POINTER(C.c_int), C.c_int, _vp]),
     "avl_nav_last_plan": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "avl_navmany_snap": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "avl_navmany_plan": (C.c_int, [_vp, _f64, _f64, _vp, _i64, _vp, _vp, C.POINTER(_i64), _vp]),
+    "avl_navmany_path": (C.c_int, [_vp, _i64, _vp, C.POINTER(C.c_int), C.c_int, _vp]),
+    "avl_navmany_count_walks": (C.c_int, [_vp, C.c_int]),
+    "avl_navmany_stats": (C.c_int, [_vp, _vp]),
     "avl_morph_binary": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
     "avl_gauss2d_f64": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _f64, _vp, _vp]),
     "avl_resize2x_up_f64": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),

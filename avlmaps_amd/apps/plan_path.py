@@ -6,6 +6,7 @@ setup_scene + move_to (robot/habitat_lang_robot.py:88-104, 432-461) without the 
                                         [--customize-obstacles [--potential-obstacles a,b,c --obstacles a,b]
                                          [--dilate-iter N] [--gaussian-sigma S]]
                                         [--relation left|right|between|north|south|east|west|face --heading DEG [--query-b NAME]]
+                                        [--nearest euclid|path]
 
 Loads <scene>/vlmap/vlmaps.h5df (with --text-model hash a missing map is first created with the model-free feature stand-in, as
 apps.create_map --features hash does), builds the obstacle map (Map.generate_obstacle_map), takes the goal from
@@ -28,6 +29,10 @@ With --customize-obstacles the path is planned on Map.get_customized_obstacle_cr
 (habitat_lang_robot.py:89-104): VLMap.customize_obstacle_map keeps only the obstacles whose class is one of --obstacles among
 --potential-obstacles and smooths the map (Map._dilate_map with --dilate-iter and --gaussian-sigma).  The four values default to
 the map config's (config/map_config/vlmaps.yaml:14-15 upstream).
+
+With --nearest path the goal is the --query object's contour point with the shortest travel distance from --start
+(Map.get_nearest_reachable_pos: one shortest-path tree and one launch over all candidates) instead of the nearest as the crow
+flies, which may lie behind a wall.
 
 With --relation the goal is one of the robot's spatial-relation goals (Map.get_left_pos, get_right_pos, get_pos_in_between,
 get_north_pos / get_south_pos / get_east_pos / get_west_pos; map.py:366-485 upstream) for a robot at --start heading --heading
@@ -70,7 +75,12 @@ def parse_args(argv=None):
     ap.add_argument("--relation", choices=RELATIONS, default=None, help="take the goal from a spatial relation to --query")
     ap.add_argument("--heading", type=float, default=None, metavar="DEG", help="the robot's heading for --relation (0 = up, clockwise)")
     ap.add_argument("--query-b", default=None, metavar="NAME", help="the second object of --relation between")
+    ap.add_argument("--nearest", choices=["euclid", "path"], default="euclid",
+                    help="which --query object is the goal: euclid = the nearest as the crow flies (Map.get_nearest_pos); "
+                         "path = the one with the shortest travel distance (Map.get_nearest_reachable_pos)")
     args = ap.parse_args(argv)
+    if args.nearest == "path" and (args.relation is not None or args.area or args.sound or args.image or args.goal_2d):
+        ap.error("--nearest path chooses among the --query objects: no --relation, --area, --sound, --image or --goal-2d")
     if args.relation is None and (args.heading is not None or args.query_b is not None):
         ap.error("--heading and --query-b belong to --relation")
     if args.relation is not None:
@@ -182,7 +192,7 @@ def main(argv=None):
         if args.query_b:
             extra["query_b"] = args.query_b
     elif avlmap is None:
-        goal = vm.get_nearest_pos(start, args.query)
+        goal = None if args.nearest == "path" else vm.get_nearest_pos(start, args.query)
     elif args.goal_2d:
         g = avlmap.index_goal_2d(obj=args.query, area=args.area or None, sound=args.sound or None, want_heat=False)
         goal = [int(g.cell[0]), int(g.cell[1])]
@@ -202,7 +212,10 @@ def main(argv=None):
     nav = Navigator()
     try:
         nav.build_visgraph(obstacles, vm.rmin, vm.cmin)
-        path = nav.plan_to(start, goal)
+        if args.nearest == "path":
+            goal, path = vm.get_nearest_reachable_pos(start, args.query, nav)
+        else:
+            path = nav.plan_to(start, goal)
     finally:
         nav.close()
     out = {"query": args.query, "start": start, "goal": [float(goal[0]), float(goal[1])],

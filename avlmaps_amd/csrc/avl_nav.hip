@@ -556,6 +556,132 @@ __global__ __launch_bounds__(256) void nav_pred_kernel(NavNodes G, const double*
     if ((threadIdx.x & (kWave - 1)) == 0) pred[v] = (int32_t)u;
 }
 
+// ----------------------------------------------------------------------------------------------- many goals
+// One wave per goal against the finished shortest-path tree `dist` of the start (the goal node took no part in it):
+//   out_dist[k] = min(fl(dist[u] + |u g_k|) over vertices u that see g_k, dist[u] finite, usable_end at u; |s g_k| if the start sees it)
+//   out_via[k]  = the node nav_pred_kernel would pick for the goal: the smallest vertex id attaining the minimum, else V (the
+//                 start); -1 with +inf when nothing reaches the goal.
+// The lanes hold 64 raster-consecutive vertices and the words are visited in ascending id order.  A lane walks to the goal only
+// when its candidate can still win: strictly below the best so far, or equal to it while the best is the start's (a vertex beats
+// the start on a tie; an equal vertex with a larger id never wins).  The walk runs from the goal to the vertex in float64, as
+// nav_query_kernel's; the start-goal walk runs from the start.  walks[0] / walks[1] count the lanes that walked / had a finite
+// candidate (integer atomics, for the probe only; null = not counted).
+__global__ __launch_bounds__(256) void nav_goals_kernel(NavGrid g, NavNodes G, const double* __restrict__ dist,
+                                                       const double* __restrict__ goals, int64_t M, double* __restrict__ out_dist,
+                                                       int32_t* __restrict__ out_via, unsigned long long* __restrict__ walks) {
+    const int64_t k = (int64_t)blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave;
+    if (k >= M) return;
+    const int lane = threadIdx.x & (kWave - 1);
+    // (wave-uniform points go through a lane shuffle so that the walk keeps them in VGPRs, see nav_visibility_kernel)
+    const double gr = __shfl(goals[2 * k], lane, kWave), gc = __shfl(goals[2 * k + 1], lane, kWave);
+    const double sr = __shfl(G.sr, lane, kWave), sc = __shfl(G.sc, lane, kWave);
+    // the start's candidate is kept apart from the vertices': a vertex needs best <= the start's (it wins that tie), and a strictly
+    // smaller value than every vertex before it
+    const int s_vis = nav_visible<double>(g, sr, sc, gr, gc) ? 1 : 0;
+    const double s_best = s_vis ? dist[G.V] + edge_len(sr, sc, gr, gc) : INFINITY;
+    double best = INFINITY;
+    int via = -1;
+    unsigned long long n_walk = 0, n_cand = 0;
+    for (int64_t w = 0; w < G.W64; ++w) {
+        const int64_t u = w * 64 + lane;
+        double cand = INFINITY;
+        double ur = 0.0, uc = 0.0;
+        if (u < G.V) {
+            const double du = dist[u];
+            ur = (double)G.verts[2 * u];
+            uc = (double)G.verts[2 * u + 1];
+            if (du < INFINITY && usable_end(G, u, G.vspan[u], gr - ur, gc - uc)) cand = du + edge_len(ur, uc, gr, gc);
+        }
+        const int need = (cand < best && cand <= s_best) ? 1 : 0;
+        if (walks) {
+            n_cand += (unsigned long long)__popcll(__ballot(cand < INFINITY));
+            n_walk += (unsigned long long)__popcll(__ballot(need));
+        }
+        if (!__ballot(need)) continue;
+        int vis = 0;
+        if (need) vis = nav_visible<double>(g, gr, gc, ur, uc) ? 1 : 0;
+        const double m = wave_min(vis ? cand : INFINITY);
+        if (m < best) {
+            const unsigned long long hit = __ballot(vis && cand == m);
+            best = m;
+            via = (int)(w * 64) + (__ffsll((long long)hit) - 1);
+        }
+    }
+    if (lane == 0) {
+        const int by_vertex = via >= 0 ? 1 : 0;
+        out_dist[k] = by_vertex ? best : s_best;
+        out_via[k] = by_vertex ? via : (s_vis ? (int)G.V : -1);
+        if (walks) {
+            atomicAdd(&walks[0], n_walk);
+            atomicAdd(&walks[1], n_cand);
+        }
+    }
+}
+
+// Is any cell of the map free?  (snapping needs one; asked once per graph)
+__global__ __launch_bounds__(256) void nav_any_free_kernel(const uint16_t* __restrict__ pix, int H, int W, int32_t* __restrict__ flag) {
+    const int64_t n = (int64_t)H * W;
+    int any = 0;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x)
+        any |= (pix[(size_t)(t / W + 1) * (W + 2) + (size_t)(t % W + 1)] & kObs) ? 0 : 1;
+    if (__ballot(any) && (threadIdx.x & (kWave - 1)) == 0) atomicOr(flag, 1);
+}
+
+// navigation_utils._in_obstacle + _nearest_free, one thread per point.  A point is inside the obstacle set when its int() cell is an
+// obstacle, or when it lies strictly beyond the hypotenuse of the triangle fill whose free corner is that cell.  Such a point moves
+// to the free cell with the smallest fl(fl(a * a) + fl(b * b)), a = fl(r - pr), b = fl(c - pc) (NumPy's float64 expression), the
+// first in raster order on ties.  The search goes outward over the square rings round the int() cell (fr, fc): a cell of ring d has
+// |r - pr| >= d - 1 or |c - pc| >= d - 1, d - 1 and its square are exact in float64 and rounding is monotone, so its value is at
+// least (d - 1)^2; the search stops at the first ring whose bound exceeds the best value found (a cell further out neither beats
+// nor ties it).  The map holds a free cell (checked by the host), so the search ends.
+__global__ __launch_bounds__(256) void nav_snap_kernel(NavGrid g, const double* __restrict__ pts, int64_t M, double* __restrict__ out,
+                                                      uint8_t* __restrict__ moved) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= M) return;
+    const double pr = pts[2 * t], pc = pts[2 * t + 1];
+    const int fr = (int)pr, fc = (int)pc;                               // points lie in [0, H - 1] x [0, W - 1]: int() = floor
+    const uint32_t p = pix_at(g, fr, fc);
+    int inside = (p & kObs) ? 1 : 0;
+    if (!inside && pr != (double)fr && pc != (double)fc && fr + 1 < g.H && fc + 1 < g.W && (p & 1u) && (p & 0x40u) && (p & 0x80u))
+        inside = (pr - (double)fr) + (pc - (double)fc) > 1.0 ? 1 : 0;   // E, S and SE are obstacles: the hypotenuse is u + v = 1
+    double orr = pr, occ = pc;
+    if (inside) {
+        double best = INFINITY;
+        int br = 0, bc = 0;
+        const int dmax = max(max(fr, g.H - 1 - fr), max(fc, g.W - 1 - fc));
+        if (!(p & kObs)) {                                              // ring 0, inside a fill: the free corner (fr, fc) itself
+            const double a = (double)fr - pr, b = (double)fc - pc;
+            best = a * a + b * b;
+            br = fr;
+            bc = fc;
+        }
+        for (int d = 1; d <= dmax; ++d) {
+            const double lo = (double)(d - 1) * (double)(d - 1);
+            if (lo > best) break;
+            const int r0 = fr - d, r1 = fr + d, c0 = fc - d, c1 = fc + d;
+            for (int r = max(r0, 0); r <= min(r1, g.H - 1); ++r) {
+                const int full = (r == r0 || r == r1) ? 1 : 0;          // the ring's top and bottom rows; else its two side cells
+                const int ca = full ? max(c0, 0) : c0, cb = full ? min(c1, g.W - 1) : c1, step = full ? 1 : c1 - c0;
+                for (int c = ca; c <= cb; c += step) {
+                    if (c < 0 || c >= g.W || (pix_at(g, r, c) & kObs)) continue;
+                    const double a = (double)r - pr, b = (double)c - pc;
+                    const double d2 = a * a + b * b;
+                    if (d2 < best || (d2 == best && (r < br || (r == br && c < bc)))) {
+                        best = d2;
+                        br = r;
+                        bc = c;
+                    }
+                }
+            }
+        }
+        orr = (double)br;
+        occ = (double)bc;
+    }
+    out[2 * t] = orr;
+    out[2 * t + 1] = occ;
+    moved[t] = (uint8_t)inside;
+}
+
 static unsigned nav_blocks(int64_t n, int threads) {
     return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + threads - 1) / threads, (int64_t)num_cus() * 16));
 }
@@ -580,13 +706,39 @@ struct AvlNavGraph {
     int planned = 0;
     double q[4] = {0, 0, 0, 0};
     int last_buf = 0;
+    // many goals (avl_navmany_*): buffers of their own, so that avl_nav_last_plan keeps describing the last single plan
+    unsigned long long* m_qbits = nullptr;   // 2 x W64: row 0 = visible from the start, row 1 = all zero (no goal node)
+    int32_t* m_sg = nullptr;                 // 0: the goal node is not connected
+    double* m_dist = nullptr;                // 2 x (V + 2): the tree of the last batch's start
+    int32_t* m_flags = nullptr;              // V + 4
+    int32_t* m_pred = nullptr;               // V + 2
+    unsigned long long* m_walks = nullptr;   // 2 counters of the last batch: walks started, finite candidates
+    double* m_goals = nullptr;               // 2 x m_cap points (goals of a batch, or the points of a snap)
+    double* m_out = nullptr;                 // 2 x m_cap: per-goal distances (first m_cap), or the snapped points
+    int32_t* m_via = nullptr;                // m_cap
+    uint8_t* m_moved = nullptr;              // m_cap
+    int32_t* m_free = nullptr;               // 1: the map has a free cell
+    int64_t m_cap = 0;
+    int free_known = 0, has_free = 0;
+    int many_planned = 0;
+    int64_t many_M = 0;
+    int32_t* h_many_pred = nullptr;          // host copies for avl_navmany_path: the tree's predecessors and via[] of the last batch
+    int32_t* h_many_via = nullptr;
+    int64_t h_many_via_cap = 0;
+    unsigned long long many_walks[2] = {0, 0};
+    int count_walks = 0;                     // avl_navmany_count_walks: batches count their walks (off: the kernel gets no counters)
+    int many_counted = 0;                    // the last batch counted
 };
 
 static void nav_free(AvlNavGraph* g) {
     if (!g) return;
-    void* ptrs[] = {g->pix, g->verts, g->bits, g->qbits, g->sg, g->dist, g->flags, g->pred, g->vspan, g->vrun};
+    void* ptrs[] = {g->pix,     g->verts,  g->bits,   g->qbits,   g->sg,      g->dist,  g->flags, g->pred,  g->vspan,   g->vrun,
+                    g->m_qbits, g->m_sg,   g->m_dist, g->m_flags, g->m_pred,  g->m_walks, g->m_goals, g->m_out, g->m_via, g->m_moved,
+                    g->m_free};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
+    delete[] g->h_many_pred;
+    delete[] g->h_many_via;
     delete g;
 }
 
@@ -731,6 +883,37 @@ extern "C" int avl_nav_export_visibility(void* graph, uint64_t* h_bits, void* st
     return AVL_OK;
 }
 
+// The rounds of the shortest path from node V over `nodes` (d0, d1: the two initialised distance buffers, flags: zeroed), then the
+// predecessors.  After it both buffers hold the distances.
+static int nav_relax(const NavNodes& nodes, double* d0, double* d1, int32_t* flags, int32_t* pred, const char* who, hipStream_t st) {
+    const int64_t N = nodes.V + 2;
+    const unsigned nblk = (unsigned)((N + 3) / 4);
+    // a shortest path has at most N - 1 edges, so round N - 1 changes nothing: at most N + 1 rounds
+    int64_t k = 0;
+    bool converged = false;
+    while (k <= N && !converged) {
+        const int64_t k1 = std::min<int64_t>(k + kNavRoundBatch, N + 1);
+        for (; k < k1; ++k) {
+            const double* din = (k & 1) ? d1 : d0;
+            double* dout = (k & 1) ? d0 : d1;
+            hipLaunchKernelGGL(nav_round_kernel, dim3(nblk), dim3(256), 0, st, nodes, din, dout, flags, k);
+        }
+        AVL_HIP_CHECK(hipGetLastError());
+        int32_t last = 1;
+        AVL_HIP_CHECK(hipMemcpyAsync(&last, flags + (k - 1), sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        AVL_HIP_CHECK(hipStreamSynchronize(st));
+        converged = last == 0;
+    }
+    if (!converged) {
+        set_error("%s: the relaxation did not converge in %lld rounds", who, (long long)(N + 1));
+        return AVL_ERR_STATE;
+    }
+    // after a round that changed nothing both buffers hold the same distances
+    hipLaunchKernelGGL(nav_pred_kernel, dim3(nblk), dim3(256), 0, st, nodes, d0, pred);
+    AVL_HIP_CHECK(hipGetLastError());
+    return AVL_OK;
+}
+
 extern "C" int avl_nav_plan(void* graph, double sr, double sc, double gr, double gc, double* h_dist, int32_t* h_path, int* h_len,
                             int cap, void* stream) {
     AVL_REQUIRE(graph && h_dist && h_len, "avl_nav_plan: null pointer");
@@ -753,30 +936,8 @@ extern "C" int avl_nav_plan(void* graph, double sr, double sc, double gr, double
     AVL_HIP_CHECK(hipMemsetAsync(g->flags, 0, sizeof(int32_t) * (size_t)(N + 2), st));
     AVL_HIP_CHECK(hipGetLastError());
     const NavNodes nodes{g->verts, V, g->W64, g->bits, g->qbits, g->sg, g->vspan, g->vrun, sr, sc, gr, gc};
-    const unsigned nblk = (unsigned)((N + 3) / 4);
-    // a shortest path has at most N - 1 edges, so round N - 1 changes nothing: at most N + 1 rounds
-    int64_t k = 0;
-    bool converged = false;
-    while (k <= N && !converged) {
-        const int64_t k1 = std::min<int64_t>(k + kNavRoundBatch, N + 1);
-        for (; k < k1; ++k) {
-            const double* din = (k & 1) ? d1 : d0;
-            double* dout = (k & 1) ? d0 : d1;
-            hipLaunchKernelGGL(nav_round_kernel, dim3(nblk), dim3(256), 0, st, nodes, din, dout, g->flags, k);
-        }
-        AVL_HIP_CHECK(hipGetLastError());
-        int32_t last = 1;
-        AVL_HIP_CHECK(hipMemcpyAsync(&last, g->flags + (k - 1), sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        AVL_HIP_CHECK(hipStreamSynchronize(st));
-        converged = last == 0;
-    }
-    if (!converged) {
-        set_error("avl_nav_plan: the relaxation did not converge in %lld rounds", (long long)(N + 1));
-        return AVL_ERR_STATE;
-    }
-    // after a round that changed nothing both buffers hold the same distances
-    hipLaunchKernelGGL(nav_pred_kernel, dim3(nblk), dim3(256), 0, st, nodes, d0, g->pred);
-    AVL_HIP_CHECK(hipGetLastError());
+    const int rrc = nav_relax(nodes, d0, d1, g->flags, g->pred, "avl_nav_plan", st);
+    if (rrc != AVL_OK) return rrc;
     int32_t* pred = new (std::nothrow) int32_t[(size_t)N];
     AVL_REQUIRE(pred, "avl_nav_plan: out of host memory");
     double dgoal = INFINITY;
@@ -830,5 +991,204 @@ extern "C" int avl_nav_last_plan(void* graph, double* h_dist, int32_t* h_pred, u
         AVL_HIP_CHECK(hipMemcpyAsync(h_qbits, g->qbits, sizeof(uint64_t) * 2 * (size_t)g->W64, hipMemcpyDeviceToHost, st));
     if (h_sg) AVL_HIP_CHECK(hipMemcpyAsync(h_sg, g->sg, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     AVL_HIP_CHECK(hipStreamSynchronize(st));
+    return AVL_OK;
+}
+
+// ----------------------------------------------------------------------------------------------- many goals: entry points
+constexpr int64_t kNavManyMax = (int64_t)1 << 20;
+
+// the per-point buffers of a batch or a snap, grown to M points (never shrunk)
+static int navmany_reserve(AvlNavGraph* g, int64_t M) {
+    if (M <= g->m_cap) return AVL_OK;
+    int64_t cap = std::max<int64_t>(g->m_cap * 2, 1024);
+    while (cap < M) cap *= 2;
+    cap = std::min<int64_t>(cap, kNavManyMax);
+    void** bufs[] = {(void**)&g->m_goals, (void**)&g->m_out, (void**)&g->m_via, (void**)&g->m_moved};
+    for (void** b : bufs) {
+        if (*b) (void)hipFree(*b);
+        *b = nullptr;
+    }
+    g->m_cap = 0;
+    int rc;
+    if ((rc = nav_alloc((void**)&g->m_goals, sizeof(double) * 2 * (size_t)cap)) != AVL_OK) return rc;
+    if ((rc = nav_alloc((void**)&g->m_out, sizeof(double) * 2 * (size_t)cap)) != AVL_OK) return rc;
+    if ((rc = nav_alloc((void**)&g->m_via, sizeof(int32_t) * (size_t)cap)) != AVL_OK) return rc;
+    if ((rc = nav_alloc((void**)&g->m_moved, (size_t)cap)) != AVL_OK) return rc;
+    g->m_cap = cap;
+    return AVL_OK;
+}
+
+static int navmany_check_points(const AvlNavGraph* g, const double* pts, int64_t M, const char* who) {
+    for (int64_t k = 0; k < M; ++k) {
+        const double r = pts[2 * k], c = pts[2 * k + 1];
+        AVL_REQUIRE(std::isfinite(r) && std::isfinite(c), "%s: point %lld is not finite", who, (long long)k);
+        AVL_REQUIRE(r >= 0.0 && r <= g->H - 1 && c >= 0.0 && c <= g->W - 1, "%s: point %lld (%g, %g) outside the %d x %d map", who,
+                    (long long)k, r, c, g->H, g->W);
+    }
+    return AVL_OK;
+}
+
+extern "C" int avl_navmany_snap(void* graph, const double* h_pts, int64_t M, double* h_out, uint8_t* h_moved, void* stream) {
+    AVL_REQUIRE(graph, "avl_navmany_snap: null handle");
+    AvlNavGraph* g = static_cast<AvlNavGraph*>(graph);
+    AVL_REQUIRE(M >= 0 && M <= kNavManyMax, "avl_navmany_snap: %lld points (0 .. %lld)", (long long)M, (long long)kNavManyMax);
+    if (M == 0) return AVL_OK;
+    AVL_REQUIRE(h_pts && h_out && h_moved, "avl_navmany_snap: null pointer");
+    int rc = navmany_check_points(g, h_pts, M, "avl_navmany_snap");
+    if (rc != AVL_OK) return rc;
+    hipStream_t st = as_stream(stream);
+    if (!g->free_known) {
+        if (!g->m_free && (rc = nav_alloc((void**)&g->m_free, sizeof(int32_t))) != AVL_OK) return rc;
+        int32_t any = 0;
+        AVL_HIP_CHECK(hipMemsetAsync(g->m_free, 0, sizeof(int32_t), st));
+        hipLaunchKernelGGL(nav_any_free_kernel, dim3(nav_blocks((int64_t)g->H * g->W, 256)), dim3(256), 0, st, g->pix, g->H, g->W, g->m_free);
+        AVL_HIP_CHECK(hipGetLastError());
+        AVL_HIP_CHECK(hipMemcpyAsync(&any, g->m_free, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        AVL_HIP_CHECK(hipStreamSynchronize(st));
+        g->has_free = any != 0;
+        g->free_known = 1;
+    }
+    if (!g->has_free) {                 // every point lies on an obstacle cell and has nowhere to go
+        set_error("avl_navmany_snap: the obstacle map has no free cell");
+        return AVL_ERR_STATE;
+    }
+    if ((rc = navmany_reserve(g, M)) != AVL_OK) return rc;
+    AVL_HIP_CHECK(hipMemcpyAsync(g->m_goals, h_pts, sizeof(double) * 2 * (size_t)M, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(nav_snap_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, NavGrid{g->pix, g->H, g->W}, g->m_goals, M,
+                       g->m_out, g->m_moved);
+    AVL_HIP_CHECK(hipGetLastError());
+    AVL_HIP_CHECK(hipMemcpyAsync(h_out, g->m_out, sizeof(double) * 2 * (size_t)M, hipMemcpyDeviceToHost, st));
+    AVL_HIP_CHECK(hipMemcpyAsync(h_moved, g->m_moved, (size_t)M, hipMemcpyDeviceToHost, st));
+    AVL_HIP_CHECK(hipStreamSynchronize(st));
+    return AVL_OK;
+}
+
+extern "C" int avl_navmany_plan(void* graph, double sr, double sc, const double* h_goals, int64_t M, double* h_dist, int32_t* h_via,
+                                int64_t* h_best, void* stream) {
+    AVL_REQUIRE(graph && h_best, "avl_navmany_plan: null pointer");
+    AvlNavGraph* g = static_cast<AvlNavGraph*>(graph);
+    *h_best = -1;
+    AVL_REQUIRE(M >= 0 && M <= kNavManyMax, "avl_navmany_plan: %lld goals (0 .. %lld)", (long long)M, (long long)kNavManyMax);
+    AVL_REQUIRE(M == 0 || (h_goals && h_dist && h_via), "avl_navmany_plan: null pointer");
+    const double s[2] = {sr, sc};
+    int rc = navmany_check_points(g, s, 1, "avl_navmany_plan (start)");
+    if (rc == AVL_OK) rc = navmany_check_points(g, h_goals, M, "avl_navmany_plan");
+    if (rc != AVL_OK) return rc;
+    hipStream_t st = as_stream(stream);
+    const NavGrid grid{g->pix, g->H, g->W};
+    const int64_t V = g->V, N = V + 2, W64 = g->W64;
+    // (each buffer under its own check: a call that failed half way leaves nothing to allocate twice)
+    if (!g->m_qbits && (rc = nav_alloc((void**)&g->m_qbits, sizeof(unsigned long long) * 2 * (size_t)std::max<int64_t>(W64, 1))) != AVL_OK) return rc;
+    if (!g->m_sg && (rc = nav_alloc((void**)&g->m_sg, sizeof(int32_t))) != AVL_OK) return rc;
+    if (!g->m_flags && (rc = nav_alloc((void**)&g->m_flags, sizeof(int32_t) * (size_t)(N + 2))) != AVL_OK) return rc;
+    if (!g->m_pred && (rc = nav_alloc((void**)&g->m_pred, sizeof(int32_t) * (size_t)N)) != AVL_OK) return rc;
+    if (!g->m_walks && (rc = nav_alloc((void**)&g->m_walks, sizeof(unsigned long long) * 2)) != AVL_OK) return rc;
+    if (!g->m_dist && (rc = nav_alloc((void**)&g->m_dist, sizeof(double) * 2 * (size_t)N)) != AVL_OK) return rc;
+    if (!g->h_many_pred) {
+        g->h_many_pred = new (std::nothrow) int32_t[(size_t)N];
+        AVL_REQUIRE(g->h_many_pred, "avl_navmany_plan: out of host memory");
+    }
+    if (M > g->h_many_via_cap) {
+        delete[] g->h_many_via;
+        g->h_many_via_cap = 0;
+        g->h_many_via = new (std::nothrow) int32_t[(size_t)M];
+        AVL_REQUIRE(g->h_many_via, "avl_navmany_plan: out of host memory");
+        g->h_many_via_cap = M;
+    }
+    if ((rc = navmany_reserve(g, M)) != AVL_OK) return rc;
+    g->many_planned = 0;
+    // the tree: the start's row, an all-zero goal row and sg = 0, so that the goal node neither pulls nor is pulled from
+    AVL_HIP_CHECK(hipMemsetAsync(g->m_qbits, 0, sizeof(unsigned long long) * 2 * (size_t)std::max<int64_t>(W64, 1), st));
+    hipLaunchKernelGGL(nav_query_kernel, dim3((unsigned)(V / 256 + 1), 1), dim3(256), 0, st, grid, g->verts, V, W64, sr, sc, sr, sc,
+                       g->m_qbits, g->m_sg);
+    AVL_HIP_CHECK(hipMemsetAsync(g->m_sg, 0, sizeof(int32_t), st));      // (the kernel's start-"goal" bit is not wanted)
+    double* d0 = g->m_dist;
+    double* d1 = g->m_dist + N;
+    hipLaunchKernelGGL(nav_init_kernel, dim3(nav_blocks(N, 256)), dim3(256), 0, st, N, V, d0, d1);
+    AVL_HIP_CHECK(hipMemsetAsync(g->m_flags, 0, sizeof(int32_t) * (size_t)(N + 2), st));
+    AVL_HIP_CHECK(hipMemsetAsync(g->m_walks, 0, sizeof(unsigned long long) * 2, st));
+    AVL_HIP_CHECK(hipGetLastError());
+    const NavNodes nodes{g->verts, V, W64, g->bits, g->m_qbits, g->m_sg, g->vspan, g->vrun, sr, sc, sr, sc};
+    if ((rc = nav_relax(nodes, d0, d1, g->m_flags, g->m_pred, "avl_navmany_plan", st)) != AVL_OK) return rc;
+    if (M > 0) {
+        AVL_HIP_CHECK(hipMemcpyAsync(g->m_goals, h_goals, sizeof(double) * 2 * (size_t)M, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(nav_goals_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, grid, nodes, d0, g->m_goals, M, g->m_out,
+                           g->m_via, g->count_walks ? g->m_walks : nullptr);
+        AVL_HIP_CHECK(hipGetLastError());
+        AVL_HIP_CHECK(hipMemcpyAsync(h_dist, g->m_out, sizeof(double) * (size_t)M, hipMemcpyDeviceToHost, st));
+        AVL_HIP_CHECK(hipMemcpyAsync(g->h_many_via, g->m_via, sizeof(int32_t) * (size_t)M, hipMemcpyDeviceToHost, st));
+    }
+    AVL_HIP_CHECK(hipMemcpyAsync(g->h_many_pred, g->m_pred, sizeof(int32_t) * (size_t)N, hipMemcpyDeviceToHost, st));
+    AVL_HIP_CHECK(hipMemcpyAsync(g->many_walks, g->m_walks, sizeof(unsigned long long) * 2, hipMemcpyDeviceToHost, st));
+    AVL_HIP_CHECK(hipStreamSynchronize(st));
+    int64_t best = -1;
+    for (int64_t k = 0; k < M; ++k) {                    // the smallest k with the smallest finite distance
+        h_via[k] = g->h_many_via[k];
+        if (h_dist[k] < INFINITY && (best < 0 || h_dist[k] < h_dist[best])) best = k;
+    }
+    *h_best = best;
+    g->many_M = M;
+    g->many_planned = 1;
+    g->many_counted = g->count_walks;
+    return AVL_OK;
+}
+
+extern "C" int avl_navmany_path(void* graph, int64_t k, int32_t* h_path, int* h_len, int cap, void* stream) {
+    (void)stream;                                        // the tree and via[] of the last batch are kept on the host
+    AVL_REQUIRE(graph && h_len, "avl_navmany_path: null pointer");
+    AvlNavGraph* g = static_cast<AvlNavGraph*>(graph);
+    *h_len = 0;
+    if (!g->many_planned) {
+        set_error("avl_navmany_path: no batch has been planned on this graph");
+        return AVL_ERR_STATE;
+    }
+    AVL_REQUIRE(k >= 0 && k < g->many_M, "avl_navmany_path: goal %lld of %lld", (long long)k, (long long)g->many_M);
+    AVL_REQUIRE(cap >= 0 && (cap == 0 || h_path), "avl_navmany_path: bad path buffer");
+    const int64_t V = g->V, N = V + 2;
+    int64_t v = g->h_many_via[k];
+    if (v < 0) return AVL_OK;                            // unreachable: an empty path
+    // goal -> via -> the tree's predecessors -> start (distances strictly decrease: at most N nodes), then reversed
+    int64_t len = 0;
+    if (cap > 0) h_path[0] = (int32_t)(V + 1);
+    len = 1;
+    for (; v >= 0 && v <= V && len <= N; v = g->h_many_pred[v]) {
+        if (len < cap) h_path[len] = (int32_t)v;
+        ++len;
+        if (v == V) break;
+    }
+    if (v != V) {
+        set_error("avl_navmany_path: the predecessor chain of goal %lld does not reach the start", (long long)k);
+        return AVL_ERR_STATE;
+    }
+    if (len > cap) {
+        set_error("avl_navmany_path: the path has %lld nodes, the buffer %d", (long long)len, cap);
+        return AVL_ERR_INVALID;
+    }
+    std::reverse(h_path, h_path + len);
+    *h_len = (int)len;
+    return AVL_OK;
+}
+
+// counting is off by default: a batch then hands the kernel no counters and pays nothing for them
+extern "C" int avl_navmany_count_walks(void* graph, int on) {
+    AVL_REQUIRE(graph, "avl_navmany_count_walks: null handle");
+    static_cast<AvlNavGraph*>(graph)->count_walks = on ? 1 : 0;
+    return AVL_OK;
+}
+
+// the pruning of the last batch, for the probe: h_counts[0] = walks started, h_counts[1] = candidates with a finite distance
+extern "C" int avl_navmany_stats(void* graph, uint64_t* h_counts) {
+    AVL_REQUIRE(graph && h_counts, "avl_navmany_stats: null pointer");
+    AvlNavGraph* g = static_cast<AvlNavGraph*>(graph);
+    if (!g->many_planned) {
+        set_error("avl_navmany_stats: no batch has been planned on this graph");
+        return AVL_ERR_STATE;
+    }
+    if (!g->many_counted) {
+        set_error("avl_navmany_stats: the last batch did not count its walks (avl_navmany_count_walks)");
+        return AVL_ERR_STATE;
+    }
+    h_counts[0] = g->many_walks[0];
+    h_counts[1] = g->many_walks[1];
     return AVL_OK;
 }

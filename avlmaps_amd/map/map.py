@@ -146,6 +146,20 @@ class Map:
         k = self.select_nearest_obj(centers, bbox_list, curr_pos)
         return self.nearest_point_on_polygon(curr_pos, contours[k])
 
+    def get_nearest_reachable_pos(self, curr_pos: List[float], name: str, navigator):
+        """-> (pos, path): the contour point of a sizeable `name` object with the shortest TRAVEL distance from curr_pos on the
+        navigator's obstacle map, and the path to it (Navigator.plan_to_nearest; full-map (row, col)).  The candidates are the
+        contour points of every island that survives filter_small_objects(area_thres=10), island by island in get_pos order; ties
+        go to the first candidate.  (curr_pos, [curr_pos]) when there is no island; NoPathError when no candidate can be reached.
+        get_nearest_pos picks as the crow flies, which may be the object behind the wall."""
+        contours, centers, bbox_list = self.get_pos(name)
+        keep = self.filter_small_objects(bbox_list, area_thres=10)
+        if not keep:
+            return curr_pos, [curr_pos]
+        cand = np.concatenate([np.asarray(contours[i]).reshape(-1, 2) for i in keep], axis=0)
+        k, path = navigator.plan_to_nearest(curr_pos, cand)
+        return [int(cand[k, 0]), int(cand[k, 1])], path
+
     @staticmethod
     def nearest_point_on_polygon(coord: List[float], polygon) -> List[int]:
         """The exact nearest point to `coord` on the closed ring through `polygon`'s points (no shapely): among equally near points

@@ -9,7 +9,8 @@ from typing import List, Tuple
 
 import numpy as np
 
-from ..utils.navigation_utils import NoPathError, build_visgraph_with_obs_map, plan_to_pos_v2  # noqa: F401
+from ..utils.navigation_utils import (NoPathError, build_visgraph_with_obs_map, path_lengths, plan_to_nearest_pos,  # noqa: F401
+                                      plan_to_pos_v2)
 
 
 class Navigator:
@@ -36,6 +37,27 @@ class Navigator:
         goal = self._convert_full_map_pos_to_cropped_map_pos(goal_full_map)
         paths = plan_to_pos_v2(start, goal, self.obs_map, self.visgraph, vis)
         return self.shift_path(paths, self.rowmin, self.colmin)
+
+    def path_lengths(self, start_full_map: Tuple[float, float], goals_full_map) -> np.ndarray:
+        """(M,) float64 travel distances from the start to every goal of (M, 2) full-map points, inf where plan_to would raise
+        NoPathError: one shortest-path tree from the start and one launch over the goals"""
+        if self.visgraph is None:
+            raise RuntimeError("build_visgraph first")
+        start = self._convert_full_map_pos_to_cropped_map_pos(start_full_map)
+        return path_lengths(start, self._goals_to_cropped(goals_full_map), self.obs_map, self.visgraph)
+
+    def plan_to_nearest(self, start_full_map: Tuple[float, float], goals_full_map):
+        """-> (index, path): the goal with the shortest travel distance (the first on ties) and plan_to's path to it, in full-map
+        coordinates.  NoPathError when no goal can be reached."""
+        if self.visgraph is None:
+            raise RuntimeError("build_visgraph first")
+        start = self._convert_full_map_pos_to_cropped_map_pos(start_full_map)
+        k, paths = plan_to_nearest_pos(start, self._goals_to_cropped(goals_full_map), self.obs_map, self.visgraph)
+        return k, self.shift_path(paths, self.rowmin, self.colmin)
+
+    def _goals_to_cropped(self, goals_full_map) -> np.ndarray:
+        goals = np.asarray(goals_full_map, dtype=np.float64).reshape(-1, 2)
+        return goals - np.array([self.rowmin, self.colmin], np.float64)
 
     def shift_path(self, paths: List[List[float]], row_shift: float, col_shift: float) -> List[List[float]]:
         return [[p[0] + row_shift, p[1] + col_shift] for p in paths]

@@ -1481,6 +1481,7 @@ def goal_fuse(terms, grid_pos, want_heat=True, stream=None) -> GoalResult:
 # ---------------------------------------------------------------------------------------- visibility-graph navigation
 NAV_MAX_VERTICES = 65536
 NAV_MAX_SIDE = 32768
+NAV_MANY_MAX = 1 << 20          # points per snap / goals per plan_many
 
 
 class NavGraph:
@@ -1494,6 +1495,7 @@ class NavGraph:
         self.V = V
         self.W64 = (V + 63) // 64
         self._verts = None
+        self._many = 0              # serial of the last plan_many: its NavPlanMany alone may read paths
 
     def _handle(self):
         if self._h is None:
@@ -1546,6 +1548,56 @@ class NavGraph:
                                                  None), "avl_nav_last_plan")
         return dict(dist=dist, pred=pred, qvis=unpack_rows(q[:, :self.W64], self.V), sg=bool(sg[0]))
 
+    def _points(self, points, what):
+        """(M, 2) float64 points checked like plan's: finite and inside the map"""
+        pts = np.ascontiguousarray(np.asarray(points, dtype=np.float64).reshape(-1, 2))
+        if len(pts) > NAV_MANY_MAX:
+            raise ValueError(f"{len(pts)} {what}: at most {NAV_MANY_MAX} per call")
+        H, W = self.shape
+        ok = np.isfinite(pts).all(axis=1) & (pts[:, 0] >= 0.0) & (pts[:, 0] <= H - 1) & (pts[:, 1] >= 0.0) & (pts[:, 1] <= W - 1)
+        if not ok.all():
+            k = int(np.argmin(ok))
+            raise ValueError(f"point ({pts[k, 0]}, {pts[k, 1]}) lies outside the {H} x {W} map")
+        return pts
+
+    def snap(self, points):
+        """navigation_utils._in_obstacle + _nearest_free for (M, 2) points, on the device -> (points_out (M, 2) float64, moved (M,)
+        bool): a point inside the obstacle set (an obstacle cell, or strictly inside a triangle fill) moves to the free cell with
+        the smallest squared distance, the first in raster order on ties; the others come back unchanged.  AvlError when the map
+        has no free cell."""
+        pts = self._points(points, "points")
+        out = np.empty_like(pts)
+        moved = np.zeros(len(pts), np.uint8)
+        _lib.check(_lib.load().avl_navmany_snap(self._handle(), pts.ctypes.data, len(pts), out.ctypes.data, moved.ctypes.data, None),
+                   "avl_navmany_snap")
+        return out, moved.astype(bool)
+
+    def plan_many(self, start, goals) -> "NavPlanMany":
+        """the shortest-path tree from start (row, col), computed once, and every goal of (M, 2) `goals` against it in one launch:
+        dist, via and best of avl_navmany_plan.  dist[k] and path(k) equal plan(start, goals[k]) exactly."""
+        handle = self._handle()
+        s = self._points([start], "points")[0]
+        pts = self._points(goals, "goals")
+        M = len(pts)
+        dist = np.empty(M, np.float64)
+        via = np.empty(M, np.int32)
+        best = C.c_int64(-1)
+        _lib.check(_lib.load().avl_navmany_plan(handle, float(s[0]), float(s[1]), pts.ctypes.data, M, dist.ctypes.data,
+                                                via.ctypes.data, C.byref(best), None), "avl_navmany_plan")
+        self._many += 1
+        return NavPlanMany(self, self._many, dist, via, int(best.value))
+
+    def count_walks(self, on=True):
+        """have the following plan_many calls count their walks for many_stats (off by default: counting costs a little per word)"""
+        _lib.check(_lib.load().avl_navmany_count_walks(self._handle(), 1 if on else 0), "avl_navmany_count_walks")
+
+    def many_stats(self) -> dict:
+        """the pruning of the last plan_many (after count_walks()): walks started, and goal-vertex pairs with a finite candidate
+        (the walks without pruning)"""
+        n = np.zeros(2, np.uint64)
+        _lib.check(_lib.load().avl_navmany_stats(self._handle(), n.ctypes.data), "avl_navmany_stats")
+        return dict(walks=int(n[0]), candidates=int(n[1]))
+
     def close(self):
         if self._h is not None:
             h, self._h = self._h, None
@@ -1556,6 +1608,29 @@ class NavGraph:
 
     def __del__(self):
         self.close()
+
+
+class NavPlanMany:
+    """One NavGraph.plan_many: dist (M,) float64 (inf = unreachable), via (M,) int32 (the node each goal hangs on: a vertex id,
+    V = the start, -1 = unreachable), best (the first goal with the smallest finite distance, -1 = none) and path(k), the node ids
+    start .. goal k (V = start, V + 1 = goal; [] when unreachable).  path() reads the tree kept on the graph, so it answers only
+    until the graph's next plan_many."""
+
+    def __init__(self, graph, serial, dist, via, best):
+        self._g, self._serial = graph, serial
+        self.dist, self.via, self.best = dist, via, best
+
+    def path(self, k):
+        k = int(k)
+        if not 0 <= k < len(self.dist):
+            raise IndexError(f"goal {k} of {len(self.dist)}")
+        if self._g._many != self._serial:
+            raise ValueError("the graph has planned another batch since: this one's paths are gone")
+        cap = self._g.V + 2
+        ids = np.zeros(cap, np.int32)
+        n = C.c_int(0)
+        _lib.check(_lib.load().avl_navmany_path(self._g._handle(), k, ids.ctypes.data, C.byref(n), cap, None), "avl_navmany_path")
+        return ids[:n.value].tolist()
 
 
 def unpack_rows(words: np.ndarray, n: int) -> np.ndarray:

@@ -183,6 +183,76 @@ def plan_to_pos_v2(start, goal, obstacles, G=None, vis=False):
     return path
 
 
+def _snapped_batch(start, goals, obstacles, G):
+    """start and goals checked like plan_to_pos_v2's and snapped by its rule on the device -> (s, start_moved, goals (M, 2))"""
+    from .. import _lib
+    s = list(_inside(obstacles, start))
+    goals = np.asarray(goals, dtype=np.float64).reshape(-1, 2)
+    H, W = np.shape(obstacles)
+    ok = np.isfinite(goals).all(axis=1) & (goals >= 0.0).all(axis=1) & (goals[:, 0] <= H - 1) & (goals[:, 1] <= W - 1)
+    if not ok.all():
+        _inside(obstacles, goals[int(np.argmin(ok))])        # raises, with plan_to_pos_v2's message
+    try:
+        out, moved = G.snap(np.vstack([np.array([s], np.float64), goals]))
+    except _lib.AvlError as e:
+        if "no free cell" in str(e):
+            raise NoPathError("the obstacle map has no free cell") from None
+        raise
+    return [float(out[0, 0]), float(out[0, 1])], bool(moved[0]), out[1:]
+
+
+def path_lengths(start, goals, obstacles, G=None):
+    """(M,) float64 travel distances from start to every goal of (M, 2) `goals` on the obstacle map: for each goal the length of
+    plan_to_pos_v2's path summed left to right, inf where that raises NoPathError -- from one shortest-path tree and one launch
+    over the goals (NavGraph.plan_many) instead of one plan per goal.  Start and goals snap by plan_to_pos_v2's rule, on the
+    device (NavGraph.snap); a goal equal to the start has length 0."""
+    obstacles = np.asarray(obstacles)
+    own = G is None
+    if own:
+        _inside(obstacles, start)                        # argument errors before any device work
+        G = build_visgraph_with_obs_map(obstacles)
+    try:
+        s, _, goals = _snapped_batch(start, goals, obstacles, G)
+        return G.plan_many(s, goals).dist
+    finally:
+        if own:
+            G.close()
+
+
+def plan_to_nearest_pos(start, goals, obstacles, G=None):
+    """-> (k, path): the goal with the shortest travel distance from start (the first one on ties) and the path to it, as
+    plan_to_pos_v2(start, goals[k], ...) returns it: a snapped start is listed twice, a goal equal to the start gives [start].
+    NoPathError when no goal can be reached (also for an empty goal list)."""
+    obstacles = np.asarray(obstacles)
+    own = G is None
+    if own:
+        _inside(obstacles, start)
+        G = build_visgraph_with_obs_map(obstacles)
+    try:
+        s, s_moved, goals = _snapped_batch(start, goals, obstacles, G)
+        pm = G.plan_many(s, goals)
+        k = int(pm.best)
+        if k < 0:
+            raise NoPathError(f"none of the {len(goals)} goals can be reached from {s} on the obstacle map")
+        g = [float(goals[k, 0]), float(goals[k, 1])]
+        path = [list(s)] if s_moved else []
+        if s == g:
+            path.append(list(s))
+            return k, path
+        verts = G.vertices()
+        for v in pm.path(k):
+            if v == G.V:
+                path.append(list(s))
+            elif v == G.V + 1:
+                path.append(list(g))
+            else:
+                path.append([float(verts[v, 0]), float(verts[v, 1])])
+        return k, path
+    finally:
+        if own:
+            G.close()
+
+
 def get_bbox(center, size):
     """(min corner, max corner) of the box of `size` centred at `center` (navigation_utils.py:200-206)"""
     center, size = np.asarray(center), np.asarray(size)

@@ -765,6 +765,43 @@ AVL_API int avl_nav_plan(void* graph, double sr, double sc, double gr, double gc
  * of the start and of the goal, h_sg the start-goal visibility.  Synchronous. */
 AVL_API int avl_nav_last_plan(void* graph, double* h_dist, int32_t* h_pred, uint64_t* h_qbits, int32_t* h_sg, void* stream);
 
+/* Many goals from one start (DESIGN.md 4.6 "Many goals").  (The prefix is avl_navmany_, not avl_nav_: the set of avl_nav_*
+ * declarations is pinned by tests/test_navigator_host.py and stays the single-plan interface.)  These entry points work on the avl_nav_create handle and keep buffers of
+ * their own on it (grown on demand, freed by avl_nav_destroy): single plans and batches may interleave on one graph, and
+ * avl_nav_last_plan keeps describing the last avl_nav_plan.  At most 2^20 points per call; M = 0 is valid and touches no output
+ * array.  Every point must be finite and inside [0, H - 1] x [0, W - 1] (AVL_ERR_INVALID otherwise, as in avl_nav_plan).
+ * Synchronous.
+ *
+ * avl_navmany_snap: navigation_utils._in_obstacle + _nearest_free for M points, h_pts (M, 2) float64 (row, col).  A point is inside
+ * the obstacle set when its int() cell is an obstacle, or when that cell is free, the other three cells of the 2 x 2 window below
+ * and right of it are obstacles and the point lies strictly beyond the hypotenuse ((r - int r) + (c - int c) > 1, not on a grid
+ * line).  Such a point moves to the free cell with the smallest (r - pr) * (r - pr) + (c - pc) * (c - pc), evaluated in float64
+ * without contraction; ties go to the first cell in raster order (smallest row, then smallest column), which is np.argmin over
+ * np.where.  h_out (M, 2) float64 gets the cell (h_moved[k] = 1) or the point unchanged (h_moved[k] = 0).  The search goes outward
+ * ring by ring from the point's cell and stops once no cell further out can beat or tie the best.  A map without a free cell:
+ * AVL_ERR_STATE. */
+AVL_API int avl_navmany_snap(void* graph, const double* h_pts, int64_t M, double* h_out, uint8_t* h_moved, void* stream);
+/* avl_navmany_plan: the start's visibility row and the shortest-path tree from (sr, sc) over the V vertices (the relaxation and the
+ * predecessor rule of avl_nav_plan, no goal node taking part), then every goal of h_goals (M, 2) float64 against the tree:
+ *   h_dist[k] = min(fl(D[u] + |u g_k|) over the vertices u that see g_k, with D[u] finite and the edge usable at u; |s g_k| when the
+ *               start sees the goal); +inf when nothing reaches the goal;
+ *   h_via[k]  = the node the goal hangs on: the SMALLEST vertex id that attains the minimum, V (the start) only when no vertex does;
+ *               -1 for an unreachable goal;
+ *   *h_best   = the SMALLEST k with the smallest finite h_dist[k]; -1 when there is none (also for M = 0).
+ * h_dist[k] and the path of goal k equal avl_nav_plan's for the same start and goal, bit for bit. */
+AVL_API int avl_navmany_plan(void* graph, double sr, double sc, const double* h_goals, int64_t M, double* h_dist, int32_t* h_via,
+                             int64_t* h_best, void* stream);
+/* the node ids start .. goal k of the last avl_navmany_plan, read from the tree's predecessors and via[k] (no second relaxation):
+ * V = the start, V + 1 = the goal, as in avl_nav_plan.  *h_len = 0 for an unreachable goal.  AVL_ERR_STATE before the first batch,
+ * AVL_ERR_INVALID for k outside the batch or a buffer that is too small (V + 2 always suffices). */
+AVL_API int avl_navmany_path(void* graph, int64_t k, int32_t* h_path, int* h_len, int cap, void* stream);
+/* the pruning of the last avl_navmany_plan, for tools/probe_plan_many.py ("the share of walks that pruning skipped"):
+ * h_counts[0] = goal-vertex walks started, h_counts[1] = goal-vertex pairs with a finite candidate distance (the walks an unpruned
+ * kernel would start).  Counting is off until avl_navmany_count_walks(graph, 1): a batch then costs nothing for it.
+ * avl_navmany_stats after a batch that did not count: AVL_ERR_STATE. */
+AVL_API int avl_navmany_count_walks(void* graph, int on);
+AVL_API int avl_navmany_stats(void* graph, uint64_t* h_counts);
+
 /* ------------------------------------------------------------------------------------------------
  * (9) 2-D image morphology on top-down masks (csrc/avl_morph2d.hip): the SciPy / OpenCV calls of the planner's map smoothing.
  *     All pointers are device pointers unless named h_*; images are row-major, uint8 (nonzero = true on input, 0 / 1 on output)
