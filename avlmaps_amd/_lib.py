@@ -175,6 +175,12 @@ _SIGS = {
     "avl_trace_islands": (C.c_int, [_vp, C.c_int, C.c_int, _i32, _vp, _vp, _vp, _i64, _vp]),
     "avl_nearest_pair_work_bytes": (C.c_int, [_i64, _i64, C.POINTER(_sz)]),
     "avl_nearest_pair_i32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "avl_render_colorize": (C.c_int, [_vp, C.c_int, _vp, _vp, _i64, _f64, _vp, _vp, _vp]),
+    "avl_render_topdown_work_bytes": (C.c_int, [C.c_int, C.c_int, C.POINTER(_sz)]),
+    "avl_render_topdown": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f64, _vp, _vp, _vp,
+                                     _sz, _vp]),
+    "avl_render_view_work_bytes": (C.c_int, [C.c_int, C.c_int, C.POINTER(_sz)]),
+    "avl_render_view": (C.c_int, [_vp, _vp, _i64, _vp, _f64, _f64, _f64, _f64, C.c_int, C.c_int, _f64, _f64, _vp, _vp, _vp, _sz, _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -5,12 +5,18 @@ and image branches, :23-142; the Open3D viewer and the habitat branches are not 
                                          [--decay-rate R] [--text-model clip|hash]
     python -m avlmaps_amd.apps.index_map --data-dir <scene> --modality fused [--object NAME]... [--area NAME]... [--sound NAME]...
                                          [--image PNG] [--object-decay R] [--area-decay R] [--sound-decay R] [--image-decay R]
+    ... any modality ...                 [--render PNG [--view topdown|frame:<i>|orbit] [--render-size W H]] [--save-ply PLY]
 
 object (default): the VLMap text query; area: the area map's frame embeddings (area_map/clip_sparse_map.h5df); sound: the sound
 map (audio_video/audio_data_<difficulty>.pkl); image: --image (a PNG) localised at row --image-pose of poses.txt (the model-free
 localiser; upstream uses HLoc); fused: the cross-modal goal, the product of every --object, --area, --sound and --image heat
 (AVLMap.index_goal; at least one of them, decay rates default to the stand-alone queries' 0.1, 0.1, 0.01, 0.01).  Prints the heat statistics and the voxel the navigator would go to (argmax of the heat,
-habitat_lang_robot.py:427-430); --save writes the (N,) heat vector as .npy (float64 for fused)."""
+habitat_lang_robot.py:427-430); --save writes the (N,) heat vector as .npy (float64 for fused).
+
+--render writes the picture the reference shows in a window (visualize_heatmap_3d, application/index_map.py): the heat in JET
+colours over the map's own, rendered on the GPU (AVLMap.render_heat).  --view topdown (default) is the map from above, frame:<i>
+what the robot's camera saw at frame i, orbit an outside view of the whole map.  --save-ply writes the coloured voxels as a binary
+PLY point cloud (visualize_heatmap_3d with save_path) for any viewer."""
 from __future__ import annotations
 
 import argparse
@@ -41,7 +47,13 @@ def parse_args(argv=None):
     ap.add_argument("--sound-decay", type=float, default=None, help="fused: decay rate of the sound heats (default 0.01)")
     ap.add_argument("--image-decay", type=float, default=None, help="fused: decay rate of the image heat (default 0.01)")
     ap.add_argument("--save", default=None)
+    ap.add_argument("--render", default=None, metavar="PNG", help="write the heat over the map's colours as a PNG")
+    ap.add_argument("--view", default="topdown", help="topdown (default), frame:<i> (the camera of frame i) or orbit")
+    ap.add_argument("--render-size", type=int, nargs=2, default=[640, 480], metavar=("W", "H"), help="image size of a camera view")
+    ap.add_argument("--save-ply", default=None, metavar="PLY", help="write the coloured voxels as a binary PLY point cloud")
     args = ap.parse_args(argv)
+    if not valid_view(args.view):
+        ap.error(f"--view {args.view}: expected topdown, orbit or frame:<i> with a frame number")
     if args.modality == "fused":
         if not (args.object or args.area or args.sound or args.image):
             ap.error("--modality fused needs at least one of --object, --area, --sound, --image")
@@ -52,6 +64,26 @@ def parse_args(argv=None):
     elif args.modality == "image" and not args.image:
         ap.error("--modality image needs --image")
     return args
+
+
+def valid_view(view: str) -> bool:
+    if view in ("topdown", "orbit"):
+        return True
+    return view.startswith("frame:") and view[len("frame:"):].isdigit()
+
+
+def write_pictures(avlmap, heat, args) -> None:
+    """--render and --save-ply of a finished query"""
+    if args.render:
+        from PIL import Image
+        img = avlmap.render_heat(heat, view=args.view, size=tuple(args.render_size))
+        Image.fromarray(img).save(args.render)
+        print(f"wrote {args.render}: {args.view} view, {img.shape[1]} x {img.shape[0]}")
+    if args.save_ply:
+        from avlmaps_amd.utils.visualize_utils import visualize_heatmap_3d
+        vm = avlmap.vlmap
+        visualize_heatmap_3d(vm.grid_pos, heat, vm.grid_rgb, save_path=args.save_ply)
+        print(f"wrote {args.save_ply}: {len(heat)} points")
 
 
 def fused_decay_rates(args) -> dict:
@@ -95,6 +127,7 @@ def main(argv=None):
               f"goal voxel id {goal.voxel} at grid_pos {goal.pos.tolist()} (heat {goal.value:.3f})")
         if args.save:
             np.save(args.save, heat)
+        write_pictures(avlmap, heat, args)
         return heat
     if args.modality == "object":
         cats = None
@@ -117,6 +150,7 @@ def main(argv=None):
           f"goal voxel id {idx} at grid_pos {vm.grid_pos[idx].tolist()} (heat {val:.3f})")
     if args.save:
         np.save(args.save, heat)
+    write_pictures(avlmap, heat, args)
     return heat
 
 

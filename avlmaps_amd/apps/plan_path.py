@@ -6,7 +6,7 @@ setup_scene + move_to (robot/habitat_lang_robot.py:88-104, 432-461) without the 
                                         [--customize-obstacles [--potential-obstacles a,b,c --obstacles a,b]
                                          [--dilate-iter N] [--gaussian-sigma S]]
                                         [--relation left|right|between|north|south|east|west|face --heading DEG [--query-b NAME]]
-                                        [--nearest euclid|path]
+                                        [--nearest euclid|path] [--render PNG]
 
 Loads <scene>/vlmap/vlmaps.h5df (with --text-model hash a missing map is first created with the model-free feature stand-in, as
 apps.create_map --features hash does), builds the obstacle map (Map.generate_obstacle_map), takes the goal from
@@ -39,7 +39,11 @@ get_north_pos / get_south_pos / get_east_pos / get_west_pos; map.py:366-485 upst
 degrees (0 = towards smaller rows, clockwise positive).  `between` takes the second object from --query-b.  The JSON line then has
 "relation", "heading" and "goal_cell", the method's own result; "goal" is that point clamped into the cropped obstacle map.
 `face` plans nothing: it prints the angle to turn right to face the nearest --query object (Map.get_delta_angle_to) as
-"turn_right_deg".  A relation with nothing in front of the robot ends with a message and exit status 1."""
+"turn_right_deg".  A relation with nothing in front of the robot ends with a message and exit status 1.
+
+With --render the plan is also drawn: the top-down colour map of the obstacle crop (Map.generate_rgb_topdown_map) with the
+obstacle cells the planner used darkened, the path as a polyline, the start in green and the goal in red, as a PNG.  The JSON line
+then has "render", the file."""
 from __future__ import annotations
 
 import argparse
@@ -78,7 +82,10 @@ def parse_args(argv=None):
     ap.add_argument("--nearest", choices=["euclid", "path"], default="euclid",
                     help="which --query object is the goal: euclid = the nearest as the crow flies (Map.get_nearest_pos); "
                          "path = the one with the shortest travel distance (Map.get_nearest_reachable_pos)")
+    ap.add_argument("--render", default=None, metavar="PNG", help="draw the crop, its obstacles, the path, start and goal")
     args = ap.parse_args(argv)
+    if args.render and args.relation == "face":
+        ap.error("--relation face plans no path: nothing to --render")
     if args.nearest == "path" and (args.relation is not None or args.area or args.sound or args.image or args.goal_2d):
         ap.error("--nearest path chooses among the --query objects: no --relation, --area, --sound, --image or --goal-2d")
     if args.relation is None and (args.heading is not None or args.query_b is not None):
@@ -135,6 +142,23 @@ def clamp_cell(cell, rmin, cmin, shape):
     """the full-map cell moved into the (H, W) crop that starts at (rmin, cmin)"""
     return [min(max(int(cell[0]), int(rmin)), int(rmin) + int(shape[0]) - 1),
             min(max(int(cell[1]), int(cmin)), int(cmin) + int(shape[1]) - 1)]
+
+
+def render_plan(vm, obstacles, start, goal, path):
+    """(H, W, 3) uint8: the crop of the top-down colour map, obstacle cells (obstacles == 0) at a third of their brightness, the
+    path in yellow, the start green, the goal red.  Host drawing on the small image (utils.visualize_utils: integer Bresenham)."""
+    import numpy as np
+    from avlmaps_amd.utils.visualize_utils import draw_marker, draw_polyline
+    r0, c0 = int(vm.rmin), int(vm.cmin)
+    H, W = obstacles.shape
+    img = np.ascontiguousarray(vm.generate_rgb_topdown_map()[r0:r0 + H, c0:c0 + W])
+    blocked = np.asarray(obstacles) == 0
+    img[blocked] = img[blocked] // 3
+    local = [(float(p[0]) - r0, float(p[1]) - c0) for p in path]
+    draw_polyline(img, local, (255, 255, 0))
+    draw_marker(img, (float(start[0]) - r0, float(start[1]) - c0), (0, 255, 0))
+    draw_marker(img, (float(goal[0]) - r0, float(goal[1]) - c0), (255, 0, 0))
+    return img
 
 
 def main(argv=None):
@@ -221,6 +245,10 @@ def main(argv=None):
     out = {"query": args.query, "start": start, "goal": [float(goal[0]), float(goal[1])],
            "path": [[float(p[0]), float(p[1])] for p in path]}
     out.update(extra)
+    if args.render:
+        from PIL import Image
+        Image.fromarray(render_plan(vm, obstacles, start, goal, path)).save(args.render)
+        out["render"] = args.render
     print(json.dumps(out))
     return out
 

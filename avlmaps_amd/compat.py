@@ -11,6 +11,9 @@ so `from avlmaps.utils.clip_utils import get_lseg_score` in avlmaps/map/vlmap.py
   avlmaps.utils.index_utils.get_dynamic_obstacles_map_3d (index_utils.py:138-184)
   avlmaps.utils.visualize_utils.get_heatmap_from_mask_3d (visualize_utils.py:29-49) -> heat kernels
   avlmaps.utils.visualize_utils.pool_3d_label_to_2d      (visualize_utils.py:77-83)
+  avlmaps.utils.visualize_utils.convert_heatmap_to_rgb, pool_3d_rgb_to_2d, visualize_rgb_map_3d, visualize_heatmap_3d,
+      visualize_masked_map_3d, visualize_rgb_map_2d, visualize_heatmap_2d, visualize_masked_map_2d (visualize_utils.py:10-138)
+      -> render kernels and file writers; headless, so a call without save_path raises instead of opening a window
   avlmaps.map.vlmap_builder.VLMapBuilder.create_mobile_base_map (vlmap_builder.py:54-185) -> builder kernels
   avlmaps.map.map.Map.generate_obstacle_map / generate_rgb_topdown_map (map.py:79-95, :106-113) -> top-down scatter kernels
   avlmaps.map.map.Map._dilate_map                  (map.py:169-181)          -> 2-D morphology kernels (avl_dilate_map)
@@ -135,6 +138,9 @@ def install(upstream: str = "avlmaps") -> Dict[str, int]:
     swap("utils.index_utils", "get_dynamic_obstacles_map_3d", my_iu.get_dynamic_obstacles_map_3d)
     swap("utils.visualize_utils", "get_heatmap_from_mask_3d", my_vu.get_heatmap_from_mask_3d)
     swap("utils.visualize_utils", "pool_3d_label_to_2d", my_vu.pool_3d_label_to_2d)
+    for fn in ("convert_heatmap_to_rgb", "pool_3d_rgb_to_2d", "visualize_rgb_map_3d", "visualize_heatmap_3d", "visualize_masked_map_3d",
+               "visualize_rgb_map_2d", "visualize_heatmap_2d", "visualize_masked_map_2d"):
+        swap("utils.visualize_utils", fn, getattr(my_vu, fn))        # headless: they write files (save_path) and open no window
     try:
         vb = importlib.import_module(f"{upstream}.map.vlmap_builder")
         cls = vb.VLMapBuilder

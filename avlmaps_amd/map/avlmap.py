@@ -347,6 +347,39 @@ class AVLMap:
             raise ValueError(f"heat must be ({len(self.vlmap.grid_pos)},), got {heat.shape}")
         return ops.goal_fuse([ops.GoalTerm.dense(heat)], self.vlmap._device_pos(), want_heat=False).pos
 
+    # ------------------------------------------------------------------ pictures
+    def render_heat(self, heat, view="topdown", transparency: float = 0.5, table=None, size=(640, 480), window=None,
+                    intrinsics=None, znear: float = 0.5, smax: float = 16, background=(0, 0, 0)) -> np.ndarray:
+        """A uint8 RGB image of a per-voxel heat (what the index_* queries and index_goal(...).heat return; host array or
+        DeviceArray, float32 or float64) blended over the map's colours with the colour table (default ops.jet_table()), rendered
+        on the GPU from the resident grid_pos and grid_rgb: only the image comes back.
+
+        view="topdown": ops.render_topdown over `window` = (rmin, rmax, cmin, cmax), default the whole (gs, gs) map; `size` is not
+        used.  Any other view is a pinhole camera of size = (W, H) through ops.render_view: "frame:<i>" = the camera that took
+        frame i (utils.visualize_utils.camera_of_frame: what the robot saw there, coloured by the query), "orbit" = an outside
+        view of the whole map (orbit_camera), or a (3, 4) matrix T from cell coordinates to the camera frame (look_at).
+        intrinsics = (fx, fy, cx, cy), default the 90-degree pinhole of the simulator's frames for that size."""
+        from .. import ops
+        from ..utils import visualize_utils as vu
+        vm = self.vlmap
+        if vm.grid_pos is None or vm.grid_rgb is None:
+            raise ValueError("render_heat needs a loaded map with grid_rgb")
+        pos, rgb = vm._device_pos(), vm._device_rgb()
+        if isinstance(view, str) and view == "topdown":
+            return ops.render_topdown(pos, heat, rgb, vm.gs, window=window, transparency=transparency, table=table, background=background)
+        if isinstance(view, str) and view == "orbit":
+            T = vu.orbit_camera(vm.grid_pos)
+        elif isinstance(view, str) and view.startswith("frame:"):
+            T = vu.camera_of_frame(vm, int(view[len("frame:"):]))
+        elif isinstance(view, str):
+            raise ValueError(f"view must be 'topdown', 'orbit', 'frame:<i>' or a (3, 4) matrix, got {view!r}")
+        else:
+            T = np.asarray(view, dtype=np.float64)
+        fx, fy, cx, cy = vu.frame_intrinsics(size) if intrinsics is None else intrinsics
+        color = ops.colorize_heat(heat, rgb, transparency, table=table, as_uint8=True, device=True)
+        return ops.render_view(pos, color, T, fx, fy, cx, cy, size, znear=znear, smax=smax, background=background)
+
+
 
 class Goal:
     """AVLMap.index_goal's answer: heat (N,) float64 (None with want_heat=False), voxel = the first index of its maximum, value =

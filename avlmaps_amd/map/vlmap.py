@@ -170,6 +170,14 @@ class VLMap(Map):
             self._dev_pos_src = self.grid_pos
         return self._dev_pos
 
+    def _device_rgb(self):
+        """grid_rgb mirrored into HBM once as (N, 3) uint8 (re-uploaded only if the host array object changes): the renderer's colours"""
+        from ..device import DeviceArray
+        if getattr(self, "_dev_rgb", None) is None or self._dev_rgb_src is not self.grid_rgb:
+            self._dev_rgb = DeviceArray.from_numpy(np.ascontiguousarray(self.grid_rgb).astype(np.uint8, copy=False).reshape(-1, 3))
+            self._dev_rgb_src = self.grid_rgb
+        return self._dev_rgb
+
     def _heat_plan(self):
         """ops.HeatPlan of this map's voxel positions (cell order + grid buffers), rebuilt only when the positions change; None
         for a map whose bounding box is too large for one (callers then use the stateless ops.heatmap_from_mask)."""

@@ -903,6 +903,39 @@ AVL_API int avl_nearest_pair_work_bytes(int64_t na, int64_t nb, size_t* bytes);
 AVL_API int avl_nearest_pair_i32(const int32_t* d_a, int64_t na, const int32_t* d_b, int64_t nb, int64_t* d_out3, void* ws, size_t ws_bytes,
                                  void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * (12) headless rendering of a per-voxel heat (csrc/avl_render.hip)
+ *     d_table is the colour map as data: (256, 3) uint8 RGB, 768 bytes of device memory.  d_heat is (N,) float32 or float64
+ *     (heat_is_f64 = 0 | 1); a heat that is NaN or outside [0, 1] has no defined uint8 cast: AVL_ERR_INVALID, nothing is clamped.
+ *     The blend is NumPy 2's:  float64(float32(table[idx]) * float32(t)) + float64(rgb) * (1 - t),  idx = (heat * 255).astype(uint8)
+ *     with the product in the heat's own dtype.  0 <= transparency <= 1.  Images are row-major (rows, columns, 3) uint8; every image
+ *     is unique (its bytes do not depend on scheduling).  N < 2^31.
+ * ------------------------------------------------------------------------------------------------ */
+/* avlmaps/utils/visualize_utils.py:59-64 convert_heatmap_to_rgb per voxel: d_out_f64 (N, 3) float64 is the expression itself,
+ * d_out_u8 (N, 3) its truncating .astype(np.uint8) (visualize_utils.py:111); either may be NULL, not both.  Synchronous. */
+AVL_API int avl_render_colorize(const void* d_heat, int heat_is_f64, const uint8_t* d_grid_rgb, const uint8_t* d_table, int64_t N,
+                                double transparency, double* d_out_f64, uint8_t* d_out_u8, void* stream);
+AVL_API int avl_render_topdown_work_bytes(int H, int W, size_t* bytes);
+/* avlmaps/utils/visualize_utils.py:117-128 visualize_heatmap_2d on the window rows [rmin, rmax], columns [cmin, cmax] (inclusive) of
+ * the (gs, gs) map, without a dense heat image: per cell the colour of the voxel with the largest h (avlmaps/map/map.py:106-113 with the
+ * height test upstream meant) blended with table[idx(the largest heat of the column)].  d_out (rmax - rmin + 1, cmax - cmin + 1, 3);
+ * cells without a voxel get h_background3.  Positions wrap and fail like avl_rgb_topdown's.  ws: avl_render_topdown_work_bytes of the
+ * window's shape.  Synchronous. */
+AVL_API int avl_render_topdown(const int32_t* d_grid_pos, const void* d_heat, int heat_is_f64, const uint8_t* d_grid_rgb,
+                               const uint8_t* d_table, int64_t N, int gs, int rmin, int rmax, int cmin, int cmax, double transparency,
+                               const uint8_t* h_background3, uint8_t* d_out, void* ws, size_t ws_bytes, void* stream);
+AVL_API int avl_render_view_work_bytes(int W, int H, size_t* bytes);
+/* avlmaps/utils/visualize_utils.py:10-26 visualize_rgb_map_3d without a window: a z-buffered splat of the voxels from a pinhole
+ * camera.  h_T34: 3 x 4 float64, row-major, from cell coordinates (row, col, h, 1) to the camera frame (x right, y down, z forward,
+ * in cells).  Per voxel, in float64 and this order: p = T (row, col, h, 1) as a left-to-right sum of four products per row; culled
+ * unless z > znear; u = fx * x / z + cx, v = fy * y / z + cy; half = min(0.5 * fx / z, 0.5 * smax); pixels floor(u - half) ..
+ * floor(u + half) by floor(v - half) .. floor(v + half), clipped to the image.  A pixel shows d_color_u8 (N, 3) of the voxel with
+ * the smallest (float32(z), id), or h_background3.  1 <= W, H <= 8192, znear >= 0, 1 <= smax <= 8192.  d_out (H, W, 3).
+ * Asynchronous. */
+AVL_API int avl_render_view(const int32_t* d_grid_pos, const uint8_t* d_color_u8, int64_t N, const double* h_T34, double fx, double fy,
+                            double cx, double cy, int W, int H, double znear, double smax, const uint8_t* h_background3, uint8_t* d_out,
+                            void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
