@@ -181,6 +181,12 @@ _SIGS = {
                                      _sz, _vp]),
     "avl_render_view_work_bytes": (C.c_int, [C.c_int, C.c_int, C.POINTER(_sz)]),
     "avl_render_view": (C.c_int, [_vp, _vp, _i64, _vp, _f64, _f64, _f64, _f64, C.c_int, C.c_int, _f64, _f64, _vp, _vp, _vp, _sz, _vp]),
+    "avl_pnp_lds_stage": (C.c_int, []),
+    "avl_loc_lift": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _i64, _vp, _vp, _vp, C.POINTER(_i64), _vp]),
+    "avl_pnp_ransac_work_bytes": (C.c_int, [C.c_int, C.POINTER(_sz)]),
+    "avl_pnp_ransac": (C.c_int, [_vp, _vp, _i64, _f64, _f64, _f64, _f64, C.c_uint32, C.c_int, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "avl_pnp_score": (C.c_int, [_vp, _vp, _i64, _vp, C.c_int, _f64, _f64, _f64, _f64, _vp, _vp, _vp]),
+    "avl_pnp_refine": (C.c_int, [_vp, _vp, _i64, _vp, _f64, _f64, _f64, _f64, C.c_int, _f64, _vp, _vp, _vp, _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -936,6 +936,51 @@ AVL_API int avl_render_view(const int32_t* d_grid_pos, const uint8_t* d_color_u8
                             double cx, double cy, int W, int H, double znear, double smax, const uint8_t* h_background3, uint8_t* d_out,
                             void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * (13) image localization geometry (csrc/avl_pnp.hip, csrc/avl_pnp_math.h)
+ *     Float64 throughout.  Correspondences are d_points (M, 3) in the reference camera's frame and d_pixels (M, 2) in the query
+ *     image, used as given (no half-pixel shift).  The query camera is the reference's SIMPLE_PINHOLE: f = K[0,0], cx = K[0,2],
+ *     cy = K[1,2].  A pose is a row-major 3 x 4 [R|t], query camera from reference camera.  With (x, y, z) = R X + t, each row the
+ *     left-to-right sum ((r0 X + r1 Y) + r2 Z) + t, a correspondence is an inlier when z > 0, x y z are finite and
+ *     ((f (x / z) + cx) - u)^2 + ((f (y / z) + cy) - v)^2 <= max_error^2; a NaN anywhere is an outlier.  M <= 2^24.
+ * ------------------------------------------------------------------------------------------------ */
+/* the number of correspondences the RANSAC and scoring kernels stage in LDS at a time (larger M takes several stages) */
+AVL_API int avl_pnp_lds_stage(void);
+/* avlmaps/utils/localization_utils.py:461-473 with avlmaps/utils/mapping_utils.py:226-251 (depth2pc) evaluated at the matched pixels
+ * only: d_kp_ref (M, 2) (x, y) in the reference image is truncated toward zero like astype(np.int32); the point is
+ * ((Kinv[i,0] (x + 0.5) + Kinv[i,1] (y + 0.5)) + Kinv[i,2]) * depth[y, x], h_Kinv9 = inv(K_ref) row-major; it is kept when
+ * 0.1 < p_z < 10.  d_depth (H, W) float32 or float64 (depth_is_f64) metres.  d_points (M, 3) / d_pixels (M, 2) receive the kept
+ * points and their d_kp_query rows, compacted in input order; *h_count = M'.  d_counter2: two int32 of device scratch (M' and the
+ * error word, read back in one copy).  A key point that is not finite or truncates outside the image (negative included: NumPy would
+ * wrap it, no matcher produces it) is AVL_ERR_INVALID, the reference's IndexError; nothing is clamped.  Synchronous. */
+AVL_API int avl_loc_lift(const void* d_depth, int depth_is_f64, int H, int W, const double* h_Kinv9, const double* d_kp_ref,
+                         const double* d_kp_query, int64_t M, double* d_points, double* d_pixels, int32_t* d_counter2, int64_t* h_count,
+                         void* stream);
+AVL_API int avl_pnp_ransac_work_bytes(int n_hyp, size_t* bytes);
+/* avlmaps/utils/localization_utils.py:478-498, the estimation half of pycolmap.absolute_pose_estimation: n_hyp P3P hypotheses.
+ * Hypothesis h draws three distinct indices from the counter hash of (seed, h, draw) documented at the top of csrc/avl_pnp.hip
+ * (d_triples (n_hyp, 3) int32, or NULL), solves Grunert's P3P for up to four poses (none for repeated or collinear points or when
+ * no root is real and positive) and counts the inliers of each over all M correspondences.  d_hyp_counts (n_hyp,) int32: the best
+ * count of each hypothesis (ties: the smallest solution index; 0 without a solution).  d_pose12 / d_count: the hypothesis with the
+ * largest count, ties to the smallest h; [I|0] and 0 when no hypothesis has a solution.  ws (avl_pnp_ransac_work_bytes) holds the
+ * (n_hyp, 3, 4) float64 best pose of every hypothesis afterwards, [I|0] where there is none.  3 <= M.  Asynchronous. */
+AVL_API int avl_pnp_ransac(const double* d_points, const double* d_pixels, int64_t M, double f, double cx, double cy, double max_error,
+                           uint32_t seed, int n_hyp, int32_t* d_triples, int32_t* d_hyp_counts, double* d_pose12, int32_t* d_count,
+                           void* ws, size_t ws_bytes, void* stream);
+/* inlier counts d_counts (P,) int32 of caller-supplied poses d_poses (P, 3, 4), and the uint8 inlier mask of pose 0 (d_mask0 (M,), or
+ * NULL): the inlier test of avl_pnp_ransac, the same device function.  Asynchronous. */
+AVL_API int avl_pnp_score(const double* d_points, const double* d_pixels, int64_t M, const double* d_poses, int P, double f, double cx,
+                          double cy, double max_error, int32_t* d_counts, uint8_t* d_mask0, void* stream);
+/* avlmaps/utils/localization_utils.py:486-498, the refinement half (refine_focal_length False): Levenberg-Marquardt on the inliers
+ * of d_pose12 (fixed for the whole refinement), minimising the plain sum of squared pixel residuals over the update
+ * R <- exp([w]x) R, t <- t + dt, in ONE launch that iterates on the device until the step norm |(w, dt)| < step_tol or max_iter
+ * steps were tried.  The normal equations are summed in a fixed order.  d_out13: the refined 3 x 4 pose and the final cost;
+ * d_out3 int32: steps tried, the inlier count of the refined pose over all M, the number of correspondences refined on; d_mask
+ * (M,) uint8: the inlier mask of the refined pose.  Fewer than 3 inliers: the pose is returned as given.  Asynchronous. */
+AVL_API int avl_pnp_refine(const double* d_points, const double* d_pixels, int64_t M, const double* d_pose12, double f, double cx,
+                           double cy, double max_error, int max_iter, double step_tol, double* d_out13, int32_t* d_out3, uint8_t* d_mask,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif
