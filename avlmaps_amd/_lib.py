@@ -187,6 +187,10 @@ _SIGS = {
     "avl_pnp_ransac": (C.c_int, [_vp, _vp, _i64, _f64, _f64, _f64, _f64, C.c_uint32, C.c_int, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "avl_pnp_score": (C.c_int, [_vp, _vp, _i64, _vp, C.c_int, _f64, _f64, _f64, _f64, _vp, _vp, _vp]),
     "avl_pnp_refine": (C.c_int, [_vp, _vp, _i64, _vp, _f64, _f64, _f64, _f64, C.c_int, _f64, _vp, _vp, _vp, _vp]),
+    "avl_audio_decode_pcm16": (C.c_int, [_vp, _i64, C.c_int, _vp, _vp]),
+    "avl_audio_segment_work_bytes": (C.c_int, [_i64, C.POINTER(_sz)]),
+    "avl_audio_segment": (C.c_int, [_vp, _i64, C.c_float, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "avl_audio_pack": (C.c_int, [_vp, _i64, _vp, _i64, _i64, C.c_float, _vp, _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

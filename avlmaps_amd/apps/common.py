@@ -21,7 +21,9 @@ DEFAULTS = {
         "obstacle_names": ["wall", "chair", "table", "window", "stairs", "other"],
     },
     # the sound queries' categories (ESC-50 classes by major category; utils/audio_utils.get_level_categories)
-    "sound_data_collect_params": {"difficulty": "level_3"},
+    # (the values of upstream's config/sound_data_collect_params/sound_collect_default.yaml that the sound map reads)
+    "sound_data_collect_params": {"difficulty": "level_3", "fps": 25, "sample_rate": 44100, "silence_duration_s": 1,
+                                  "silence_threshold": 0, "considered_seq_num_per_scene": 20},
     "sound_config": {
         "difficulty": {
             "level_1": ["Interior/domestic sounds"],
@@ -168,6 +170,24 @@ class HashAudioText:
 
     def encode_text(self, texts):
         return np.stack([_hash_unit(t, self.D) for t in texts]) if len(texts) else np.zeros((0, self.D), np.float32)
+
+
+class HashAudioEncoder:
+    """Stand-in for AudioCLIP's audio head (demo / smoke runs): a D-d unit vector per row of a (B, L) float32 batch, deterministic
+    from the row's bytes, so equal five-second contexts get equal features and different ones are nearly orthogonal."""
+
+    def __init__(self, D=1024):
+        self.D = D
+
+    def __call__(self, batch):
+        b = np.ascontiguousarray(batch, dtype=np.float32)
+        b = b.reshape(1, -1) if b.ndim == 1 else b
+        rows = []
+        for row in b:
+            seed = int.from_bytes(hashlib.sha256(row.tobytes()).digest()[:8], "little")
+            v = np.random.default_rng(seed).standard_normal(self.D).astype(np.float32)
+            rows.append(v / np.linalg.norm(v))
+        return np.stack(rows) if rows else np.zeros((0, self.D), np.float32)
 
 
 class FixedPoseLocalizer:

@@ -1,10 +1,14 @@
 """Build a VLMap for one scene directory.  Counterpart of the reference's application/create_map.py:7-17.
 
     python -m avlmaps_amd.apps.create_map --data-dir <scene> [--config cfg.yaml] [--features lseg|hash] [--seed N]
+                                          [--sound [--audio-model hash]]
 
 <scene>/ holds rgb/*.png, depth/*.npy (float32 metres) and poses.txt (x y z qx qy qz qw per line), the layout of the
 reference's dataset/README.md:76-93; the map goes to <scene>/vlmap/vlmaps.h5df (a real HDF5 file: through h5py, or through
 the HDF5 C library where h5py is missing).
+--sound also builds the sound map (<scene>/audio_video/audio_data_<level>.pkl) from <scene>/audio_video/<seq>/ (a .wav next to
+output_with_audio_<level>.mp4, or the video itself when ffmpeg is installed; poses.txt; the meta file); --audio-model hash is the
+model-free audio encoder, the only one built in (AudioCLIP is attached through AVLMap(audio_encoder=...) from Python).
 Multi-GPU: launch with torchrun; frames are sharded over ranks and merged with one row-sharded RCCL exchange (every --save-every
 frames per rank as a checkpoint, and at the end); an interrupted run is continued with --resume; with --seed the N-rank map
 equals the single-process map (every rank replays the RNG draws of the frames before its shard)."""
@@ -40,10 +44,13 @@ def main(argv=None):
     ap.add_argument("--save-every", type=int, default=None, help="checkpoint every N frames (per rank); default 100 like upstream")
     ap.add_argument("--resume", action="store_true",
                     help="continue from an existing vlmaps.h5df and skip the frames it lists (upstream re-fuses every frame)")
+    ap.add_argument("--sound", action="store_true", help="also build the sound map from <scene>/audio_video")
+    ap.add_argument("--audio-model", choices=["hash"], default="hash",
+                    help="--sound: the audio encoder; hash = model-free stand-in (apps/common.HashAudioEncoder)")
     args = ap.parse_args(argv)
 
     from avlmaps_amd import parallel
-    from avlmaps_amd.apps.common import HashFeatureExtractor, load_config
+    from avlmaps_amd.apps.common import HashAudioEncoder, HashFeatureExtractor, load_config
     from avlmaps_amd.map import AVLMap
     rank, ws, _ = parallel.init_distributed()
     cfg = load_config(args.config)
@@ -79,6 +86,9 @@ def main(argv=None):
         vb.VLMapBuilder.__init__ = patched
     t0 = time.perf_counter()
     avlmap.create_map(args.data_dir, feat_extractor=extractor)
+    if args.sound and rank == 0:
+        path = avlmap.sound_map.create_sound_map(args.data_dir, audio_encoder=HashAudioEncoder())
+        print(f"sound map with {len(avlmap.sound_map.load_sound_map(args.data_dir))} segments written to {path}")
     if rank == 0:
         n = len(avlmap.vlmap.map_builder.last_map["grid_pos"]) if hasattr(avlmap.vlmap.map_builder, "last_map") else -1
         print(f"map with {n} voxels written to {avlmap.vlmap.map_builder.map_save_path} in {time.perf_counter() - t0:.2f} s")

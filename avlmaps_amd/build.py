@@ -35,6 +35,7 @@ SOURCES = {
     "avl_islands.hip": ["-ffp-contract=off"],      # integer kernels; the flag keeps the file in line with the other 2-D sources
     "avl_render.hip": ["-ffp-contract=off"],       # the colour blend rounds like NumPy's float32 and float64 products, unfused
     "avl_pnp.hip": ["-ffp-contract=off"],          # the inlier test and the lift are NumPy's float64 expressions, operation for operation
+    "avl_audio.hip": ["-ffp-contract=off"],        # compares, one product and one division per sample: nothing to fuse, and it stays so
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fvisibility=hidden", "-Wall",
           "-Wno-unused-function", "-munsafe-fp-atomics"]

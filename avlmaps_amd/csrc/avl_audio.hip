@@ -1,0 +1,355 @@
+// The audio side of the sound map for gfx950: PCM16 decoding, silence segmentation of a whole recording, and the zero-padded
+// fixed-length batch the audio encoder reads.  The recording stays in HBM from the upload to the encoder's batch.
+//
+// Replaces (upstream reference, path:line):
+//   avlmaps/utils/audio_utils.py:515-546   segment_audio_with_silence   a Python loop over every sample above the threshold
+//   avlmaps/utils/audio_utils.py:569-583   get_five_second_contexts_audio   one zero-padded float64 host buffer per segment
+//   avlmaps/utils/audio_mapping_utils.py:85   x.astype(np.float32) * 32768.0 per segment
+//
+// Segmentation.  A sample i is loud iff audio[i] > threshold (float32 compare, so NaN is never loud).  With prev(i) the last loud
+// sample before i, a loud sample STARTS a segment iff it has no prev or i - prev(i) >= gap.  Segment k is (l_k, r_k): its start and
+// the last loud sample before the next start (the last loud sample of all for the last segment).  That is upstream's loop in closed
+// form: its `r` is always the previous loud sample when a new loud one is looked at.  prev is an exclusive running maximum of
+// "index if loud else -1", a scan; the starts are then flagged independently and numbered by a second scan.  Reduce-then-scan, five
+// launches, no workgroup waits on another and there are no atomics:
+//   (a) tile_last   every tile of 256 threads x 16 samples: its last loud index or -1
+//   (b) carry       one workgroup: exclusive running maximum of the tile summaries (a loop when there are more tiles than threads)
+//   (c) count       every tile again with its carried value: the starts are flagged and counted
+//   (d) offsets     one workgroup: exclusive sum of the counts, the total to d_count
+//   (e) write       every tile a third time: start k writes l_k and r_(k-1) = its prev; the last tile writes the last r from the
+//                   final summary
+// A thread keeps its 16 samples as a 16-bit loud mask (four 16-byte loads when the pointer allows), the scans inside a tile are wave
+// shuffles over 64 lanes plus one LDS step over the four waves.  Indices fit int32: n <= 2^31 - 1.
+//
+// Pack.  out[k, j] = audio[start_k + j] * scale for j < min(stop_k - start_k, L), else +0.  Rows are independent: a workgroup owns
+// a chunk of one row and stores 16 bytes per lane when L and the output pointer allow.  Ranges are clamped to [0, n] in the kernel, so
+// whatever the device array holds nothing is read out of bounds.
+#include <algorithm>
+#include <climits>
+#include <cmath>
+
+#include "avl_common.h"
+
+namespace avl {
+
+constexpr int kAudThreads = 256;
+constexpr int kAudPer = 16;                           // samples per thread
+constexpr int kAudTile = kAudThreads * kAudPer;       // 4096 samples per workgroup
+constexpr int kAudWaves = kAudThreads / kWave;
+constexpr int kAudMaxChannels = 8;
+constexpr int64_t kAudMaxSamples = INT_MAX;
+constexpr int kPackPer = 16;                          // floats per thread of the pack kernel
+constexpr int kPackChunk = kAudThreads * kPackPer;
+constexpr int kPackMaxRowsY = 32768;
+
+static inline size_t aud_align(size_t b) { return (b + 255) & ~(size_t)255; }
+static inline int64_t aud_tiles(int64_t n) { return (n + kAudTile - 1) / kAudTile; }
+
+// 16-bit mask of the loud samples among the 16 of this thread; base is the index of the first one
+__device__ __forceinline__ unsigned aud_loud_mask(const float* __restrict__ audio, int64_t n, int64_t base, float threshold, bool vec) {
+    unsigned m = 0;
+    if (vec && base + kAudPer <= n) {
+        const float4* p = reinterpret_cast<const float4*>(audio + base);
+#pragma unroll
+        for (int q = 0; q < kAudPer / 4; ++q) {
+            const float4 v = p[q];
+            m |= (unsigned)(v.x > threshold) << (4 * q) | (unsigned)(v.y > threshold) << (4 * q + 1) |
+                 (unsigned)(v.z > threshold) << (4 * q + 2) | (unsigned)(v.w > threshold) << (4 * q + 3);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < kAudPer; ++j)
+            if (base + j < n && audio[base + j] > threshold) m |= 1u << j;
+    }
+    return m;
+}
+
+__device__ __forceinline__ int aud_mask_last(unsigned m, int64_t base) { return m ? (int)base + 31 - __clz((int)m) : -1; }
+
+__device__ __forceinline__ int aud_wave_incl_max(int v, int lane) {
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const int o = __shfl_up(v, d, kWave);
+        if (lane >= d) v = max(v, o);
+    }
+    return v;
+}
+
+template <typename T>
+__device__ __forceinline__ T aud_wave_incl_sum(T v, int lane) {
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const T o = __shfl_up(v, d, kWave);
+        if (lane >= d) v += o;
+    }
+    return v;
+}
+
+// exclusive running maximum over the 256 threads of a workgroup (-1 before the first); *total = the maximum over all of them.
+// lds: kAudWaves ints.  Ends with every thread past its reads of lds only after the caller's next barrier: callers that reuse lds
+// put a __syncthreads() in between.
+__device__ __forceinline__ int aud_block_excl_max(int v, int* lds, int* total) {
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    const int incl = aud_wave_incl_max(v, lane);
+    if (lane == kWave - 1) lds[wave] = incl;
+    __syncthreads();
+    int before = -1, all = -1;
+#pragma unroll
+    for (int w = 0; w < kAudWaves; ++w) {
+        const int x = lds[w];
+        if (w < wave) before = max(before, x);
+        all = max(all, x);
+    }
+    const int up = __shfl_up(incl, 1, kWave);
+    *total = all;
+    return lane ? max(before, up) : before;
+}
+
+template <typename T>
+__device__ __forceinline__ T aud_block_excl_sum(T v, T* lds, T* total) {
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    const T incl = aud_wave_incl_sum(v, lane);
+    if (lane == kWave - 1) lds[wave] = incl;
+    __syncthreads();
+    T before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < kAudWaves; ++w) {
+        const T x = lds[w];
+        if (w < wave) before += x;
+        all += x;
+    }
+    *total = all;
+    return before + incl - v;
+}
+
+// (a)
+__global__ __launch_bounds__(kAudThreads) void aud_tile_last_kernel(const float* __restrict__ audio, int64_t n, float threshold, bool vec,
+                                                                   int* __restrict__ tile_last) {
+    __shared__ int lds[kAudWaves];
+    const int64_t base = (int64_t)blockIdx.x * kAudTile + (int64_t)threadIdx.x * kAudPer;
+    const unsigned m = aud_loud_mask(audio, n, base, threshold, vec);
+    int v = aud_mask_last(m, base);
+#pragma unroll
+    for (int d = kWave / 2; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d, kWave));
+    if ((threadIdx.x & (kWave - 1)) == 0) lds[threadIdx.x / kWave] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int r = lds[0];
+#pragma unroll
+        for (int w = 1; w < kAudWaves; ++w) r = max(r, lds[w]);
+        tile_last[blockIdx.x] = r;
+    }
+}
+
+// (b) one workgroup
+__global__ __launch_bounds__(kAudThreads) void aud_carry_kernel(const int* __restrict__ tile_last, int64_t tiles, int* __restrict__ carry) {
+    __shared__ int lds[kAudWaves];
+    int running = -1;
+    for (int64_t b = 0; b < tiles; b += kAudThreads) {
+        const int64_t t = b + threadIdx.x;
+        const int v = t < tiles ? tile_last[t] : -1;
+        int total;
+        const int ex = aud_block_excl_max(v, lds, &total);
+        if (t < tiles) carry[t] = max(running, ex);
+        running = max(running, total);
+        __syncthreads();                              // lds is written again in the next round
+    }
+}
+
+// the starts among this thread's samples, given prev = the last loud index before its first sample (or -1): a 16-bit mask.
+// The writer repeats the walk, because it needs every start's own prev.
+__device__ __forceinline__ unsigned aud_start_mask(unsigned m, int64_t base, int prev, int64_t gap) {
+    unsigned s = 0;
+    while (m) {
+        const int j = __ffs((int)m) - 1;
+        m &= m - 1;
+        const int i = (int)base + j;
+        if (prev < 0 || (int64_t)i - prev >= gap) s |= 1u << j;
+        prev = i;
+    }
+    return s;
+}
+
+// (c)
+__global__ __launch_bounds__(kAudThreads) void aud_count_kernel(const float* __restrict__ audio, int64_t n, float threshold, int64_t gap,
+                                                               bool vec, const int* __restrict__ carry, int* __restrict__ tile_count) {
+    __shared__ int lds[kAudWaves];
+    __shared__ int lds2[kAudWaves];
+    const int64_t base = (int64_t)blockIdx.x * kAudTile + (int64_t)threadIdx.x * kAudPer;
+    const unsigned m = aud_loud_mask(audio, n, base, threshold, vec);
+    int total;
+    const int prev = max(carry[blockIdx.x], aud_block_excl_max(aud_mask_last(m, base), lds, &total));
+    const int c = __popc(aud_start_mask(m, base, prev, gap));
+    int sum;
+    aud_block_excl_sum<int>(c, lds2, &sum);
+    if (threadIdx.x == 0) tile_count[blockIdx.x] = sum;
+}
+
+// (d) one workgroup
+__global__ __launch_bounds__(kAudThreads) void aud_offsets_kernel(const int* __restrict__ tile_count, int64_t tiles,
+                                                                 int64_t* __restrict__ offsets, int64_t* __restrict__ d_count) {
+    __shared__ int64_t lds[kAudWaves];
+    int64_t running = 0;
+    for (int64_t b = 0; b < tiles; b += kAudThreads) {
+        const int64_t t = b + threadIdx.x;
+        const int64_t v = t < tiles ? tile_count[t] : 0;
+        int64_t total;
+        const int64_t ex = aud_block_excl_sum<int64_t>(v, lds, &total);
+        if (t < tiles) offsets[t] = running + ex;
+        running += total;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) d_count[0] = running;
+}
+
+// (e)
+__global__ __launch_bounds__(kAudThreads) void aud_write_kernel(const float* __restrict__ audio, int64_t n, float threshold, int64_t gap,
+                                                               bool vec, const int* __restrict__ carry, const int* __restrict__ tile_last,
+                                                               const int64_t* __restrict__ offsets, int64_t* __restrict__ segments,
+                                                               int64_t cap) {
+    __shared__ int lds[kAudWaves];
+    __shared__ int lds2[kAudWaves];
+    const int64_t base = (int64_t)blockIdx.x * kAudTile + (int64_t)threadIdx.x * kAudPer;
+    unsigned m = aud_loud_mask(audio, n, base, threshold, vec);
+    int total;
+    int prev = max(carry[blockIdx.x], aud_block_excl_max(aud_mask_last(m, base), lds, &total));
+    const unsigned s = aud_start_mask(m, base, prev, gap);
+    int sum;
+    int64_t k = offsets[blockIdx.x] + aud_block_excl_sum<int>(__popc(s), lds2, &sum);
+    while (m) {
+        const int j = __ffs((int)m) - 1;
+        m &= m - 1;
+        const int i = (int)base + j;
+        if (s >> j & 1u) {
+            if (k < cap) segments[2 * k] = i;
+            if (k >= 1 && k - 1 < cap) segments[2 * (k - 1) + 1] = prev;      // k >= 1: a start with an earlier start has a prev
+            ++k;
+        }
+        prev = i;
+    }
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
+        const int64_t count = offsets[blockIdx.x] + sum;
+        if (count >= 1 && count - 1 < cap) segments[2 * (count - 1) + 1] = max(carry[blockIdx.x], tile_last[blockIdx.x]);
+    }
+}
+
+__global__ __launch_bounds__(kAudThreads) void aud_decode_kernel(const int16_t* __restrict__ pcm, int64_t n, int channels,
+                                                                float* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * kAudThreads + threadIdx.x;
+    if (i >= n) return;
+    const int16_t* p = pcm + i * channels;
+    float s = (float)p[0] / 32768.0f;
+    for (int c = 1; c < channels; ++c) s += (float)p[c] / 32768.0f;
+    out[i] = s / (float)channels;
+}
+
+template <bool kVec>
+__global__ __launch_bounds__(kAudThreads) void aud_pack_kernel(const float* __restrict__ audio, int64_t n, const int64_t* __restrict__ ranges,
+                                                              int64_t S, int64_t L, float scale, float* __restrict__ out) {
+    const int64_t j0 = (int64_t)blockIdx.x * kPackChunk;
+    for (int64_t k = blockIdx.y; k < S; k += gridDim.y) {
+        const int64_t start = min(max(ranges[2 * k], (int64_t)0), n);
+        const int64_t stop = min(max(ranges[2 * k + 1], start), n);
+        const int64_t len = min(stop - start, L);
+        const float* src = audio + start;
+        float* dst = out + k * L;
+        if (kVec) {
+#pragma unroll
+            for (int q = 0; q < kPackPer / 4; ++q) {
+                const int64_t j = j0 + ((int64_t)q * kAudThreads + threadIdx.x) * 4;
+                if (j >= L) break;                    // L % 4 == 0: a group of four is inside the row or outside
+                float4 v;
+                v.x = j < len ? src[j] * scale : 0.0f;
+                v.y = j + 1 < len ? src[j + 1] * scale : 0.0f;
+                v.z = j + 2 < len ? src[j + 2] * scale : 0.0f;
+                v.w = j + 3 < len ? src[j + 3] * scale : 0.0f;
+                *reinterpret_cast<float4*>(dst + j) = v;
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < kPackPer; ++q) {
+                const int64_t j = j0 + (int64_t)q * kAudThreads + threadIdx.x;
+                if (j >= L) break;
+                dst[j] = j < len ? src[j] * scale : 0.0f;
+            }
+        }
+    }
+}
+
+static size_t aud_segment_bytes(int64_t n) {
+    const size_t t = (size_t)aud_tiles(n);
+    return 3 * aud_align(t * sizeof(int)) + aud_align(t * sizeof(int64_t));
+}
+
+}  // namespace avl
+
+using namespace avl;
+
+extern "C" {
+
+int avl_audio_decode_pcm16(const int16_t* d_pcm, int64_t n, int channels, float* d_audio_f32, void* stream) {
+    AVL_REQUIRE(d_pcm && d_audio_f32, "avl_audio_decode_pcm16: null pointer");
+    AVL_REQUIRE(n >= 1 && n <= kAudMaxSamples, "avl_audio_decode_pcm16: n=%lld outside 1 .. 2^31 - 1", (long long)n);
+    AVL_REQUIRE(channels >= 1 && channels <= kAudMaxChannels, "avl_audio_decode_pcm16: channels=%d outside 1 .. %d", channels,
+                kAudMaxChannels);
+    const unsigned blocks = (unsigned)((n + kAudThreads - 1) / kAudThreads);
+    hipLaunchKernelGGL(aud_decode_kernel, dim3(blocks), dim3(kAudThreads), 0, as_stream(stream), d_pcm, n, channels, d_audio_f32);
+    AVL_HIP_CHECK(hipGetLastError());
+    return AVL_OK;
+}
+
+int avl_audio_segment_work_bytes(int64_t n, size_t* h_bytes) {
+    AVL_REQUIRE(h_bytes, "avl_audio_segment_work_bytes: null pointer");
+    AVL_REQUIRE(n >= 1 && n <= kAudMaxSamples, "avl_audio_segment_work_bytes: n=%lld outside 1 .. 2^31 - 1", (long long)n);
+    *h_bytes = aud_segment_bytes(n);
+    return AVL_OK;
+}
+
+int avl_audio_segment(const float* d_audio, int64_t n, float threshold, int64_t gap, int64_t* d_segments, int64_t cap, int64_t* d_count,
+                      void* d_ws, size_t ws_bytes, void* stream) {
+    AVL_REQUIRE(d_audio && d_count && d_ws, "avl_audio_segment: null pointer");
+    AVL_REQUIRE(n >= 1 && n <= kAudMaxSamples, "avl_audio_segment: n=%lld outside 1 .. 2^31 - 1", (long long)n);
+    AVL_REQUIRE(gap >= 1, "avl_audio_segment: gap=%lld, at least one sample is required", (long long)gap);
+    AVL_REQUIRE(!std::isnan(threshold), "avl_audio_segment: the threshold is NaN");
+    AVL_REQUIRE(cap >= 0 && (cap == 0 || d_segments), "avl_audio_segment: cap=%lld without a segment buffer", (long long)cap);
+    AVL_REQUIRE(((uintptr_t)d_audio & 3) == 0, "avl_audio_segment: d_audio is not aligned to 4 bytes");
+    AVL_REQUIRE(ws_bytes >= aud_segment_bytes(n), "avl_audio_segment: workspace of %zu bytes, %zu needed", ws_bytes, aud_segment_bytes(n));
+    const int64_t tiles = aud_tiles(n);
+    char* w = static_cast<char*>(d_ws);
+    const size_t ib = aud_align((size_t)tiles * sizeof(int));
+    int* tile_last = reinterpret_cast<int*>(w);
+    int* carry = reinterpret_cast<int*>(w + ib);
+    int* tile_count = reinterpret_cast<int*>(w + 2 * ib);
+    int64_t* offsets = reinterpret_cast<int64_t*>(w + 3 * ib);
+    const bool vec = ((uintptr_t)d_audio & 15) == 0;
+    hipStream_t st = as_stream(stream);
+    const dim3 grid((unsigned)tiles), block(kAudThreads);
+    hipLaunchKernelGGL(aud_tile_last_kernel, grid, block, 0, st, d_audio, n, threshold, vec, tile_last);
+    hipLaunchKernelGGL(aud_carry_kernel, dim3(1), block, 0, st, tile_last, tiles, carry);
+    hipLaunchKernelGGL(aud_count_kernel, grid, block, 0, st, d_audio, n, threshold, gap, vec, carry, tile_count);
+    hipLaunchKernelGGL(aud_offsets_kernel, dim3(1), block, 0, st, tile_count, tiles, offsets, d_count);
+    hipLaunchKernelGGL(aud_write_kernel, grid, block, 0, st, d_audio, n, threshold, gap, vec, carry, tile_last, offsets, d_segments, cap);
+    AVL_HIP_CHECK(hipGetLastError());
+    return AVL_OK;
+}
+
+int avl_audio_pack(const float* d_audio, int64_t n, const int64_t* d_ranges, int64_t S, int64_t L, float scale, float* d_out,
+                   void* stream) {
+    AVL_REQUIRE(d_audio && d_out && (d_ranges || S == 0), "avl_audio_pack: null pointer");
+    AVL_REQUIRE(n >= 1 && n <= kAudMaxSamples, "avl_audio_pack: n=%lld outside 1 .. 2^31 - 1", (long long)n);
+    AVL_REQUIRE(L >= 1 && L <= kAudMaxSamples, "avl_audio_pack: L=%lld outside 1 .. 2^31 - 1", (long long)L);
+    AVL_REQUIRE(S >= 0 && S <= ((int64_t)1 << 40) / L, "avl_audio_pack: S=%lld rows of %lld samples are out of range", (long long)S,
+                (long long)L);
+    AVL_REQUIRE(((uintptr_t)d_audio & 3) == 0 && ((uintptr_t)d_out & 3) == 0, "avl_audio_pack: a buffer is not aligned to 4 bytes");
+    if (S == 0) return AVL_OK;
+    const dim3 grid((unsigned)((L + kPackChunk - 1) / kPackChunk), (unsigned)std::min<int64_t>(S, kPackMaxRowsY));
+    const bool vec = (L & 3) == 0 && ((uintptr_t)d_out & 15) == 0;
+    if (vec)
+        hipLaunchKernelGGL(aud_pack_kernel<true>, grid, dim3(kAudThreads), 0, as_stream(stream), d_audio, n, d_ranges, S, L, scale, d_out);
+    else
+        hipLaunchKernelGGL(aud_pack_kernel<false>, grid, dim3(kAudThreads), 0, as_stream(stream), d_audio, n, d_ranges, S, L, scale, d_out);
+    AVL_HIP_CHECK(hipGetLastError());
+    return AVL_OK;
+}
+
+}  // extern "C"

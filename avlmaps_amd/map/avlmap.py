@@ -37,9 +37,10 @@ def _opt(cfg, key, default=None):
 
 
 class AVLMap:
-    def __init__(self, config, data_dir: str = "", area_text_model=None, audio_text_model=None, localizer=None):
+    def __init__(self, config, data_dir: str = "", area_text_model=None, audio_text_model=None, localizer=None, audio_encoder=None):
         """area_text_model: the CLIP ViT-L/14 text tower (or a stand-in) of the area queries, loaded on demand when None;
-        audio_text_model: AudioCLIP's text side (map/sound_map.py); localizer: the image localiser (map/visual_map.py)."""
+        audio_text_model: AudioCLIP's text side (map/sound_map.py); localizer: the image localiser (map/visual_map.py);
+        audio_encoder: AudioCLIP's audio head or a stand-in, for create_map's sound map and get_pos_with_audio."""
         from .area_map import AreaMap
         from .visual_map import VisualMap
         self.config = config
@@ -51,17 +52,24 @@ class AVLMap:
         if sound_cfg is not None and sound_params is not None:
             from .sound_map import SoundMap
             self.sound_map = SoundMap(data_dir, sound_cfg, sound_params, is_ambiguous=False, is_real=False,
-                                      audio_text_model=audio_text_model)
+                                      audio_text_model=audio_text_model, audio_encoder=audio_encoder)
         self._area_loaded = self._sound_loaded = False
         self._dataloader = None
         self._area_cells = self._sound_cells = None
 
     # ------------------------------------------------------------------ build / load
-    def create_map(self, data_dir, feat_extractor=None, area_encoder=None) -> bool:
-        """Reference: avlmap.py:38-46.  area_encoder(rgb) -> (768,): also build the area map (area_map/clip_sparse_map.h5df)."""
+    def create_map(self, data_dir, feat_extractor=None, area_encoder=None, audio_encoder=None) -> bool:
+        """Reference: avlmap.py:38-46.  area_encoder(rgb) -> (768,): also build the area map (area_map/clip_sparse_map.h5df).
+        audio_encoder(batch (B, 5 * sample_rate)) -> (B, D): also build the sound map (audio_video/audio_data_<level>.pkl) when the
+        configuration has a sound part and the scene an audio_video directory."""
         self.vlmap.create_map(data_dir, feat_extractor=feat_extractor)
         if area_encoder is not None:
             self.area_map.create_map(data_dir, image_encoder=area_encoder)
+        if audio_encoder is not None:
+            if self.sound_map is None:
+                raise MissingSubMap("AVLMap.create_map(audio_encoder=...) needs sound_config and sound_data_collect_params in the "
+                                    "configuration")
+            self.sound_map.create_sound_map(data_dir, audio_encoder=audio_encoder)
         return True
 
     def load_map(self, data_dir: str) -> bool:

@@ -2139,3 +2139,158 @@ def retrieve_frame(ref_desc, query_desc, stream=None):
                    out_scores=scores, col_support=None)
         idx[j], val[j] = argmax_f32(DeviceView(scores.ptr, (N,), np.float32), stream)
     return (int(idx[0]), float(val[0])) if single else (idx, val)
+
+
+# ---------------------------------------------------------------------------------------- sound map audio (csrc/avl_audio.hip)
+AUDIO_MAX_SAMPLES = 2 ** 31 - 1
+AUDIO_MAX_CHANNELS = 8
+
+
+def _audio_f32(audio, stream):
+    """a mono float32 recording, host or device -> (ptr, n, DeviceArray / view that keeps it alive)"""
+    if isinstance(audio, (DeviceArray, DeviceView)) or _is_torch(audio):
+        ptr, shape, keep = as_device(audio, np.float32, stream)
+        if len(shape) != 1:
+            raise ValueError(f"expected a mono recording of shape (n,), got {tuple(shape)}")
+        return ptr, int(shape[0]), keep
+    a = np.asarray(audio)
+    if a.ndim != 1:
+        raise ValueError(f"expected a mono recording of shape (n,), got {a.shape}")
+    if a.dtype != np.float32:
+        raise TypeError(f"expected float32 samples, got {a.dtype} (decode_pcm16 converts int16 PCM)")
+    if not 1 <= a.shape[0] <= AUDIO_MAX_SAMPLES:
+        raise ValueError(f"a recording of {a.shape[0]} samples is outside 1 .. 2^31 - 1")
+    _lib.require_gpu()
+    d = DeviceArray.from_numpy(a, stream)
+    return d.ptr, int(a.shape[0]), d
+
+
+def decode_pcm16(pcm, device=True, stream=None):
+    """Interleaved int16 PCM, (n,) or (n, channels) with channels <= 8, host or int16 DeviceArray -> the mono float32 recording
+    np.mean(pcm.astype(np.float32) / 32768, axis=1), the documented meaning of librosa.load(..., mono=True) for PCM16 input
+    (never compared with librosa or libsndfile, which this project does not have).  A DeviceArray (n,) with device=True."""
+    lib = _lib.load()
+    if isinstance(pcm, (DeviceArray, DeviceView)):
+        ptr, shape, keep = as_device(pcm, np.int16, stream)
+    else:
+        a = np.asarray(pcm)
+        if a.dtype != np.int16:
+            raise TypeError(f"expected int16 PCM, got {a.dtype}")
+        shape, ptr, keep = a.shape, None, a
+    if len(shape) not in (1, 2):
+        raise ValueError(f"expected PCM of shape (n,) or (n, channels), got {tuple(shape)}")
+    n, ch = int(shape[0]), int(shape[1]) if len(shape) == 2 else 1
+    if not 1 <= n <= AUDIO_MAX_SAMPLES or not 1 <= ch <= AUDIO_MAX_CHANNELS:
+        raise ValueError(f"{n} frames of {ch} channels: outside 1 .. 2^31 - 1 frames, 1 .. {AUDIO_MAX_CHANNELS} channels")
+    _lib.require_gpu()
+    if ptr is None:
+        keep = DeviceArray.from_numpy(np.ascontiguousarray(keep), stream)
+        ptr = keep.ptr
+    out = DeviceArray((n,), np.float32)
+    _lib.check(lib.avl_audio_decode_pcm16(ptr, n, ch, out.ptr, stream), "avl_audio_decode_pcm16")
+    return _result(out, device, stream, keep=(keep,))
+
+
+class AudioSegments:
+    """segment_audio's result.  segments: (S, 2) int64 (l, r) per segment, host array (a DeviceArray with device=True;
+    segments_host always holds the host copy); time_ranges: (S, 2) float64 = segments / float(sample_rate), librosa's samples_to_time;
+    audio: the recording on the device, (n,) float32, alive as long as this object."""
+
+    def __init__(self, segments_dev, segments_host, sample_rate, audio, n, device):
+        self.segments_dev, self.segments_host = segments_dev, segments_host
+        self.segments = segments_dev if device else segments_host
+        self.sample_rate, self.audio, self.n = sample_rate, audio, n
+        self.time_ranges = segments_host / float(sample_rate)
+
+    def __len__(self):
+        return len(self.segments_host)
+
+
+def segment_audio(audio, sample_rate, silence_duration_s=1.0, silence_thres=0.0, device=False, stream=None) -> AudioSegments:
+    """audio_utils.py:515-546 segment_audio_with_silence on a mono float32 recording (host array or DeviceArray): sample i is loud
+    iff audio[i] > silence_thres; a loud sample starts a segment iff it is the first one or follows the previous loud sample by
+    gap = int(silence_duration_s * sample_rate) samples or more; a segment is (l, r), the track upstream cuts audio[l:r].
+    Departures: a recording without a loud sample returns zero segments (upstream: IndexError); gap must be at least 1 (upstream's
+    loop then emits an extra leading (l, l)); a threshold that float32 cannot hold exactly raises ValueError, because the compare
+    runs in float32."""
+    lib = _lib.load()
+    thr = float(silence_thres)
+    if thr != thr or float(np.float32(thr)) != thr:
+        raise ValueError(f"silence_thres={silence_thres!r} is not exactly representable in float32")
+    gap = int(silence_duration_s * sample_rate)
+    if gap < 1:
+        raise ValueError(f"silence_duration_s * sample_rate = {silence_duration_s * sample_rate}: the gap must be at least one sample")
+    ap, n, keep = _audio_f32(audio, stream)
+    nws = C.c_size_t(0)
+    _lib.check(lib.avl_audio_segment_work_bytes(n, C.byref(nws)), "avl_audio_segment_work_bytes")
+    _lib.require_gpu()
+    cap = (n - 1) // gap + 1                      # two starts are at least gap samples apart
+    ws, cnt = DeviceArray((nws.value,), np.uint8), DeviceArray((1,), np.int64)
+    seg = DeviceArray((cap, 2), np.int64)
+    _lib.check(lib.avl_audio_segment(ap, n, thr, gap, seg.ptr, cap, cnt.ptr, ws.ptr, nws.value, stream), "avl_audio_segment")
+    S = int(cnt.numpy(stream)[0])
+    if S > cap:
+        raise _lib.AvlError(f"avl_audio_segment: {S} segments for a capacity of {cap}")
+    host = seg.numpy(stream)[:S].copy() if S else np.zeros((0, 2), np.int64)
+    dev = None
+    if device:                                    # an exact-size copy: the capacity buffer goes back to the pool
+        dev = DeviceArray((S, 2), np.int64)
+        if S:
+            _lib.check(lib.avl_memcpy_d2d(dev.ptr, seg.ptr, S * 16, stream), "avl_memcpy_d2d")
+            _lib.check(lib.avl_stream_sync(stream), "avl_stream_sync")
+    res = AudioSegments(dev, host, sample_rate, keep if isinstance(keep, (DeviceArray, DeviceView)) else DeviceView(ap, (n,), np.float32),
+                        n, device)
+    res._keep = keep
+    return res
+
+
+def _check_ranges(ranges, n):
+    r = np.asarray(ranges)
+    if r.size == 0:
+        return np.zeros((0, 2), np.int64)
+    if r.ndim != 2 or r.shape[1] != 2 or r.dtype.kind not in "iu":
+        raise ValueError(f"expected (S, 2) integer (start, stop) ranges, got shape {r.shape} of {r.dtype}")
+    r = np.ascontiguousarray(r, dtype=np.int64)
+    if (r[:, 0] < 0).any() or (r[:, 0] > r[:, 1]).any() or (r[:, 1] > n).any():
+        raise ValueError(f"ranges must satisfy 0 <= start <= stop <= {n}")
+    return r
+
+
+def pack_tracks(audio, ranges, length, scale=32768.0, device=False, stream=None):
+    """(S, length) float32: row k is audio[start_k:stop_k] * scale cut or zero-padded to `length` samples.  With scale = 32768 and
+    length = 5 * sample_rate this is audio_mapping_utils.py:85 followed by get_five_second_contexts_audio(track, [2.5], sr) for all
+    segments at once (the same numbers as upstream's float64 buffers: the scale is a power of two).  ranges: (S, 2) host integers,
+    0 <= start <= stop <= n, checked here."""
+    lib = _lib.load()
+    length, scale = int(length), float(scale)
+    if not 1 <= length <= AUDIO_MAX_SAMPLES:
+        raise ValueError(f"length={length} outside 1 .. 2^31 - 1")
+    if float(np.float32(scale)) != scale:
+        raise ValueError(f"scale={scale!r} is not exactly representable in float32")
+    ap, n, keep = _audio_f32(audio, stream)
+    r = _check_ranges(ranges, n)
+    S = len(r)
+    _lib.require_gpu()
+    out = DeviceArray((S, length), np.float32)
+    if S:
+        rd = DeviceArray.from_numpy(r, stream)
+        _lib.check(lib.avl_audio_pack(ap, n, rd.ptr, S, length, scale, out.ptr, stream), "avl_audio_pack")
+        keep = (keep, rd)
+    return _result(out, device, stream, keep=(keep,))
+
+
+def context_ranges(n, times, sample_rate, seconds=5.0):
+    """Host code: the (start, stop) slices audio_utils.py:569-583 get_five_second_contexts_audio takes of an n-sample recording,
+    one per kept time, as (S, 2) int64 with 0 <= start <= stop <= n, ready for pack_tracks.  A time is skipped when
+    t - seconds / 2 > (n - 1) / sample_rate; the bounds are (np.asarray([t - 2.5, t + 2.5]) * sr).astype(int) (librosa's
+    time_to_samples); Python's slice rules then apply: a negative bound counts from the end, both are clipped to [0, n], and
+    start >= stop is an empty slice (stop = start here)."""
+    n, half = int(n), seconds / 2
+    out = []
+    for t in times:
+        if t - half > (n - 1) / sample_rate:
+            continue
+        b = (np.asarray([t - half, t + half]) * sample_rate).astype(int)
+        start, stop, _ = slice(int(b[0]), int(b[1])).indices(n)
+        out.append((start, max(start, stop)))
+    return np.asarray(out, dtype=np.int64).reshape(-1, 2)

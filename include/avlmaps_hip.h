@@ -981,6 +981,33 @@ AVL_API int avl_pnp_refine(const double* d_points, const double* d_pixels, int64
                            double cy, double max_error, int max_iter, double step_tol, double* d_out13, int32_t* d_out3, uint8_t* d_mask,
                            void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * (14) the audio side of the sound map (csrc/avl_audio.hip)
+ *     A recording is mono float32 in device memory, 1 <= n <= 2^31 - 1 samples.  Null pointers and ranges are rejected before any
+ *     device work.  All three calls are asynchronous on `stream`.
+ * ------------------------------------------------------------------------------------------------ */
+/* d_pcm: n interleaved frames of `channels` int16 (1 <= channels <= 8); d_audio_f32 (n,):
+ * np.mean(pcm.astype(np.float32) / 32768, axis=1) in float32.  The sum of at most eight multiples of 2^-15 is exact in every
+ * order, so the only rounding is the division by `channels`; one and two channels are exact. */
+AVL_API int avl_audio_decode_pcm16(const int16_t* d_pcm, int64_t n, int channels, float* d_audio_f32, void* stream);
+AVL_API int avl_audio_segment_work_bytes(int64_t n, size_t* h_bytes);
+/* avlmaps/utils/audio_utils.py:515-546 segment_audio_with_silence on a whole recording.  Sample i is loud iff
+ * d_audio[i] > threshold (float32; NaN is never loud; a NaN threshold is AVL_ERR_INVALID).  A loud sample starts a segment iff it is
+ * the first loud sample or lies gap or more samples after the previous loud one; gap >= 1.  Segment k is (l, r): its start and the
+ * last loud sample before the next start (or the last loud sample of all); the track upstream cuts is audio[l:r], r excluded, so a
+ * lone loud sample gives l == r.  d_segments (cap, 2) int64 receives the first min(count, cap) pairs in ascending order and
+ * d_count[0] (int64) the true count, which may exceed cap (cap = 0 only counts; d_segments may then be NULL).  d_ws:
+ * avl_audio_segment_work_bytes(n).  Five launches, none waits on another, no atomics. */
+AVL_API int avl_audio_segment(const float* d_audio, int64_t n, float threshold, int64_t gap, int64_t* d_segments, int64_t cap,
+                              int64_t* d_count, void* d_ws, size_t ws_bytes, void* stream);
+/* avlmaps/utils/audio_utils.py:569-583 get_five_second_contexts_audio(track, [2.5], sr) of audio_mapping_utils.py:85's scaled
+ * tracks, for every segment at once: d_ranges (S, 2) int64 (start, stop) with 0 <= start <= stop <= n (the caller checks its host
+ * copy; the kernel clamps, so a bad range reads nothing out of bounds), d_out (S, L) float32:
+ * out[k, j] = audio[start_k + j] * scale for j < min(stop_k - start_k, L), +0 elsewhere.  1 <= L <= 2^31 - 1, S * L <= 2^40;
+ * S = 0 does nothing. */
+AVL_API int avl_audio_pack(const float* d_audio, int64_t n, const int64_t* d_ranges, int64_t S, int64_t L, float scale, float* d_out,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif
