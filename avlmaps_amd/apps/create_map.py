@@ -1,7 +1,7 @@
 """Build a VLMap for one scene directory.  Counterpart of the reference's application/create_map.py:7-17.
 
     python -m avlmaps_amd.apps.create_map --data-dir <scene> [--config cfg.yaml] [--features lseg|hash] [--seed N]
-                                          [--sound [--audio-model hash]]
+                                          [--sound [--audio-model hash]] [--explored [--ray-stride N]]
 
 <scene>/ holds rgb/*.png, depth/*.npy (float32 metres) and poses.txt (x y z qx qy qz qw per line), the layout of the
 reference's dataset/README.md:76-93; the map goes to <scene>/vlmap/vlmaps.h5df (a real HDF5 file: through h5py, or through
@@ -9,6 +9,9 @@ the HDF5 C library where h5py is missing).
 --sound also builds the sound map (<scene>/audio_video/audio_data_<level>.pkl) from <scene>/audio_video/<seq>/ (a .wav next to
 output_with_audio_<level>.mp4, or the video itself when ffmpeg is installed; poses.txt; the meta file); --audio-model hash is the
 model-free audio encoder, the only one built in (AudioCLIP is attached through AVLMap(audio_encoder=...) from Python).
+--explored also carves the sight rays of every depth frame into the explored map (<scene>/vlmap/explored.npz: per cell the first
+frame that saw it, Map.create_explored_map), one ray per --ray-stride pixels in both image directions; VLMap.load_map picks the
+file up, and the known-free map and the frontier goals need it.
 Multi-GPU: launch with torchrun; frames are sharded over ranks and merged with one row-sharded RCCL exchange (every --save-every
 frames per rank as a checkpoint, and at the end); an interrupted run is continued with --resume; with --seed the N-rank map
 equals the single-process map (every rank replays the RNG draws of the frames before its shard)."""
@@ -47,7 +50,11 @@ def main(argv=None):
     ap.add_argument("--sound", action="store_true", help="also build the sound map from <scene>/audio_video")
     ap.add_argument("--audio-model", choices=["hash"], default="hash",
                     help="--sound: the audio encoder; hash = model-free stand-in (apps/common.HashAudioEncoder)")
+    ap.add_argument("--explored", action="store_true", help="also build the explored map (<scene>/vlmap/explored.npz) from the depth frames")
+    ap.add_argument("--ray-stride", type=int, default=4, metavar="N", help="--explored: one sight ray per N pixels in both image directions")
     args = ap.parse_args(argv)
+    if args.ray_stride < 1:
+        ap.error("--ray-stride must be at least 1")
 
     from avlmaps_amd import parallel
     from avlmaps_amd.apps.common import HashAudioEncoder, HashFeatureExtractor, load_config
@@ -89,6 +96,10 @@ def main(argv=None):
     if args.sound and rank == 0:
         path = avlmap.sound_map.create_sound_map(args.data_dir, audio_encoder=HashAudioEncoder())
         print(f"sound map with {len(avlmap.sound_map.load_sound_map(args.data_dir))} segments written to {path}")
+    if args.explored and rank == 0:
+        first_seen = avlmap.vlmap.create_explored_map(args.data_dir, stride=args.ray_stride)
+        print(f"explored map: {int((first_seen >= 0).sum())} cells seen in {avlmap.vlmap.explored_params['n_frames']} frames, written to "
+              f"{avlmap.vlmap.data_dir / 'vlmap' / avlmap.vlmap.EXPLORED_FILE}")
     if rank == 0:
         n = len(avlmap.vlmap.map_builder.last_map["grid_pos"]) if hasattr(avlmap.vlmap.map_builder, "last_map") else -1
         print(f"map with {n} voxels written to {avlmap.vlmap.map_builder.map_save_path} in {time.perf_counter() - t0:.2f} s")

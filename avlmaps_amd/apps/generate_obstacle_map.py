@@ -3,12 +3,15 @@ application/generate_obstacle_map.py (:19-33), with PNG files where upstream ope
 
     python -m avlmaps_amd.apps.generate_obstacle_map --data-dir <scene> [--out-dir DIR] [--text-model clip|hash]
                                                      [--potential-obstacles a,b,c --obstacles a,b] [--dilate-iter N] [--gaussian-sigma S]
+                                                     [--known-free]
 
 Loads <scene>/vlmap/vlmaps.h5df, builds the obstacle map from the occupancy between --h-min and --h-max
 (Map.generate_obstacle_map), then keeps only the obstacles of the classes --obstacles and smooths the map
 (VLMap.customize_obstacle_map; the class lists and the smoothing parameters default to the map config's).  Writes obstacles.png
 and obstacles_customized.png (white = free, the cropped maps) under --out-dir (default <scene>/vlmap) and prints one JSON line with
-the crop and the number of obstacle cells of both maps."""
+the crop and the number of obstacle cells of both maps.  With --known-free it also writes obstacles_known_free.png: the obstacle map
+AND-ed with the explored map (Map.get_known_free_cropped; needs <scene>/vlmap/explored.npz, apps.create_map --explored), in which a
+cell no camera ever looked at is not free."""
 from __future__ import annotations
 
 import argparse
@@ -29,6 +32,7 @@ def parse_args(argv=None):
     ap.add_argument("--obstacles", default=None, help="comma separated classes (of --potential-obstacles) that stay obstacles")
     ap.add_argument("--dilate-iter", type=int, default=None)
     ap.add_argument("--gaussian-sigma", type=float, default=None)
+    ap.add_argument("--known-free", action="store_true", help="also write obstacles_known_free.png (free AND observed)")
     return ap.parse_args(argv)
 
 
@@ -64,6 +68,13 @@ def main(argv=None):
     out = {"crop": [int(vm.rmin), int(vm.rmax), int(vm.cmin), int(vm.cmax)], "shape": [int(raw.shape[0]), int(raw.shape[1])],
            "obstacle_cells": int((raw == 0).sum()), "customized_obstacle_cells": int((custom == 0).sum()),
            "files": [str(out_dir / "obstacles.png"), str(out_dir / "obstacles_customized.png")]}
+    if args.known_free:
+        if vm.first_seen is None:
+            raise SystemExit(f"no explored map under {args.data_dir}: run apps.create_map --explored first")
+        known = vm.get_known_free_cropped()
+        save_mask_png(out_dir / "obstacles_known_free.png", known)
+        out["known_free_blocked_cells"] = int((known == 0).sum())
+        out["files"].append(str(out_dir / "obstacles_known_free.png"))
     print(json.dumps(out))
     return out
 

@@ -6,7 +6,7 @@ setup_scene + move_to (robot/habitat_lang_robot.py:88-104, 432-461) without the 
                                         [--customize-obstacles [--potential-obstacles a,b,c --obstacles a,b]
                                          [--dilate-iter N] [--gaussian-sigma S]]
                                         [--relation left|right|between|north|south|east|west|face --heading DEG [--query-b NAME]]
-                                        [--nearest euclid|path] [--render PNG]
+                                        [--nearest euclid|path] [--known-free] [--goal object|frontier] [--render PNG]
 
 Loads <scene>/vlmap/vlmaps.h5df (with --text-model hash a missing map is first created with the model-free feature stand-in, as
 apps.create_map --features hash does), builds the obstacle map (Map.generate_obstacle_map), takes the goal from
@@ -41,6 +41,13 @@ degrees (0 = towards smaller rows, clockwise positive).  `between` takes the sec
 `face` plans nothing: it prints the angle to turn right to face the nearest --query object (Map.get_delta_angle_to) as
 "turn_right_deg".  A relation with nothing in front of the robot ends with a message and exit status 1.
 
+With --known-free the path is planned on Map.get_known_free_cropped(): the obstacle map (the customised one with
+--customize-obstacles) AND-ed with the explored map, so that the plan stays in space a camera has seen (needs
+<scene>/vlmap/explored.npz, apps.create_map --explored).  With --goal frontier the goal is not an object at all but where to look
+next: the frontier of the explored area with the shortest travel distance from --start (Map.get_frontiers,
+Navigator.plan_to_nearest_frontier), planned on the known-free map; --query is not needed, and the JSON line has "frontiers", the
+number of frontier islands, and "frontier_cells", the size of the chosen one.
+
 With --render the plan is also drawn: the top-down colour map of the obstacle crop (Map.generate_rgb_topdown_map) with the
 obstacle cells the planner used darkened, the path as a polyline, the start in green and the goal in red, as a PNG.  The JSON line
 then has "render", the file."""
@@ -56,7 +63,7 @@ RELATIONS = ("left", "right", "between", "north", "south", "east", "west", "face
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--data-dir", required=True)
-    ap.add_argument("--query", required=True)
+    ap.add_argument("--query", default=None, help="the object to go to (not needed with --goal frontier)")
     ap.add_argument("--start", type=float, nargs=2, required=True, metavar=("ROW", "COL"), help="full-map cell of the robot")
     ap.add_argument("--config", default=None)
     ap.add_argument("--text-model", choices=["clip", "hash"], default="clip",
@@ -82,8 +89,17 @@ def parse_args(argv=None):
     ap.add_argument("--nearest", choices=["euclid", "path"], default="euclid",
                     help="which --query object is the goal: euclid = the nearest as the crow flies (Map.get_nearest_pos); "
                          "path = the one with the shortest travel distance (Map.get_nearest_reachable_pos)")
+    ap.add_argument("--known-free", action="store_true", help="plan on the obstacle map AND-ed with the explored map (Map.get_known_free_cropped)")
+    ap.add_argument("--goal", choices=["object", "frontier"], default="object",
+                    help="object = go to --query (default); frontier = go to the nearest frontier of the explored area")
     ap.add_argument("--render", default=None, metavar="PNG", help="draw the crop, its obstacles, the path, start and goal")
     args = ap.parse_args(argv)
+    if args.goal == "frontier":
+        if args.query is not None or args.relation is not None or args.area or args.sound or args.image or args.goal_2d or args.nearest == "path":
+            ap.error("--goal frontier takes its goal from the explored map: no --query, --relation, --area, --sound, --image, --goal-2d or --nearest path")
+        args.known_free = True
+    elif args.query is None:
+        ap.error("--query is required (or --goal frontier)")
     if args.render and args.relation == "face":
         ap.error("--relation face plans no path: nothing to --render")
     if args.nearest == "path" and (args.relation is not None or args.area or args.sound or args.image or args.goal_2d):
@@ -189,16 +205,21 @@ def main(argv=None):
     if hashed:
         vm.clip_feat_dim = vm.grid_feat.shape[1]
         vm.clip_model = HashClip(vm.clip_feat_dim)
-    else:
+    elif args.goal != "frontier" or args.customize_obstacles:          # a frontier goal asks the text tower nothing
         vm._init_clip()
-    cats = ([c.strip() for c in args.categories.split(",")] if args.categories
-            else [args.query] + ([args.query_b] if args.query_b else []) + ["other"])
-    vm.init_categories(cats)
+    if args.goal != "frontier":
+        cats = ([c.strip() for c in args.categories.split(",")] if args.categories
+                else [args.query] + ([args.query_b] if args.query_b else []) + ["other"])
+        vm.init_categories(cats)
     vm.generate_obstacle_map(args.h_min, args.h_max)
     obstacles = vm.get_obstacle_cropped()
     if args.customize_obstacles:
         vm.customize_obstacle_map(cfg.map_config.potential_obstacle_names, cfg.map_config.obstacle_names)
         obstacles = vm.get_customized_obstacle_cropped()
+    if args.known_free:
+        if vm.first_seen is None:
+            raise SystemExit(f"no explored map under {args.data_dir}: run apps.create_map --explored first")
+        obstacles = vm.get_known_free_cropped(customized=args.customize_obstacles)
     start = [float(args.start[0]), float(args.start[1])]
     extra = {}
     if args.relation == "face":
@@ -215,6 +236,11 @@ def main(argv=None):
         extra = {"relation": args.relation, "heading": args.heading, "goal_cell": cell}
         if args.query_b:
             extra["query_b"] = args.query_b
+    elif args.goal == "frontier":
+        frontiers = vm.get_frontiers()
+        if len(frontiers[0]) == 0:
+            raise SystemExit("--goal frontier: the explored area has no frontier (of at least 5 cells) left")
+        goal = None
     elif avlmap is None:
         goal = None if args.nearest == "path" else vm.get_nearest_pos(start, args.query)
     elif args.goal_2d:
@@ -236,7 +262,11 @@ def main(argv=None):
     nav = Navigator()
     try:
         nav.build_visgraph(obstacles, vm.rmin, vm.cmin)
-        if args.nearest == "path":
+        if args.goal == "frontier":
+            k, path = nav.plan_to_nearest_frontier(start, frontiers)
+            goal = [int(frontiers[0][k, 0]), int(frontiers[0][k, 1])]
+            extra = {"goal_kind": "frontier", "frontiers": int(len(frontiers[0])), "frontier_cells": int(frontiers[1][k])}
+        elif args.nearest == "path":
             goal, path = vm.get_nearest_reachable_pos(start, args.query, nav)
         else:
             path = nav.plan_to(start, goal)

@@ -49,6 +49,7 @@
 #include <vector>
 
 #include "avl_builder_state.h"
+#include "avl_pinhole.h"
 
 namespace avl {
 
@@ -110,13 +111,7 @@ __device__ __forceinline__ void warm_kernel_arguments() {
 #endif
 }
 
-__device__ __forceinline__ int py_int(double v) {
-    // Python int(): truncate toward zero.  Far-out values saturate at +-2e9 and NaN goes to -2e9 (all of them fail the range
-    // tests that follow: grid, image and feature-image bounds are far below that), which lets the conversion be ONE instruction
-    // (v_cvt_i32_f64) instead of the ~15 of a float64 -> int64 conversion -- five of those sat on every sample's chain in K1.
-    return (int)fmin(fmax(v, -2.0e9), 2.0e9);
-}
-
+// (py_int, bp_backproject and bp_transform: avl_pinhole.h, shared with the bounding-box pass and the free-space carver)
 __device__ __forceinline__ double gemv3(const double* a, double x0, double x1, double x2) {
     // numpy (3,3)@(3,1) -> OpenBLAS dgemv tail:  fma(a2,x2, fma(a0,x0, a1*x1))   (oracle/avl_oracle.c)
     return fma(a[2], x2, fma(a[0], x0, a[1] * x1));
@@ -206,16 +201,14 @@ __device__ __forceinline__ SampleRec bp_voxelize_body(int blk, const FrameParams
     const float* dsrc = ok0 ? depth : reinterpret_cast<const float*>(cell_slot);   // (batched launches carry no frame-level pointers)
     const double x = (double)(pixc % fp.W) + 0.5, y = (double)(pixc / fp.W) + 0.5;
     const double z = fp.depth_u16 ? (double)reinterpret_cast<const uint16_t*>(dsrc)[pixc] / fp.depth_div : (double)dsrc[pixc];
-    const double pl0 = fma(fp.kinv[2], 1.0, fma(fp.kinv[1], y, fp.kinv[0] * x)) * z;
-    const double pl1 = fma(fp.kinv[5], 1.0, fma(fp.kinv[4], y, fp.kinv[3] * x)) * z;
-    const double pl2 = fma(fp.kinv[8], 1.0, fma(fp.kinv[7], y, fp.kinv[6] * x)) * z;
+    double pl0, pl1, pl2;
+    bp_backproject(fp.kinv, x, y, z, pl0, pl1, pl2);
     const bool ok1 = ok0 && (pl2 > fp.min_depth) && (pl2 < fp.max_depth);  // strict on both sides, NaN fails
     AVL_RESTAMP(pt2);
     // transform_pc: pose @ [pc; 1]  (dgemm FMA chain k = 0..3)
-    const double g0 = fma(T[3], 1.0, fma(T[2], pl2, fma(T[1], pl1, T[0] * pl0)));
-    const double g1 = fma(T[7], 1.0, fma(T[6], pl2, fma(T[5], pl1, T[4] * pl0)));
-    const double g2 = fma(T[11], 1.0, fma(T[10], pl2, fma(T[9], pl1, T[8] * pl0)));
-    int row, col, h;          // (32-bit from here on: saturated values fail the range tests, in-range ones are small)
+    double g0, g1, g2;
+    bp_transform(T, pl0, pl1, pl2, g0, g1, g2);
+    int row, col, h;         // (32-bit from here on: saturated values fail the range tests, in-range ones are small)
     if (fp.mode == 0) {       // (kernel-uniform)
         // base_pos2grid_id_3d: int(gs/2 - int(x/cs)) with a true fp64 divide
         row = py_int(fp.half_gs - (double)py_int(g0 / fp.cs));

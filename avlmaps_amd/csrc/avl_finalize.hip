@@ -11,6 +11,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "avl_builder_state.h"
+#include "avl_pinhole.h"
 
 namespace avl {
 
@@ -284,13 +285,11 @@ __global__ __launch_bounds__(256) void bbox_kernel(FrameParams fp, const float* 
     if (pix < 0 || pix >= fp.H * fp.W) return;
     const double x = (double)(pix % fp.W) + 0.5, y = (double)(pix / fp.W) + 0.5;
     const double z = fp.depth_u16 ? (double)reinterpret_cast<const uint16_t*>(depth)[pix] / fp.depth_div : (double)depth[pix];
-    const double pl0 = fma(fp.kinv[2], 1.0, fma(fp.kinv[1], y, fp.kinv[0] * x)) * z;
-    const double pl1 = fma(fp.kinv[5], 1.0, fma(fp.kinv[4], y, fp.kinv[3] * x)) * z;
-    const double pl2 = fma(fp.kinv[8], 1.0, fma(fp.kinv[7], y, fp.kinv[6] * x)) * z;
+    double pl0, pl1, pl2;
+    bp_backproject(fp.kinv, x, y, z, pl0, pl1, pl2);
     if (!((pl2 > fp.min_depth) && (pl2 < fp.max_depth))) return;
-    const double g[3] = {fma(fp.t[3], 1.0, fma(fp.t[2], pl2, fma(fp.t[1], pl1, fp.t[0] * pl0))),
-                         fma(fp.t[7], 1.0, fma(fp.t[6], pl2, fma(fp.t[5], pl1, fp.t[4] * pl0))),
-                         fma(fp.t[11], 1.0, fma(fp.t[10], pl2, fma(fp.t[9], pl1, fp.t[8] * pl0)))};
+    double g[3];
+    bp_transform(fp.t, pl0, pl1, pl2, g[0], g[1], g[2]);
     for (int c = 0; c < 3; ++c) {
         const unsigned long long k = f64_key(g[c]);
         atomicMin(&minmax[c], k);

@@ -35,6 +35,8 @@ class Map:
         self.grid_rgb = None
         self.obstacles_map = None
         self.obstacles_cropped = None
+        self.first_seen = None            # (gs, gs) int32, the first frame that saw a cell, -1 = never (create_explored_map / load_explored_map)
+        self.explored_params = None
         self._setup_transforms()
         if data_dir:
             self._setup_paths(data_dir)
@@ -124,6 +126,139 @@ class Map:
     def get_customized_obstacle_cropped(self) -> np.ndarray:
         """the map VLMap.customize_obstacle_map left behind.  Reference: map.py:162-163."""
         return self.obstacles_new_cropped
+
+    # ------------------------------------------------------------------------ observed free space (csrc/avl_explore.hip)
+    # generate_obstacle_map calls a cell free when no voxel was fused in its height band, which is also true of every cell no camera
+    # ever looked at.  The explored map says which cells a sight ray crossed; upstream only has the unused seed of it
+    # (mapping_utils.py:403-454 generate_mask).  DESIGN.md 4.14.
+    EXPLORED_FILE = "explored.npz"
+
+    def create_explored_map(self, data_dir=None, stride: int = 4, h_min: float = 0, h_max: float = 1.5, batch: int = 16) -> np.ndarray:
+        """Carve the sight rays of every depth frame of the scene into self.first_seen (gs, gs) int32 -- the first frame that saw a
+        cell inside the height band, -1 = never -- and write <data_dir>/vlmap/explored.npz.  Reads poses.txt and depth/*.npy as the
+        builder does: its frame_transforms, cam_calib_mat, min_depth and max_depth.  Frames go up in batches of `batch`, one
+        loader thread ahead of the GPU; one ray per stride-th pixel in both directions."""
+        import queue
+        import threading
+        from .. import ops
+        from ..device import DeviceArray
+        from ..utils.mapping_utils import load_depth_npy
+        from .vlmap_builder import VLMapBuilder
+        if data_dir is not None:
+            self._setup_paths(data_dir)
+        if not hasattr(self, "data_dir"):
+            raise ValueError("create_explored_map: no scene directory (pass data_dir)")
+        if int(batch) < 1:
+            raise ValueError(f"create_explored_map: batch {batch} < 1")
+        builder = VLMapBuilder(self.data_dir, self.map_config, self.pose_path, self.rgb_paths, self.depth_paths, self.base2cam_tf,
+                               self.base_transform)
+        calib = np.array(list(cfg_get(self.map_config, "cam_calib_mat")), dtype=np.float64).reshape((3, 3))
+        poses = np.loadtxt(self.pose_path).reshape((-1, 7))
+        transforms = np.stack(builder.frame_transforms(poses)) if len(poses) else np.zeros((0, 4, 4))
+        n = min(len(self.depth_paths), len(poses))
+        gs, cs = int(self.gs), float(self.cs)
+        params = dict(gs=gs, cs=cs, stride=int(stride), h_min=float(h_min), h_max=float(h_max), min_depth=float(builder.min_depth),
+                      max_depth=float(builder.max_depth))
+        batches = queue.Queue(maxsize=2)
+
+        def load():
+            try:
+                for lo in range(0, n, int(batch)):
+                    hi = min(n, lo + int(batch))
+                    batches.put((lo, hi, np.stack([np.asarray(load_depth_npy(self.depth_paths[i]), dtype=np.float32) for i in range(lo, hi)])))
+                batches.put(None)
+            except BaseException as e:          # surfaced on the calling thread
+                batches.put(e)
+        loader = threading.Thread(target=load, name="avl-explore-load", daemon=True)
+        loader.start()
+        first_seen = DeviceArray.from_numpy(np.full((gs, gs), ops.NEVER_SEEN, np.int32))
+        try:
+            while True:
+                item = batches.get()
+                if item is None:
+                    break
+                if isinstance(item, BaseException):
+                    raise item
+                lo, hi, depth = item
+                ops.carve_free_space(first_seen, DeviceArray.from_numpy(depth), calib, transforms[lo:hi], np.arange(lo, hi), device=True,
+                                     **params)
+            loader.join()
+            self.first_seen = first_seen.numpy()
+        finally:
+            first_seen.free()
+        self.explored_params = dict(params, n_frames=n)
+        out_dir = self.data_dir / "vlmap"
+        out_dir.mkdir(parents=True, exist_ok=True)
+        np.savez_compressed(out_dir / self.EXPLORED_FILE, first_seen=self.first_seen, **self.explored_params)
+        return self.first_seen
+
+    def load_explored_map(self, data_dir=None) -> bool:
+        """Read <data_dir>/vlmap/explored.npz into self.first_seen / self.explored_params; False (and no explored map) when the file
+        does not exist.  A file made for another grid is an error, not a silent crop."""
+        path = Path(data_dir if data_dir is not None else self.data_dir) / "vlmap" / self.EXPLORED_FILE
+        self.first_seen, self.explored_params = None, None
+        if not path.exists():
+            return False
+        with np.load(path, allow_pickle=False) as z:
+            first_seen = np.ascontiguousarray(z["first_seen"], dtype=np.int32)
+            params = {k: z[k].item() for k in z.files if k != "first_seen"}
+        if first_seen.shape != (self.gs, self.gs) or float(params.get("cs", self.cs)) != float(self.cs):
+            raise ValueError(f"{path}: explored map of grid {first_seen.shape}, cell {params.get('cs')} does not belong to this "
+                             f"map ({self.gs}, cell {self.cs})")
+        self.first_seen, self.explored_params = first_seen, params
+        return True
+
+    def _require_explored(self) -> np.ndarray:
+        if getattr(self, "first_seen", None) is None:
+            raise RuntimeError("no explored map loaded: run create_explored_map (apps.create_map --explored) or load a scene that has "
+                               "vlmap/explored.npz")
+        return self.first_seen
+
+    def generate_explored_map(self) -> np.ndarray:
+        """(gs, gs) bool, True = a sight ray crossed the cell inside the height band"""
+        self.explored_map = self._require_explored() >= 0
+        return self.explored_map
+
+    def _explored_crop(self) -> np.ndarray:
+        explored = self.generate_explored_map()
+        if self.obstacles_cropped is None:
+            self.generate_obstacle_map()
+        return explored[self.rmin:self.rmax + 1, self.cmin:self.cmax + 1]
+
+    def get_explored_cropped(self) -> np.ndarray:
+        """the explored map over the obstacle crop (generated on first use)"""
+        return self._explored_crop()
+
+    def generate_known_free_map(self, h_min: float = 0, h_max: float = 1.5) -> np.ndarray:
+        """(gs, gs) bool, True = free AND observed: generate_obstacle_map(h_min, h_max) & generate_explored_map()"""
+        self._require_explored()
+        return self.generate_obstacle_map(h_min, h_max) & self.generate_explored_map()
+
+    def get_known_free_cropped(self, customized: bool = False) -> np.ndarray:
+        """The obstacle crop (customized: obstacles_new_cropped) AND-ed with the explored crop: the same window, so a Navigator takes
+        it as it takes any obstacle map -- and no longer plans through space nobody observed."""
+        explored = self._explored_crop()
+        base = self.get_customized_obstacle_cropped() if customized else self.get_obstacle_cropped()
+        return (np.asarray(base) != 0) & explored
+
+    def get_frontiers(self, min_cells: int = 5):
+        """-> (centres (n, 2) int, sizes (n,) int): the frontier of the explored area over the obstacle crop -- explored free cells with an
+        unknown 4-neighbour (ops.frontier_mask) -- grouped into 8-connected islands (ops.label_islands) of at least min_cells cells,
+        largest first (equal sizes in raster order of their first cell).  A centre is the island's own cell nearest to its centroid
+        (the first in raster order among equals), in full-map (row, col): a frontier cell, so a planner can end on it."""
+        from .. import ops
+        explored = self._explored_crop()
+        free = np.asarray(self.get_obstacle_cropped()) != 0
+        mask = ops.frontier_mask(free, explored, device=True)
+        with ops.label_islands(mask) as isl:
+            labels, areas = np.asarray(isl.labels), isl.table[:, 0].astype(np.int64)
+        keep = [k for k in np.argsort(-areas, kind="stable") if areas[k] >= int(min_cells)]
+        centres = np.zeros((len(keep), 2), dtype=np.int64)
+        for i, k in enumerate(keep):
+            cells = np.argwhere(labels == k + 1)
+            d2 = np.sum((cells - cells.mean(axis=0)) ** 2, axis=1)
+            centres[i] = cells[int(np.argmin(d2))] + (int(self.rmin), int(self.cmin))
+        return centres, (areas[keep] if keep else np.zeros((0,), np.int64))
 
     @staticmethod
     def _dilate_map(binary_map: np.ndarray, dilate_iter: int = 0, gaussian_sigma: float = 1.0):

@@ -73,6 +73,7 @@ class VLMap(Map):
         (self.mapped_iter_list, self.grid_feat, self.grid_pos, self.weight, self.occupied_ids,
          self.grid_rgb) = load_3d_map(self.map_save_path)[:6]
         self._dev_feat = None
+        self.load_explored_map(data_dir)                 # vlmap/explored.npz when it exists; a map without it behaves as ever
         # straight after a multi-GPU build in this process the merged map already lies row-sharded in the ranks' HBM
         # (VLMapBuilder.map_shard): take this rank's block as the resident copy instead of uploading it again from the file
         shard = getattr(getattr(self, "map_builder", None), "map_shard", None)

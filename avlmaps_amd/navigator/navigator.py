@@ -55,6 +55,16 @@ class Navigator:
         k, paths = plan_to_nearest_pos(start, self._goals_to_cropped(goals_full_map), self.obs_map, self.visgraph)
         return k, self.shift_path(paths, self.rowmin, self.colmin)
 
+    def plan_to_nearest_frontier(self, start_full_map: Tuple[float, float], frontiers):
+        """-> (index, path): plan_to_nearest over the frontier centres of Map.get_frontiers (its (centres, sizes) pair, or an (n, 2)
+        array of full-map cells): where to look next, by travel distance.  Build the graph on Map.get_known_free_cropped() so that
+        the path stays in observed space.  ValueError when there is no frontier, NoPathError when none can be reached."""
+        centres = frontiers[0] if isinstance(frontiers, tuple) else frontiers
+        centres = np.asarray(centres, dtype=np.float64).reshape(-1, 2)
+        if len(centres) == 0:
+            raise ValueError("plan_to_nearest_frontier: no frontier to go to")
+        return self.plan_to_nearest(start_full_map, centres)
+
     def _goals_to_cropped(self, goals_full_map) -> np.ndarray:
         goals = np.asarray(goals_full_map, dtype=np.float64).reshape(-1, 2)
         return goals - np.array([self.rowmin, self.colmin], np.float64)

@@ -1008,6 +1008,31 @@ AVL_API int avl_audio_segment(const float* d_audio, int64_t n, float threshold, 
 AVL_API int avl_audio_pack(const float* d_audio, int64_t n, const int64_t* d_ranges, int64_t S, int64_t L, float scale, float* d_out,
                            void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * (15) observed free space and the frontier of the 2-D map (csrc/avl_explore.hip)
+ *     d_first_seen is a (gs, gs) int32 map in device memory: the smallest frame id whose sight rays crossed the cell inside the
+ *     height band, -1 where no ray ever did (the device map has the host's encoding: the fold is a minimum of the bits as unsigned
+ *     integers).  1 <= gs <= 16384.  Both calls are asynchronous; every result is unique (an integer minimum: the bytes do not
+ *     depend on the order of rays, frames, launches or calls).
+ * ------------------------------------------------------------------------------------------------ */
+/* Takes the place of avlmaps/utils/mapping_utils.py:403-454 (get_frustum_4pts, generate_mask), in the base-frame conventions of
+ * the builder instead of theirs.  d_depth: F frames of (H, W), float32 metres or uint16 (metres = value / depth_div), as
+ * avl_points_bbox takes them; h_calib_inv: inv(K), 3 x 3 row-major; h_transforms: F camera -> map transforms, 4 x 4 row-major
+ * (VLMapBuilder.frame_transforms); h_frame_ids: F ids >= 0.  One ray per pixel of the lattice stride / 2, stride / 2 + stride, ...
+ * in both image directions, defined operation by operation at the top of csrc/avl_explore.hip: the point of avl_builder's K1
+ * (skipped unless p_z > min_depth, pulled back to max_depth when p_z >= max_depth), the part of the segment from the camera to
+ * it whose height lies in [h_min, h_max], and an all-octant integer Bresenham between the cells of its two ends (cells by
+ * base_pos2grid_id_3d's rule) that marks every cell it visits inside the grid -- but not the end cell of a ray that ends on a
+ * surface inside the band.  The camera's own cell is marked once per frame.  d_first_seen is updated in place: continuing a map in
+ * a second call is part of the contract.  F = 0 does nothing.  h_min <= h_max, 0 <= min_depth < max_depth, stride >= 1. */
+AVL_API int avl_carve_free_space(const void* d_depth, int depth_is_u16, double depth_div, int F, int H, int W, const double* h_calib_inv,
+                                 const double* h_transforms, const int32_t* h_frame_ids, int gs, double cs, int stride, double h_min,
+                                 double h_max, double min_depth, double max_depth, int32_t* d_first_seen, void* stream);
+/* d_out_u8 (H, W): 1 where a cell is explored and free (both non-zero) and at least one of its 4 neighbours inside the image is
+ * unknown, i.e. not explored and free; else 0.  A cell that holds an obstacle (free == 0) is known whether or not a ray crossed
+ * it.  1 <= H, W <= 16384. */
+AVL_API int avl_frontier_mask(const uint8_t* d_free_u8, const uint8_t* d_explored_u8, int H, int W, uint8_t* d_out_u8, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
