@@ -191,6 +191,9 @@ _SIGS = {
     "avl_audio_segment_work_bytes": (C.c_int, [_i64, C.POINTER(_sz)]),
     "avl_audio_segment": (C.c_int, [_vp, _i64, C.c_float, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
     "avl_audio_pack": (C.c_int, [_vp, _i64, _vp, _i64, _i64, C.c_float, _vp, _vp]),
+    "avl_audio_decode_pcm": (C.c_int, [_vp, _i64, C.c_int, C.c_int, _vp, _vp]),
+    "avl_audio_resample": (C.c_int, [_vp, _i64, C.c_int, C.c_int, _vp, _i64, _vp, _i64, _vp]),
+    "avl_audio_resample_limits": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "avl_carve_free_space": (C.c_int, [_vp, C.c_int, _f64, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _f64, C.c_int, _f64, _f64,
                                        _f64, _f64, _vp, _vp]),
     "avl_frontier_mask": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp]),

@@ -7,7 +7,8 @@
 reference's dataset/README.md:76-93; the map goes to <scene>/vlmap/vlmaps.h5df (a real HDF5 file: through h5py, or through
 the HDF5 C library where h5py is missing).
 --sound also builds the sound map (<scene>/audio_video/audio_data_<level>.pkl) from <scene>/audio_video/<seq>/ (a .wav next to
-output_with_audio_<level>.mp4, or the video itself when ffmpeg is installed; poses.txt; the meta file); --audio-model hash is the
+output_with_audio_<level>.mp4 at any sample rate, as 16-, 24- or 32-bit PCM or 32-bit float: it is resampled on the GPU to the
+configured rate; or the video itself when ffmpeg is installed; poses.txt; the meta file); --audio-model hash is the
 model-free audio encoder, the only one built in (AudioCLIP is attached through AVLMap(audio_encoder=...) from Python).
 --explored also carves the sight rays of every depth frame into the explored map (<scene>/vlmap/explored.npz: per cell the first
 frame that saw it, Map.create_explored_map), one ray per --ray-stride pixels in both image directions; VLMap.load_map picks the
@@ -47,7 +48,8 @@ def main(argv=None):
     ap.add_argument("--save-every", type=int, default=None, help="checkpoint every N frames (per rank); default 100 like upstream")
     ap.add_argument("--resume", action="store_true",
                     help="continue from an existing vlmaps.h5df and skip the frames it lists (upstream re-fuses every frame)")
-    ap.add_argument("--sound", action="store_true", help="also build the sound map from <scene>/audio_video")
+    ap.add_argument("--sound", action="store_true", help="also build the sound map from <scene>/audio_video (a .wav next to the video may have any sample rate and PCM "
+                                                         "width: it is resampled on the GPU to sound_data_collect_params.sample_rate)")
     ap.add_argument("--audio-model", choices=["hash"], default="hash",
                     help="--sound: the audio encoder; hash = model-free stand-in (apps/common.HashAudioEncoder)")
     ap.add_argument("--explored", action="store_true", help="also build the explored map (<scene>/vlmap/explored.npz) from the depth frames")

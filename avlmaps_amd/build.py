@@ -36,6 +36,7 @@ SOURCES = {
     "avl_render.hip": ["-ffp-contract=off"],       # the colour blend rounds like NumPy's float32 and float64 products, unfused
     "avl_pnp.hip": ["-ffp-contract=off"],          # the inlier test and the lift are NumPy's float64 expressions, operation for operation
     "avl_audio.hip": ["-ffp-contract=off"],        # compares, one product and one division per sample: nothing to fuse, and it stays so
+    "avl_resample.hip": ["-ffp-contract=off"],     # a filter term is a float64 product, then a float64 add: SciPy's upfirdn, unfused
     "avl_explore.hip": ["-ffp-contract=off"],      # a ray's points are K1's (the explicit fma chain), its slab and end points plain float64 operations
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fvisibility=hidden", "-Wall",

@@ -125,7 +125,8 @@ class SoundMap:
     def get_pos_with_audio(self, audio_path: str, sample_rate: int, audio_encoder=None):
         """The locations of the segment whose feature is most similar to the recording at audio_path (its first five seconds,
         scaled by 32768, through the audio encoder).  Reference: sound_map.py:122-133; a missing path returns ([], []) like
-        upstream.  Load, pack and encode, then ops.retrieve_frame."""
+        upstream; a clip recorded at another rate is resampled to sample_rate, as upstream's librosa.load does.  Load, pack and
+        encode, then ops.retrieve_frame."""
         import os
         from .. import ops
         from ..utils.audio_mapping_utils import TRACK_SCALE
@@ -135,7 +136,7 @@ class SoundMap:
         enc = audio_encoder if audio_encoder is not None else self.audio_encoder
         if enc is None:
             raise RuntimeError("SoundMap.get_pos_with_audio: no audio encoder attached (audio_encoder=)")
-        audio = load_wav(audio_path, sample_rate, device=True)
+        audio = load_wav(audio_path, sample_rate, device=True, resample=True)
         q = encode_audio_batch([(0, audio.shape[0])], enc, sample_rate, audio=audio, scale=TRACK_SCALE)
         feats, locations = self.get_all_audio_features_and_locations()
         idx, _ = ops.retrieve_frame(np.ascontiguousarray(feats, dtype=np.float32), q[0])

@@ -2296,6 +2296,140 @@ def context_ranges(n, times, sample_rate, seconds=5.0):
     return np.asarray(out, dtype=np.int64).reshape(-1, 2)
 
 
+# ---------------------------------------------------------------------------------------- any rate, any PCM width (csrc/avl_resample.hip)
+RESAMPLE_MAX_RATIO = 4096       # 1 <= up, down; every pair of the rates 8 000 .. 192 000 Hz needs at most 2 560 (11 025 <-> 192 000)
+RESAMPLE_TILE = 1024            # outputs per tile of the kernel
+RESAMPLE_LDS_TAPS = 9216        # the tap table is staged in LDS up to this many taps, read from global memory beyond
+RESAMPLE_LDS_WINDOW = 8192      # a tile's input window is staged in LDS up to this many samples
+_RESAMPLE_TAPS_KEPT = 8
+_RESAMPLE_TAPS = {}             # (device, up, down) -> the taps' DeviceArray, most recent last
+
+
+def resample_limits():
+    """(tile, lds_taps, lds_window) as the library was compiled; RESAMPLE_TILE, RESAMPLE_LDS_TAPS and RESAMPLE_LDS_WINDOW state them"""
+    t, a, w = C.c_int(0), C.c_int(0), C.c_int(0)
+    _lib.check(_lib.load().avl_audio_resample_limits(C.byref(t), C.byref(a), C.byref(w)), "avl_audio_resample_limits")
+    return t.value, a.value, w.value
+
+
+def resample_ratio(sr_in, sr_out):
+    """(up, down) = (sr_out, sr_in) / gcd; ValueError unless both rates are positive integers and 1 <= up, down <= 4096"""
+    import math
+    if int(sr_in) != sr_in or int(sr_out) != sr_out or sr_in < 1 or sr_out < 1:
+        raise ValueError(f"sample rates must be positive integers, got {sr_in!r} and {sr_out!r}")
+    sr_in, sr_out = int(sr_in), int(sr_out)
+    g = math.gcd(sr_in, sr_out)
+    up, down = sr_out // g, sr_in // g
+    if max(up, down) > RESAMPLE_MAX_RATIO:
+        raise ValueError(f"{sr_in} Hz -> {sr_out} Hz is the ratio {up} / {down}: both terms must be at most {RESAMPLE_MAX_RATIO}")
+    return up, down
+
+
+def resample_taps(up, down) -> np.ndarray:
+    """Host code: the float64 taps of scipy.signal.resample_poly(x, up, down)'s default filter,
+    firwin(2 * half + 1, 1 / M, window=("kaiser", 5.0)) * up with M = max(up, down) and half = 10 * M, from NumPy alone: the
+    windowed sinc, normalised to unit gain at 0 Hz, times up.  Within 5.6e-16 of SciPy's for the ratios the tests list."""
+    up, down = int(up), int(down)
+    if not (1 <= up <= RESAMPLE_MAX_RATIO and 1 <= down <= RESAMPLE_MAX_RATIO):
+        raise ValueError(f"ratio {up} / {down}: both terms must lie in 1 .. {RESAMPLE_MAX_RATIO}")
+    M = max(up, down)
+    half = 10 * M
+    L = 2 * half + 1
+    i = np.arange(L) - half
+    t = np.sinc(i / M) / M * np.kaiser(L, 5.0)
+    return t / t.sum() * up
+
+
+def _device_taps(up, down, stream):
+    key = (_lib.current_device(), up, down)
+    d = _RESAMPLE_TAPS.pop(key, None)
+    if d is None:
+        d = DeviceArray.from_numpy(resample_taps(up, down), stream)
+    _RESAMPLE_TAPS[key] = d
+    while len(_RESAMPLE_TAPS) > _RESAMPLE_TAPS_KEPT:
+        del _RESAMPLE_TAPS[next(iter(_RESAMPLE_TAPS))]
+    return d
+
+
+def _audio_len(audio):
+    """the length of a mono float32 recording, host or device, checked without any device work"""
+    if isinstance(audio, (DeviceArray, DeviceView)):
+        shape, dt = audio.shape, audio.dtype
+    elif _is_torch(audio):
+        shape, dt = tuple(audio.shape), np.dtype(np.float32) if str(audio.dtype) == "torch.float32" else str(audio.dtype)
+    else:
+        a = np.asarray(audio)
+        shape, dt = a.shape, a.dtype
+    if len(shape) != 1:
+        raise ValueError(f"expected a mono recording of shape (n,), got {tuple(shape)}")
+    if dt != np.float32:
+        raise TypeError(f"expected float32 samples, got {dt} (decode_pcm converts PCM)")
+    if not 1 <= int(shape[0]) <= AUDIO_MAX_SAMPLES:
+        raise ValueError(f"a recording of {shape[0]} samples is outside 1 .. 2^31 - 1")
+    return int(shape[0])
+
+
+def resample_audio(audio, sr_in, sr_out, device=False, stream=None):
+    """scipy.signal.resample_poly(audio, up, down) with its default filter, a float64 accumulator and one rounding to float32, where
+    up / down is sr_out / sr_in reduced: stands in for the resampling of librosa.load(path, sr=sr_out) (audio_mapping_utils.py:238),
+    whose own filter (soxr_hq) this is NOT.  audio: a mono float32 host array, DeviceArray or DeviceView; the result has
+    ceil(n * up / down) samples, a host array or (device=True) a DeviceArray.  sr_in == sr_out returns `audio` itself.  The taps
+    (resample_taps) are kept on the device per (up, down)."""
+    up, down = resample_ratio(sr_in, sr_out)
+    n = _audio_len(audio)
+    if up == down:
+        return audio
+    n_out = -(-n * up // down)
+    if n_out > AUDIO_MAX_SAMPLES:
+        raise ValueError(f"{n} samples at {up} / {down} are {n_out} samples, more than 2^31 - 1")
+    lib = _lib.load()
+    ap, n, keep = _audio_f32(audio, stream)
+    taps = _device_taps(up, down, stream)
+    out = DeviceArray((n_out,), np.float32)
+    _lib.check(lib.avl_audio_resample(ap, n, up, down, taps.ptr, taps.shape[0], out.ptr, n_out, stream), "avl_audio_resample")
+    return _result(out, device, stream, keep=(keep, taps))
+
+
+def decode_pcm(data, width=None, channels=None, device=True, stream=None):
+    """Interleaved PCM of any of the widths a WAV file has -> the mono float32 recording (a DeviceArray (n,) with device=True):
+      int16  (n,) or (n, channels)   decode_pcm16, unchanged
+      int32  (n,) or (n, channels)   32-bit PCM, or 24-bit left-justified in 32 bits (scipy.io.wavfile's convention): width 4
+      uint8  with width=3            the raw little-endian 3-byte samples of a 24-bit file, any shape of n * channels * 3 bytes
+                                     (channels defaults to 1, or to shape[1] of an (n, channels, 3) array)
+    host arrays, DeviceArrays or DeviceViews.  Widths 3 and 4: float32((sum_c float64(s[i, c]) / 2^(8 width - 1)) / channels), the
+    NumPy expression ((s.astype(np.float64) / 2.0 ** (8 * width - 1)).sum(axis=1) / channels).astype(np.float32)."""
+    dev = isinstance(data, (DeviceArray, DeviceView))
+    a = data if dev else np.asarray(data)
+    dt, shape = np.dtype(a.dtype), tuple(a.shape)
+    if dt == np.int16 and width in (None, 2):
+        if channels not in (None, shape[1] if len(shape) == 2 else 1):
+            raise ValueError(f"channels={channels} does not match PCM of shape {shape}")
+        return decode_pcm16(data, device=device, stream=stream)
+    if dt == np.int32 and width in (None, 4):
+        width = 4
+        if len(shape) not in (1, 2):
+            raise ValueError(f"expected PCM of shape (n,) or (n, channels), got {shape}")
+        n, ch = shape[0], shape[1] if len(shape) == 2 else 1
+        if channels not in (None, ch):
+            raise ValueError(f"channels={channels} does not match PCM of shape {shape}")
+    elif dt == np.uint8 and width == 3:
+        ch = int(channels) if channels is not None else (shape[1] if len(shape) == 3 and shape[2] == 3 else 1)
+        size = int(np.prod(shape, dtype=np.int64))
+        if ch < 1 or size % (3 * ch):
+            raise ValueError(f"{size} bytes are not whole frames of {ch} channels of 3 bytes")
+        n = size // (3 * ch)
+    else:
+        raise ValueError(f"{dt} samples with width={width}: int16, int32, or uint8 bytes with width=3 are decoded")
+    if not 1 <= n <= AUDIO_MAX_SAMPLES or not 1 <= ch <= AUDIO_MAX_CHANNELS:
+        raise ValueError(f"{n} frames of {ch} channels: outside 1 .. 2^31 - 1 frames, 1 .. {AUDIO_MAX_CHANNELS} channels")
+    lib = _lib.load()
+    _lib.require_gpu()
+    keep = a if dev else DeviceArray.from_numpy(np.ascontiguousarray(a), stream)
+    out = DeviceArray((n,), np.float32)
+    _lib.check(lib.avl_audio_decode_pcm(keep.ptr, n, ch, width, out.ptr, stream), "avl_audio_decode_pcm")
+    return _result(out, device, stream, keep=(keep,))
+
+
 # ---------------------------------------------------------------------------------------- observed free space (csrc/avl_explore.hip)
 EXPLORE_MAX_SIDE = 16384
 NEVER_SEEN = -1             # first_seen of a cell no sight ray crossed

@@ -7,8 +7,8 @@
     <data_dir>/audio_video/audio_data<manual>_<level>.pkl                     the result: {id: {"audio_features", "locations"}}
     <data_dir>/audio_video/audio_map_statistics<manual>_<level>.pkl           the last two fields of every meta line
 
-Per sequence the recording is uploaded once; decoding, segmentation and the encoder's zero-padded batch run on the GPU
-(csrc/avl_audio.hip), and only the (B, 5 * sample_rate) batches come back for the encoder."""
+Per sequence the recording is uploaded once; decoding, resampling to the configured rate (a .wav at any rate and PCM width:
+csrc/avl_resample.hip), segmentation and the encoder's zero-padded batch run on the GPU (csrc/avl_audio.hip), and only the (B, 5 * sample_rate) batches come back for the encoder."""
 from __future__ import annotations
 
 import os
@@ -78,7 +78,7 @@ def create_audio_map_batch(data_dir: str, audio_encoder, sample_rate: int = 4410
             if not os.path.exists(os.path.join(seq_dir, meta_name)):
                 continue
             wav = find_audio(os.path.join(seq_dir, video_name), sample_rate, tmp)
-            audio = load_wav(wav, sample_rate, device=True)
+            audio = load_wav(wav, sample_rate, device=True, resample=True)
             seg = ops.segment_audio(audio, sample_rate, silence_duration_s, silence_thres)
             if len(seg) == 0:
                 continue

@@ -2,9 +2,13 @@
 segmentation, the five-second contexts and the encoder batches.  The per-sample work (PCM decoding, segmentation, packing) runs in
 csrc/avl_audio.hip through ops; there is no CPU fallback.
 
-Not here: resampling (load_wav raises when the file's rate differs from the requested one; upstream's librosa.load resamples),
-AudioCLIP and its spectrogram front end (any callable audio_encoder(batch (B, 5 * sr) float32) -> (B, D) stands in;
-apps/common.HashAudioEncoder is a model-free one), noisereduce, and the dataset-synthesis functions (assign_sound_to_video*)."""
+A file at another rate than the one asked for is resampled on the GPU with load_wav(..., resample=True) (ops.resample_audio,
+csrc/avl_resample.hip: scipy.signal.resample_poly's default filter, not the soxr_hq of upstream's librosa.load, with which nothing
+here was compared); 16-, 24- and 32-bit PCM and 32-bit float files are read.
+
+Not here: AudioCLIP and its spectrogram front end (any callable audio_encoder(batch (B, 5 * sr) float32) -> (B, D) stands in;
+apps/common.HashAudioEncoder is a model-free one), noisereduce, 8-bit and float64 WAV files, and the dataset-synthesis functions
+(assign_sound_to_video*)."""
 from __future__ import annotations
 
 import os
@@ -32,54 +36,76 @@ def setup_audio_paths(root_dir: str) -> Tuple[str, List[str]]:
     return audio_video_dir, sorted(os.path.join(audio_video_dir, x) for x in os.listdir(audio_video_dir) if not x.endswith(".pkl"))
 
 
-def read_wav(path):
-    """(rate, samples): int16 PCM as (n,) or (n, channels) int16, a float32 WAV as float32 (multi-channel averaged in float32).
-    The standard library's wave module reads PCM16; scipy.io.wavfile reads what wave does not (IEEE float)."""
+def read_wav(path, raw24=False):
+    """(rate, samples): 16-bit PCM as (n,) or (n, channels) int16; 24- and 32-bit PCM as int32, a 24-bit sample left-justified
+    (value * 256: scipy.io.wavfile's convention); a float32 WAV as float32 (multi-channel averaged in float32).  With raw24 a
+    24-bit file the wave module reads comes back as its packed frames, (n, channels, 3) uint8, for ops.decode_pcm(width=3).
+    The standard library's wave module reads plain PCM; scipy.io.wavfile reads what wave does not (IEEE float, and
+    WAVE_FORMAT_EXTENSIBLE where wave refuses it).  Other formats (8-bit, float64) raise ValueError."""
     import wave
     try:
         with wave.open(str(path), "rb") as w:
-            if w.getsampwidth() != 2 or w.getcomptype() != "NONE":
-                raise wave.Error("not 16-bit PCM")
+            width = w.getsampwidth()
+            if width not in (2, 3, 4) or w.getcomptype() != "NONE":
+                raise wave.Error("not 16-, 24- or 32-bit PCM")
             rate, ch = w.getframerate(), w.getnchannels()
-            pcm = np.frombuffer(w.readframes(w.getnframes()), dtype="<i2").astype(np.int16, copy=False)
-        return rate, pcm.reshape(-1, ch) if ch > 1 else pcm
+            raw = w.readframes(w.getnframes())
+        if width == 3:
+            b = np.frombuffer(raw, dtype=np.uint8).reshape(-1, ch, 3)
+            if raw24:
+                return rate, b
+            wide = np.zeros(b.shape[:2] + (4,), np.uint8)
+            wide[..., 1:] = b
+            pcm = wide.view("<i4").astype(np.int32, copy=False).reshape(-1, ch)
+        else:
+            pcm = np.frombuffer(raw, dtype="<i2" if width == 2 else "<i4").astype(np.int16 if width == 2 else np.int32, copy=False)
+            pcm = pcm.reshape(-1, ch)
+        return rate, pcm if ch > 1 else pcm[:, 0]
     except wave.Error:
         pass
     from scipy.io import wavfile
     rate, data = wavfile.read(str(path))
-    if data.dtype == np.int16:
+    if data.dtype in (np.int16, np.int32):
         return rate, data
     if data.dtype != np.float32:
-        raise ValueError(f"{path}: {data.dtype} samples; only 16-bit PCM and 32-bit float WAV files are read")
+        raise ValueError(f"{path}: {data.dtype} samples; only 16-, 24- and 32-bit PCM and 32-bit float WAV files are read")
     return rate, data if data.ndim == 1 else data.mean(axis=1, dtype=np.float32)
 
 
-def load_wav(path, sample_rate, device=False):
-    """The mono float32 recording of a WAV file (host array, or the DeviceArray with device=True): PCM16 is decoded on the GPU
-    (ops.decode_pcm16), a float32 file is passed through.  Stands in for librosa.load(path, sr=sample_rate) WITHOUT resampling: a
-    file recorded at another rate raises ValueError."""
+def load_wav(path, sample_rate, device=False, resample=False):
+    """The mono float32 recording of a WAV file (host array, or the DeviceArray with device=True): PCM is decoded on the GPU
+    (ops.decode_pcm16 / ops.decode_pcm; a plain 24-bit file is uploaded as its packed 3-byte frames), a float32 file is passed
+    through.  Stands in for librosa.load(path, sr=sample_rate): with resample=True a file recorded at another rate is resampled
+    on the GPU (ops.resample_audio: SciPy's resample_poly filter, not librosa's soxr_hq); without it such a file raises
+    ValueError."""
     from .. import ops
     from ..device import DeviceArray
-    rate, data = read_wav(path)
-    if int(rate) != int(sample_rate):
-        raise ValueError(f"{path}: recorded at {rate} Hz, asked for {sample_rate} Hz; resampling is not implemented")
+    rate, data = read_wav(path, raw24=True)
+    if int(rate) != int(sample_rate) and not resample:
+        raise ValueError(f"{path}: recorded at {rate} Hz, asked for {sample_rate} Hz; resampling is off (pass resample=True)")
     if len(data) == 0:
         raise ValueError(f"{path}: no samples")
-    if data.dtype == np.int16:
-        return ops.decode_pcm16(data, device=device)
-    data = np.ascontiguousarray(data, dtype=np.float32)
-    return DeviceArray.from_numpy(data) if device else data
+    convert = int(rate) != int(sample_rate)
+    if data.dtype == np.float32:
+        data = np.ascontiguousarray(data, dtype=np.float32)
+        audio = DeviceArray.from_numpy(data) if device or convert else data
+    elif data.dtype == np.int16:
+        audio = ops.decode_pcm16(data, device=device or convert)
+    else:
+        audio = ops.decode_pcm(data, width=3 if data.dtype == np.uint8 else 4, device=device or convert)
+    return ops.resample_audio(audio, int(rate), int(sample_rate), device=device) if convert else audio
 
 
 def segment_audio_with_silence(audio_path, silence_duration_s: float = 1, silence_thres: float = 0, sample_rate: int = 44100):
     """(time ranges [(start s, end s)], tracks [audio[l:r] float32 host copies]) of a WAV path or a mono float32 array.
     Reference: audio_utils.py:515-546; a missing path returns ([], []) like upstream, a recording without a loud sample too
-    (upstream: IndexError).  The segmentation is ops.segment_audio."""
+    (upstream: IndexError).  A path at another rate is resampled like upstream's librosa.load (load_wav(..., resample=True)).  The
+    segmentation is ops.segment_audio."""
     from .. import ops
     if isinstance(audio_path, (str, os.PathLike)):
         if not os.path.exists(audio_path):
             return [], []
-        audio = load_wav(audio_path, sample_rate, device=True)
+        audio = load_wav(audio_path, sample_rate, device=True, resample=True)
     else:
         audio = audio_path
     seg = ops.segment_audio(audio, sample_rate, silence_duration_s, silence_thres)

@@ -1007,6 +1007,22 @@ AVL_API int avl_audio_segment(const float* d_audio, int64_t n, float threshold, 
  * S = 0 does nothing. */
 AVL_API int avl_audio_pack(const float* d_audio, int64_t n, const int64_t* d_ranges, int64_t S, int64_t L, float scale, float* d_out,
                            void* stream);
+/* (csrc/avl_resample.hip)  avlmaps/utils/audio_mapping_utils.py:238, librosa.load(path, sr=sample_rate), in two steps: the PCM
+ * widths avl_audio_decode_pcm16 does not read, and the change of rate.
+ * d_pcm: n interleaved frames of `channels` samples (1 <= channels <= 8), width = 3: packed little-endian 24-bit, read byte by
+ * byte (no alignment); width = 4: int32 (also a 24-bit sample left-justified in 32 bits).  d_out (n,):
+ * float32((sum_c float64(s[i, c]) / 2^(8 width - 1)) / channels): an exact float64 sum, one float64 division, one rounding. */
+AVL_API int avl_audio_decode_pcm(const void* d_pcm, int64_t n, int channels, int width, float* d_out, void* stream);
+/* Rational resampling by up / down (reduced by the caller, 1 <= up, down <= 4096) with the FIR d_taps[0 .. n_taps), n_taps odd and
+ * at most 81 921, half = (n_taps - 1) / 2; the taps are data (ops.resample_taps designs scipy.signal.resample_poly's default).
+ * d_out (n_out,), n_out == ceil(n * up / down) <= 2^31 - 1:
+ *     out[m] = float32(sum_k d_taps[m * down + half - k * up] * float64(d_audio[k]))
+ * over every 0 <= k < n whose tap index lies in [0, n_taps), added in ascending k with separate float64 multiplies and adds:
+ * scipy.signal.resample_poly(x, up, down) with a float64 accumulator.  One launch, no atomics. */
+AVL_API int avl_audio_resample(const float* d_audio, int64_t n, int up, int down, const double* d_taps, int64_t n_taps, float* d_out,
+                               int64_t n_out, void* stream);
+/* outputs per tile of avl_audio_resample, and how many taps / input samples it stages in LDS before it reads them from global memory */
+AVL_API int avl_audio_resample_limits(int* h_tile, int* h_lds_taps, int* h_lds_window);
 
 /* ------------------------------------------------------------------------------------------------
  * (15) observed free space and the frontier of the 2-D map (csrc/avl_explore.hip)
