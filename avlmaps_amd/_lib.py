@@ -197,6 +197,12 @@ _SIGS = {
     "avl_carve_free_space": (C.c_int, [_vp, C.c_int, _f64, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _f64, C.c_int, _f64, _f64,
                                        _f64, _f64, _vp, _vp]),
     "avl_frontier_mask": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp]),
+    "avl_gt_vote": (C.c_int, [_vp, C.c_int, _f64, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _f64, C.c_int, C.c_int, _f64, _f64,
+                              _vp, C.c_int, C.c_int, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "avl_gt_labels": (C.c_int, [_vp, _i64, C.c_int, _vp, _vp, _vp]),
+    "avl_pool_labels_2d": (C.c_int, [_vp, _i64, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "avl_label_confusion": (C.c_int, [_vp, _vp, _i64, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "avl_label_confusion_limits": (C.c_int, [C.POINTER(C.c_int)]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

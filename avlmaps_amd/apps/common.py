@@ -92,6 +92,11 @@ def _deep_update(dst, src):
             dst[k] = v
 
 
+def read_categories_file(path):
+    """class names, one per line (blank lines dropped); the line number is the class id"""
+    return [line.strip() for line in Path(path).read_text().splitlines() if line.strip()]
+
+
 class HashFeatureExtractor:
     """Stand-in for LSeg when no checkpoint is available (demo / smoke runs): a fixed random projection of a small
     colour + position code to D channels, normalised to the LSeg logit scale, computed on the GPU, channels-last."""

@@ -2,6 +2,7 @@
 
     python -m avlmaps_amd.apps.create_map --data-dir <scene> [--config cfg.yaml] [--features lseg|hash] [--seed N]
                                           [--sound [--audio-model hash]] [--explored [--ray-stride N]]
+                                          [--gt [--obj2cls FILE] [--categories-file FILE]]
 
 <scene>/ holds rgb/*.png, depth/*.npy (float32 metres) and poses.txt (x y z qx qy qz qw per line), the layout of the
 reference's dataset/README.md:76-93; the map goes to <scene>/vlmap/vlmaps.h5df (a real HDF5 file: through h5py, or through
@@ -13,6 +14,10 @@ model-free audio encoder, the only one built in (AudioCLIP is attached through A
 --explored also carves the sight rays of every depth frame into the explored map (<scene>/vlmap/explored.npz: per cell the first
 frame that saw it, Map.create_explored_map), one ray per --ray-stride pixels in both image directions; VLMap.load_map picks the
 file up, and the known-free map and the frontier goals need it.
+--gt also builds the ground-truth label map (<scene>/vlmap/gt_labels.npz, GTMap.create_map) from <scene>/semantic/*.npy, the object
+id of every pixel: --obj2cls is the object id -> class id table (.json dict or list, or .npy; default <scene>/semantic/obj2cls.json
+when it exists, else the frames are taken as class ids), --categories-file a text file with one class name per line, the line
+number being the class id.  apps.evaluate_map scores a map against it.
 Multi-GPU: launch with torchrun; frames are sharded over ranks and merged with one row-sharded RCCL exchange (every --save-every
 frames per rank as a checkpoint, and at the end); an interrupted run is continued with --resume; with --seed the N-rank map
 equals the single-process map (every rank replays the RNG draws of the frames before its shard)."""
@@ -54,9 +59,14 @@ def main(argv=None):
                     help="--sound: the audio encoder; hash = model-free stand-in (apps/common.HashAudioEncoder)")
     ap.add_argument("--explored", action="store_true", help="also build the explored map (<scene>/vlmap/explored.npz) from the depth frames")
     ap.add_argument("--ray-stride", type=int, default=4, metavar="N", help="--explored: one sight ray per N pixels in both image directions")
+    ap.add_argument("--gt", action="store_true", help="also build the ground-truth label map (<scene>/vlmap/gt_labels.npz) from <scene>/semantic")
+    ap.add_argument("--obj2cls", default=None, metavar="FILE", help="--gt: object id -> class id table (.json or .npy)")
+    ap.add_argument("--categories-file", default=None, metavar="FILE", help="--gt: class names, one per line; the line number is the class id")
     args = ap.parse_args(argv)
     if args.ray_stride < 1:
         ap.error("--ray-stride must be at least 1")
+    if (args.obj2cls or args.categories_file) and not args.gt:
+        ap.error("--obj2cls and --categories-file belong to --gt")
 
     from avlmaps_amd import parallel
     from avlmaps_amd.apps.common import HashAudioEncoder, HashFeatureExtractor, load_config
@@ -102,6 +112,17 @@ def main(argv=None):
         first_seen = avlmap.vlmap.create_explored_map(args.data_dir, stride=args.ray_stride)
         print(f"explored map: {int((first_seen >= 0).sum())} cells seen in {avlmap.vlmap.explored_params['n_frames']} frames, written to "
               f"{avlmap.vlmap.data_dir / 'vlmap' / avlmap.vlmap.EXPLORED_FILE}")
+    if args.gt and rank == 0:
+        from avlmaps_amd.apps.common import read_categories_file
+        from avlmaps_amd.map import GTMap
+        gt = GTMap(cfg.map_config)
+        vm = avlmap.vlmap
+        if vm.occupied_ids is None and not vm.load_map(args.data_dir):
+            raise SystemExit(1)
+        gt.create_map(args.data_dir, vlmap=vm, obj2cls=args.obj2cls,
+                      categories=read_categories_file(args.categories_file) if args.categories_file else None)
+        print(f"GT map: {int((gt.labels >= 0).sum())} of {len(gt.labels)} voxels labelled by {int(gt.stats[3])} votes of "
+              f"{gt.gt_params['n_frames']} frames, written to {gt.data_dir / 'vlmap' / gt.GT_FILE}")
     if rank == 0:
         n = len(avlmap.vlmap.map_builder.last_map["grid_pos"]) if hasattr(avlmap.vlmap.map_builder, "last_map") else -1
         print(f"map with {n} voxels written to {avlmap.vlmap.map_builder.map_save_path} in {time.perf_counter() - t0:.2f} s")

@@ -33,6 +33,25 @@ class VLMapsDataloaderHabitat:
         self.init_base_tf = self.base_transform @ cvt_pose_vec2tf(self.base_poses[0]) @ np.linalg.inv(self.base_transform)
         self.inv_init_base_tf = np.linalg.inv(self.init_base_tf)
         self.full_map_pose = None  # (row, col, theta_deg)
+        if load_gt_map:
+            # upstream stops at "TODO: implement loading GT map option" (habitat_dataloader.py:85); its two getters below read
+            # a gt_cropped nothing sets.  Here it is the scene's GT label map (map/gtmap.py) over the obstacle crop
+            from ..map.gtmap import GTMap
+            self.gt_map = GTMap(map_config)
+            if not self.gt_map.load_map(data_dir, vlmap=self.map):
+                raise FileNotFoundError(f"GT map loading fails. It could be because the GT map hasn't been created at {data_dir} "
+                                        "(apps.create_map --gt).")
+            self.gt_cropped = self.gt_map.grid_gt[self.rmin:self.rmax + 1, self.cmin:self.cmax + 1]
+
+    # ---- ground truth (habitat_dataloader.py:90-107); only with load_gt_map=True
+    def get_obstacles_cropped_no_floor(self) -> np.ndarray:
+        floor_mask = self.gt_cropped == 2
+        obstacles_cropped_no_floor = self.obstacles_cropped.copy()
+        obstacles_cropped_no_floor[floor_mask] = 1
+        return obstacles_cropped_no_floor
+
+    def get_gt_semantic_cropped(self) -> np.ndarray:
+        return self.gt_cropped
 
     # ---- obstacle map: only the cropped conversions need it
     def _ensure_obstacles(self):

@@ -315,6 +315,23 @@ class VLMap(Map):
             self.generate_obstacle_map()
         return int(self.rmin), int(self.rmax) + 1, int(self.cmin), int(self.cmax) + 1
 
+    def _argmax_device(self):
+        """the (N,) int32 argmax over scores_mat's columns -- the predicted category of every voxel -- on the device"""
+        from ..device import DeviceArray
+        if self.scores_mat is None or self.categories is None:
+            raise Exception("Categories are not preloaded. Call init_categories(categories: List[str]) to initialize categories.")
+        if getattr(self, "_argmax_src", None) is not self.scores_mat:       # scores_mat was replaced from outside
+            self._argmax, self._argmax_src = np.argmax(self.scores_mat, axis=1), self.scores_mat
+        if getattr(self, "_dev_argmax_src", None) is not self._argmax:      # the argmax goes up once per init_categories
+            self._dev_argmax = DeviceArray.from_numpy(np.ascontiguousarray(self._argmax, dtype=np.int32))
+            self._dev_argmax_src = self._argmax
+        return self._dev_argmax
+
+    def evaluate(self, gt, dim: str = "3d"):
+        """ops.MapScores of this map against a GTMap (GTMap.evaluate from the other side): pixel accuracy, mean accuracy, mIoU and
+        frequency-weighted IoU over its voxels (dim="3d") or over the cells of the top-down maps (dim="2d")"""
+        return gt.evaluate(self, dim)
+
     def _predict_mask_device(self, name: str):
         """the (gs, gs) uint8 top-down mask of the voxels whose argmax is `name`'s category, on the device"""
         from .. import ops
@@ -323,12 +340,7 @@ class VLMap(Map):
         if self.scores_mat is None or self.categories is None:
             raise Exception("Categories are not preloaded. Call init_categories(categories: List[str]) to initialize categories.")
         cat_id = find_similar_category_id(name, self.categories)
-        if getattr(self, "_argmax_src", None) is not self.scores_mat:       # scores_mat was replaced from outside
-            self._argmax, self._argmax_src = np.argmax(self.scores_mat, axis=1), self.scores_mat
-        if getattr(self, "_dev_argmax_src", None) is not self._argmax:      # the argmax goes up once per init_categories
-            self._dev_argmax = DeviceArray.from_numpy(np.ascontiguousarray(self._argmax, dtype=np.int32))
-            self._dev_argmax_src = self._argmax
-        mask = ops.mask_from_argmax(self._dev_argmax, cat_id)
+        mask = ops.mask_from_argmax(self._argmax_device(), cat_id)
         return ops.pool_label_2d(mask, self._device_pos(), int(self.gs), device=True)
 
     def get_predict_mask(self, name: str) -> np.ndarray:

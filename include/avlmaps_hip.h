@@ -1049,6 +1049,51 @@ AVL_API int avl_carve_free_space(const void* d_depth, int depth_is_u16, double d
  * it.  1 <= H, W <= 16384. */
 AVL_API int avl_frontier_mask(const uint8_t* d_free_u8, const uint8_t* d_explored_u8, int H, int W, uint8_t* d_out_u8, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * (16) the ground-truth label map and the scores of a map against it (csrc/avl_gtmap.hip)
+ *     Every result is an integer with one value: no output depends on the order of pixels, frames, launches or calls.  All calls
+ *     are asynchronous on `stream`, check their arguments before any device work and allocate nothing.  d_err_flag (nullable) is
+ *     a device int32 the caller zeroes: bit 0 is set when data on the device is out of range (each call says which).
+ *     Upstream has NO vote pass to mirror (dataset/README.md:78 says the semantic frames "can be used for creating a GT semantic
+ *     map" and stops; gtmap.py loads a grid_gt_1.npy no program writes): the definitions below are this project's own, written
+ *     out operation by operation at the top of csrc/avl_gtmap.hip and in DESIGN.md 4.16.
+ * ------------------------------------------------------------------------------------------------ */
+/* Produces what avlmaps/map/gtmap.py:18-30 loads and avlmaps/dataloader/habitat_dataloader.py:85-107 reads (gt_cropped), from the
+ * semantic frames.  d_depth: F frames of (H, W), float32 metres or uint16 (metres = value / depth_div), and d_semantic: F frames
+ * of (H, W) int32 object ids, as avl_carve_free_space takes its depth; h_calib_inv: inv(K) 3 x 3 row-major; h_transforms: F
+ * camera -> map transforms, 4 x 4 row-major (VLMapBuilder.frame_transforms).  Per pixel of the lattice stride / 2,
+ * stride / 2 + stride, ... in both directions: (1) the point of avl_builder's K1, dropped unless min_depth < p_z < max_depth; (2)
+ * its cell (row, col, h) by base_pos2grid_id_3d's rule, dropped outside (gs, gs, vh) -- (1) and (2) count in d_stats[0]; (3) its
+ * class c = d_obj2cls[o] for the object id o (dropped when o is outside [0, n_obj)), or c = o when d_obj2cls is NULL (n_obj = 0);
+ * dropped when c is outside [0, n_classes) -- counts in d_stats[1]; (4) its voxel r = d_occupied_ids[row, col, h] ((gs, gs, vh)
+ * int32), dropped when r < 0 -- counts in d_stats[2]; r >= n_voxels sets bit 0 of *d_err_flag and the pixel is dropped; (5)
+ * d_votes[r * n_classes + c] += 1 (uint32, (n_voxels, n_classes) row-major, updated in place; a counter wraps after 2^32 hits)
+ * -- counts in d_stats[3].  d_stats: uint64[4], updated in place.  Continuing d_votes and d_stats in a second call is part of
+ * the contract.  1 <= n_classes <= 4096, gs <= 16384, n_voxels * n_classes < 2^40, stride >= 1, 0 <= min_depth < max_depth. */
+AVL_API int avl_gt_vote(const void* d_depth, int depth_is_u16, double depth_div, const int32_t* d_semantic, int F, int H, int W,
+                        const double* h_calib_inv, const double* h_transforms, int gs, double cs, int vh, int stride, double min_depth,
+                        double max_depth, const int32_t* d_obj2cls, int n_obj, int n_classes, const int32_t* d_occupied_ids,
+                        int64_t n_voxels, uint32_t* d_votes, uint64_t* d_stats, int32_t* d_err_flag, void* stream);
+/* The majority label of every voxel (the per-voxel form of the grid gtmap.py:18-30 loads).  d_label (n_voxels,) int32: the lowest
+ * class whose count is the maximum of the voxel's row of d_votes, -1 when the row is all zero; d_support (n_voxels,) uint32: the
+ * row's sum, wrapping like the counters.  d_votes is read once. */
+AVL_API int avl_gt_labels(const uint32_t* d_votes, int64_t n_voxels, int n_classes, int32_t* d_label, uint32_t* d_support, void* stream);
+/* avlmaps/utils/visualize_utils.py:77-83 pool_3d_label_to_2d for labels instead of one mask: d_out (r1 - r0 + 1, c1 - c0 + 1) int32
+ * over the window of rows r0 .. r1 and columns c0 .. c1 (inclusive) of the (gs, gs, vh) voxel index; out[r, c] is the label of
+ * the highest h whose voxel exists (id >= 0) and has d_label[id] >= 0, -1 when the column has none.  An id >= n_voxels sets bit 0
+ * of *d_err_flag and counts as no voxel. */
+AVL_API int avl_pool_labels_2d(const int32_t* d_label, int64_t n_voxels, const int32_t* d_occupied_ids, int gs, int vh, int r0, int r1,
+                               int c0, int c1, int32_t* d_out, int32_t* d_err_flag, void* stream);
+/* The confusion matrix of two label arrays of n entries (voxels, or the cells of two avl_pool_labels_2d maps; gtmap.py:41-71 and
+ * habitat_dataloader.py:85-107 only ever look at the ground truth, nothing upstream compares it with a map).  d_conf
+ * (n_gt_classes, n_pred_classes) uint64 row-major and d_skipped uint64[2], both updated in place: gt[i] < 0 counts in
+ * d_skipped[0]; otherwise pred[i] < 0 counts in d_skipped[1]; otherwise gt[i] >= n_gt_classes or pred[i] >= n_pred_classes sets
+ * bit 0 of *d_err_flag; otherwise d_conf[gt[i], pred[i]] += 1.  Sides 1 .. 65536, at most 2^28 counters, n < 2^40. */
+AVL_API int avl_label_confusion(const int32_t* d_gt, const int32_t* d_pred, int64_t n, int n_gt_classes, int n_pred_classes,
+                                uint64_t* d_conf, uint64_t* d_skipped, int32_t* d_err_flag, void* stream);
+/* the largest n_gt_classes * n_pred_classes avl_label_confusion counts in block-private LDS counters; above it: global atomics */
+AVL_API int avl_label_confusion_limits(int* h_lds_counters);
+
 #ifdef __cplusplus
 }
 #endif
