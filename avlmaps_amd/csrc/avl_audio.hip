@@ -29,6 +29,7 @@
 #include <cmath>
 
 #include "avl_common.h"
+#include "avl_wave.h"
 
 namespace avl {
 
@@ -42,7 +43,6 @@ constexpr int kPackPer = 16;                          // floats per thread of th
 constexpr int kPackChunk = kAudThreads * kPackPer;
 constexpr int kPackMaxRowsY = 32768;
 
-static inline size_t aud_align(size_t b) { return (b + 255) & ~(size_t)255; }
 static inline int64_t aud_tiles(int64_t n) { return (n + kAudTile - 1) / kAudTile; }
 
 // 16-bit mask of the loud samples among the 16 of this thread; base is the index of the first one
@@ -66,71 +66,15 @@ __device__ __forceinline__ unsigned aud_loud_mask(const float* __restrict__ audi
 
 __device__ __forceinline__ int aud_mask_last(unsigned m, int64_t base) { return m ? (int)base + 31 - __clz((int)m) : -1; }
 
-__device__ __forceinline__ int aud_wave_incl_max(int v, int lane) {
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const int o = __shfl_up(v, d, kWave);
-        if (lane >= d) v = max(v, o);
-    }
-    return v;
-}
-
-template <typename T>
-__device__ __forceinline__ T aud_wave_incl_sum(T v, int lane) {
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const T o = __shfl_up(v, d, kWave);
-        if (lane >= d) v += o;
-    }
-    return v;
-}
-
-// exclusive running maximum over the 256 threads of a workgroup (-1 before the first); *total = the maximum over all of them.
-// lds: kAudWaves ints.  Ends with every thread past its reads of lds only after the caller's next barrier: callers that reuse lds
-// put a __syncthreads() in between.
-__device__ __forceinline__ int aud_block_excl_max(int v, int* lds, int* total) {
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    const int incl = aud_wave_incl_max(v, lane);
-    if (lane == kWave - 1) lds[wave] = incl;
-    __syncthreads();
-    int before = -1, all = -1;
-#pragma unroll
-    for (int w = 0; w < kAudWaves; ++w) {
-        const int x = lds[w];
-        if (w < wave) before = max(before, x);
-        all = max(all, x);
-    }
-    const int up = __shfl_up(incl, 1, kWave);
-    *total = all;
-    return lane ? max(before, up) : before;
-}
-
-template <typename T>
-__device__ __forceinline__ T aud_block_excl_sum(T v, T* lds, T* total) {
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    const T incl = aud_wave_incl_sum(v, lane);
-    if (lane == kWave - 1) lds[wave] = incl;
-    __syncthreads();
-    T before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < kAudWaves; ++w) {
-        const T x = lds[w];
-        if (w < wave) before += x;
-        all += x;
-    }
-    *total = all;
-    return before + incl - v;
-}
-
+// The scans below are block_excl_scan over the kAudWaves waves of a tile: the running maximum starts at -1 ("no loud sample yet"),
+// the sums at 0.  A kernel that scans twice uses two LDS arrays; the one-workgroup loops put a barrier before the next round.
 // (a)
 __global__ __launch_bounds__(kAudThreads) void aud_tile_last_kernel(const float* __restrict__ audio, int64_t n, float threshold, bool vec,
                                                                    int* __restrict__ tile_last) {
     __shared__ int lds[kAudWaves];
     const int64_t base = (int64_t)blockIdx.x * kAudTile + (int64_t)threadIdx.x * kAudPer;
     const unsigned m = aud_loud_mask(audio, n, base, threshold, vec);
-    int v = aud_mask_last(m, base);
-#pragma unroll
-    for (int d = kWave / 2; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d, kWave));
+    const int v = wave_max(aud_mask_last(m, base));
     if ((threadIdx.x & (kWave - 1)) == 0) lds[threadIdx.x / kWave] = v;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -149,7 +93,7 @@ __global__ __launch_bounds__(kAudThreads) void aud_carry_kernel(const int* __res
         const int64_t t = b + threadIdx.x;
         const int v = t < tiles ? tile_last[t] : -1;
         int total;
-        const int ex = aud_block_excl_max(v, lds, &total);
+        const int ex = block_excl_scan<kAudWaves>(v, OpMax{}, -1, lds, &total);
         if (t < tiles) carry[t] = max(running, ex);
         running = max(running, total);
         __syncthreads();                              // lds is written again in the next round
@@ -178,10 +122,10 @@ __global__ __launch_bounds__(kAudThreads) void aud_count_kernel(const float* __r
     const int64_t base = (int64_t)blockIdx.x * kAudTile + (int64_t)threadIdx.x * kAudPer;
     const unsigned m = aud_loud_mask(audio, n, base, threshold, vec);
     int total;
-    const int prev = max(carry[blockIdx.x], aud_block_excl_max(aud_mask_last(m, base), lds, &total));
+    const int prev = max(carry[blockIdx.x], block_excl_scan<kAudWaves>(aud_mask_last(m, base), OpMax{}, -1, lds, &total));
     const int c = __popc(aud_start_mask(m, base, prev, gap));
     int sum;
-    aud_block_excl_sum<int>(c, lds2, &sum);
+    block_excl_scan<kAudWaves>(c, OpSum{}, 0, lds2, &sum);
     if (threadIdx.x == 0) tile_count[blockIdx.x] = sum;
 }
 
@@ -194,10 +138,10 @@ __global__ __launch_bounds__(kAudThreads) void aud_offsets_kernel(const int* __r
         const int64_t t = b + threadIdx.x;
         const int64_t v = t < tiles ? tile_count[t] : 0;
         int64_t total;
-        const int64_t ex = aud_block_excl_sum<int64_t>(v, lds, &total);
+        const int64_t ex = block_excl_scan<kAudWaves>(v, OpSum{}, (int64_t)0, lds, &total);
         if (t < tiles) offsets[t] = running + ex;
         running += total;
-        __syncthreads();
+        __syncthreads();                              // lds is written again in the next round
     }
     if (threadIdx.x == 0) d_count[0] = running;
 }
@@ -212,10 +156,10 @@ __global__ __launch_bounds__(kAudThreads) void aud_write_kernel(const float* __r
     const int64_t base = (int64_t)blockIdx.x * kAudTile + (int64_t)threadIdx.x * kAudPer;
     unsigned m = aud_loud_mask(audio, n, base, threshold, vec);
     int total;
-    int prev = max(carry[blockIdx.x], aud_block_excl_max(aud_mask_last(m, base), lds, &total));
+    int prev = max(carry[blockIdx.x], block_excl_scan<kAudWaves>(aud_mask_last(m, base), OpMax{}, -1, lds, &total));
     const unsigned s = aud_start_mask(m, base, prev, gap);
     int sum;
-    int64_t k = offsets[blockIdx.x] + aud_block_excl_sum<int>(__popc(s), lds2, &sum);
+    int64_t k = offsets[blockIdx.x] + block_excl_scan<kAudWaves>((int)__popc(s), OpSum{}, 0, lds2, &sum);
     while (m) {
         const int j = __ffs((int)m) - 1;
         m &= m - 1;
@@ -276,9 +220,18 @@ __global__ __launch_bounds__(kAudThreads) void aud_pack_kernel(const float* __re
     }
 }
 
-static size_t aud_segment_bytes(int64_t n) {
+// workspace of avl_audio_segment: one value per tile in each piece
+struct AudWork { int *tile_last, *carry, *tile_count; int64_t* offsets; size_t total; };
+static AudWork aud_work(int64_t n, void* ws) {
     const size_t t = (size_t)aud_tiles(n);
-    return 3 * aud_align(t * sizeof(int)) + aud_align(t * sizeof(int64_t));
+    Carver c(ws);
+    AudWork w;
+    w.tile_last = c.ptr<int>(t * sizeof(int));
+    w.carry = c.ptr<int>(t * sizeof(int));
+    w.tile_count = c.ptr<int>(t * sizeof(int));
+    w.offsets = c.ptr<int64_t>(t * sizeof(int64_t));
+    w.total = c.total();
+    return w;
 }
 
 }  // namespace avl
@@ -301,7 +254,7 @@ int avl_audio_decode_pcm16(const int16_t* d_pcm, int64_t n, int channels, float*
 int avl_audio_segment_work_bytes(int64_t n, size_t* h_bytes) {
     AVL_REQUIRE(h_bytes, "avl_audio_segment_work_bytes: null pointer");
     AVL_REQUIRE(n >= 1 && n <= kAudMaxSamples, "avl_audio_segment_work_bytes: n=%lld outside 1 .. 2^31 - 1", (long long)n);
-    *h_bytes = aud_segment_bytes(n);
+    *h_bytes = aud_work(n, nullptr).total;
     return AVL_OK;
 }
 
@@ -313,22 +266,17 @@ int avl_audio_segment(const float* d_audio, int64_t n, float threshold, int64_t 
     AVL_REQUIRE(!std::isnan(threshold), "avl_audio_segment: the threshold is NaN");
     AVL_REQUIRE(cap >= 0 && (cap == 0 || d_segments), "avl_audio_segment: cap=%lld without a segment buffer", (long long)cap);
     AVL_REQUIRE(((uintptr_t)d_audio & 3) == 0, "avl_audio_segment: d_audio is not aligned to 4 bytes");
-    AVL_REQUIRE(ws_bytes >= aud_segment_bytes(n), "avl_audio_segment: workspace of %zu bytes, %zu needed", ws_bytes, aud_segment_bytes(n));
+    const AudWork w = aud_work(n, d_ws);
+    AVL_REQUIRE(ws_bytes >= w.total, "avl_audio_segment: workspace of %zu bytes, %zu needed", ws_bytes, w.total);
     const int64_t tiles = aud_tiles(n);
-    char* w = static_cast<char*>(d_ws);
-    const size_t ib = aud_align((size_t)tiles * sizeof(int));
-    int* tile_last = reinterpret_cast<int*>(w);
-    int* carry = reinterpret_cast<int*>(w + ib);
-    int* tile_count = reinterpret_cast<int*>(w + 2 * ib);
-    int64_t* offsets = reinterpret_cast<int64_t*>(w + 3 * ib);
     const bool vec = ((uintptr_t)d_audio & 15) == 0;
     hipStream_t st = as_stream(stream);
     const dim3 grid((unsigned)tiles), block(kAudThreads);
-    hipLaunchKernelGGL(aud_tile_last_kernel, grid, block, 0, st, d_audio, n, threshold, vec, tile_last);
-    hipLaunchKernelGGL(aud_carry_kernel, dim3(1), block, 0, st, tile_last, tiles, carry);
-    hipLaunchKernelGGL(aud_count_kernel, grid, block, 0, st, d_audio, n, threshold, gap, vec, carry, tile_count);
-    hipLaunchKernelGGL(aud_offsets_kernel, dim3(1), block, 0, st, tile_count, tiles, offsets, d_count);
-    hipLaunchKernelGGL(aud_write_kernel, grid, block, 0, st, d_audio, n, threshold, gap, vec, carry, tile_last, offsets, d_segments, cap);
+    hipLaunchKernelGGL(aud_tile_last_kernel, grid, block, 0, st, d_audio, n, threshold, vec, w.tile_last);
+    hipLaunchKernelGGL(aud_carry_kernel, dim3(1), block, 0, st, w.tile_last, tiles, w.carry);
+    hipLaunchKernelGGL(aud_count_kernel, grid, block, 0, st, d_audio, n, threshold, gap, vec, w.carry, w.tile_count);
+    hipLaunchKernelGGL(aud_offsets_kernel, dim3(1), block, 0, st, w.tile_count, tiles, w.offsets, d_count);
+    hipLaunchKernelGGL(aud_write_kernel, grid, block, 0, st, d_audio, n, threshold, gap, vec, w.carry, w.tile_last, w.offsets, d_segments, cap);
     AVL_HIP_CHECK(hipGetLastError());
     return AVL_OK;
 }

@@ -45,4 +45,25 @@ void trim_mempool(uint64_t keep_bytes);   // hipMemPoolTrimTo on the device's de
 
 constexpr int kWave = 64;
 
+constexpr size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+// the first 256-aligned address at or after p (entry points whose callers may pass any address; their totals carry the slack)
+static inline void* align256_ptr(void* p) { return reinterpret_cast<void*>(align256(reinterpret_cast<uintptr_t>(p))); }
+
+// Lays a workspace out as consecutive 256-aligned pieces.  An entry point's *_work_bytes and its consumer call ONE layout function
+// built on this (the size query with a null base), so every piece is written once: the consumer never recomputes an offset or
+// derives a size by subtraction.  Slack for a base that the entry point aligns itself is added to total() by the layout function.
+struct Carver {
+    uintptr_t base;
+    size_t used = 0;
+    explicit Carver(void* b = nullptr) : base(reinterpret_cast<uintptr_t>(b)) {}
+    size_t take(size_t bytes) {                       // the piece's offset
+        const size_t at = used;
+        used += align256(bytes);
+        return at;
+    }
+    template <typename T>
+    T* ptr(size_t bytes) { return reinterpret_cast<T*>(base + take(bytes)); }
+    size_t total() const { return used; }
+};
+
 }  // namespace avl

@@ -27,6 +27,7 @@
 #include <cmath>
 
 #include "avl_common.h"
+#include "avl_wave.h"
 
 namespace avl {
 
@@ -87,11 +88,6 @@ __global__ __launch_bounds__(kEdtCols* kEdtSegs) void edt_column_kernel(const ui
     }
 }
 
-__device__ __forceinline__ unsigned wave_min_u32(unsigned v) {
-    for (int off = 32; off > 0; off >>= 1) v = min(v, (unsigned)__shfl_xor((int)v, off, kWave));
-    return v;
-}
-
 // NumPy: t = 1 - (d / cell_size) * decay_rate, t < 0 -> 0
 __device__ __forceinline__ double edt_decay(double d, double cell_size, double decay_rate) {
     const double t = 1.0 - __ddiv_rn(d, cell_size) * decay_rate;
@@ -118,7 +114,7 @@ __global__ __launch_bounds__(kEdtRowThreads) void edt_row_kernel(const int32_t* 
             if (gv >= 0) v = (unsigned)gv;
         }
         s_g[c] = (unsigned short)v;
-        const unsigned m = wave_min_u32(v);
+        const unsigned m = wave_min(v);
         if ((threadIdx.x & (kWave - 1)) == 0) s_tmin[c / kEdtTile] = m * m;
     }
     __syncthreads();
@@ -163,28 +159,7 @@ __global__ __launch_bounds__(kEdtRowThreads) void edt_row_kernel(const int32_t* 
         }
         out[(int64_t)r * W + c] = v;
     }
-    if (DECAY && minmax) {
-        for (int off = 32; off > 0; off >>= 1) {
-            mn = fmin(mn, __shfl_xor(mn, off, kWave));
-            mx = fmax(mx, __shfl_xor(mx, off, kWave));
-        }
-        const int w = threadIdx.x / kWave;
-        if ((threadIdx.x & (kWave - 1)) == 0) {
-            s_red[2 * w] = mn;
-            s_red[2 * w + 1] = mx;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            for (int k = 1; k < kEdtRowThreads / kWave; ++k) {
-                mn = fmin(mn, s_red[2 * k]);
-                mx = fmax(mx, s_red[2 * k + 1]);
-            }
-            if (mn <= mx) {
-                atomicMin(&minmax[0], (unsigned long long)__double_as_longlong(mn));
-                atomicMax(&minmax[1], (unsigned long long)__double_as_longlong(mx));
-            }
-        }
-    }
+    if (DECAY && minmax) block_minmax_atomic<kEdtRowThreads>(mn, mx, minmax, s_red);
 }
 
 // NumPy: (t - min) / (max - min), in place (field_normalize_kernel's expression on an (H, W) image)
@@ -193,8 +168,6 @@ __global__ __launch_bounds__(256) void edt_normalize_kernel(double* __restrict__
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         t[i] = __ddiv_rn(t[i] - mn, span);
 }
-
-static size_t edt_align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 static int edt_check_shape(const char* what, int H, int W) {
     AVL_REQUIRE(H > 0 && W > 0 && H <= kEdtMaxSide && W <= kEdtMaxSide, "%s: bad shape %d x %d (sides 1 .. %d)", what, H, W, kEdtMaxSide);
@@ -234,7 +207,7 @@ int avl_edt2d_work_bytes(int H, int W, size_t* bytes) {
     AVL_REQUIRE(bytes, "avl_edt2d_work_bytes: null output");
     int rc = edt_check_shape("avl_edt2d_work_bytes", H, W);
     if (rc != AVL_OK) return rc;
-    *bytes = edt_align256((size_t)H * W * sizeof(int32_t));
+    *bytes = align256((size_t)H * W * sizeof(int32_t));
     return AVL_OK;
 }
 

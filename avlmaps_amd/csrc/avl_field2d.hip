@@ -27,6 +27,7 @@
 #include <cmath>
 
 #include "avl_common.h"
+#include "avl_wave.h"
 #include "avl_field_math.h"
 
 namespace avl {
@@ -39,43 +40,6 @@ __device__ __forceinline__ long long tile_d2(int r, int c, int r0, int r1, int c
     const long long dr = r < r0 ? (long long)r0 - r : (r > r1 ? (long long)r - r1 : 0);
     const long long dc = c < c0 ? (long long)c0 - c : (c > c1 ? (long long)c - c1 : 0);
     return dr * dr + dc * dc;
-}
-
-__device__ __forceinline__ double wave_min_f64(double v) {
-    for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off, kWave));
-    return v;
-}
-__device__ __forceinline__ double wave_max_f64(double v) {
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, kWave));
-    return v;
-}
-
-// min / max of the tile's values into d_minmax (non-negative values: their IEEE bit patterns order like the values)
-template <typename T, typename U>
-__device__ __forceinline__ void tile_minmax(T v, bool inside, U* minmax, double* red /* [2 * waves] */) {
-    double mn = wave_min_f64(inside ? (double)v : INFINITY);
-    double mx = wave_max_f64(inside ? (double)v : -INFINITY);
-    const int w = threadIdx.x / kWave;
-    if ((threadIdx.x & (kWave - 1)) == 0) {
-        red[2 * w] = mn;
-        red[2 * w + 1] = mx;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < kFieldThreads / kWave; ++k) {
-            mn = fmin(mn, red[2 * k]);
-            mx = fmax(mx, red[2 * k + 1]);
-        }
-        if (mn <= mx) {                           // some cell of the tile lies inside the grid
-            if constexpr (sizeof(T) == 8) {
-                atomicMin(&minmax[0], (U)__double_as_longlong(mn));
-                atomicMax(&minmax[1], (U)__double_as_longlong(mx));
-            } else {
-                atomicMin(&minmax[0], (U)__float_as_uint((float)mn));
-                atomicMax(&minmax[1], (U)__float_as_uint((float)mx));
-            }
-        }
-    }
 }
 
 __global__ __launch_bounds__(kFieldThreads) void field_area_kernel(const int32_t* __restrict__ cells, const double* __restrict__ peaks,
@@ -93,7 +57,7 @@ __global__ __launch_bounds__(kFieldThreads) void field_area_kernel(const int32_t
     double best = 0.0;
     for (int64_t base = 0; base < P; base += kFieldThreads) {
         // smallest running maximum of the tile: a pose whose clipped peak is not above it cannot raise any cell
-        const double m = wave_min_f64(inside ? best : 2.0);
+        const double m = wave_min(inside ? best : 2.0);
         if ((threadIdx.x & (kWave - 1)) == 0) s_red[w] = m;
         if (threadIdx.x == 0) s_n = 0;
         __syncthreads();
@@ -131,7 +95,8 @@ __global__ __launch_bounds__(kFieldThreads) void field_area_kernel(const int32_t
         __syncthreads();                                                   // LDS is refilled by the next chunk
     }
     if (inside) field[(size_t)r * gs + c] = best;
-    tile_minmax<double>(best, inside, minmax, s_red);
+    // min / max of the tile into d_minmax (non-negative values: their bit patterns order like the values)
+    block_minmax_atomic<kFieldThreads>(inside ? best : INFINITY, inside ? best : -INFINITY, minmax, s_red);
 }
 
 __global__ __launch_bounds__(kFieldThreads) void field_sound_kernel(const int64_t* __restrict__ offsets, const int32_t* __restrict__ cells,
@@ -170,7 +135,7 @@ __global__ __launch_bounds__(kFieldThreads) void field_sound_kernel(const int64_
         }
     }
     if (inside) field[(size_t)r * gs + c] = acc;
-    tile_minmax<float>(acc, inside, minmax, s_red);
+    block_minmax_atomic<kFieldThreads>(inside ? (double)acc : INFINITY, inside ? (double)acc : -INFINITY, minmax, s_red);
 }
 
 // heat[i] = f32((D[row, col] - min) / (max - min)) for the voxel's column, 0 for a voxel outside the (gs, gs, vh) grid -- the

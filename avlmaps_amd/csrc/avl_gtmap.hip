@@ -49,6 +49,7 @@
 #include <cmath>
 
 #include "avl_pinhole.h"
+#include "avl_wave.h"
 
 namespace avl {
 
@@ -190,14 +191,6 @@ __global__ __launch_bounds__(256) void pool_labels_kernel(const int32_t* __restr
     out[(size_t)r * Ww + c] = res;
 }
 
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-    for (int m = kWave >> 1; m > 0; m >>= 1) {
-        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, m, kWave), hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), m, kWave);
-        v += ((unsigned long long)hi << 32) | lo;
-    }
-    return v;
-}
-
 template <bool LDS>
 __global__ __launch_bounds__(256) void confusion_kernel(const int32_t* __restrict__ gt, const int32_t* __restrict__ pred, long long n,
                                                         long long per_block, int Cg, int Cp, unsigned long long* __restrict__ conf,
@@ -224,8 +217,8 @@ __global__ __launch_bounds__(256) void confusion_kernel(const int32_t* __restric
             atomicAdd(conf + (size_t)g * Cp + q, 1ull);
         }
     }
-    s0 = wave_sum_u64(s0);
-    s1 = wave_sum_u64(s1);
+    s0 = wave_sum(s0);
+    s1 = wave_sum(s1);
     if ((threadIdx.x & (kWave - 1)) == 0) {
         if (s0) atomicAdd(skipped + 0, s0);
         if (s1) atomicAdd(skipped + 1, s1);

@@ -23,6 +23,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "avl_common.h"
+#include "avl_wave.h"
 
 namespace avl {
 
@@ -41,10 +42,8 @@ __global__ __launch_bounds__(256) void heat_bbox_kernel(const int32_t* __restric
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        for (int off = 32; off > 0; off >>= 1) {
-            mn[c] = min(mn[c], __shfl_xor(mn[c], off, 64));
-            mx[c] = max(mx[c], __shfl_xor(mx[c], off, 64));
-        }
+        mn[c] = wave_min(mn[c]);
+        mx[c] = wave_max(mx[c]);
         if ((threadIdx.x & 63) == 0) {
             red[c][threadIdx.x >> 6] = mn[c];
             red[3 + c][threadIdx.x >> 6] = mx[c];

@@ -36,6 +36,7 @@
 #include <climits>
 
 #include "avl_common.h"
+#include "avl_wave.h"
 
 namespace avl {
 
@@ -124,27 +125,6 @@ __global__ __launch_bounds__(256) void isl_flatten_kernel(int* __restrict__ pare
     }
 }
 
-// exclusive scan of one int per thread over the workgroup; *total = the sum.  s_w: blockDim.x / 64 + 1 ints of LDS
-__device__ __forceinline__ int isl_block_scan(int v, int* s_w, int* total) {
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave, nw = blockDim.x / kWave;
-    int inc = v;
-    for (int off = 1; off < kWave; off <<= 1) {
-        const int t = __shfl_up(inc, off, kWave);
-        if (lane >= off) inc += t;
-    }
-    __syncthreads();                                          // s_w may still be read from an earlier call
-    if (lane == kWave - 1) s_w[wave] = inc;
-    __syncthreads();
-    int before = 0, sum = 0;
-    for (int k = 0; k < nw; ++k) {
-        const int t = s_w[k];
-        if (k < wave) before += t;
-        sum += t;
-    }
-    *total = sum;
-    return before + inc - v;
-}
-
 __device__ __forceinline__ int isl_root_flags(const int* __restrict__ parent, int64_t cells, int64_t i0) {
     int f = 0;
 #pragma unroll
@@ -156,22 +136,23 @@ __device__ __forceinline__ int isl_root_flags(const int* __restrict__ parent, in
 }
 
 __global__ __launch_bounds__(kIslScanThreads) void isl_count_kernel(const int* __restrict__ parent, int64_t cells, int* __restrict__ counts) {
-    __shared__ int s_w[kIslScanThreads / kWave + 1];
+    __shared__ int s_w[kIslScanThreads / kWave];
     const int f = isl_root_flags(parent, cells, (int64_t)blockIdx.x * kIslScanBlock + threadIdx.x * kIslScanPer);
     int total;
-    isl_block_scan(__popc(f), s_w, &total);
+    block_excl_scan<kIslScanThreads / kWave>((int)__popc(f), OpSum{}, 0, s_w, &total);
     if (threadIdx.x == 0) counts[blockIdx.x] = total;
 }
 
 // counts -> exclusive offsets in place, the total to *n; one workgroup
 __global__ __launch_bounds__(1024) void isl_offsets_kernel(int* __restrict__ counts, int nblocks, int* __restrict__ n) {
-    __shared__ int s_w[1024 / kWave + 1];
+    __shared__ int s_w[1024 / kWave];
     int carry = 0;
     for (int b0 = 0; b0 < nblocks; b0 += 1024) {
         const int b = b0 + threadIdx.x;
         const int v = b < nblocks ? counts[b] : 0;
         int total;
-        const int ex = isl_block_scan(v, s_w, &total);
+        __syncthreads();                                          // s_w may still be read from the round before
+        const int ex = block_excl_scan<1024 / kWave>(v, OpSum{}, 0, s_w, &total);
         if (b < nblocks) counts[b] = carry + ex;
         carry += total;
     }
@@ -180,11 +161,11 @@ __global__ __launch_bounds__(1024) void isl_offsets_kernel(int* __restrict__ cou
 
 __global__ __launch_bounds__(kIslScanThreads) void isl_number_kernel(const int* __restrict__ parent, int64_t cells, const int* __restrict__ offsets,
                                                                      int* __restrict__ labels) {
-    __shared__ int s_w[kIslScanThreads / kWave + 1];
+    __shared__ int s_w[kIslScanThreads / kWave];
     const int64_t i0 = (int64_t)blockIdx.x * kIslScanBlock + threadIdx.x * kIslScanPer;
     const int f = isl_root_flags(parent, cells, i0);
     int total;
-    int rank = offsets[blockIdx.x] + isl_block_scan(__popc(f), s_w, &total);
+    int rank = offsets[blockIdx.x] + block_excl_scan<kIslScanThreads / kWave>((int)__popc(f), OpSum{}, 0, s_w, &total);
 #pragma unroll
     for (int k = 0; k < kIslScanPer; ++k)
         if (f >> k & 1) labels[i0 + k] = ++rank;
@@ -374,12 +355,23 @@ __global__ __launch_bounds__(kNpThreads) void np_final_kernel(const long long* _
     }
 }
 
-static size_t isl_align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 static int isl_check_shape(const char* what, int H, int W) {
     AVL_REQUIRE(H > 0 && W > 0 && H <= kIslMaxSide && W <= kIslMaxSide && (int64_t)H * W <= kIslMaxCells,
                 "%s: bad shape %d x %d (sides 1 .. %d, at most %lld cells)", what, H, W, kIslMaxSide, (long long)kIslMaxCells);
     return AVL_OK;
+}
+
+// workspace of avl_label_islands: the union-find parents, then one root count per scan block
+struct IslWork { int nblocks, *parent, *counts; size_t total; };
+static IslWork isl_work(int H, int W, void* ws) {
+    const int64_t cells = (int64_t)H * W;
+    Carver c(ws);
+    IslWork w;
+    w.nblocks = (int)((cells + kIslScanBlock - 1) / kIslScanBlock);
+    w.parent = c.ptr<int>((size_t)cells * sizeof(int32_t));
+    w.counts = c.ptr<int>((size_t)w.nblocks * sizeof(int32_t));
+    w.total = c.total();
+    return w;
 }
 
 static dim3 isl_seg_grid(int H, int W) { return dim3((unsigned)((W + kIslSeg - 1) / kIslSeg), (unsigned)((H + kIslWaves - 1) / kIslWaves)); }
@@ -409,26 +401,20 @@ int avl_label_islands_work_bytes(int H, int W, size_t* bytes) {
     AVL_REQUIRE(bytes, "avl_label_islands_work_bytes: null output");
     int rc = isl_check_shape("avl_label_islands_work_bytes", H, W);
     if (rc != AVL_OK) return rc;
-    const int64_t cells = (int64_t)H * W, nblocks = (cells + kIslScanBlock - 1) / kIslScanBlock;
-    *bytes = isl_align256((size_t)cells * sizeof(int32_t)) + isl_align256((size_t)nblocks * sizeof(int32_t));
+    *bytes = isl_work(H, W, nullptr).total;
     return AVL_OK;
 }
 
 int avl_label_islands(const uint8_t* d_mask_u8, int64_t ld, int H, int W, int32_t* d_labels, int32_t* d_n, void* ws, size_t ws_bytes,
                       void* stream) {
-    size_t need = 0;
     int rc = isl_check_shape("avl_label_islands", H, W);
     if (rc != AVL_OK) return rc;
     AVL_REQUIRE(d_mask_u8 && d_labels && d_n, "avl_label_islands: null mask, label or count pointer");
     AVL_REQUIRE(ld >= W, "avl_label_islands: rows of %lld cells cannot hold %d columns", (long long)ld, W);
-    rc = avl_label_islands_work_bytes(H, W, &need);
-    if (rc != AVL_OK) return rc;
+    const auto [nblocks, parent, counts, need] = isl_work(H, W, ws);
     AVL_REQUIRE(ws && ws_bytes >= need, "avl_label_islands: workspace of %zu bytes, need %zu", ws_bytes, need);
     hipStream_t st = as_stream(stream);
     const int64_t cells = (int64_t)H * W;
-    const int nblocks = (int)((cells + kIslScanBlock - 1) / kIslScanBlock);
-    int* parent = (int*)ws;
-    int* counts = (int*)((char*)ws + isl_align256((size_t)cells * sizeof(int32_t)));
     const dim3 seg = isl_seg_grid(H, W), segb(kIslSeg * kIslWaves);
     const unsigned sb = isl_stride_blocks(cells);
     hipLaunchKernelGGL(isl_init_kernel, seg, segb, 0, st, d_mask_u8, ld, H, W, parent);
@@ -485,7 +471,7 @@ int avl_nearest_pair_work_bytes(int64_t na, int64_t nb, size_t* bytes) {
     if (rc != AVL_OK) return rc;
     unsigned gx, gy;
     np_grid(na, nb, &gx, &gy);
-    *bytes = isl_align256((size_t)gx * gy * 3 * sizeof(int64_t));
+    *bytes = align256((size_t)gx * gy * 3 * sizeof(int64_t));
     return AVL_OK;
 }
 

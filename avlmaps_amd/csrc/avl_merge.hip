@@ -15,6 +15,7 @@
 #include <rocprim/iterator/transform_iterator.hpp>
 
 #include "avl_common.h"
+#include "avl_wave.h"
 
 namespace avl {
 
@@ -56,11 +57,8 @@ __global__ __launch_bounds__(256) void merge_partition_kernel(long long n, const
         kmin = k < kmin ? k : kmin;
         kmax = k > kmax ? k : kmax;
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        const long long a = __shfl_xor(kmin, off, 64), b = __shfl_xor(kmax, off, 64);
-        kmin = a < kmin ? a : kmin;
-        kmax = b > kmax ? b : kmax;
-    }
+    kmin = wave_min(kmin);
+    kmax = wave_max(kmax);
     if ((threadIdx.x & 63) == 0) {
         smin[threadIdx.x >> 6] = kmin;
         smax[threadIdx.x >> 6] = kmax;
@@ -285,8 +283,6 @@ __global__ void merge_side_unpack_kernel(long long R, const long long* __restric
     }
 }
 
-static size_t al256(size_t b) { return (b + 255) / 256 * 256; }
-
 static hipError_t scan_flags(void* tmp, size_t& tmp_bytes, const uint8_t* flags, long long* out, long long n, hipStream_t st) {
     auto it = rocprim::make_transform_iterator(flags, FlagToCount{});
     return rocprim::exclusive_scan(tmp, tmp_bytes, it, out, 0ll, (size_t)n, rocprim::plus<long long>(), st);
@@ -308,6 +304,55 @@ static hipError_t sort_u32_i64(void* tmp, size_t& tmp_bytes, const uint32_t* k, 
 
 static unsigned grid_for(long long n) { return (unsigned)std::min<long long>((n + 255) / 256, 2048); }
 
+// Work buffers of the merge entry points.  Callers may pass any address: the pieces start at the first 256-aligned one, and the
+// totals carry 512 bytes of slack for that.  who = nullptr: the size query (null base, no check of the buffer).
+// avl_merge_partition / avl_merge_dir_scan: [keys u32 | sorted keys u32 | values i64 | rocPRIM's storage (the larger of the narrow
+// and the wide sort)]
+struct MergeWork { uint32_t *keys, *keys_out; long long* iota; void* tmp; size_t tmp_bytes, total; };
+static int carve_work(int64_t n, void* d_work, size_t work_bytes, MergeWork& w, const char* who) {
+    AVL_REQUIRE(n >= 0 && n < (1ll << 31), "%s: bad arguments", who ? who : "avl_merge_work_bytes");
+    size_t t1 = 0, t32 = 0;
+    const long long m = n ? n : 1;
+    AVL_HIP_CHECK(sort_u32_i64(nullptr, t1, nullptr, nullptr, nullptr, nullptr, m, 8, nullptr));
+    AVL_HIP_CHECK(sort_u32_i64(nullptr, t32, nullptr, nullptr, nullptr, nullptr, m, 31, nullptr));
+    Carver c(align256_ptr(d_work));
+    w.keys = c.ptr<uint32_t>((size_t)m * 4);
+    w.keys_out = c.ptr<uint32_t>((size_t)m * 4);
+    w.iota = c.ptr<long long>((size_t)m * 8);
+    w.tmp_bytes = align256(std::max(t1, t32));
+    w.tmp = c.ptr<void>(w.tmp_bytes);
+    w.total = c.total() + 512;
+    if (who) {
+        AVL_REQUIRE(d_work && work_bytes >= w.total, "%s: work buffer of %zu bytes, %zu needed (avl_merge_work_bytes)", who, work_bytes, w.total);
+    }
+    return AVL_OK;
+}
+
+// avl_merge_rows_new / avl_merge_dir_rows / avl_merge_rows_other: [offsets | keys | sorted keys | indices | a second offset / row
+// vector | rocPRIM's storage]
+struct RowsWork { long long *off, *idx, *aux; unsigned long long *keys, *keys_out; void* tmp; size_t tmp_bytes, total; };
+static int carve_rows_work(int64_t n, void* d_work, size_t work_bytes, RowsWork& w, const char* who) {
+    AVL_REQUIRE(n >= 0 && n < (1ll << 31), "%s: bad arguments", who ? who : "avl_merge_rows_work_bytes");
+    const long long m = n ? n : 1;
+    size_t t_scan = 0, t_max = 0, t_sort = 0;
+    AVL_HIP_CHECK(scan_flags(nullptr, t_scan, nullptr, nullptr, m, nullptr));
+    AVL_HIP_CHECK(scan_max(nullptr, t_max, nullptr, nullptr, m, nullptr));
+    AVL_HIP_CHECK(sort_u64_i64(nullptr, t_sort, nullptr, nullptr, nullptr, nullptr, m, 63, nullptr));
+    Carver c(align256_ptr(d_work));
+    w.off = c.ptr<long long>((size_t)m * 8);
+    w.keys = c.ptr<unsigned long long>((size_t)m * 8);
+    w.keys_out = c.ptr<unsigned long long>((size_t)m * 8);
+    w.idx = c.ptr<long long>((size_t)m * 8);
+    w.aux = c.ptr<long long>((size_t)m * 8);
+    w.tmp_bytes = align256(std::max(std::max(t_scan, t_max), t_sort));
+    w.tmp = c.ptr<void>(w.tmp_bytes);
+    w.total = c.total() + 512;
+    if (who) {
+        AVL_REQUIRE(d_work && work_bytes >= w.total, "%s: work buffer of %zu bytes, %zu needed (avl_merge_rows_work_bytes)", who, work_bytes, w.total);
+    }
+    return AVL_OK;
+}
+
 }  // namespace avl
 
 using namespace avl;
@@ -315,35 +360,11 @@ using namespace avl;
 extern "C" {
 
 int avl_merge_work_bytes(int64_t n, size_t* h_bytes) {
-    AVL_REQUIRE(h_bytes && n >= 0 && n < (1ll << 31), "avl_merge_work_bytes: bad arguments");
-    size_t t1 = 0, t32 = 0;
-    const long long m = n ? n : 1;
-    AVL_HIP_CHECK(sort_u32_i64(nullptr, t1, nullptr, nullptr, nullptr, nullptr, m, 8, nullptr));
-    AVL_HIP_CHECK(sort_u32_i64(nullptr, t32, nullptr, nullptr, nullptr, nullptr, m, 31, nullptr));
-    // [keys u32 | sorted keys u32 | values i64 | rocPRIM's storage (the larger of the narrow and the wide sort)]
-    *h_bytes = 2 * al256((size_t)m * 4) + al256((size_t)m * 8) + al256(std::max(t1, t32)) + 512;
-    return AVL_OK;
-}
-
-struct MergeWork {
-    uint32_t *keys, *keys_out;
-    long long* iota;
-    void* tmp;
-    size_t tmp_bytes;
-};
-
-static int carve_work(int64_t n, void* d_work, size_t work_bytes, MergeWork& w, const char* who) {
-    size_t need = 0;
-    int rc = avl_merge_work_bytes(n, &need);
+    AVL_REQUIRE(h_bytes, "avl_merge_work_bytes: bad arguments");
+    MergeWork w;
+    int rc = carve_work(n, nullptr, 0, w, nullptr);
     if (rc != AVL_OK) return rc;
-    AVL_REQUIRE(d_work && work_bytes >= need, "%s: work buffer of %zu bytes, %zu needed (avl_merge_work_bytes)", who, work_bytes, need);
-    const long long m = n ? n : 1;
-    char* p = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(d_work) + 255) / 256 * 256);
-    w.keys = reinterpret_cast<uint32_t*>(p); p += al256((size_t)m * 4);
-    w.keys_out = reinterpret_cast<uint32_t*>(p); p += al256((size_t)m * 4);
-    w.iota = reinterpret_cast<long long*>(p); p += al256((size_t)m * 8);
-    w.tmp = p;
-    w.tmp_bytes = need - 512 - 2 * al256((size_t)m * 4) - al256((size_t)m * 8);
+    *h_bytes = w.total;
     return AVL_OK;
 }
 
@@ -352,15 +373,17 @@ int avl_merge_partition(int64_t n, const int32_t* d_cell, const int64_t* d_key, 
     AVL_REQUIRE(n >= 0 && n < (1ll << 31) && ws >= 1 && ws <= kMaxRanks, "avl_merge_partition: bad arguments (at most %d ranks)", kMaxRanks);
     AVL_REQUIRE(d_head, "avl_merge_partition: null head");
     hipStream_t st = as_stream(stream);
+    MergeWork w;
+    if (n > 0) {                                                // (every check before the first launch: a refused call writes nothing)
+        AVL_REQUIRE(d_cell && d_key && d_ordd && d_cell_sorted, "avl_merge_partition: null pointer");
+        int rc = carve_work(n, d_work, work_bytes, w, "avl_merge_partition");
+        if (rc != AVL_OK) return rc;
+    }
     hipLaunchKernelGGL(merge_head_init_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<long long*>(d_head), ws, (long long)n);
     if (n == 0) {
         AVL_HIP_CHECK(hipGetLastError());
         return AVL_OK;
     }
-    AVL_REQUIRE(d_cell && d_key && d_ordd && d_cell_sorted, "avl_merge_partition: null pointer");
-    MergeWork w;
-    int rc = carve_work(n, d_work, work_bytes, w, "avl_merge_partition");
-    if (rc != AVL_OK) return rc;
     hipLaunchKernelGGL(merge_partition_kernel, dim3(grid_for(n)), dim3(256), 0, st, (long long)n, d_cell, reinterpret_cast<const long long*>(d_key),
                        ws, w.keys, w.iota, reinterpret_cast<long long*>(d_head));
     int bits = 1;
@@ -379,12 +402,14 @@ int avl_merge_dir_scan(int64_t R, const int32_t* d_recv, const int64_t* d_rc, in
     AVL_REQUIRE(R >= 0 && R < (1ll << 31) && ws >= 1 && ws <= kMaxRanks && cell_bits >= 1 && cell_bits <= 31, "avl_merge_dir_scan: bad arguments");
     AVL_REQUIRE(d_cnt && d_rc, "avl_merge_dir_scan: null pointer");
     hipStream_t st = as_stream(stream);
+    MergeWork w;
+    if (R > 0) {
+        AVL_REQUIRE(d_recv && d_perm && d_first && d_prev_r && d_next_r && d_reply && d_m3r && d_m4r, "avl_merge_dir_scan: null pointer");
+        int rc = carve_work(R, d_work, work_bytes, w, "avl_merge_dir_scan");
+        if (rc != AVL_OK) return rc;
+    }
     AVL_HIP_CHECK(hipMemsetAsync(d_cnt, 0, (size_t)(2 * ws + 1) * sizeof(int64_t), st));
     if (R == 0) return AVL_OK;
-    AVL_REQUIRE(d_recv && d_perm && d_first && d_prev_r && d_next_r && d_reply && d_m3r && d_m4r, "avl_merge_dir_scan: null pointer");
-    MergeWork w;
-    int rc = carve_work(R, d_work, work_bytes, w, "avl_merge_dir_scan");
-    if (rc != AVL_OK) return rc;
     hipLaunchKernelGGL(merge_iota_kernel, dim3(grid_for(R)), dim3(256), 0, st, (long long)R, w.iota);
     size_t tb = w.tmp_bytes;
     // arrivals are grouped by source rank, so the STABLE sort by cell is the (cell, source rank) order
@@ -412,38 +437,11 @@ int avl_merge_classify(int64_t n, const int32_t* d_back, const int64_t* d_ordd, 
 }
 
 int avl_merge_rows_work_bytes(int64_t n, size_t* h_bytes) {
-    AVL_REQUIRE(h_bytes && n >= 0 && n < (1ll << 31), "avl_merge_rows_work_bytes: bad arguments");
-    const long long m = n ? n : 1;
-    size_t t_scan = 0, t_max = 0, t_sort = 0;
-    AVL_HIP_CHECK(scan_flags(nullptr, t_scan, nullptr, nullptr, m, nullptr));
-    AVL_HIP_CHECK(scan_max(nullptr, t_max, nullptr, nullptr, m, nullptr));
-    AVL_HIP_CHECK(sort_u64_i64(nullptr, t_sort, nullptr, nullptr, nullptr, nullptr, m, 63, nullptr));
-    // [offsets | keys | sorted keys | indices | a second offset / row vector | rocPRIM's storage]
-    *h_bytes = 5 * al256((size_t)m * 8) + al256(std::max(std::max(t_scan, t_max), t_sort)) + 512;
-    return AVL_OK;
-}
-
-struct RowsWork {
-    long long *off, *idx, *aux;
-    unsigned long long *keys, *keys_out;
-    void* tmp;
-    size_t tmp_bytes;
-};
-
-static int carve_rows_work(int64_t n, void* d_work, size_t work_bytes, RowsWork& w, const char* who) {
-    size_t need = 0;
-    int rc = avl_merge_rows_work_bytes(n, &need);
+    AVL_REQUIRE(h_bytes, "avl_merge_rows_work_bytes: bad arguments");
+    RowsWork w;
+    int rc = carve_rows_work(n, nullptr, 0, w, nullptr);
     if (rc != AVL_OK) return rc;
-    AVL_REQUIRE(d_work && work_bytes >= need, "%s: work buffer of %zu bytes, %zu needed (avl_merge_rows_work_bytes)", who, work_bytes, need);
-    const size_t b = al256((size_t)(n ? n : 1) * 8);
-    char* p = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(d_work) + 255) / 256 * 256);
-    w.off = reinterpret_cast<long long*>(p); p += b;
-    w.keys = reinterpret_cast<unsigned long long*>(p); p += b;
-    w.keys_out = reinterpret_cast<unsigned long long*>(p); p += b;
-    w.idx = reinterpret_cast<long long*>(p); p += b;
-    w.aux = reinterpret_cast<long long*>(p); p += b;
-    w.tmp = p;
-    w.tmp_bytes = need - 512 - 5 * b;
+    *h_bytes = w.total;
     return AVL_OK;
 }
 

@@ -31,6 +31,7 @@
 #include <rocprim/iterator/transform_iterator.hpp>
 
 #include "avl_common.h"
+#include "avl_wave.h"
 
 // rocPRIM's radix sort falls back to a merge sort below 2^20 items: ~18 block-merge launches of 5 us each for a rank's 290 k voxels, four
 // times per merge.  Onesweep from 4 096 items on (a histogram + one pass per 8 key bits): fewer, fuller launches
@@ -105,7 +106,7 @@ __global__ __launch_bounds__(256) void m2_segments_kernel(long long E, const uin
         headflag[se[i]] = head ? 1 : 0;
         heads += head ? 1u : 0u;
     }
-    for (int off = 32; off > 0; off >>= 1) heads += __shfl_xor(heads, off, 64);
+    heads = wave_sum(heads);
     if ((threadIdx.x & 63) == 0) sh_heads[threadIdx.x >> 6] = heads;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -369,7 +370,6 @@ __global__ __launch_bounds__(256) void m2_fold_feat_kernel(long long n_own, int 
     }
 }
 
-static size_t m2_al(size_t b) { return (b + 255) / 256 * 256; }
 static unsigned m2_grid(long long n) { return (unsigned)std::min<long long>((n + 255) / 256, 4096); }
 static int bit_length(unsigned long long v) {
     int b = 0;
@@ -395,20 +395,48 @@ static int m2_layout(long long E, long long n, int ws, int nchunk, M2Layout& L) 
         AVL_HIP_CHECK(rocprim::exclusive_scan(nullptr, t_scan, it, (int32_t*)nullptr, 0, m, rocprim::plus<int32_t>(), nullptr));
         AVL_HIP_CHECK(rocprim::exclusive_scan(nullptr, t_scan_e, it, (int32_t*)nullptr, 0, e, rocprim::plus<int32_t>(), nullptr));
     }
-    size_t p = 0;
-    auto take = [&](size_t bytes) { const size_t at = p; p += m2_al(bytes); return at; };
-    L.row = take(m * 4); L.prev = take(m * 4); L.next = take(m * 4); L.order = take(m * 4); L.sidx = take(m * 4);
-    L.selA = take(m * 8); L.selB = take(m * 8); L.idx_prev = take(m * 4); L.idx_next = take(m * 4);
-    L.rowcell = take(e * 4);
-    L.res = take((size_t)(2 + (3 + 2 * nchunk) * ws * ws) * 8);
-    L.ecell = take(e * 4); L.eidx = take(e * 4); L.erank = take(e); L.scell = take(e * 4); L.se = take(e * 4); L.hp = take(e * 4);
-    L.pn = take(e * 2); L.headflag = take(e); L.rowscan = take(e * 4);
-    L.krow = take(m * 4); L.vslot = take(m * 4); L.krow_s = take(m * 4); L.single = take(m); L.kp = take(m * 4); L.kn = take(m * 4);
-    L.kps = take(m * 4);
+    Carver c;
+    L.row = c.take(m * 4); L.prev = c.take(m * 4); L.next = c.take(m * 4); L.order = c.take(m * 4); L.sidx = c.take(m * 4);
+    L.selA = c.take(m * 8); L.selB = c.take(m * 8); L.idx_prev = c.take(m * 4); L.idx_next = c.take(m * 4);
+    L.rowcell = c.take(e * 4);
+    L.res = c.take((size_t)(2 + (3 + 2 * nchunk) * ws * ws) * 8);
+    L.ecell = c.take(e * 4); L.eidx = c.take(e * 4); L.erank = c.take(e); L.scell = c.take(e * 4); L.se = c.take(e * 4); L.hp = c.take(e * 4);
+    L.pn = c.take(e * 2); L.headflag = c.take(e); L.rowscan = c.take(e * 4);
+    L.krow = c.take(m * 4); L.vslot = c.take(m * 4); L.krow_s = c.take(m * 4); L.single = c.take(m); L.kp = c.take(m * 4); L.kn = c.take(m * 4);
+    L.kps = c.take(m * 4);
     L.tmp_bytes = std::max(std::max(t_cell, t_scan_e), std::max(std::max(t_row, t_small), t_scan));
-    L.tmp = take(L.tmp_bytes ? L.tmp_bytes : 16);
-    L.total = p + 256;
+    L.tmp = c.take(L.tmp_bytes ? L.tmp_bytes : 16);
+    L.total = c.total() + 256;
     return AVL_OK;
+}
+
+// work buffer of avl_merge2_prepare (any address; 256 bytes of slack): the sort's values 0..n-1, then rocPRIM's storage
+struct M2PrepareWork { int32_t* iota; void* tmp; size_t tmp_bytes, total; };
+static int m2_prepare_work(int64_t n, void* d_work, M2PrepareWork& w) {
+    size_t t = 0;
+    const size_t m = (size_t)(n > 0 ? n : 1);
+    AVL_HIP_CHECK(rocprim::radix_sort_pairs<M2SortCfg>(nullptr, t, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, m, 0, 64,
+                                            nullptr));
+    Carver c(align256_ptr(d_work));
+    w.iota = c.ptr<int32_t>(m * 4);
+    w.tmp_bytes = align256(t ? t : 16);
+    w.tmp = c.ptr<void>(w.tmp_bytes);
+    w.total = c.total() + 256;
+    return AVL_OK;
+}
+
+// work buffer of avl_merge2_fold (256-aligned by the caller): the [n_own][ws] record table, then sum alpha (f64) and the "features
+// still to do" flag of every row
+struct M2FoldWork { int32_t* table; double* wsum; uint8_t* need; size_t total; };
+static M2FoldWork m2_fold_work(int64_t n_own, int ws, void* d_work) {
+    const size_t m = (size_t)(n_own > 0 ? n_own : 1);
+    Carver c(d_work);
+    M2FoldWork w;
+    w.table = c.ptr<int32_t>(m * ws * sizeof(int32_t));
+    w.wsum = c.ptr<double>(m * 8);
+    w.need = c.ptr<uint8_t>(m);
+    w.total = c.total() + 256;
+    return w;
 }
 
 }  // namespace avl
@@ -430,11 +458,10 @@ int avl_merge2_load(void) {
 
 int avl_merge2_prepare_work_bytes(int64_t n, size_t* h_bytes) {
     AVL_REQUIRE(h_bytes && n >= 0 && n < (1ll << 31), "avl_merge2_prepare_work_bytes: bad arguments");
-    size_t t = 0;
-    const size_t m = (size_t)(n > 0 ? n : 1);
-    AVL_HIP_CHECK(rocprim::radix_sort_pairs<M2SortCfg>(nullptr, t, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, m, 0, 64,
-                                            nullptr));
-    *h_bytes = m2_al(m * 4) + m2_al(t ? t : 16) + 256;
+    M2PrepareWork w;
+    int rc = m2_prepare_work(n, nullptr, w);
+    if (rc != AVL_OK) return rc;
+    *h_bytes = w.total;
     return AVL_OK;
 }
 
@@ -444,17 +471,14 @@ int avl_merge2_prepare(int64_t n, const int64_t* d_key, const int32_t* d_cell, i
     hipStream_t st = as_stream(stream);
     if (n > 0) {
         AVL_REQUIRE(d_key && d_cell && d_key_sorted && d_cell_sorted && d_perm, "avl_merge2_prepare: null pointer");
-        size_t need = 0;
-        int rc = avl_merge2_prepare_work_bytes(n, &need);
+        M2PrepareWork w;
+        int rc = m2_prepare_work(n, d_work, w);
         if (rc != AVL_OK) return rc;
-        AVL_REQUIRE(d_work && work_bytes >= need, "avl_merge2_prepare: work buffer of %zu bytes, %zu needed", work_bytes, need);
-        char* base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(d_work) + 255) / 256 * 256);
-        int32_t* iota = reinterpret_cast<int32_t*>(base);
-        void* tmp = base + m2_al((size_t)n * 4);
-        size_t tb = need - 256 - m2_al((size_t)n * 4);
-        hipLaunchKernelGGL(m2_iota_kernel, dim3(m2_grid(n)), dim3(256), 0, st, (long long)n, iota);
-        AVL_HIP_CHECK(rocprim::radix_sort_pairs<M2SortCfg>(tmp, tb, reinterpret_cast<const unsigned long long*>(d_key), reinterpret_cast<unsigned long long*>(d_key_sorted),
-                                                iota, d_perm, (size_t)n, 0, key_bits, st));
+        AVL_REQUIRE(d_work && work_bytes >= w.total, "avl_merge2_prepare: work buffer of %zu bytes, %zu needed", work_bytes, w.total);
+        size_t tb = w.tmp_bytes;
+        hipLaunchKernelGGL(m2_iota_kernel, dim3(m2_grid(n)), dim3(256), 0, st, (long long)n, w.iota);
+        AVL_HIP_CHECK(rocprim::radix_sort_pairs<M2SortCfg>(w.tmp, tb, reinterpret_cast<const unsigned long long*>(d_key), reinterpret_cast<unsigned long long*>(d_key_sorted),
+                                                w.iota, d_perm, (size_t)n, 0, key_bits, st));
     }
     hipLaunchKernelGGL(m2_presorted_kernel, dim3(n > 0 ? m2_grid(n) : 1), dim3(256), 0, st, (long long)n, d_cell, d_perm,
                        reinterpret_cast<const long long*>(d_key_sorted), (long long)flags, d_cell_sorted, reinterpret_cast<long long*>(d_hdr));
@@ -464,8 +488,7 @@ int avl_merge2_prepare(int64_t n, const int64_t* d_key, const int32_t* d_cell, i
 
 int avl_merge2_fold_work_bytes(int64_t n_own, int ws, size_t* h_bytes) {
     AVL_REQUIRE(h_bytes && n_own >= 0 && ws >= 1 && ws <= kM2MaxRanks, "avl_merge2_fold_work_bytes: bad arguments");
-    const size_t m = (size_t)(n_own > 0 ? n_own : 1);
-    *h_bytes = m2_al(m * ws * sizeof(int32_t)) + m2_al(m * 8) + m2_al(m) + 256;
+    *h_bytes = m2_fold_work(n_own, ws, nullptr).total;
     return AVL_OK;
 }
 
@@ -510,7 +533,7 @@ int avl_merge2_plan(int ws, int rank, const int64_t* h_n_all, int64_t nmax, cons
     int rc = m2_layout(E, n, ws, nchunk, L);
     if (rc != AVL_OK) return rc;
     AVL_REQUIRE(d_work && work_bytes >= L.total, "avl_merge2_plan: work buffer of %zu bytes, %zu needed (avl_merge2_work_bytes)", work_bytes, L.total);
-    char* base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(d_work) + 255) / 256 * 256);
+    char* base = static_cast<char*>(align256_ptr(d_work));
     const int64_t shift = base - reinterpret_cast<char*>(d_work);
     const size_t offs[11] = {L.row, L.prev, L.next, L.order, L.sidx, L.selA, L.selB, L.idx_prev, L.idx_next, L.rowcell, L.res};
     for (int k = 0; k < 11; ++k) h_off[k] = (int64_t)offs[k] + shift;
@@ -611,11 +634,10 @@ int avl_merge2_fold(int64_t n_own, int64_t r0, int ws, int D, int gs, int vh, co
     if (n_own == 0) return AVL_OK;
     AVL_REQUIRE(h_side && h_done && h_part && h_count && d_rowcell && d_grid_feat && d_grid_pos && d_weight && d_grid_rgb && d_work,
                 "avl_merge2_fold: null pointer");
-    size_t need_bytes = 0;
-    (void)avl_merge2_fold_work_bytes(n_own, ws, &need_bytes);
-    AVL_REQUIRE(work_bytes >= need_bytes && (reinterpret_cast<uintptr_t>(d_work) & 255) == 0, "avl_merge2_fold: %zu bytes of 256-aligned work needed (avl_merge2_fold_work_bytes)",
-                need_bytes);
-    int32_t* d_table = reinterpret_cast<int32_t*>(d_work);
+    const M2FoldWork w = m2_fold_work(n_own, ws, d_work);
+    AVL_REQUIRE(work_bytes >= w.total && (reinterpret_cast<uintptr_t>(d_work) & 255) == 0, "avl_merge2_fold: %zu bytes of 256-aligned work needed (avl_merge2_fold_work_bytes)",
+                w.total);
+    int32_t* d_table = w.table;
     M2Peers pe{};
     long long R = 0;
     for (int p = 0; p < ws; ++p) {
@@ -631,16 +653,12 @@ int avl_merge2_fold(int64_t n_own, int64_t r0, int ws, int D, int gs, int vh, co
     if (R > 0)
         hipLaunchKernelGGL(m2_fold_index_kernel, dim3(m2_grid(R)), dim3(256), 0, st, R, ws, pe, (long long)n_own, d_table, reinterpret_cast<int*>(d_err_flag));
     const long long ldf = (D + 1) / 2 * 2;      // float32 rows are padded to whole 8-byte words
-    // scratch behind the table: sum alpha (f64) and the "features still to do" flag of every row
-    char* sb = reinterpret_cast<char*>(d_table) + m2_al((size_t)n_own * ws * sizeof(int32_t));
-    double* wsum = reinterpret_cast<double*>(sb);
-    uint8_t* need = reinterpret_cast<uint8_t*>(sb + m2_al((size_t)n_own * 8));
     hipLaunchKernelGGL(m2_fold_scalar_kernel, dim3(m2_grid(n_own)), dim3(256), 0, st, (long long)n_own, (long long)r0, ws, gs, vh, pe, d_table, d_rowcell,
-                       have_log, d_grid_pos, d_weight, d_grid_rgb, d_cell, wsum, need, reinterpret_cast<int*>(d_err_flag));
+                       have_log, d_grid_pos, d_weight, d_grid_rgb, d_cell, w.wsum, w.need, reinterpret_cast<int*>(d_err_flag));
     int64_t blocks = ((n_own + 15) / 16 + 3) / 4;
     const int64_t maxb = (int64_t)num_cus() * 32;
     if (blocks > maxb) blocks = maxb;
-    hipLaunchKernelGGL(m2_fold_feat_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (long long)n_own, ws, D, ldf, (long long)D, pe, d_table, wsum, need,
+    hipLaunchKernelGGL(m2_fold_feat_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (long long)n_own, ws, D, ldf, (long long)D, pe, d_table, w.wsum, w.need,
                        d_grid_feat);
     AVL_HIP_CHECK(hipGetLastError());
     return AVL_OK;

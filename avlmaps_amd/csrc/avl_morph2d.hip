@@ -227,8 +227,6 @@ __global__ __launch_bounds__(256) void fill_from_flag_kernel(const int* __restri
 
 static dim3 grid2d(int H, int W) { return dim3((unsigned)((W + 63) / 64), (unsigned)((H + 3) / 4)); }
 
-static size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 // one morphology op on an (H, W) image with row stride ld; d_tmp (H * W bytes) is used above the stencil radius only
 static int launch_morph(const uint8_t* in, int64_t ld, int H, int W, int erode, int box, int k, uint8_t* out, uint8_t* tmp, hipStream_t st) {
     if (k <= kStencilMax) {
@@ -263,6 +261,35 @@ static void gaussian_weights(double sigma, int radius, double* w) {
 }
 
 constexpr int kMaxSide = 32768;
+
+// workspace of avl_dilate_map for an (H, W) map: a flag word, then three images at twice the resolution
+static bool dilate_shape_ok(int H, int W) { return H > 0 && W > 0 && H <= kMaxSide / 2 && W <= kMaxSide / 2; }
+struct DilateWork { int* any; double* tmp; uint8_t *thr, *dist; size_t total; };
+static DilateWork dilate_work(int H, int W, void* ws) {
+    const size_t up = (size_t)4 * H * W;
+    Carver c(ws);
+    DilateWork w;
+    w.any = c.ptr<int>(sizeof(int));
+    w.tmp = c.ptr<double>(up * sizeof(double));
+    w.thr = c.ptr<uint8_t>(up);
+    w.dist = c.ptr<uint8_t>(up);
+    w.total = c.total();
+    return w;
+}
+
+// workspace of avl_mask_foreground for an (H, W) crop
+static bool foreground_shape_ok(int H, int W) { return H > 0 && W > 0 && H <= kMaxSide && W <= kMaxSide; }
+struct ForegroundWork { double* tmp; uint8_t *a, *b; size_t total; };
+static ForegroundWork foreground_work(int H, int W, void* ws) {
+    const size_t cells = (size_t)H * W;
+    Carver c(ws);
+    ForegroundWork w;
+    w.tmp = c.ptr<double>(cells * sizeof(double));
+    w.a = c.ptr<uint8_t>(cells);
+    w.b = c.ptr<uint8_t>(cells);
+    w.total = c.total();
+    return w;
+}
 
 }  // namespace avl
 
@@ -343,17 +370,15 @@ int avl_resize2x_down_f64(const void* d_in, int in_is_u8, int H, int W, double* 
 
 int avl_dilate_map_work_bytes(int H, int W, size_t* bytes) {
     AVL_REQUIRE(bytes, "avl_dilate_map_work_bytes: null output");
-    AVL_REQUIRE(H > 0 && W > 0 && H <= kMaxSide / 2 && W <= kMaxSide / 2, "avl_dilate_map_work_bytes: bad shape %d x %d", H, W);
-    const size_t up = (size_t)4 * H * W;
-    *bytes = 256 + align256(up * sizeof(double)) + 2 * align256(up);
+    AVL_REQUIRE(dilate_shape_ok(H, W), "avl_dilate_map_work_bytes: bad shape %d x %d", H, W);
+    *bytes = dilate_work(H, W, nullptr).total;
     return AVL_OK;
 }
 
 int avl_dilate_map(const uint8_t* d_binary_u8, int H, int W, int dilate_iter, double sigma, double* d_out_f64, uint8_t* d_out_zero_u8,
                    void* ws, size_t ws_bytes, void* stream) {
-    size_t need = 0;
-    int rc = avl_dilate_map_work_bytes(H, W, &need);
-    if (rc != AVL_OK) return rc;
+    AVL_REQUIRE(dilate_shape_ok(H, W), "avl_dilate_map: bad shape %d x %d", H, W);
+    const auto [any, tmp, thr, dist, need] = dilate_work(H, W, ws);
     AVL_REQUIRE(d_binary_u8 && (d_out_f64 || d_out_zero_u8), "avl_dilate_map: null input or no output requested");
     AVL_REQUIRE(ws && ws_bytes >= need, "avl_dilate_map: workspace of %zu bytes, need %zu", ws_bytes, need);
     AVL_REQUIRE(dilate_iter >= 0 && 2 * dilate_iter <= kMorphMaxRadius, "avl_dilate_map: dilate_iter %d outside [0, %d]", dilate_iter,
@@ -366,12 +391,6 @@ int avl_dilate_map(const uint8_t* d_binary_u8, int H, int W, int dilate_iter, do
     gaussian_weights(sigma, radius, gw.w);
     hipStream_t st = as_stream(stream);
     const int H2 = 2 * H, W2 = 2 * W;
-    const size_t up = (size_t)H2 * W2;
-    char* base = (char*)ws;
-    int* any = (int*)base;
-    double* tmp = (double*)(base + 256);
-    uint8_t* thr = (uint8_t*)(base + 256 + align256(up * sizeof(double)));
-    uint8_t* dist = thr + align256(up);
     if (dilate_iter == 0) AVL_HIP_CHECK(hipMemsetAsync(any, 0, sizeof(int), st));
     hipLaunchKernelGGL(gauss_axis0_kernel<SrcUp2>, grid2d(H2, W2), dim3(256), 0, st, SrcUp2{d_binary_u8, H, W}, H2, W2, gw, radius, tmp);
     hipLaunchKernelGGL(gauss_axis1_kernel<double>, grid2d(H2, W2), dim3(256), 0, st, (const double*)tmp, H2, W2, gw, radius, (double*)nullptr, thr, 0.5,
@@ -392,9 +411,8 @@ int avl_dilate_map(const uint8_t* d_binary_u8, int H, int W, int dilate_iter, do
 
 int avl_mask_foreground_work_bytes(int H, int W, size_t* bytes) {
     AVL_REQUIRE(bytes, "avl_mask_foreground_work_bytes: null output");
-    AVL_REQUIRE(H > 0 && W > 0 && H <= kMaxSide && W <= kMaxSide, "avl_mask_foreground_work_bytes: bad shape %d x %d", H, W);
-    const size_t cells = (size_t)H * W;
-    *bytes = align256(cells * sizeof(double)) + 2 * align256(cells);
+    AVL_REQUIRE(foreground_shape_ok(H, W), "avl_mask_foreground_work_bytes: bad shape %d x %d", H, W);
+    *bytes = foreground_work(H, W, nullptr).total;
     return AVL_OK;
 }
 
@@ -403,21 +421,16 @@ int avl_mask_foreground(const uint8_t* d_mask2d_u8, int64_t ld, int r0, int r1, 
     AVL_REQUIRE(d_mask2d_u8 && d_out_u8 && r0 >= 0 && c0 >= 0 && r1 > r0 && c1 > c0 && (int64_t)c1 <= ld,
                 "avl_mask_foreground: bad crop [%d:%d, %d:%d] of rows of %lld cells", r0, r1, c0, c1, (long long)ld);
     const int H = r1 - r0, W = c1 - c0;
-    size_t need = 0;
-    int rc = avl_mask_foreground_work_bytes(H, W, &need);
-    if (rc != AVL_OK) return rc;
+    AVL_REQUIRE(foreground_shape_ok(H, W), "avl_mask_foreground: bad shape %d x %d", H, W);
+    const auto [tmp, a, b, need] = foreground_work(H, W, ws);
     AVL_REQUIRE(ws && ws_bytes >= need, "avl_mask_foreground: workspace of %zu bytes, need %zu", ws_bytes, need);
     hipStream_t st = as_stream(stream);
-    const size_t cells = (size_t)H * W;
-    double* tmp = (double*)ws;
-    uint8_t* a = (uint8_t*)ws + align256(cells * sizeof(double));
-    uint8_t* b = a + align256(cells);
     const int radius = 2;                       // int(3 * 0.8 + 0.5)
     GaussW gw;
     for (int i = 0; i < 2 * kGaussMaxRadius + 1; ++i) gw.w[i] = 0.0;
     gaussian_weights(0.8, radius, gw.w);
     // binary_closing(iterations=3): dilation, then erosion, both with the crop's own border
-    rc = launch_morph(d_mask2d_u8 + (int64_t)r0 * ld + c0, ld, H, W, 0, 0, 3, a, nullptr, st);
+    int rc = launch_morph(d_mask2d_u8 + (int64_t)r0 * ld + c0, ld, H, W, 0, 0, 3, a, nullptr, st);
     if (rc != AVL_OK) return rc;
     rc = launch_morph(a, W, H, W, 1, 0, 3, b, nullptr, st);
     if (rc != AVL_OK) return rc;

@@ -28,6 +28,7 @@
 #include <new>
 
 #include "avl_common.h"
+#include "avl_wave.h"
 
 namespace avl {
 
@@ -265,21 +266,13 @@ __global__ __launch_bounds__(kNavScanThreads) void nav_vertex_write_kernel(const
     __shared__ int s_w[kNavScanThreads / kWave];
     const int64_t n = (int64_t)H * W;
     const int64_t base = (int64_t)blockIdx.x * kNavScanThreads * kNavScanRounds;
-    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
     int64_t run = offsets[blockIdx.x];
     for (int k = 0; k < kNavScanRounds; ++k) {
         const int64_t t = base + (int64_t)k * kNavScanThreads + threadIdx.x;
         bool v = false;
         if (t < n) v = is_vertex(pix[(size_t)(t / W + 1) * (W + 2) + (size_t)(t % W + 1)]);
-        const unsigned long long bal = __ballot(v);
-        if (lane == 0) s_w[w] = __popcll(bal);
-        __syncthreads();
-        int before = 0, total = 0;
-        for (int q = 0; q < kNavScanThreads / kWave; ++q) {
-            before += q < w ? s_w[q] : 0;
-            total += s_w[q];
-        }
-        const int64_t idx = run + before + __popcll(bal & ((1ull << lane) - 1ull));
+        int total;
+        const int64_t idx = run + block_compact_rank<kNavScanThreads / kWave>(v, s_w, &total);
         if (v && idx < V) {
             verts[2 * idx] = (int32_t)(t / W);
             verts[2 * idx + 1] = (int32_t)(t % W);
@@ -509,11 +502,6 @@ __device__ __forceinline__ int64_t scan_node(const NavNodes& G, const double* __
         }
     }
     return -1;
-}
-
-__device__ __forceinline__ double wave_min(double v) {
-    for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off, kWave));
-    return v;
 }
 
 __global__ __launch_bounds__(256) void nav_init_kernel(int64_t N, int64_t src, double* __restrict__ d0, double* __restrict__ d1) {

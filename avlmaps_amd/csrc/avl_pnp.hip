@@ -18,6 +18,7 @@
 // correspondences lane, lane + 64, ... of a stage and the 64 integer counts are summed across the wave.  Integer sums only: the
 // counts do not depend on the order.  The winner is picked by a second, single-block kernel on the key (count, -h).
 #include "avl_common.h"
+#include "avl_wave.h"
 #include "avl_pnp_math.h"
 
 namespace avl {
@@ -50,11 +51,6 @@ __device__ __forceinline__ void load_stage(Stage& s, const double* __restrict__ 
     }
 }
 
-__device__ __forceinline__ int wave_sum_i32(int v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-    return v;
-}
-
 // Counts the inliers of `np` (<= NP) poses held by this wave over all M correspondences; every wave of the block must call it
 // (the stages are loaded by the whole block).  active = false: the wave only helps loading.  mask0: inlier mask of pose 0 or null.
 template <int NP>
@@ -80,7 +76,7 @@ __device__ __forceinline__ void count_staged(Stage& st, const double* __restrict
             }
         }
     }
-    for (int s = 0; s < NP; ++s) cnt[s] = wave_sum_i32(cnt[s]);
+    for (int s = 0; s < NP; ++s) cnt[s] = wave_sum(cnt[s]);
 }
 
 // ---- lift -----------------------------------------------------------------------------------------------------------------
@@ -90,7 +86,6 @@ __global__ __launch_bounds__(kBlock) void loc_lift_kernel(const void* __restrict
                                                           const double* __restrict__ kp_ref, const double* __restrict__ kp_query, int64_t M,
                                                           double* __restrict__ out_pts, double* __restrict__ out_pix, int* __restrict__ counter) {
     __shared__ int wcount[kWavesPerBlock];
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
     int64_t run = 0;
     for (int64_t base = 0; base < M; base += kBlock) {
         const int64_t i = base + threadIdx.x;
@@ -115,16 +110,9 @@ __global__ __launch_bounds__(kBlock) void loc_lift_kernel(const void* __restrict
                 }
             }
         }
-        const unsigned long long b = __ballot(keep);
-        if (lane == 0) wcount[wave] = __popcll(b);
-        __syncthreads();
-        int before = 0, total = 0;
-        for (int w = 0; w < kWavesPerBlock; ++w) {
-            before += w < wave ? wcount[w] : 0;
-            total += wcount[w];
-        }
+        int total;
+        const int64_t o = run + block_compact_rank<kWavesPerBlock>(keep, wcount, &total);
         if (keep) {
-            const int64_t o = run + before + __popcll(b & ((1ull << lane) - 1ull));
             out_pts[3 * o] = px;
             out_pts[3 * o + 1] = py;
             out_pts[3 * o + 2] = pz;
@@ -132,7 +120,7 @@ __global__ __launch_bounds__(kBlock) void loc_lift_kernel(const void* __restrict
             out_pix[2 * o + 1] = kp_query[2 * i + 1];
         }
         run += total;
-        __syncthreads();
+        __syncthreads();                                 // wcount is rewritten by the next chunk
     }
     if (threadIdx.x == 0) counter[0] = (int)run;
 }
@@ -220,11 +208,6 @@ __global__ __launch_bounds__(kBlock) void pnp_score_kernel(const double* __restr
 // Levenberg-Marquardt in ONE launch of one block.  Every pass over the correspondences gives thread t the terms of t, t + 256, ...
 // in that order; the 28 sums are then added across each wave by a fixed xor butterfly and across the four waves in wave order by
 // thread 0, which also solves the 6 x 6 system and decides.  Nothing depends on scheduling.
-__device__ __forceinline__ double wave_sum_f64(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-    return v;
-}
-
 struct RefineShared {
     double wave_acc[kWavesPerBlock][kNormal];
     int wave_bad[kWavesPerBlock];
@@ -244,8 +227,8 @@ __device__ __forceinline__ void refine_pass(RefineShared& sh, const double* pose
         if (!used[i]) continue;
         if (!normal_terms(P, cam, pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], pix[2 * i], pix[2 * i + 1], acc)) bad = 1;
     }
-    for (int k = 0; k < kNormal; ++k) acc[k] = wave_sum_f64(acc[k]);
-    bad = wave_sum_i32(bad);
+    for (int k = 0; k < kNormal; ++k) acc[k] = wave_sum(acc[k]);
+    bad = wave_sum(bad);
     if (lane == 0) {
         for (int k = 0; k < kNormal; ++k) sh.wave_acc[wave][k] = acc[k];
         sh.wave_bad[wave] = bad;

@@ -9,6 +9,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "avl_builder_state.h"
+#include "avl_wave.h"
 
 namespace avl {
 
@@ -151,7 +152,7 @@ __global__ __launch_bounds__(256) void log_count_kernel(const uint32_t* __restri
     const long long lo = (long long)blockIdx.x * chunk, hi = lo + chunk < L ? lo + chunk : L;
     int c = 0;
     for (long long i = lo + threadIdx.x; i < hi; i += 256) c += slot[i] != 0xFFFFFFFFu;
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
+    c = wave_sum(c);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
@@ -181,27 +182,19 @@ __global__ __launch_bounds__(256) void log_compact_kernel(const uint32_t* __rest
                                                           uint32_t* __restrict__ active_slot) {
     __shared__ int wsum[4];
     const long long lo = (long long)blockIdx.x * chunk, hi = lo + chunk < L ? lo + chunk : L;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     long long base = offsets[blockIdx.x];
     for (long long i0 = lo; i0 < hi; i0 += 256) {                 // (chunk is a multiple of 256: a uniform trip count per workgroup)
         const long long i = i0 + threadIdx.x;
         const uint32_t sl = i < hi ? slot[i] : 0xFFFFFFFFu;
         const bool keep = sl != 0xFFFFFFFFu;
-        const unsigned long long m = __ballot(keep);
-        const int rank = __popcll(m & ((1ull << lane) - 1ull));
-        if (lane == 0) wsum[wave] = __popcll(m);
-        __syncthreads();
-        int before = 0, all = 0;
-        for (int w = 0; w < 4; ++w) {
-            before += w < wave ? wsum[w] : 0;
-            all += wsum[w];
-        }
+        int all;
+        const int rank = block_compact_rank<4>(keep, wsum, &all);
         if (keep) {
-            active[base + before + rank] = (int32_t)i;
-            active_slot[base + before + rank] = sl;
+            active[base + rank] = (int32_t)i;
+            active_slot[base + rank] = sl;
         }
         base += all;
-        __syncthreads();
+        __syncthreads();                                          // wsum is rewritten by the next round
     }
 }
 
@@ -217,13 +210,12 @@ struct LogSegments {
     void* tmp = nullptr;
     char *block1 = nullptr, *block2 = nullptr;   // TWO pool allocations hold all of the above (a hipMallocAsync / hipFreeAsync pair costs
                                                  // ~90 us of host time: nine of them were most of a small rank's replay)
-    static size_t al(size_t bytes) { return (bytes + 255) / 256 * 256; }
     int build(avl_builder* b, int64_t n, hipStream_t st) {
         const long long L = b->log_used;
         const long long chunk = ((L + kLogParts - 1) / kLogParts + 255) / 256 * 256;
         size_t tmp_bytes = 0;
-        const size_t b_active = al((size_t)L * sizeof(int32_t)), b_seg = al((size_t)n * sizeof(long long));
-        const size_t b_counts = al(kLogParts * sizeof(int)), b_off = al(kLogParts * sizeof(long long));
+        const size_t b_active = align256((size_t)L * sizeof(int32_t)), b_seg = align256((size_t)n * sizeof(long long));
+        const size_t b_counts = align256(kLogParts * sizeof(int)), b_off = align256(kLogParts * sizeof(long long));
         // the two L-sized arrays (and, below, the two La-sized ones + the sort's storage) come from the scratch allocated with the log
         // when it is there and large enough; the small per-voxel arrays always from the pool
         const bool own = b->rs_mem && b->rs_bytes >= 4 * b_active + b->rs_tmp_bytes + 256;
@@ -255,14 +247,14 @@ struct LogSegments {
         if (La > 0)
             AVL_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr,
                                                     (size_t)La, 0, bits, st));
-        const size_t b_ls = al(Ls * sizeof(uint32_t));
+        const size_t b_ls = align256(Ls * sizeof(uint32_t));
         if (own && tmp_bytes <= b->rs_tmp_bytes) {
             char* p2 = b->rs_mem + 2 * b_active;
             sorted_slot = reinterpret_cast<uint32_t*>(p2);
             order = reinterpret_cast<int32_t*>(p2 + b_ls);
             tmp = p2 + 2 * b_active;                   // (behind the four L-sized words: La <= L)
         } else {
-            AVL_HIP_CHECK(hipMallocAsync((void**)&block2, 2 * b_ls + al(tmp_bytes ? tmp_bytes : 16), st));
+            AVL_HIP_CHECK(hipMallocAsync((void**)&block2, 2 * b_ls + align256(tmp_bytes ? tmp_bytes : 16), st));
             sorted_slot = reinterpret_cast<uint32_t*>(block2);
             order = reinterpret_cast<int32_t*>(block2 + b_ls);
             tmp = block2 + 2 * b_ls;

@@ -139,19 +139,32 @@ static hipError_t argsort_bits_impl(void* tmp, size_t& tmp_bytes, const void* ke
                                      (size_t)n, 0, bits, st);
 }
 
-static size_t argsort_align(size_t b) { return (b + 255) / 256 * 256; }
+// work buffer of avl_argsort_bits: [values 0..n-1 | sorted keys | rocPRIM's own storage (its size depends on the bit range: rocPRIM
+// picks the passes by it)] from the first 256-aligned address on; the total carries 256 bytes of slack for that
+struct ArgsortWork { int64_t* iota; void *keys_out, *tmp; size_t tmp_bytes, total; };
+static int argsort_layout(int64_t n, int key_bytes, int bits, void* d_work, ArgsortWork& w) {
+    size_t t = 0;
+    const hipError_t e = key_bytes == 8 ? argsort_bits_impl<uint64_t>(nullptr, t, nullptr, nullptr, nullptr, nullptr, n ? n : 1, bits, nullptr)
+                                        : argsort_bits_impl<uint32_t>(nullptr, t, nullptr, nullptr, nullptr, nullptr, n ? n : 1, bits, nullptr);
+    AVL_HIP_CHECK(e);
+    Carver c(align256_ptr(d_work));
+    w.iota = c.ptr<int64_t>((size_t)n * 8);
+    w.keys_out = c.ptr<void>((size_t)n * key_bytes);
+    w.tmp_bytes = align256(t);
+    w.tmp = c.ptr<void>(w.tmp_bytes);
+    w.total = c.total() + 256;
+    return AVL_OK;
+}
 
 extern "C" {
 
 int avl_argsort_bits_work_bytes(int64_t n, int key_bytes, int bits, size_t* h_bytes) {
     AVL_REQUIRE(h_bytes && n >= 0 && n < (1ll << 31) && (key_bytes == 4 || key_bytes == 8) && bits >= 1 && bits <= 8 * key_bytes - 1,
                 "avl_argsort_bits_work_bytes: bad arguments");
-    size_t tmp_bytes = 0;
-    const hipError_t e = key_bytes == 8 ? argsort_bits_impl<uint64_t>(nullptr, tmp_bytes, nullptr, nullptr, nullptr, nullptr, n ? n : 1, bits, nullptr)
-                                        : argsort_bits_impl<uint32_t>(nullptr, tmp_bytes, nullptr, nullptr, nullptr, nullptr, n ? n : 1, bits, nullptr);
-    AVL_HIP_CHECK(e);
-    // [values 0..n-1 | sorted keys | rocPRIM's own storage (its size depends on the bit range: rocPRIM picks the passes by it)]
-    *h_bytes = argsort_align((size_t)n * 8) + argsort_align((size_t)n * key_bytes) + argsort_align(tmp_bytes) + 256;
+    ArgsortWork w;
+    int rc = argsort_layout(n, key_bytes, bits, nullptr, w);
+    if (rc != AVL_OK) return rc;
+    *h_bytes = w.total;
     return AVL_OK;
 }
 
@@ -162,19 +175,15 @@ int avl_argsort_bits(int64_t n, const void* d_keys, int key_bytes, int bits, int
     AVL_REQUIRE(bits >= 1 && bits <= 8 * key_bytes - 1, "avl_argsort_bits: bits must be in [1, %d]", 8 * key_bytes - 1);
     if (n == 0) return AVL_OK;
     AVL_REQUIRE(d_keys && d_perm && d_work, "avl_argsort_bits: null pointer");
-    size_t need = 0;
-    int rc = avl_argsort_bits_work_bytes(n, key_bytes, bits, &need);
+    ArgsortWork w;
+    int rc = argsort_layout(n, key_bytes, bits, d_work, w);
     if (rc != AVL_OK) return rc;
-    AVL_REQUIRE(work_bytes >= need, "avl_argsort_bits: work buffer of %zu bytes, %zu needed (avl_argsort_bits_work_bytes)", work_bytes, need);
+    AVL_REQUIRE(work_bytes >= w.total, "avl_argsort_bits: work buffer of %zu bytes, %zu needed (avl_argsort_bits_work_bytes)", work_bytes, w.total);
     hipStream_t st = as_stream(stream);
-    char* w = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(d_work) + 255) / 256 * 256);
-    int64_t* iota = reinterpret_cast<int64_t*>(w);
-    void* keys_out = w + argsort_align((size_t)n * 8);
-    void* tmp = reinterpret_cast<char*>(keys_out) + argsort_align((size_t)n * key_bytes);
-    size_t tmp_bytes = need - 256 - argsort_align((size_t)n * 8) - argsort_align((size_t)n * key_bytes);
-    hipLaunchKernelGGL(iota64_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, st, iota, n);
-    const hipError_t e = key_bytes == 8 ? argsort_bits_impl<uint64_t>(tmp, tmp_bytes, d_keys, keys_out, iota, d_perm, n, bits, st)
-                                        : argsort_bits_impl<uint32_t>(tmp, tmp_bytes, d_keys, keys_out, iota, d_perm, n, bits, st);
+    hipLaunchKernelGGL(iota64_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, st, w.iota, n);
+    size_t tmp_bytes = w.tmp_bytes;
+    const hipError_t e = key_bytes == 8 ? argsort_bits_impl<uint64_t>(w.tmp, tmp_bytes, d_keys, w.keys_out, w.iota, d_perm, n, bits, st)
+                                        : argsort_bits_impl<uint32_t>(w.tmp, tmp_bytes, d_keys, w.keys_out, w.iota, d_perm, n, bits, st);
     if (e != hipSuccess) {
         set_error("avl_argsort_bits: %s", hipGetErrorString(e));
         return AVL_ERR_HIP;

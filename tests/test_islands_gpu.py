@@ -177,6 +177,13 @@ def test_labels_of_the_largest_crop(ops):
     check_labels(ops, mask, "1000 x 1000")
 
 
+def test_labels_over_two_rounds_of_the_offsets_scan(ops):
+    """1025 x 1024 pixels are 1025 scan blocks of 1024 pixels, one more than the offsets workgroup has threads: its loop (and the
+    barrier between its rounds) runs twice"""
+    mask = (np.random.default_rng(1025).random((1025, 1024)) < 0.05).astype(np.uint8)
+    check_labels(ops, mask, "1025 x 1024")
+
+
 def test_bool_device_and_two_runs_give_identical_bytes(ops):
     from avlmaps_amd.device import DeviceArray
     mask = random_masks(0.45)[0]

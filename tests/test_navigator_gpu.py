@@ -629,6 +629,16 @@ def test_dense_clutter_matches_the_oracle(seed):
     g.close()
 
 
+def test_vertices_over_two_compaction_blocks():
+    """33 x 37 = 1221 pixels: a second block of the vertex compaction (1024 pixels each) whose only round ends inside a wave"""
+    free = _random_map(11, H=33, W=37, blocks=6, walls=8, noise=0.1)
+    g = _graph(free)
+    verts = oracle_vertices(free)
+    assert len(verts) > 64 and (verts[:, 0] * 37 + verts[:, 1] >= 1024).any()
+    assert np.array_equal(g.vertices(), verts)
+    g.close()
+
+
 def test_plans_reuse_the_graph():
     free = _random_map(7)
     rng = np.random.default_rng(7)
