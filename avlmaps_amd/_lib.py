@@ -203,6 +203,12 @@ _SIGS = {
     "avl_pool_labels_2d": (C.c_int, [_vp, _i64, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
     "avl_label_confusion": (C.c_int, [_vp, _vp, _i64, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "avl_label_confusion_limits": (C.c_int, [C.POINTER(C.c_int)]),
+    "avl_resize_work_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_sz)]),
+    "avl_resize_u8": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int,
+                                C.c_int, C.c_int, C.c_int, _vp, _vp, _sz, _vp]),
+    "avl_clip_preprocess": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int,
+                                      C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _sz, _vp]),
+    "avl_resize_limits": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

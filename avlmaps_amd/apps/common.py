@@ -165,6 +165,29 @@ class HashImageEncoder:
         return (f / np.linalg.norm(f)).astype(np.float32)
 
 
+class HashBatchImageEncoder:
+    """Stand-in for CLIP ViT-L/14's image tower on PREPROCESSED batches (AreaMap.create_map(batch_encoder=...), demo / smoke runs):
+    the 4 x 4 grid of means of each of the 3 planes of a (B, 3, n_px, n_px) tensor (48 numbers, plane-major), through a fixed seeded
+    projection to D = 768 channels, L2-normalised.  Means, projection and norm are float64 on the device the batch lives on (a
+    torch tensor stays where it is; an array is taken on the host), so that the float32 rows it returns, a host array (B, D), do not
+    depend on the device beyond their last bit."""
+
+    def __init__(self, D=768, seed=0, n_px=224):
+        self.D, self.n_px = D, n_px
+        self.proj = np.random.default_rng(seed).standard_normal((48, D))
+
+    def __call__(self, batch):
+        import torch
+        t = batch if isinstance(batch, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(batch.numpy() if hasattr(batch, "ptr") else batch))
+        t = t.double()
+        B, _, h, w = t.shape
+        code = torch.stack([t[:, c, i * h // 4:(i + 1) * h // 4, j * w // 4:(j + 1) * w // 4].mean(dim=(1, 2))
+                            for c in range(3) for i in range(4) for j in range(4)], dim=1)
+        f = code @ torch.from_numpy(self.proj).to(t.device)
+        f = f / f.norm(dim=1, keepdim=True)
+        return f.float().cpu().numpy()
+
+
 class HashAudioText:
     """Stand-in for AudioCLIP's text side (demo / smoke runs): deterministic 1024-d unit vectors per category name and a fixed
     logit scale (log 100 -> the clamp's upper end)."""

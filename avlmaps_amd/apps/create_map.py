@@ -3,6 +3,7 @@
     python -m avlmaps_amd.apps.create_map --data-dir <scene> [--config cfg.yaml] [--features lseg|hash] [--seed N]
                                           [--sound [--audio-model hash]] [--explored [--ray-stride N]]
                                           [--gt [--obj2cls FILE] [--categories-file FILE]]
+                                          [--area [--area-model clip|hash] [--area-batch N]]
 
 <scene>/ holds rgb/*.png, depth/*.npy (float32 metres) and poses.txt (x y z qx qy qz qw per line), the layout of the
 reference's dataset/README.md:76-93; the map goes to <scene>/vlmap/vlmaps.h5df (a real HDF5 file: through h5py, or through
@@ -18,6 +19,9 @@ file up, and the known-free map and the frontier goals need it.
 id of every pixel: --obj2cls is the object id -> class id table (.json dict or list, or .npy; default <scene>/semantic/obj2cls.json
 when it exists, else the frames are taken as class ids), --categories-file a text file with one class name per line, the line
 number being the class id.  apps.evaluate_map scores a map against it.
+--area also builds the area map (<scene>/area_map/clip_sparse_map.h5df, AreaMap.create_map: one image embedding per frame, what
+apps.index_map --modality area reads): the frames are preprocessed for CLIP on the GPU --area-batch at a time and encoded as
+batches; --area-model clip is OpenAI CLIP ViT-L/14 (it must be installed), hash the model-free stand-in.
 Multi-GPU: launch with torchrun; frames are sharded over ranks and merged with one row-sharded RCCL exchange (every --save-every
 frames per rank as a checkpoint, and at the end); an interrupted run is continued with --resume; with --seed the N-rank map
 equals the single-process map (every rank replays the RNG draws of the frames before its shard)."""
@@ -62,7 +66,13 @@ def main(argv=None):
     ap.add_argument("--gt", action="store_true", help="also build the ground-truth label map (<scene>/vlmap/gt_labels.npz) from <scene>/semantic")
     ap.add_argument("--obj2cls", default=None, metavar="FILE", help="--gt: object id -> class id table (.json or .npy)")
     ap.add_argument("--categories-file", default=None, metavar="FILE", help="--gt: class names, one per line; the line number is the class id")
+    ap.add_argument("--area", action="store_true", help="also build the area map (<scene>/area_map/clip_sparse_map.h5df) from the rgb frames")
+    ap.add_argument("--area-model", choices=["clip", "hash"], default="clip",
+                    help="--area: the image encoder; clip = OpenAI CLIP ViT-L/14, hash = model-free stand-in (apps/common.HashBatchImageEncoder)")
+    ap.add_argument("--area-batch", type=int, default=64, metavar="N", help="--area: frames preprocessed and encoded per batch")
     args = ap.parse_args(argv)
+    if args.area_batch < 1:
+        ap.error("--area-batch must be at least 1")
     if args.ray_stride < 1:
         ap.error("--ray-stride must be at least 1")
     if (args.obj2cls or args.categories_file) and not args.gt:
@@ -108,6 +118,11 @@ def main(argv=None):
     if args.sound and rank == 0:
         path = avlmap.sound_map.create_sound_map(args.data_dir, audio_encoder=HashAudioEncoder())
         print(f"sound map with {len(avlmap.sound_map.load_sound_map(args.data_dir))} segments written to {path}")
+    if args.area and rank == 0:
+        from avlmaps_amd.apps.common import HashBatchImageEncoder
+        avlmap.area_map.create_map(args.data_dir, batch_encoder=HashBatchImageEncoder() if args.area_model == "hash" else None,
+                                   batch_size=args.area_batch)
+        print(f"area map with {len(avlmap.area_map.clip_sparse_map)} frame embeddings written to {avlmap.area_map.data_dir / 'area_map'}")
     if args.explored and rank == 0:
         first_seen = avlmap.vlmap.create_explored_map(args.data_dir, stride=args.ray_stride)
         print(f"explored map: {int((first_seen >= 0).sum())} cells seen in {avlmap.vlmap.explored_params['n_frames']} frames, written to "

@@ -2,8 +2,9 @@
 and the pose it was taken from.  Scoring a text query against the F frame embeddings runs through the similarity kernel
 (ops.sim_scores, float32-exact form) on a device copy kept per loaded map.
 
-The image encoder and the text tower are pluggable: upstream both are CLIP ViT-L/14 (768-d); `image_encoder(rgb) -> (768,)`
-and any object with encode_text (+ tokenize, as utils/clip_utils.get_text_feats expects) can stand in."""
+The image encoder and the text tower are pluggable: upstream both are CLIP ViT-L/14 (768-d); `image_encoder(rgb) -> (768,)`,
+`batch_encoder((B, 3, n_px, n_px) tensor) -> (B, 768)` on frames preprocessed by the GPU (ops.clip_preprocess), and any object
+with encode_text (+ tokenize, as utils/clip_utils.get_text_feats expects) can stand in."""
 from __future__ import annotations
 
 from pathlib import Path
@@ -52,33 +53,66 @@ class AreaMap:
     def map_exists(data_dir) -> bool:
         return map_file_exists(Path(data_dir) / AREA_MAP_FILE)
 
-    def create_map(self, data_dir: Union[Path, str], image_encoder: Optional[Callable[[np.ndarray], np.ndarray]] = None) -> None:
+    def create_map(self, data_dir: Union[Path, str], image_encoder: Optional[Callable[[np.ndarray], np.ndarray]] = None,
+                   batch_encoder: Optional[Callable] = None, batch_size: int = 64) -> None:
         """One embedding per frame of rgb/*.png and its habitat pose from poses.txt.  Reference: area_map.py:66-98.
-        image_encoder(rgb uint8 (H, W, 3)) -> (clip_feat_dim,) L2-normalised; None = CLIP ViT-L/14 (get_img_feats)."""
+        image_encoder(rgb uint8 (H, W, 3)) -> (clip_feat_dim,) L2-normalised: the frames are encoded one at a time.
+        batch_encoder((B, 3, n_px, n_px) float32 torch tensor on the GPU) -> (B, clip_feat_dim) L2-normalised rows (a tensor or an
+        array): the frames are decoded on the host, preprocessed `batch_size` at a time by ops.clip_preprocess (CLIP's preprocess
+        in one launch pair, n_px = batch_encoder.n_px or 224) and encoded as batches; all frames must have one size.
+        Neither: CLIP ViT-L/14's image tower on such batches, the norm taken on the device."""
         self._setup_paths(data_dir)
-        if image_encoder is None:
-            image_encoder = self._clip_image_encoder()
+        if image_encoder is not None and batch_encoder is not None:
+            raise ValueError("AreaMap.create_map: give image_encoder or batch_encoder, not both")
         base_poses = np.loadtxt(self.pose_path).reshape(-1, 7)
         n = len(self.rgb_paths)
         sparse = np.zeros((n, self.clip_feat_dim), dtype=np.float32)
         poses = []
-        for i, (rgb_path, pose) in enumerate(zip(self.rgb_paths, base_poses)):
-            sparse[i] = np.asarray(image_encoder(load_rgb_png(rgb_path)), dtype=np.float32).reshape(-1)
-            poses.append(cvt_pose_vec2tf(pose))
+        if image_encoder is not None:
+            for i, (rgb_path, pose) in enumerate(zip(self.rgb_paths, base_poses)):
+                sparse[i] = np.asarray(image_encoder(load_rgb_png(rgb_path)), dtype=np.float32).reshape(-1)
+                poses.append(cvt_pose_vec2tf(pose))
+        else:
+            m = min(n, len(base_poses))
+            self._encode_batches(batch_encoder or self._clip_batch_encoder(), self.rgb_paths[:m], int(batch_size), sparse)
+            poses = [cvt_pose_vec2tf(pose) for pose in base_poses[:m]]
         self.map_save_dir.mkdir(parents=True, exist_ok=True)
         write_map_datasets(self.data_dir / AREA_MAP_FILE, {"clip_sparse_map": sparse, "robot_pose_list": np.asarray(poses, np.float64)})
         self._set(sparse, np.asarray(poses, np.float64))
 
-    def _clip_image_encoder(self):
+    @staticmethod
+    def _encode_batches(batch_encoder, paths, batch_size, sparse) -> None:
+        """sparse[i] = the embedding of paths[i].  PNG decoding stays on the host, on at most four threads, one batch ahead of the
+        GPU; everything between the decoded bytes and the embedding runs on the device."""
+        from concurrent.futures import ThreadPoolExecutor
+        from .. import ops
+        if batch_size < 1:
+            raise ValueError(f"batch_size={batch_size} must be at least 1")
+        n_px = int(getattr(batch_encoder, "n_px", 224))
+        chunks = [paths[s:s + batch_size] for s in range(0, len(paths), batch_size)]
+        with ThreadPoolExecutor(max_workers=4, thread_name_prefix="avl-png") as pool:
+            ahead = [pool.submit(load_rgb_png, p) for p in chunks[0]] if chunks else []
+            at = 0
+            for ci, chunk in enumerate(chunks):
+                frames = [f.result() for f in ahead]
+                ahead = [pool.submit(load_rgb_png, p) for p in chunks[ci + 1]] if ci + 1 < len(chunks) else []
+                if any(f.shape != frames[0].shape for f in frames):
+                    raise ValueError(f"AreaMap.create_map: the frames {chunk[0].name} .. {chunk[-1].name} differ in size; the batched "
+                                     "path needs one size (image_encoder= takes them one at a time)")
+                feats = batch_encoder(ops.clip_preprocess(np.stack(frames), n_px=n_px, as_torch=True))
+                feats = feats.detach().float().cpu().numpy() if hasattr(feats, "detach") else np.asarray(feats)
+                sparse[at:at + len(chunk)] = feats.astype(np.float32).reshape(len(chunk), -1)
+                at += len(chunk)
+
+    def _clip_batch_encoder(self):
         import torch
-        from PIL import Image
         self._init_clip()
 
-        def enc(rgb):
+        def enc(x):
             with torch.no_grad():
-                f = self.clip_model.encode_image(self.preprocess(Image.fromarray(np.uint8(rgb)))[None].cuda()).float()
-            f /= f.norm(dim=-1, keepdim=True)
-            return f.cpu().numpy().astype(np.float32)
+                f = self.clip_model.encode_image(x).float()
+            return f / f.norm(dim=-1, keepdim=True)
+        enc.n_px = int(getattr(getattr(self.clip_model, "visual", None), "input_resolution", 224))
         return enc
 
     def load_map(self, data_dir: Union[Path, str]) -> bool:

@@ -58,13 +58,16 @@ class AVLMap:
         self._area_cells = self._sound_cells = None
 
     # ------------------------------------------------------------------ build / load
-    def create_map(self, data_dir, feat_extractor=None, area_encoder=None, audio_encoder=None) -> bool:
-        """Reference: avlmap.py:38-46.  area_encoder(rgb) -> (768,): also build the area map (area_map/clip_sparse_map.h5df).
+    def create_map(self, data_dir, feat_extractor=None, area_encoder=None, audio_encoder=None, area_batch_encoder=None) -> bool:
+        """Reference: avlmap.py:38-46.  area_encoder(rgb) -> (768,): also build the area map (area_map/clip_sparse_map.h5df), frame by
+        frame; area_batch_encoder((B, 3, n_px, n_px) device tensor) -> (B, 768): build it in batches preprocessed on the GPU.
         audio_encoder(batch (B, 5 * sample_rate)) -> (B, D): also build the sound map (audio_video/audio_data_<level>.pkl) when the
         configuration has a sound part and the scene an audio_video directory."""
         self.vlmap.create_map(data_dir, feat_extractor=feat_extractor)
         if area_encoder is not None:
             self.area_map.create_map(data_dir, image_encoder=area_encoder)
+        elif area_batch_encoder is not None:
+            self.area_map.create_map(data_dir, batch_encoder=area_batch_encoder)
         if audio_encoder is not None:
             if self.sound_map is None:
                 raise MissingSubMap("AVLMap.create_map(audio_encoder=...) needs sound_config and sound_data_collect_params in the "

@@ -53,6 +53,10 @@ from .gtmap import (  # noqa: F401
     _dtype_of, gt_labels, GT_MAX_CLASSES, GT_MAX_VOTES, gt_vote, _ids_i32, label_confusion, label_confusion_limits,
     map_scores, MapScores, obj2cls_table, pool_labels_2d, UNLABELLED,
 )
+from .resize import (  # noqa: F401
+    clip_preprocess, clip_preprocess_plan, clip_table, CLIP_MEAN, CLIP_STD, resize_coeffs, RESIZE_LDS_COEFS, RESIZE_LDS_SPAN,
+    resize_limits, RESIZE_MAX_BATCH, RESIZE_MAX_CHANNELS, RESIZE_MAX_SIDE, RESIZE_TILE_W, resize_u8,
+)
 # the shared marshalling layer; its one device predicate keeps both of the names it had here
 from ._args import (  # noqa: F401
     _dev_u8, _image_any, _image_shape, _image_u8, _is_dev, _is_dev as _on_device, _result,

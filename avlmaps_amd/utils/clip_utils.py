@@ -38,6 +38,87 @@ def _build_templates() -> List[str]:
 multiple_templates = _build_templates()
 
 
+class ClipPreprocess:
+    """CLIP's `preprocess` (clip.load(...)[1], _transform(n_px)) on the GPU: a callable that takes a PIL image, an (H, W, 3) uint8
+    array or a (B, H, W, 3) batch of equally sized frames (host or device) and returns the normalised (3, n_px, n_px) float32 torch
+    tensor on the GPU, (B, 3, n_px, n_px) for a batch -- ops.clip_preprocess, Pillow's bicubic resize bit for bit.  Passed as
+    `preprocess` to get_img_feats / get_imgs_feats_batch it makes them preprocess a whole batch in one call."""
+
+    def __init__(self, n_px: int = 224, mean=None, std=None):
+        from ..ops.resize import CLIP_MEAN, CLIP_STD
+        self.n_px = int(n_px)
+        self.mean, self.std = tuple(mean or CLIP_MEAN), tuple(std or CLIP_STD)
+
+    def batch(self, images):
+        """(B, H, W, 3) uint8 frames -> (B, 3, n_px, n_px) float32 torch tensor on the GPU"""
+        from .. import ops
+        return ops.clip_preprocess(images, n_px=self.n_px, mean=self.mean, std=self.std, as_torch=True)
+
+    def __call__(self, img):
+        if not hasattr(img, "shape"):
+            img = np.asarray(img.convert("RGB") if hasattr(img, "convert") else img, dtype=np.uint8)
+        out = self.batch(img)
+        return out if len(img.shape) == 4 else out[0]
+
+
+def _image_or_black(img):
+    """upstream's guard (clip_utils.py:117-118): an image without rows or columns becomes one black pixel"""
+    img = np.asarray(img)
+    if img.ndim < 2 or img.shape[0] == 0 or img.shape[1] == 0:
+        img = np.zeros((1, 1, 3), np.uint8)
+    return np.uint8(img)
+
+
+def _encode_images(img_in, clip_model) -> np.ndarray:
+    import torch
+    with torch.no_grad():
+        f = clip_model.encode_image(img_in.cuda()).float()
+    f /= f.norm(dim=-1, keepdim=True)
+    return np.float32(f.cpu())
+
+
+def get_img_feats(img, preprocess, clip_model) -> np.ndarray:
+    """(1, D) float32, L2-normalised.  Reference: clip_utils.py:96-103."""
+    if isinstance(preprocess, ClipPreprocess):
+        return _encode_images(preprocess(np.uint8(img))[None, ...], clip_model)
+    from PIL import Image
+    return _encode_images(preprocess(Image.fromarray(np.uint8(img)))[None, ...], clip_model)
+
+
+def get_imgs_feats(raw_imgs, preprocess, clip_model, clip_feat_dim) -> np.ndarray:
+    """(len(raw_imgs), clip_feat_dim) float64, one image at a time.  Reference: clip_utils.py:106-110."""
+    imgs_feats = np.zeros((len(raw_imgs), clip_feat_dim))
+    for img_id, img in enumerate(raw_imgs):
+        imgs_feats[img_id, :] = get_img_feats(img, preprocess, clip_model)
+    return imgs_feats
+
+
+def get_imgs_feats_batch(raw_imgs, preprocess, clip_model, clip_feat_dim, batch_size=64) -> np.ndarray:
+    """(len(raw_imgs), clip_feat_dim) float64, encoded batch_size images at a time.  Reference: clip_utils.py:113-130.
+    With a ClipPreprocess, consecutive images of one size are preprocessed in ONE launch pair (images of another size start a new
+    group inside the batch) and the batch is encoded in one call; any other `preprocess` is applied per image on the host, as
+    upstream does.  An empty image counts as one black pixel."""
+    import torch
+    imgs_feats = np.zeros((len(raw_imgs), clip_feat_dim))
+    gpu = isinstance(preprocess, ClipPreprocess)
+    if not gpu:
+        from PIL import Image
+    for start in range(0, len(raw_imgs), batch_size):
+        imgs = [_image_or_black(img) for img in raw_imgs[start:start + batch_size]]
+        if gpu:
+            parts, i = [], 0
+            while i < len(imgs):
+                j = i + 1
+                while j < len(imgs) and imgs[j].shape == imgs[i].shape:
+                    j += 1
+                parts.append(preprocess.batch(np.stack(imgs[i:j])))
+                i = j
+        else:
+            parts = [preprocess(Image.fromarray(img))[None, ...] for img in imgs]
+        imgs_feats[start:start + len(imgs), :] = _encode_images(torch.cat(parts, dim=0), clip_model)
+    return imgs_feats
+
+
 def get_text_feats(in_text: Sequence[str], clip_model, clip_feat_dim: int, batch_size: int = 64) -> np.ndarray:
     """CLIP text embeddings, each row L2-normalised, float32 (len(in_text), clip_feat_dim).
     Reference: clip_utils.py:133-149.  `clip_model` is an OpenAI-CLIP style model (encode_text); the tokenizer is

@@ -1094,6 +1094,38 @@ AVL_API int avl_label_confusion(const int32_t* d_gt, const int32_t* d_pred, int6
 /* the largest n_gt_classes * n_pred_classes avl_label_confusion counts in block-private LDS counters; above it: global atomics */
 AVL_API int avl_label_confusion_limits(int* h_lds_counters);
 
+/* ------------------------------------------------------------------------------------------------
+ * (17) Pillow's 8-bit image resize and CLIP's preprocess (csrc/avl_resize.hip)
+ *     d_in is a batch of B equally sized images, (B, H, W, C) uint8 in device memory, 1 <= B <= 65535, 1 <= H, W <= 16384,
+ *     1 <= C <= 4.  A pass along an axis is given by two tables in device memory (ops.resize_coeffs builds them; they are
+ *     Pillow's precompute_coeffs and normalize_coeffs_8bpc): d_k (out_size, ksize) int32 coefficients scaled by 2^22 and d_b
+ *     (out_size, 2) int32 (first input index, number of taps <= ksize); per channel
+ *         out = clamp((2^21 + sum over i of in[first + i] * k[i]) >> 22, 0, 255)      int32, arithmetic shift
+ *     which needs 255 * sum|k| + 2^21 < 2^31 of every row (the caller's to check: the tables are not read on the host).  The
+ *     horizontal pass (d_kh, d_bh: W -> ow) runs first and is rounded to uint8, the vertical one (d_kv, d_bv: H -> oh) reads its
+ *     bytes: PIL.Image.resize((ow, oh)) for the box, bilinear and bicubic filters, bit for bit.  Both tables of a pass NULL: the
+ *     axis keeps its size (ow == W, oh == H).  Only the window of out_h x out_w pixels at (top, left) of the resized image is
+ *     computed, and only the input rows and columns that reach it are read.  An index of a table that leaves the image is
+ *     clamped.  Arguments are checked before any device work; both calls are asynchronous on `stream` and allocate nothing.
+ * ------------------------------------------------------------------------------------------------ */
+/* the workspace of the two calls below: the horizontal pass's bytes, needed (and read) only when there is a vertical pass */
+AVL_API int avl_resize_work_bytes(int B, int H, int C, int out_w, int vertical, size_t* h_bytes);
+/* Stands in for PIL.Image.resize (the resize inside avlmaps/utils/clip_utils.py:96-130's preprocess, and any other use of it).
+ * d_out (B, out_h, out_w, C) uint8. */
+AVL_API int avl_resize_u8(const uint8_t* d_in, int B, int H, int W, int C, const int32_t* d_kh, const int32_t* d_bh, int ksize_h, int ow,
+                          const int32_t* d_kv, const int32_t* d_bv, int ksize_v, int oh, int top, int left, int out_h, int out_w,
+                          uint8_t* d_out, void* d_ws, size_t ws_bytes, void* stream);
+/* Replaces avlmaps/utils/clip_utils.py:96-130's preprocess(Image.fromarray(img)) per image on the host (OpenAI CLIP's
+ * _transform: Resize, CenterCrop, ToTensor, Normalize) for a batch: the resize and window of avl_resize_u8 with C = 3, then
+ * d_out[b, c, y, x] = d_table[v * 3 + c] for the byte v, channel-planar (B, 3, out_h, out_w).  d_table (256, 3) holds float32
+ * (out_f16 = 0) or float16 (out_f16 = 1) values, which are moved as bit patterns: the caller's table is ToTensor and Normalize. */
+AVL_API int avl_clip_preprocess(const uint8_t* d_in, int B, int H, int W, const int32_t* d_kh, const int32_t* d_bh, int ksize_h, int ow,
+                                const int32_t* d_kv, const int32_t* d_bv, int ksize_v, int oh, int top, int left, int out_h, int out_w,
+                                const void* d_table, int out_f16, void* d_out, void* d_ws, size_t ws_bytes, void* stream);
+/* output columns per workgroup of the horizontal pass, and how many coefficients of such a tile / bytes of an input row it stages in
+ * LDS before it reads them from global memory */
+AVL_API int avl_resize_limits(int* h_tile_w, int* h_lds_coefs, int* h_lds_span);
+
 #ifdef __cplusplus
 }
 #endif
