@@ -209,6 +209,9 @@ _SIGS = {
     "avl_clip_preprocess": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int,
                                       C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _sz, _vp]),
     "avl_resize_limits": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "avl_label_voxels_work_bytes": (C.c_int, [_i64, C.POINTER(_sz)]),
+    "avl_label_voxels": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp, _vp, _vp, _sz, _vp]),
+    "avl_voxel_instance_table": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -5,6 +5,7 @@ and image branches, :23-142; the Open3D viewer and the habitat branches are not 
                                          [--decay-rate R] [--text-model clip|hash]
     python -m avlmaps_amd.apps.index_map --data-dir <scene> --modality fused [--object NAME]... [--area NAME]... [--sound NAME]...
                                          [--image PNG] [--object-decay R] [--area-decay R] [--sound-decay R] [--image-decay R]
+    ... --modality object --categories A,B,...   [--instances] [--instance K] [--min-voxels M] [--connectivity 6|18|26]
     ... any modality ...                 [--render PNG [--view topdown|frame:<i>|orbit] [--render-size W H]] [--save-ply PLY]
 
 object (default): the VLMap text query; area: the area map's frame embeddings (area_map/clip_sparse_map.h5df); sound: the sound
@@ -12,6 +13,10 @@ map (audio_video/audio_data_<difficulty>.pkl); image: --image (a PNG) localised 
 localiser; upstream uses HLoc); fused: the cross-modal goal, the product of every --object, --area, --sound and --image heat
 (AVLMap.index_goal; at least one of them, decay rates default to the stand-alone queries' 0.1, 0.1, 0.01, 0.01).  Prints the heat statistics and the voxel the navigator would go to (argmax of the heat,
 habitat_lang_robot.py:427-430); --save writes the (N,) heat vector as .npy (float64 for fused).
+
+--instances lists the objects of the queried category in 3-D (VLMap.get_instances_3d: the connected components of its voxels), one
+line each: label, voxels, box, centre, best score.  --instance K makes --save, --render and --save-ply use the heat of that object
+alone (AVLMap.index_object_instance).  Both need --categories; --min-voxels and --connectivity are their two parameters.
 
 --render writes the picture the reference shows in a window (visualize_heatmap_3d, application/index_map.py): the heat in JET
 colours over the map's own, rendered on the GPU (AVLMap.render_heat).  --view topdown (default) is the map from above, frame:<i>
@@ -37,6 +42,11 @@ def parse_args(argv=None):
                     help="clip = OpenAI CLIP on PyTorch-ROCm (as upstream); hash = model-free stand-ins for smoke runs (text towers "
                          "and the audio-text model)")
     ap.add_argument("--categories", default=None, help="comma separated list: preload scores_mat (VLMap.init_categories)")
+    ap.add_argument("--instances", action="store_true", help="object: list the category's objects in 3-D (needs --categories)")
+    ap.add_argument("--instance", type=int, default=None, metavar="K",
+                    help="object: --save / --render / --save-ply use the heat of instance K alone (needs --categories)")
+    ap.add_argument("--min-voxels", type=int, default=50, help="--instances / --instance: drop objects with fewer voxels (default 50)")
+    ap.add_argument("--connectivity", type=int, choices=[6, 18, 26], default=26, help="--instances / --instance: voxel adjacency (default 26)")
     ap.add_argument("--image", default=None, help="query image (PNG) of --modality image and fused")
     ap.add_argument("--image-pose", type=int, default=0, help="row of poses.txt the model-free localiser places the image at")
     ap.add_argument("--object", action="append", default=[], help="fused: an object name (repeatable)")
@@ -63,6 +73,9 @@ def parse_args(argv=None):
         ap.error(f"--modality {args.modality} needs --query")
     elif args.modality == "image" and not args.image:
         ap.error("--modality image needs --image")
+    if args.instances or args.instance is not None:
+        if args.modality != "object" or not args.categories:
+            ap.error("--instances and --instance need --modality object and --categories")
     return args
 
 
@@ -84,6 +97,15 @@ def write_pictures(avlmap, heat, args) -> None:
         vm = avlmap.vlmap
         visualize_heatmap_3d(vm.grid_pos, heat, vm.grid_rgb, save_path=args.save_ply)
         print(f"wrote {args.save_ply}: {len(heat)} points")
+
+
+def print_instances(instances, name: str) -> None:
+    """--instances: one line per object of VLMap.get_instances_3d"""
+    print(f"{len(instances)} instances of {name!r}")
+    for it in instances:
+        r0, r1, c0, c1, h0, h1 = it.bbox
+        print(f"  instance {it.label}: {it.count} voxels, rows {r0}..{r1}, cols {c0}..{c1}, heights {h0}..{h1}, "
+              f"centre ({it.center[0]:.2f}, {it.center[1]:.2f}, {it.center[2]:.2f}), best score {it.best_score:.4f} at voxel {it.best_voxel}")
 
 
 def fused_decay_rates(args) -> dict:
@@ -135,6 +157,16 @@ def main(argv=None):
             cats = ["void"] + [c.strip() for c in args.categories.split(",")] + ["void"]   # upstream passes categories[1:-1]
         heat = avlmap.index_object(args.query, init_categories=cats, decay_rate=decay)
         print(f"{int((heat == 1.0).sum())} of {len(heat)} voxels match {args.query!r}; ", end="")
+        if args.instances:
+            print()
+            print_instances(vm.get_instances_3d(args.query, args.min_voxels, args.connectivity), args.query)
+        if args.instance is not None:
+            try:
+                heat = avlmap.index_object_instance(args.query, args.instance, decay_rate=decay, min_voxels=args.min_voxels,
+                                                    connectivity=args.connectivity)
+            except IndexError as e:
+                raise SystemExit(f"--instance {args.instance}: {e}")
+            print(f"instance {args.instance}: ", end="")
     elif args.modality == "area":
         heat = avlmap.index_area(args.query, decay_rate=decay)
     elif args.modality == "sound":

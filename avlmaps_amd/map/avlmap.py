@@ -132,6 +132,21 @@ class AVLMap:
             raise ValueError("attempt to get argmin of an empty sequence")   # what np.argmin raises upstream (no voxel matched)
         return heat
 
+    def index_object_instance(self, object_name: str, k: int, decay_rate: float = 0.1, min_voxels: int = 50,
+                              connectivity: int = 26) -> np.ndarray:
+        """(N,) float32 heat of ONE object: instance k of VLMap.get_instances_3d(object_name, min_voxels, connectivity), 1 on its
+        voxels and decaying from them alone.  Upstream has no counterpart (avlmap.py:67-76 heats every voxel of the category).
+        Needs vlmap.init_categories.  IndexError when k is not a label of the category or the instance has fewer than min_voxels
+        voxels.  The heat can go into index_goal(extra=[...]) as it stands."""
+        cs = cfg_get(cfg_get(self.config, "params"), "cs")
+        vm = self.vlmap
+        _, inst = vm._instances_3d(object_name, connectivity)
+        if not 1 <= int(k) <= inst.n:
+            raise IndexError(f"{object_name!r} has {inst.n} instances, asked for {k}")
+        if inst.table[int(k) - 1, 0] < int(min_voxels):
+            raise IndexError(f"instance {k} of {object_name!r} has {int(inst.table[int(k) - 1, 0])} voxels, fewer than min_voxels = {min_voxels}")
+        return vm.heatmap_from_mask(inst.mask_of(int(k)), cs, decay_rate).numpy()
+
     # ------------------------------------------------------------------ area
     def _require_area(self):
         if not self._area_loaded:

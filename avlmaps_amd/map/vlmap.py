@@ -352,6 +352,39 @@ class VLMap(Map):
         pooled = self._predict_mask_device(name).numpy()
         return pooled[r0:r1, c0:c1].astype(np.asarray(self.obstacles_cropped).dtype)
 
+    def _instances_3d(self, name: str, connectivity: int = 26):
+        """(category id, ops.VoxelInstances) of the voxels whose argmax is `name`'s category, labels on the device.  The last result
+        stays on the map until the categories, the category or the connectivity change."""
+        from .. import ops
+        from ..device import DeviceArray
+        from ..utils.index_utils import find_similar_category_id
+        am = self._argmax_device()                       # raises when init_categories has not run
+        cat_id = find_similar_category_id(name, self.categories)
+        key = (self.scores_mat, self.grid_pos, cat_id, int(connectivity))
+        cached = getattr(self, "_instances_cache", None)
+        if cached is not None:
+            (scores_mat, grid_pos, *rest), inst = cached
+            if scores_mat is self.scores_mat and grid_pos is self.grid_pos and tuple(rest) == key[2:]:
+                return cat_id, inst
+            inst.close()
+            self._instances_cache = None
+        mask = ops.mask_from_argmax(am, cat_id)
+        scores = DeviceArray.from_numpy(np.ascontiguousarray(self.scores_mat[:, cat_id], dtype=np.float32))
+        inst = ops.label_voxels(self._device_pos(), mask, connectivity=connectivity, scores=scores, device=True)
+        self._instances_cache = (key, inst)
+        return cat_id, inst
+
+    def get_instances_3d(self, name: str, min_voxels: int = 50, connectivity: int = 26):
+        """The objects of a category in 3-D: a list of ops.Instance3D, one per connected component (connectivity 6 / 18 / 26) of the
+        voxels whose argmax over scores_mat is the category, in label order.  Upstream has no counterpart: vlmap_3d.py:75-100 and
+        habitat_lang_robot.py:242-265 stop at the category mask.  Needs init_categories.  Components of fewer than min_voxels voxels
+        are dropped here on the host; the others keep their labels, which are what AVLMap.index_object_instance takes.  best_voxel
+        is the voxel with the category's largest score in scores_mat."""
+        from .. import ops
+        _, inst = self._instances_3d(name, connectivity)
+        table, best = inst.table, inst.best_score
+        return [ops.Instance3D.from_row(k + 1, table[k], best[k]) for k in range(inst.n) if table[k, 0] >= int(min_voxels)]
+
     def _distribution_map_device(self, name: str, decay_rate: float = 0.1):
         from .. import ops
         window = self._crop_window()

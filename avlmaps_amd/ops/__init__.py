@@ -57,6 +57,9 @@ from .resize import (  # noqa: F401
     clip_preprocess, clip_preprocess_plan, clip_table, CLIP_MEAN, CLIP_STD, resize_coeffs, RESIZE_LDS_COEFS, RESIZE_LDS_SPAN,
     resize_limits, RESIZE_MAX_BATCH, RESIZE_MAX_CHANNELS, RESIZE_MAX_SIDE, RESIZE_TILE_W, resize_u8,
 )
+from .instances import (  # noqa: F401
+    Instance3D, INSTANCE_TABLE_COLS, INSTANCES_MAX_BOX_SIDE, label_voxels, VoxelInstances,
+)
 # the shared marshalling layer; its one device predicate keeps both of the names it had here
 from ._args import (  # noqa: F401
     _dev_u8, _image_any, _image_shape, _image_u8, _is_dev, _is_dev as _on_device, _result,

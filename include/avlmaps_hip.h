@@ -1126,6 +1126,33 @@ AVL_API int avl_clip_preprocess(const uint8_t* d_in, int B, int H, int W, const 
  * LDS before it reads them from global memory */
 AVL_API int avl_resize_limits(int* h_tile_w, int* h_lds_coefs, int* h_lds_span);
 
+/* ------------------------------------------------------------------------------------------------
+ * (18) object instances in 3-D: connected components of the masked voxels of a voxel list (csrc/avl_instances.hip)
+ *     Upstream has no counterpart: avlmaps/map/map.py:146-151 and avlmaps/map/vlmap_3d.py:75-100, the nearest lines, stop at a
+ *     category's voxel mask.  d_grid_pos is the map's (N, 3) int32 cell list (row, col, height) in any order, 0 <= N < 2^31.  Two
+ *     masked voxels are adjacent when their cells differ by at most 1 on every axis and on at most 1 / 2 / 3 axes (connectivity
+ *     6 / 18 / 26); voxels of one cell belong together; unmasked voxels take part in nothing.  Every result is unique: a minimum,
+ *     a maximum or an integer sum, whose bytes do not depend on scheduling.  Arguments are checked before any device work.
+ * ------------------------------------------------------------------------------------------------ */
+/* The workspace of avl_label_voxels, a function of N alone: 28 bytes per voxel, whatever the bounding box.  Upstream has no
+ * counterpart. */
+AVL_API int avl_label_voxels_work_bytes(int64_t N, size_t* bytes);
+/* d_labels (N,) int32: 0 where d_mask (N,) uint8 is 0, else the voxel's instance, 1 .. n in lexicographic (row, col, height) order of
+ * the instances' first cells = scipy.ndimage.label(dense, generate_binary_structure(3, 1 | 2 | 3)) of dense[row, col, height] read
+ * back at the voxels; *d_n (1 int32, device) = n.  Coordinates are any int32 for which every side of the MASKED voxels' bounding box
+ * is at most 2^20 cells: the box is read back after its pass (the call synchronises `stream` once) and a larger one returns
+ * AVL_ERR_INVALID.  N = 0 and a mask without a voxel give n = 0.  Upstream has no counterpart (a host user would scatter into a
+ * dense array and label that). */
+AVL_API int avl_label_voxels(const int32_t* d_grid_pos, const uint8_t* d_mask, int64_t N, int connectivity, int32_t* d_labels, int32_t* d_n,
+                             void* ws, size_t ws_bytes, void* stream);
+/* d_table (n, 12) int64, row k - 1 for label k: count, rmin, rmax, cmin, cmax, hmin, hmax, sum_row, sum_col, sum_height, first, best.
+ * first = the smallest voxel index at the instance's first cell; best = the voxel index of its largest d_scores (N,) float32, the
+ * smallest index among equals (+0 and -0 are equal; a NaN score leaves best undefined), -1 when d_scores is NULL.
+ * d_best_score (n,) float32 = d_scores[best], 0 without scores.  The centre of an instance is sum / count.  n is avl_label_voxels'
+ * count; n = 0 does nothing.  Asynchronous.  Upstream has no counterpart. */
+AVL_API int avl_voxel_instance_table(const int32_t* d_grid_pos, const int32_t* d_labels, const float* d_scores, int64_t N, int32_t n,
+                                     int64_t* d_table, float* d_best_score, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
