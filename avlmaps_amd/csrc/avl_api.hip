@@ -90,6 +90,11 @@ int num_cus() {
     return cached;
 }
 
+unsigned stride_blocks(int64_t items) {
+    const int64_t want = (items + 255) / 256, cap = (int64_t)num_cus() * 16;
+    return (unsigned)(want < 1 ? 1 : (want < cap ? want : cap));
+}
+
 }  // namespace avl
 
 namespace avl {

@@ -13,9 +13,10 @@
 // "index if loud else -1", a scan; the starts are then flagged independently and numbered by a second scan.  Reduce-then-scan, five
 // launches, no workgroup waits on another and there are no atomics:
 //   (a) tile_last   every tile of 256 threads x 16 samples: its last loud index or -1
-//   (b) carry       one workgroup: exclusive running maximum of the tile summaries (a loop when there are more tiles than threads)
+//   (b) carry       one workgroup: exclusive running maximum of the tile summaries (scan_counts_kernel under OpMax from -1; a loop
+//                   when there are more tiles than threads)
 //   (c) count       every tile again with its carried value: the starts are flagged and counted
-//   (d) offsets     one workgroup: exclusive sum of the counts, the total to d_count
+//   (d) offsets     one workgroup: exclusive sum of the counts, the total to d_count (scan_counts_kernel under OpSum, int64 out)
 //   (e) write       every tile a third time: start k writes l_k and r_(k-1) = its prev; the last tile writes the last r from the
 //                   final summary
 // A thread keeps its 16 samples as a 16-bit loud mask (four 16-byte loads when the pointer allows), the scans inside a tile are wave
@@ -29,7 +30,7 @@
 #include <cmath>
 
 #include "avl_common.h"
-#include "avl_wave.h"
+#include "avl_scan.h"
 
 namespace avl {
 
@@ -67,7 +68,7 @@ __device__ __forceinline__ unsigned aud_loud_mask(const float* __restrict__ audi
 __device__ __forceinline__ int aud_mask_last(unsigned m, int64_t base) { return m ? (int)base + 31 - __clz((int)m) : -1; }
 
 // The scans below are block_excl_scan over the kAudWaves waves of a tile: the running maximum starts at -1 ("no loud sample yet"),
-// the sums at 0.  A kernel that scans twice uses two LDS arrays; the one-workgroup loops put a barrier before the next round.
+// the sums at 0.  A kernel that scans twice uses two LDS arrays.
 // (a)
 __global__ __launch_bounds__(kAudThreads) void aud_tile_last_kernel(const float* __restrict__ audio, int64_t n, float threshold, bool vec,
                                                                    int* __restrict__ tile_last) {
@@ -85,21 +86,7 @@ __global__ __launch_bounds__(kAudThreads) void aud_tile_last_kernel(const float*
     }
 }
 
-// (b) one workgroup
-__global__ __launch_bounds__(kAudThreads) void aud_carry_kernel(const int* __restrict__ tile_last, int64_t tiles, int* __restrict__ carry) {
-    __shared__ int lds[kAudWaves];
-    int running = -1;
-    for (int64_t b = 0; b < tiles; b += kAudThreads) {
-        const int64_t t = b + threadIdx.x;
-        const int v = t < tiles ? tile_last[t] : -1;
-        int total;
-        const int ex = block_excl_scan<kAudWaves>(v, OpMax{}, -1, lds, &total);
-        if (t < tiles) carry[t] = max(running, ex);
-        running = max(running, total);
-        __syncthreads();                              // lds is written again in the next round
-    }
-}
-
+// (b) and (d) are avl_scan.h's scan_counts_kernel: under the maximum from -1 over the tile summaries, under the sum over the counts
 // the starts among this thread's samples, given prev = the last loud index before its first sample (or -1): a 16-bit mask.
 // The writer repeats the walk, because it needs every start's own prev.
 __device__ __forceinline__ unsigned aud_start_mask(unsigned m, int64_t base, int prev, int64_t gap) {
@@ -127,23 +114,6 @@ __global__ __launch_bounds__(kAudThreads) void aud_count_kernel(const float* __r
     int sum;
     block_excl_scan<kAudWaves>(c, OpSum{}, 0, lds2, &sum);
     if (threadIdx.x == 0) tile_count[blockIdx.x] = sum;
-}
-
-// (d) one workgroup
-__global__ __launch_bounds__(kAudThreads) void aud_offsets_kernel(const int* __restrict__ tile_count, int64_t tiles,
-                                                                 int64_t* __restrict__ offsets, int64_t* __restrict__ d_count) {
-    __shared__ int64_t lds[kAudWaves];
-    int64_t running = 0;
-    for (int64_t b = 0; b < tiles; b += kAudThreads) {
-        const int64_t t = b + threadIdx.x;
-        const int64_t v = t < tiles ? tile_count[t] : 0;
-        int64_t total;
-        const int64_t ex = block_excl_scan<kAudWaves>(v, OpSum{}, (int64_t)0, lds, &total);
-        if (t < tiles) offsets[t] = running + ex;
-        running += total;
-        __syncthreads();                              // lds is written again in the next round
-    }
-    if (threadIdx.x == 0) d_count[0] = running;
 }
 
 // (e)
@@ -273,9 +243,11 @@ int avl_audio_segment(const float* d_audio, int64_t n, float threshold, int64_t 
     hipStream_t st = as_stream(stream);
     const dim3 grid((unsigned)tiles), block(kAudThreads);
     hipLaunchKernelGGL(aud_tile_last_kernel, grid, block, 0, st, d_audio, n, threshold, vec, w.tile_last);
-    hipLaunchKernelGGL(aud_carry_kernel, dim3(1), block, 0, st, w.tile_last, tiles, w.carry);
+    hipLaunchKernelGGL((scan_counts_kernel<kAudThreads, int, int, OpMax>), dim3(1), block, 0, st, (const int*)w.tile_last, tiles, w.carry,
+                       (int*)nullptr, OpMax{}, -1);
     hipLaunchKernelGGL(aud_count_kernel, grid, block, 0, st, d_audio, n, threshold, gap, vec, w.carry, w.tile_count);
-    hipLaunchKernelGGL(aud_offsets_kernel, dim3(1), block, 0, st, w.tile_count, tiles, w.offsets, d_count);
+    hipLaunchKernelGGL((scan_counts_kernel<kAudThreads, int, int64_t, OpSum>), dim3(1), block, 0, st, (const int*)w.tile_count, tiles, w.offsets,
+                       d_count, OpSum{}, (int64_t)0);
     hipLaunchKernelGGL(aud_write_kernel, grid, block, 0, st, d_audio, n, threshold, gap, vec, w.carry, w.tile_last, w.offsets, d_segments, cap);
     AVL_HIP_CHECK(hipGetLastError());
     return AVL_OK;

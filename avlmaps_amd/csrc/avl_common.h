@@ -33,6 +33,8 @@ static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream
 
 // number of CUs of the current device (cached)
 int num_cus();
+// workgroups of 256 threads for a grid-stride kernel over `items`: one thread per item until every CU has 16 workgroups
+unsigned stride_blocks(int64_t items);
 
 // Small per-thread, per-device scratch buffer owned by the library (grown on demand, never shrunk): the SYNCHRONOUS entry
 // points that return host scalars (avl_argmax_f32, avl_topk_f32) keep their partial results here instead of allocating on

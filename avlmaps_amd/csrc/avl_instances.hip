@@ -2,8 +2,8 @@
 //
 // Upstream has no counterpart.  Its nearest lines stop at the category mask: avlmaps/map/map.py:146-151 (the mask of a category)
 // and avlmaps/map/vlmap_3d.py:75-100 (the 3-D index of a category); a user would scatter grid_pos into a dense
-// 1000 x 1000 x 30 array on the host and call scipy.ndimage.label on it.  This is avl_islands.hip's labelling on the map's own
-// voxel list instead of a dense image.
+// 1000 x 1000 x 30 array on the host and call scipy.ndimage.label on it.  This labels the map's own voxel list instead, with the
+// union-find and the numbering that avl_islands.hip uses on a dense image.
 //
 // What is pinned.  Two masked voxels are adjacent when their cells (row, col, height) differ by at most 1 on every axis and the
 // number of differing axes is <= 1 / 2 / 3 for connectivity 6 / 18 / 26; voxels that share a cell belong together; unmasked voxels
@@ -15,17 +15,18 @@
 // Labelling.  The work is done on the masked voxels in CELL order, on their ranks t = 0 .. M - 1:
 //   box      bounding box and number M of the masked voxels (one pass, read back: the sort needs M, the key the box).  A side
 //            beyond 2^20 cells is refused here: three sides of 20 bits make a key of at most 60 bits
-//   compact  the masked voxels in index order (counts per 1024 voxels, one scan, one write): key = ((row - rmin) * ny + (col - cmin))
-//            * nz + (height - hmin) as uint64, value = the voxel index
+//   compact  the masked voxels in index order (avl_scan.h: count_flagged_kernel per 1024 voxels, scan_counts_kernel, then one
+//            write): key = ((row - rmin) * ny + (col - cmin)) * nz + (height - hmin) as uint64, value = the voxel index
 //   sort     rocPRIM's stable radix sort over the key's bits: equal cells keep index order, so the smallest rank of a cell is its
 //            smallest voxel index
-//   merge    union-find on one int32 parent per rank, a parent always being a smaller rank of the same instance (isl_unite's rule).
+//   merge    union-find on one int32 parent per rank (uf_unite; avl_unionfind.h states the invariant, an element being a rank).
 //            A voxel looks at the 13 cells that precede it in raster order: the height neighbour and a second voxel of its own
 //            cell are the previous rank; the three cells of each of the four preceding columns (row - 1, col - 1 .. col + 1) and
 //            (row, col - 1) are consecutive ranks, found by ONE binary search per column among the ranks before t
-//   flatten  parent = root; one pass, a thread walks the whole chain
-//   number   root flags counted per 1024 ranks, scanned, every root receives 1 + the number of roots before it.  Roots are first
-//            cells and ranks are in cell order, which is the lexicographic order of (row, col, height)
+//   flatten  parent = root (uf_flatten_kernel)
+//   number   the roots counted per 1024 ranks, scanned, every root receives 1 + the number of roots before it (count_flagged_kernel,
+//            scan_counts_kernel, number_flagged_kernel).  Roots are first cells and ranks are in cell order, which is the
+//            lexicographic order of (row, col, height)
 //   scatter  labels[voxel of rank t] = label of t's root; the unmasked voxels keep the 0 of the memset
 // The workspace is 28 bytes per voxel of the list whatever the box (no grid over the box is kept, not even one of bits).
 //
@@ -41,7 +42,8 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "avl_common.h"
-#include "avl_wave.h"
+#include "avl_scan.h"
+#include "avl_unionfind.h"
 
 namespace avl {
 
@@ -61,33 +63,11 @@ struct VxHeader {
     int pad;
 };
 
-__device__ __forceinline__ int vx_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ int vx_find(const int* parent, int x) {
-    int y = vx_load(parent + x);
-    while (y != x) {
-        x = y;
-        y = vx_load(parent + x);
-    }
-    return x;
-}
-
-// isl_unite of avl_islands.hip: links only ever point to smaller ranks
-__device__ __forceinline__ void vx_unite(int* parent, int a, int b) {
-    for (;;) {
-        a = vx_find(parent, a);
-        b = vx_find(parent, b);
-        if (a == b) return;
-        if (a < b) {
-            const int t = a;
-            a = b;
-            b = t;
-        }
-        const int old = atomicMin(parent + a, b);
-        if (old == a) return;
-        a = old;
-    }
-}
+// the masked voxels, for avl_scan.h's counting kernel and the compaction
+struct VxMasked {
+    const uint8_t* mask;
+    __device__ __forceinline__ bool operator()(int64_t i) const { return mask[i] != 0; }
+};
 
 __global__ void vx_header_init_kernel(VxHeader* __restrict__ h) {
     if (threadIdx.x < 3) {
@@ -137,48 +117,6 @@ __global__ __launch_bounds__(256) void vx_box_kernel(const int32_t* __restrict__
     }
 }
 
-// bit k: element i0 + k is flagged
-template <typename F>
-__device__ __forceinline__ int vx_flags(int64_t n, int64_t i0, F flagged) {
-    int f = 0;
-#pragma unroll
-    for (int k = 0; k < kVxScanPer; ++k)
-        if (i0 + k < n && flagged(i0 + k)) f |= 1 << k;
-    return f;
-}
-
-__global__ __launch_bounds__(kVxScanThreads) void vx_count_masked_kernel(const uint8_t* __restrict__ mask, int64_t N, int* __restrict__ counts) {
-    __shared__ int s_w[kVxScanThreads / kWave];
-    const int f = vx_flags(N, (int64_t)blockIdx.x * kVxScanBlock + threadIdx.x * kVxScanPer, [&](int64_t i) { return mask[i] != 0; });
-    int total;
-    block_excl_scan<kVxScanThreads / kWave>((int)__popc(f), OpSum{}, 0, s_w, &total);
-    if (threadIdx.x == 0) counts[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(kVxScanThreads) void vx_count_roots_kernel(const int* __restrict__ parent, int64_t M, int* __restrict__ counts) {
-    __shared__ int s_w[kVxScanThreads / kWave];
-    const int f = vx_flags(M, (int64_t)blockIdx.x * kVxScanBlock + threadIdx.x * kVxScanPer, [&](int64_t t) { return parent[t] == (int)t; });
-    int total;
-    block_excl_scan<kVxScanThreads / kWave>((int)__popc(f), OpSum{}, 0, s_w, &total);
-    if (threadIdx.x == 0) counts[blockIdx.x] = total;
-}
-
-// counts -> exclusive offsets in place, the total to *n (when given); one workgroup
-__global__ __launch_bounds__(1024) void vx_offsets_kernel(int* __restrict__ counts, int nblocks, int* __restrict__ n) {
-    __shared__ int s_w[1024 / kWave];
-    int carry = 0;
-    for (int b0 = 0; b0 < nblocks; b0 += 1024) {
-        const int b = b0 + threadIdx.x;
-        const int v = b < nblocks ? counts[b] : 0;
-        int total;
-        __syncthreads();                                          // s_w may still be read from the round before
-        const int ex = block_excl_scan<1024 / kWave>(v, OpSum{}, 0, s_w, &total);
-        if (b < nblocks) counts[b] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0 && n) *n = carry;
-}
-
 // the masked voxels in index order: key, voxel index and the rank's own parent.  M is the count of the box pass: nothing is
 // written at or past it, whatever the mask holds by now
 __global__ __launch_bounds__(kVxScanThreads) void vx_compact_kernel(const int32_t* __restrict__ pos, const uint8_t* __restrict__ mask, int64_t N,
@@ -186,10 +124,11 @@ __global__ __launch_bounds__(kVxScanThreads) void vx_compact_kernel(const int32_
                                                                     int64_t M, unsigned long long* __restrict__ keys, int* __restrict__ idx,
                                                                     int* __restrict__ parent) {
     __shared__ int s_w[kVxScanThreads / kWave];
-    const int64_t i0 = (int64_t)blockIdx.x * kVxScanBlock + threadIdx.x * kVxScanPer;
-    const int f = vx_flags(N, i0, [&](int64_t i) { return mask[i] != 0; });
-    int total;
-    int64_t t = (int64_t)offsets[blockIdx.x] + block_excl_scan<kVxScanThreads / kWave>((int)__popc(f), OpSum{}, 0, s_w, &total);
+    const int64_t base = offsets[blockIdx.x];
+    int64_t i0;
+    int before, total;
+    const int f = block_flags<kVxScanThreads, kVxScanPer>(N, VxMasked{mask}, s_w, &i0, &before, &total);
+    int64_t t = base + before;
 #pragma unroll
     for (int k = 0; k < kVxScanPer; ++k) {
         if (!(f >> k & 1) || t >= M) continue;
@@ -220,13 +159,13 @@ __global__ __launch_bounds__(256) void vx_merge_kernel(const unsigned long long*
         if (t == 0) continue;
         const unsigned long long key = keys[t], prev = keys[t - 1];
         if (prev == key) {                                            // a second voxel of the cell: the cell's first one does the rest
-            vx_unite(parent, t, t - 1);
+            uf_unite(parent, t, t - 1);
             continue;
         }
         const int z = (int)(key % (unsigned long long)nz);
         const unsigned long long col = key / (unsigned long long)nz;
         const int y = (int)(col % (unsigned long long)ny), x = (int)(col / (unsigned long long)ny);
-        if (z > 0 && prev == key - 1) vx_unite(parent, t, t - 1);
+        if (z > 0 && prev == key - 1) uf_unite(parent, t, t - 1);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int dx = k < 3 ? -1 : 0, dy = k < 3 ? k - 1 : -1;   // (-1, -1) (-1, 0) (-1, +1) (0, -1)
@@ -239,30 +178,11 @@ __global__ __launch_bounds__(256) void vx_merge_kernel(const unsigned long long*
             for (int s = vx_lower_bound(keys, t, lo); s < t; ++s) {
                 const unsigned long long ks = keys[s];
                 if (ks > hi) break;
-                if (ks != last) vx_unite(parent, t, s);               // the first voxel of each neighbouring cell
+                if (ks != last) uf_unite(parent, t, s);               // the first voxel of each neighbouring cell
                 last = ks;
             }
         }
     }
-}
-
-__global__ __launch_bounds__(256) void vx_flatten_kernel(int* __restrict__ parent, int M) {
-    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < M; t += gridDim.x * blockDim.x) {
-        const int p = vx_load(parent + t);
-        if (p != t) parent[t] = vx_find(parent, p);
-    }
-}
-
-__global__ __launch_bounds__(kVxScanThreads) void vx_number_kernel(const int* __restrict__ parent, int64_t M, const int* __restrict__ offsets,
-                                                                   int* __restrict__ rank_label) {
-    __shared__ int s_w[kVxScanThreads / kWave];
-    const int64_t t0 = (int64_t)blockIdx.x * kVxScanBlock + threadIdx.x * kVxScanPer;
-    const int f = vx_flags(M, t0, [&](int64_t t) { return parent[t] == (int)t; });
-    int total;
-    int rank = offsets[blockIdx.x] + block_excl_scan<kVxScanThreads / kWave>((int)__popc(f), OpSum{}, 0, s_w, &total);
-#pragma unroll
-    for (int k = 0; k < kVxScanPer; ++k)
-        if (f >> k & 1) rank_label[t0 + k] = ++rank;
 }
 
 // idx[t] < N by construction (vx_compact_kernel wrote it); the comparison only keeps a foreign workspace from writing out of bounds
@@ -449,10 +369,6 @@ static VxWork vx_work(int64_t N, void* ws) {
     return w;
 }
 
-static unsigned vx_stride_blocks(int64_t items) {
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + 255) / 256, (int64_t)num_cus() * 16));
-}
-
 }  // namespace avl
 
 using namespace avl;
@@ -484,7 +400,7 @@ int avl_label_voxels(const int32_t* d_grid_pos, const uint8_t* d_mask, int64_t N
     keep_mempool_once();
     AVL_HIP_CHECK(hipMemsetAsync(d_labels, 0, (size_t)N * sizeof(int32_t), st));
     hipLaunchKernelGGL(vx_header_init_kernel, dim3(1), dim3(64), 0, st, w.header);
-    hipLaunchKernelGGL(vx_box_kernel, dim3(std::min(vx_stride_blocks(N), 512u)), dim3(256), 0, st, d_grid_pos, d_mask, N, w.header);
+    hipLaunchKernelGGL(vx_box_kernel, dim3(std::min(stride_blocks(N), 512u)), dim3(256), 0, st, d_grid_pos, d_mask, N, w.header);
     VxHeader h;
     AVL_HIP_CHECK(hipMemcpyAsync(&h, w.header, sizeof(h), hipMemcpyDeviceToHost, st));
     AVL_HIP_CHECK(hipStreamSynchronize(st));
@@ -500,8 +416,9 @@ int avl_label_voxels(const int32_t* d_grid_pos, const uint8_t* d_mask, int64_t N
     int bits = 1;
     while (bits < 60 && (1ull << bits) < cells) ++bits;
     const dim3 scan_n((unsigned)w.nblocks), scan_t(kVxScanThreads);
-    hipLaunchKernelGGL(vx_count_masked_kernel, scan_n, scan_t, 0, st, d_mask, N, w.counts);
-    hipLaunchKernelGGL(vx_offsets_kernel, dim3(1), dim3(1024), 0, st, w.counts, w.nblocks, (int*)nullptr);
+    hipLaunchKernelGGL((count_flagged_kernel<kVxScanThreads, kVxScanPer, VxMasked>), scan_n, scan_t, 0, st, N, VxMasked{d_mask}, w.counts);
+    hipLaunchKernelGGL((scan_counts_kernel<1024, int, int, OpSum>), dim3(1), dim3(1024), 0, st, (const int*)w.counts, (int64_t)w.nblocks, w.counts,
+                       (int*)nullptr, OpSum{}, 0);
     hipLaunchKernelGGL(vx_compact_kernel, scan_n, scan_t, 0, st, d_grid_pos, d_mask, N, (const int*)w.counts, h.mn[0], h.mn[1], h.mn[2], ny, nz, M,
                        w.keys_in, w.idx_in, w.parent);
     AVL_HIP_CHECK(hipGetLastError());
@@ -512,15 +429,18 @@ int avl_label_voxels(const int32_t* d_grid_pos, const uint8_t* d_mask, int64_t N
     const hipError_t e = rocprim::radix_sort_pairs(tmp, tmp_bytes, w.keys_in, w.keys, w.idx_in, w.idx, (size_t)M, 0, bits, st);
     (void)hipFreeAsync(tmp, st);
     AVL_HIP_CHECK(e);
-    const unsigned sb = vx_stride_blocks(M);
+    const unsigned sb = stride_blocks(M);
     const int mblocks = (int)((M + kVxScanBlock - 1) / kVxScanBlock);
     int* rank_label = w.idx_in;
     const int axes = connectivity == 6 ? 1 : (connectivity == 18 ? 2 : 3);
     hipLaunchKernelGGL(vx_merge_kernel, dim3(sb), dim3(256), 0, st, (const unsigned long long*)w.keys, (int)M, ny, nz, axes, w.parent);
-    hipLaunchKernelGGL(vx_flatten_kernel, dim3(sb), dim3(256), 0, st, w.parent, (int)M);
-    hipLaunchKernelGGL(vx_count_roots_kernel, dim3((unsigned)mblocks), scan_t, 0, st, (const int*)w.parent, M, w.counts);
-    hipLaunchKernelGGL(vx_offsets_kernel, dim3(1), dim3(1024), 0, st, w.counts, mblocks, (int*)d_n);
-    hipLaunchKernelGGL(vx_number_kernel, dim3((unsigned)mblocks), scan_t, 0, st, (const int*)w.parent, M, (const int*)w.counts, rank_label);
+    const dim3 scan_m((unsigned)mblocks);
+    const UfIsRoot roots{w.parent};
+    hipLaunchKernelGGL((uf_flatten_kernel<256>), dim3(sb), dim3(256), 0, st, w.parent, M);
+    hipLaunchKernelGGL((count_flagged_kernel<kVxScanThreads, kVxScanPer, UfIsRoot>), scan_m, scan_t, 0, st, M, roots, w.counts);
+    hipLaunchKernelGGL((scan_counts_kernel<1024, int, int, OpSum>), dim3(1), dim3(1024), 0, st, (const int*)w.counts, (int64_t)mblocks, w.counts,
+                       (int*)d_n, OpSum{}, 0);
+    hipLaunchKernelGGL((number_flagged_kernel<kVxScanThreads, kVxScanPer, UfIsRoot>), scan_m, scan_t, 0, st, M, roots, (const int*)w.counts, rank_label);
     hipLaunchKernelGGL(vx_scatter_labels_kernel, dim3(sb), dim3(256), 0, st, (const int*)w.parent, (const int*)rank_label, (const int*)w.idx, (int)M, N,
                        (int*)d_labels);
     AVL_HIP_CHECK(hipGetLastError());
@@ -543,7 +463,7 @@ int avl_voxel_instance_table(const int32_t* d_grid_pos, const int32_t* d_labels,
     AVL_HIP_CHECK(hipMallocAsync((void**)&first_cell, (size_t)n * (sizeof(uint64_t) + sizeof(uint32_t)), st));
     uint32_t* score_key = reinterpret_cast<uint32_t*>(first_cell + n);
     long long* table = reinterpret_cast<long long*>(d_table);
-    const dim3 rows((unsigned)((n + 255) / 256)), sb(vx_stride_blocks(N));
+    const dim3 rows((unsigned)((n + 255) / 256)), sb(stride_blocks(N));
     hipLaunchKernelGGL(vx_table_init_kernel, rows, dim3(256), 0, st, table, first_cell, score_key, n);
     const dim3 pass1((unsigned)std::max<int64_t>(1, std::min<int64_t>((N + kVxTablePer - 1) / kVxTablePer, (int64_t)num_cus() * 4)));
     hipLaunchKernelGGL(vx_table_pass1_kernel, pass1, dim3(256), 0, st, d_grid_pos, d_labels, d_scores, N, n, table, score_key);

@@ -14,16 +14,16 @@
 // squared distances in row-major (i, j) order, which is np.argmin of the float64 norms: distinct integers below 2^52 have distinct
 // square roots.
 //
-// Labelling.  Union-find on one int32 parent per pixel, a parent always being a smaller linear index of the same island:
+// Labelling.  Union-find on one int32 parent per pixel (avl_unionfind.h states the invariant; an element is a pixel's linear index):
 //   init     a wave owns 64 columns of one row; a pixel starts at the first pixel of its horizontal run inside that segment (one
 //            ballot), so a row run is at most one link deep per segment before any merge
 //   merge    a pixel unites with the row above (N, else NW and NE; a pixel whose W and NW are set leaves N to its W neighbour) and, on
-//            the first lane, with the segment to its left.  unite() walks both sides to their roots and hangs the larger root below
-//            the smaller with atomicMin; a lost race continues from the value the atomic returned.  Links only ever point to
-//            smaller indices, so when the launch ends every island is one tree whose root is its smallest index = its first pixel
-//   flatten  parent = root.  A thread walks the whole chain, so one pass is enough however long a serpentine made it
-//   number   the root flags are counted per 1024 pixels, the counts scanned by one workgroup, and every root receives
-//            1 + the number of roots before it; the other pixels copy their root's label
+//            the first lane, with the segment to its left (uf_unite).  When the launch ends every island is one tree whose root is
+//            its first pixel
+//   flatten  parent = root (uf_flatten_kernel): one pass, however long a serpentine made a chain
+//   number   avl_scan.h: the roots are counted per 1024 pixels (count_flagged_kernel), the counts scanned by one workgroup
+//            (scan_counts_kernel), and every root receives 1 + the number of roots before it (number_flagged_kernel); the other
+//            pixels copy their root's label
 // Every result is a minimum, a maximum or a sum of integers: the bytes do not depend on the order in which the atomics land.
 //
 // Table.  Row k - 1 of label k: area, rmin, rmax, cmin, cmax, first_row, first_col, contour length (written by the count pass of the
@@ -36,7 +36,8 @@
 #include <climits>
 
 #include "avl_common.h"
-#include "avl_wave.h"
+#include "avl_scan.h"
+#include "avl_unionfind.h"
 
 namespace avl {
 
@@ -52,33 +53,6 @@ constexpr int kNpThreads = 256;
 constexpr int kNpTile = 1024;                   // points of B staged in LDS at a time
 constexpr int kNpMaxBlocks = 8192;              // workgroups of the pair kernel: beyond that a workgroup takes several tiles of B
 constexpr int64_t kNpMaxPoints = (int64_t)1 << 24;
-
-__device__ __forceinline__ int isl_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ int isl_find(const int* parent, int x) {
-    int y = isl_load(parent + x);
-    while (y != x) {
-        x = y;
-        y = isl_load(parent + x);
-    }
-    return x;
-}
-
-__device__ __forceinline__ void isl_unite(int* parent, int a, int b) {
-    for (;;) {
-        a = isl_find(parent, a);
-        b = isl_find(parent, b);
-        if (a == b) return;
-        if (a < b) {
-            const int t = a;
-            a = b;
-            b = t;
-        }
-        const int old = atomicMin(parent + a, b);   // a > b: hang a below b if a still is a root
-        if (old == a) return;
-        a = old;                                    // a had been linked meanwhile: its former parent and b remain to be united
-    }
-}
 
 // the first set pixel of lane's run within the wave's ballot m (lane's own bit is set)
 __device__ __forceinline__ int isl_run_start(unsigned long long m, int lane) {
@@ -106,69 +80,16 @@ __global__ __launch_bounds__(kIslSeg* kIslWaves) void isl_merge_kernel(const uin
     if (row[c] == 0) return;
     const int i = r * W + c;
     const bool w = c > 0 && row[c - 1] != 0;
-    if (lane == 0 && w) isl_unite(parent, i, i - 1);
+    if (lane == 0 && w) uf_unite(parent, i, i - 1);
     if (r == 0) return;
     const uint8_t* up = row - ld;
     const bool n = up[c] != 0, nw = c > 0 && up[c - 1] != 0, ne = c + 1 < W && up[c + 1] != 0;
     if (n) {
-        if (!(w && nw)) isl_unite(parent, i, i - W);          // w && nw: the W neighbour joins the same two runs
+        if (!(w && nw)) uf_unite(parent, i, i - W);          // w && nw: the W neighbour joins the same two runs
     } else {
-        if (nw) isl_unite(parent, i, i - W - 1);
-        if (ne) isl_unite(parent, i, i - W + 1);
+        if (nw) uf_unite(parent, i, i - W - 1);
+        if (ne) uf_unite(parent, i, i - W + 1);
     }
-}
-
-__global__ __launch_bounds__(256) void isl_flatten_kernel(int* __restrict__ parent, int64_t cells) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cells; i += (int64_t)gridDim.x * blockDim.x) {
-        const int p = isl_load(parent + i);
-        if (p >= 0 && p != (int)i) parent[i] = isl_find(parent, p);
-    }
-}
-
-__device__ __forceinline__ int isl_root_flags(const int* __restrict__ parent, int64_t cells, int64_t i0) {
-    int f = 0;
-#pragma unroll
-    for (int k = 0; k < kIslScanPer; ++k) {
-        const int64_t i = i0 + k;
-        if (i < cells && parent[i] == (int)i) f |= 1 << k;
-    }
-    return f;
-}
-
-__global__ __launch_bounds__(kIslScanThreads) void isl_count_kernel(const int* __restrict__ parent, int64_t cells, int* __restrict__ counts) {
-    __shared__ int s_w[kIslScanThreads / kWave];
-    const int f = isl_root_flags(parent, cells, (int64_t)blockIdx.x * kIslScanBlock + threadIdx.x * kIslScanPer);
-    int total;
-    block_excl_scan<kIslScanThreads / kWave>((int)__popc(f), OpSum{}, 0, s_w, &total);
-    if (threadIdx.x == 0) counts[blockIdx.x] = total;
-}
-
-// counts -> exclusive offsets in place, the total to *n; one workgroup
-__global__ __launch_bounds__(1024) void isl_offsets_kernel(int* __restrict__ counts, int nblocks, int* __restrict__ n) {
-    __shared__ int s_w[1024 / kWave];
-    int carry = 0;
-    for (int b0 = 0; b0 < nblocks; b0 += 1024) {
-        const int b = b0 + threadIdx.x;
-        const int v = b < nblocks ? counts[b] : 0;
-        int total;
-        __syncthreads();                                          // s_w may still be read from the round before
-        const int ex = block_excl_scan<1024 / kWave>(v, OpSum{}, 0, s_w, &total);
-        if (b < nblocks) counts[b] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) *n = carry;
-}
-
-__global__ __launch_bounds__(kIslScanThreads) void isl_number_kernel(const int* __restrict__ parent, int64_t cells, const int* __restrict__ offsets,
-                                                                     int* __restrict__ labels) {
-    __shared__ int s_w[kIslScanThreads / kWave];
-    const int64_t i0 = (int64_t)blockIdx.x * kIslScanBlock + threadIdx.x * kIslScanPer;
-    const int f = isl_root_flags(parent, cells, i0);
-    int total;
-    int rank = offsets[blockIdx.x] + block_excl_scan<kIslScanThreads / kWave>((int)__popc(f), OpSum{}, 0, s_w, &total);
-#pragma unroll
-    for (int k = 0; k < kIslScanPer; ++k)
-        if (f >> k & 1) labels[i0 + k] = ++rank;
 }
 
 // every pixel that is not a root: background 0, else its root's label (the roots were numbered by the launch before)
@@ -194,10 +115,10 @@ __global__ __launch_bounds__(256) void isl_table_init_kernel(int* __restrict__ t
 }
 
 __device__ __forceinline__ void isl_min(int* p, int v) {
-    if (v < isl_load(p)) atomicMin(p, v);
+    if (v < uf_load(p)) atomicMin(p, v);
 }
 __device__ __forceinline__ void isl_max(int* p, int v) {
-    if (v > isl_load(p)) atomicMax(p, v);
+    if (v > uf_load(p)) atomicMax(p, v);
 }
 
 __global__ __launch_bounds__(kIslSeg* kIslWaves) void isl_table_fill_kernel(const int* __restrict__ labels, int H, int W, int n,
@@ -376,10 +297,6 @@ static IslWork isl_work(int H, int W, void* ws) {
 
 static dim3 isl_seg_grid(int H, int W) { return dim3((unsigned)((W + kIslSeg - 1) / kIslSeg), (unsigned)((H + kIslWaves - 1) / kIslWaves)); }
 
-static unsigned isl_stride_blocks(int64_t cells) {
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((cells + 255) / 256, (int64_t)num_cus() * 16));
-}
-
 static void np_grid(int64_t na, int64_t nb, unsigned* gx, unsigned* gy) {
     *gx = (unsigned)((na + kNpThreads - 1) / kNpThreads);
     *gy = (unsigned)std::min<int64_t>((nb + kNpTile - 1) / kNpTile, std::max<int64_t>(1, kNpMaxBlocks / *gx));
@@ -416,13 +333,16 @@ int avl_label_islands(const uint8_t* d_mask_u8, int64_t ld, int H, int W, int32_
     hipStream_t st = as_stream(stream);
     const int64_t cells = (int64_t)H * W;
     const dim3 seg = isl_seg_grid(H, W), segb(kIslSeg * kIslWaves);
-    const unsigned sb = isl_stride_blocks(cells);
+    const unsigned sb = stride_blocks(cells);
+    const dim3 scan_n((unsigned)nblocks), scan_t(kIslScanThreads);
+    const UfIsRoot roots{parent};
     hipLaunchKernelGGL(isl_init_kernel, seg, segb, 0, st, d_mask_u8, ld, H, W, parent);
     hipLaunchKernelGGL(isl_merge_kernel, seg, segb, 0, st, d_mask_u8, ld, H, W, parent);
-    hipLaunchKernelGGL(isl_flatten_kernel, dim3(sb), dim3(256), 0, st, parent, cells);
-    hipLaunchKernelGGL(isl_count_kernel, dim3((unsigned)nblocks), dim3(kIslScanThreads), 0, st, (const int*)parent, cells, counts);
-    hipLaunchKernelGGL(isl_offsets_kernel, dim3(1), dim3(1024), 0, st, counts, nblocks, (int*)d_n);
-    hipLaunchKernelGGL(isl_number_kernel, dim3((unsigned)nblocks), dim3(kIslScanThreads), 0, st, (const int*)parent, cells, (const int*)counts,
+    hipLaunchKernelGGL((uf_flatten_kernel<256>), dim3(sb), dim3(256), 0, st, parent, cells);
+    hipLaunchKernelGGL((count_flagged_kernel<kIslScanThreads, kIslScanPer, UfIsRoot>), scan_n, scan_t, 0, st, cells, roots, counts);
+    hipLaunchKernelGGL((scan_counts_kernel<1024, int, int, OpSum>), dim3(1), dim3(1024), 0, st, (const int*)counts, (int64_t)nblocks, counts,
+                       (int*)d_n, OpSum{}, 0);
+    hipLaunchKernelGGL((number_flagged_kernel<kIslScanThreads, kIslScanPer, UfIsRoot>), scan_n, scan_t, 0, st, cells, roots, (const int*)counts,
                        (int*)d_labels);
     hipLaunchKernelGGL(isl_relabel_kernel, dim3(sb), dim3(256), 0, st, (const int*)parent, cells, (int*)d_labels);
     AVL_HIP_CHECK(hipGetLastError());

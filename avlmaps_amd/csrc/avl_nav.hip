@@ -28,7 +28,7 @@
 #include <new>
 
 #include "avl_common.h"
-#include "avl_wave.h"
+#include "avl_scan.h"
 
 namespace avl {
 
@@ -233,32 +233,7 @@ __global__ __launch_bounds__(kNavScanThreads) void nav_vertex_count_kernel(const
     }
 }
 
-// pass 2: exclusive scan of the block counts in place, total into counts[nb] (one workgroup, sequential over chunks)
-__global__ __launch_bounds__(256) void nav_scan_kernel(int32_t* __restrict__ counts, int nb) {
-    __shared__ int s_v[256];
-    __shared__ int s_carry;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    for (int base = 0; base < nb; base += 256) {
-        const int t = base + (int)threadIdx.x;
-        const int v = t < nb ? counts[t] : 0;
-        s_v[threadIdx.x] = v;
-        __syncthreads();
-        for (int off = 1; off < 256; off <<= 1) {               // Hillis-Steele inclusive scan
-            const int add = threadIdx.x >= (unsigned)off ? s_v[threadIdx.x - off] : 0;
-            __syncthreads();
-            s_v[threadIdx.x] += add;
-            __syncthreads();
-        }
-        const int carry = s_carry;
-        if (t < nb) counts[t] = carry + s_v[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == 255) s_carry = carry + s_v[255];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) counts[nb] = s_carry;
-}
-
+// pass 2 is avl_scan.h's scan_counts_kernel: the block counts become exclusive offsets in place, the total goes to counts[nb]
 // pass 3: write the vertices in raster order (ballot prefix inside a round, wave totals through LDS, the block's scanned offset)
 __global__ __launch_bounds__(kNavScanThreads) void nav_vertex_write_kernel(const uint16_t* __restrict__ pix, int H, int W,
                                                                            const int32_t* __restrict__ offsets, int64_t V,
@@ -765,7 +740,8 @@ static int nav_build(AvlNavGraph* g, const uint8_t* h_obs, hipStream_t st) {
         }
         hipLaunchKernelGGL(nav_pix_kernel, dim3(nav_blocks((int64_t)(H + 2) * (W + 2), 256)), dim3(256), 0, st, d_obs, H, W, g->pix);
         hipLaunchKernelGGL(nav_vertex_count_kernel, dim3(nb), dim3(kNavScanThreads), 0, st, g->pix, H, W, d_counts);
-        hipLaunchKernelGGL(nav_scan_kernel, dim3(1), dim3(256), 0, st, d_counts, nb);
+        hipLaunchKernelGGL((scan_counts_kernel<256, int32_t, int32_t, OpSum>), dim3(1), dim3(256), 0, st, (const int32_t*)d_counts, (int64_t)nb,
+                           d_counts, d_counts + nb, OpSum{}, 0);
         e = hipMemcpyAsync(&total, d_counts + nb, sizeof(int32_t), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e == hipSuccess) e = hipGetLastError();

@@ -118,6 +118,21 @@ def test_many_waves_and_workgroups(ops, density, connectivity, least, largest):
     assert n >= least and table[:, 0].max() >= largest          # the input is what it claims: many instances / one long union chain
 
 
+def test_labels_over_two_rounds_of_the_offsets_scan(ops):
+    """1024 * 1024 + 1 voxels are 1025 scan blocks of 1024, one more than the one-workgroup scan of the block counts has threads: its
+    second round carries the total of the first, and the last voxel, the only one of block 1024, is compacted behind it"""
+    rng = np.random.default_rng(6)
+    n_vox = 1024 * 1024 + 1
+    cells = np.argwhere(np.ones((1025, 1024, 1), bool))[rng.permutation(1025 * 1024)[:n_vox]].astype(np.int32)
+    mask = (rng.random(n_vox) < 0.3).astype(np.uint8)
+    mask[-1] = 1                                                # the voxel whose place comes from the carried total
+    labels, n, _, _ = oracle(cells, mask, 26)
+    assert n > 1024                                             # 8-connected sites at 30 %: far below percolation, tens of thousands
+    with ops.label_voxels(cells, mask, connectivity=26) as got:
+        assert got.n == n, (got.n, n)
+        assert got.labels.dtype == np.int32 and np.array_equal(got.labels, labels)
+
+
 # ------------------------------------------------------------------ 3. heights beyond one 64-bit word
 @pytest.mark.parametrize("shape,density,connectivity", [((3, 3, 130), 0.5, 6), ((40, 40, 70), 0.08, 26)])
 def test_tall_boxes(ops, shape, density, connectivity):

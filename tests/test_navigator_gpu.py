@@ -639,6 +639,17 @@ def test_vertices_over_two_compaction_blocks():
     g.close()
 
 
+def test_vertices_over_two_rounds_of_the_block_count_scan():
+    """520 x 512 = 266 240 pixels are 260 compaction blocks of 1024, more than the 256 threads of the one-workgroup scan of the block
+    counts: the vertices of the last four blocks (rows 512 and below) are written behind the total that the first round carries"""
+    free = _random_map(12, H=520, W=512, noise=0.0)           # the seed puts five of the 140 vertices there
+    verts = oracle_vertices(free)
+    assert (verts[:, 0] * 512 + verts[:, 1] >= 256 * 1024).any()
+    g = _graph(free)
+    assert np.array_equal(g.vertices(), verts)
+    g.close()
+
+
 def test_plans_reuse_the_graph():
     free = _random_map(7)
     rng = np.random.default_rng(7)
