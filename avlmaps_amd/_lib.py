@@ -212,6 +212,10 @@ _SIGS = {
     "avl_label_voxels_work_bytes": (C.c_int, [_i64, C.POINTER(_sz)]),
     "avl_label_voxels": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp, _vp, _vp, _sz, _vp]),
     "avl_voxel_instance_table": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
+    # open-set queries (csrc/avl_colselect.hip): replace map/clip_map.py:62-75, np.percentile and the comparison per category on the host
+    "avl_colselect_workspace_bytes": (C.c_int, [C.c_int, C.POINTER(_sz)]),
+    "avl_colselect_f32": (C.c_int, [_vp, _i64, C.c_int, _i64, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "avl_cols_above_f32": (C.c_int, [_vp, _i64, C.c_int, _i64, _vp, C.c_int, _vp, _vp, _vp, _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -6,6 +6,7 @@ and image branches, :23-142; the Open3D viewer and the habitat branches are not 
     python -m avlmaps_amd.apps.index_map --data-dir <scene> --modality fused [--object NAME]... [--area NAME]... [--sound NAME]...
                                          [--image PNG] [--object-decay R] [--area-decay R] [--sound-decay R] [--image-decay R]
     ... --modality object --categories A,B,...   [--instances] [--instance K] [--min-voxels M] [--connectivity 6|18|26]
+    ... --modality object --categories A,B,...   --quantile P [--instances]
     ... any modality ...                 [--render PNG [--view topdown|frame:<i>|orbit] [--render-size W H]] [--save-ply PLY]
 
 object (default): the VLMap text query; area: the area map's frame embeddings (area_map/clip_sparse_map.h5df); sound: the sound
@@ -17,6 +18,11 @@ habitat_lang_robot.py:427-430); --save writes the (N,) heat vector as .npy (floa
 --instances lists the objects of the queried category in 3-D (VLMap.get_instances_3d: the connected components of its voxels), one
 line each: label, voxels, box, centre, best score.  --instance K makes --save, --render and --save-ply use the heat of that object
 alone (AVLMap.index_object_instance).  Both need --categories; --min-voxels and --connectivity are their two parameters.
+
+--quantile P makes the object query open-set: the voxels of --query's category are those whose score lies above the P-th percentile
+of the category's own score column (VLMap.index_map_quantile; upstream's map/clip_map.py:45-75 uses 95), not those whose row
+maximum it is, so the answer does not depend on the other names in --categories.  The heat, --save, --render and --save-ply follow
+that mask, and --instances lists its connected components.  Needs --categories.
 
 --render writes the picture the reference shows in a window (visualize_heatmap_3d, application/index_map.py): the heat in JET
 colours over the map's own, rendered on the GPU (AVLMap.render_heat).  --view topdown (default) is the map from above, frame:<i>
@@ -47,6 +53,9 @@ def parse_args(argv=None):
                     help="object: --save / --render / --save-ply use the heat of instance K alone (needs --categories)")
     ap.add_argument("--min-voxels", type=int, default=50, help="--instances / --instance: drop objects with fewer voxels (default 50)")
     ap.add_argument("--connectivity", type=int, choices=[6, 18, 26], default=26, help="--instances / --instance: voxel adjacency (default 26)")
+    ap.add_argument("--quantile", type=float, default=None, metavar="P",
+                    help="object: the voxels above the P-th percentile of the category's own scores instead of the row maximum "
+                         "(needs --categories)")
     ap.add_argument("--image", default=None, help="query image (PNG) of --modality image and fused")
     ap.add_argument("--image-pose", type=int, default=0, help="row of poses.txt the model-free localiser places the image at")
     ap.add_argument("--object", action="append", default=[], help="fused: an object name (repeatable)")
@@ -76,6 +85,13 @@ def parse_args(argv=None):
     if args.instances or args.instance is not None:
         if args.modality != "object" or not args.categories:
             ap.error("--instances and --instance need --modality object and --categories")
+    if args.quantile is not None:
+        if args.modality != "object" or not args.categories:
+            ap.error("--quantile needs --modality object and --categories")
+        if not 0.0 <= args.quantile <= 100.0:
+            ap.error(f"--quantile {args.quantile}: a percentile lies in 0 .. 100")
+        if args.instance is not None:
+            ap.error("--instance picks an object of the row-maximum mask; with --quantile use --instances")
     return args
 
 
@@ -106,6 +122,27 @@ def print_instances(instances, name: str) -> None:
         r0, r1, c0, c1, h0, h1 = it.bbox
         print(f"  instance {it.label}: {it.count} voxels, rows {r0}..{r1}, cols {c0}..{c1}, heights {h0}..{h1}, "
               f"centre ({it.center[0]:.2f}, {it.center[1]:.2f}, {it.center[2]:.2f}), best score {it.best_score:.4f} at voxel {it.best_voxel}")
+
+
+def quantile_query(avlmap, args, cats, decay):
+    """--quantile: (heat, instances or None) of the voxels above the category's own percentile"""
+    from avlmaps_amd import ops
+    from avlmaps_amd.map.map import cfg_get
+    vm = avlmap.vlmap
+    vm.init_categories(cats[1:-1])
+    cat_id, mask, counts = vm._quantile_mask_device(args.query, args.quantile)
+    print(f"{int(counts[cat_id])} of {len(vm.grid_pos)} voxels lie above the {args.quantile:g}th percentile "
+          f"({vm.quantile_thresholds(args.quantile)[cat_id]:.6f}) of {vm.categories[cat_id]!r}; ", end="")
+    if not counts[cat_id]:
+        raise SystemExit(f"--quantile {args.quantile:g}: no voxel lies above it")
+    instances = None
+    if args.instances:
+        scores = np.ascontiguousarray(vm.scores_mat[:, cat_id], dtype=np.float32)
+        with ops.label_voxels(vm._device_pos(), mask, connectivity=args.connectivity, scores=scores, device=True) as inst:
+            table, best = inst.table, inst.best_score
+            instances = [ops.Instance3D.from_row(k + 1, table[k], best[k]) for k in range(inst.n) if table[k, 0] >= args.min_voxels]
+    cs = cfg_get(cfg_get(avlmap.config, "params"), "cs")
+    return vm.heatmap_from_mask(mask, cs, decay).numpy(), instances
 
 
 def fused_decay_rates(args) -> dict:
@@ -155,9 +192,15 @@ def main(argv=None):
         cats = None
         if args.categories:
             cats = ["void"] + [c.strip() for c in args.categories.split(",")] + ["void"]   # upstream passes categories[1:-1]
-        heat = avlmap.index_object(args.query, init_categories=cats, decay_rate=decay)
-        print(f"{int((heat == 1.0).sum())} of {len(heat)} voxels match {args.query!r}; ", end="")
-        if args.instances:
+        if args.quantile is not None:
+            heat, instances = quantile_query(avlmap, args, cats, decay)
+            if instances is not None:
+                print()
+                print_instances(instances, args.query)
+        else:
+            heat = avlmap.index_object(args.query, init_categories=cats, decay_rate=decay)
+            print(f"{int((heat == 1.0).sum())} of {len(heat)} voxels match {args.query!r}; ", end="")
+        if args.instances and args.quantile is None:
             print()
             print_instances(vm.get_instances_3d(args.query, args.min_voxels, args.connectivity), args.query)
         if args.instance is not None:

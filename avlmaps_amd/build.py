@@ -41,6 +41,7 @@ SOURCES = {
     "avl_gtmap.hip": ["-ffp-contract=off"],        # a vote's voxel is K1's point and cell (the explicit fma chain); everything after it is integer
     "avl_resize.hip": ["-ffp-contract=off"],       # integer kernels; the flag keeps the file in line with the other 2-D sources
     "avl_instances.hip": ["-ffp-contract=off"],    # integer kernels; the flag keeps the file in line with the other integer sources
+    "avl_colselect.hip": ["-ffp-contract=off"],    # integer kernels and one float64 comparison; nothing to fuse, and it stays so
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fvisibility=hidden", "-Wall",
           "-Wno-unused-function", "-munsafe-fp-atomics"]

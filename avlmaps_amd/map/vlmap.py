@@ -352,6 +352,72 @@ class VLMap(Map):
         pooled = self._predict_mask_device(name).numpy()
         return pooled[r0:r1, c0:c1].astype(np.asarray(self.obstacles_cropped).dtype)
 
+    # ------------------------------------------------------------------ open-set queries: a category's own score quantile
+    # closed-set above (a voxel belongs to the ONE category that is its row maximum); below, a category's voxels are those above its own
+    # score column's percentile: masks may overlap or leave voxels unclaimed.  index_map_quantile's docstring has the rule.
+    def _scores_device(self):
+        """scores_mat (N, Q) float32 resident on the device, uploaded once per init_categories (like _argmax_device)"""
+        from .. import parallel
+        from ..device import DeviceArray
+        if self.scores_mat is None or self.categories is None:
+            raise Exception("Categories are not preloaded. Call init_categories(categories: List[str]) to initialize categories.")
+        if parallel.rank_world()[1] > 1 and self.shard_index_rows:
+            raise NotImplementedError("quantile queries on rows sharded over ranks: a global quantile needs a merged histogram")
+        if getattr(self, "_dev_scores_src", None) is not self.scores_mat:
+            self._dev_scores = DeviceArray.from_numpy(np.ascontiguousarray(self.scores_mat, dtype=np.float32))
+            self._dev_scores_src = self.scores_mat
+            self._quantile_cache = {}
+        return self._dev_scores
+
+    def quantile_thresholds(self, percentile: float = 95.0) -> np.ndarray:
+        """(Q,) float64: the percentile of every column of scores_mat, np.percentile(scores_mat[:, c].astype(np.float64), percentile)
+        bit for bit (ops.column_quantiles: a radix select on the device, the interpolation in float64 on the host).  Kept per
+        percentile until init_categories runs again."""
+        from .. import ops
+        scores = self._scores_device()
+        key = float(percentile)
+        if key not in self._quantile_cache:
+            self._quantile_cache[key] = ops.column_quantiles(scores, key)
+        return self._quantile_cache[key]
+
+    def _quantile_mask_device(self, name: str, percentile: float = 95.0):
+        """(category id, (N,) uint8 device mask of the voxels above the category's own percentile, the per-category counts)"""
+        from .. import ops
+        from ..utils.index_utils import find_similar_category_id
+        scores = self._scores_device()
+        cat_id = find_similar_category_id(name, self.categories)
+        _, counts, mask = ops.cols_above(scores, self.quantile_thresholds(percentile), column=cat_id, device=True)
+        return cat_id, mask, counts
+
+    def index_map_quantile(self, name: str, percentile: float = 95.0) -> np.ndarray:
+        """bool mask (N,): float64(scores_mat[:, c]) > quantile_thresholds(percentile)[c] for `name`'s category c -- the voxels that
+        look most like the category on its own score column (95: the top twentieth), whatever the other categories score.  Needs
+        init_categories; NotImplementedError when the rows are sharded over ranks (a global quantile needs a merged histogram).
+        The rule is upstream's map/clip_map.py:45-75 (CLIPMap.load_categories), with these differences: upstream divides each column
+        by its maximum in float32 first, compares in float32 and works on a dense 2-D CLIP grid; here the threshold is the float64
+        quantile of the RAW column (np.percentile(column.astype(np.float64), percentile) bit for bit) over the map's voxel list and
+        the comparison is float64(score) > threshold.  Scaling by a positive maximum does not change the order, so the two rules
+        select the same ranks up to float32 rounding.  Nothing was compared with CLIPMap, which cannot be imported (its imports name
+        a utils package that does not exist)."""
+        return self._quantile_mask_device(name, percentile)[1].numpy().astype(bool)
+
+    def quantile_labels(self, percentile: float = 95.0):
+        """(words, counts): words (N, ceil(Q / 64)) uint64, bit c % 64 of word c / 64 of row r set iff voxel r lies above category c's
+        percentile (a voxel may carry several categories or none); counts (Q,) int64, the voxels of every category.  One pass over
+        the resident scores (ops.cols_above)."""
+        from .. import ops
+        return ops.cols_above(self._scores_device(), self.quantile_thresholds(percentile))
+
+    def get_quantile_predict_mask(self, name: str, percentile: float = 95.0) -> np.ndarray:
+        """get_predict_mask for the quantile rule: the top-down mask over the obstacle crop, 1 where a voxel of index_map_quantile's
+        mask lies in the column, in obstacles_cropped's shape and dtype (ops.pool_label_2d, cut to the crop like get_predict_mask)."""
+        from .. import ops
+        self._scores_device()                            # raises when init_categories has not run
+        r0, r1, c0, c1 = self._crop_window()
+        mask = self._quantile_mask_device(name, percentile)[1]
+        pooled = ops.pool_label_2d(mask, self._device_pos(), int(self.gs), device=True).numpy()
+        return pooled[r0:r1, c0:c1].astype(np.asarray(self.obstacles_cropped).dtype)
+
     def _instances_3d(self, name: str, connectivity: int = 26):
         """(category id, ops.VoxelInstances) of the voxels whose argmax is `name`'s category, labels on the device.  The last result
         stays on the map until the categories, the category or the connectivity change."""

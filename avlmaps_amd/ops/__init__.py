@@ -60,6 +60,9 @@ from .resize import (  # noqa: F401
 from .instances import (  # noqa: F401
     Instance3D, INSTANCE_TABLE_COLS, INSTANCES_MAX_BOX_SIDE, label_voxels, VoxelInstances,
 )
+from .select import (  # noqa: F401
+    cols_above, COLSELECT_SLOTS, column_order_stats, column_quantiles, ColumnOrderStats, quantile_index, quantile_lerp,
+)
 # the shared marshalling layer; its one device predicate keeps both of the names it had here
 from ._args import (  # noqa: F401
     _dev_u8, _image_any, _image_shape, _image_u8, _is_dev, _is_dev as _on_device, _result,

@@ -1153,6 +1153,34 @@ AVL_API int avl_label_voxels(const int32_t* d_grid_pos, const uint8_t* d_mask, i
 AVL_API int avl_voxel_instance_table(const int32_t* d_grid_pos, const int32_t* d_labels, const float* d_scores, int64_t N, int32_t n,
                                      int64_t* d_table, float* d_best_score, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * (19) open-set queries: exact column order statistics of the score matrix and "above the column's own threshold"
+ *     (csrc/avl_colselect.hip).  d_scores is a row-major float32 matrix (N, Q) with row stride ld >= Q elements, 1 <= N < 2^31.
+ *     The order is np.sort's: -inf < ... < -0 = +0 < ... < +inf < NaN, every NaN counts as one largest value, a selected zero
+ *     comes back as +0.  Every result is a count, a minimum or an element of the matrix: the bytes do not depend on scheduling.
+ *     Arguments are checked before any device work.
+ * ------------------------------------------------------------------------------------------------ */
+/* The workspace of avl_colselect_f32: one size for any number of slots (their groups of 64 use it one after the other).
+ * Replaces map/clip_map.py:62-75, which partitions a host copy of every column (np.percentile). */
+AVL_API int avl_colselect_workspace_bytes(int n_slots, size_t* bytes);
+/* Slot s = (h_columns[s], h_ks[s]), host tables of n_slots entries with 0 <= column < Q and 0 <= k < N; a column may appear in
+ * several slots.  Per slot, to device arrays of n_slots entries: d_v_k = the k-th smallest value of the column (k = 0: the minimum),
+ * d_v_next = the (k+1)-th smallest (= d_v_k when k = N - 1), d_count_lt / d_count_le = the number of elements before / up to the
+ * run of values equal to v_k in the sorted column (NaN = NaN there), d_nan_count = the column's NaNs.  A most-significant-digit
+ * radix select: five streaming passes over the matrix per 64 slots, a fixed number of launches.  Asynchronous; the host tables
+ * are read before the call returns.  Replaces map/clip_map.py:62-75 (np.percentile of every column on the host): the quantile is
+ * v_k + (v_next - v_k) * t in float64, computed by the caller. */
+AVL_API int avl_colselect_f32(const float* d_scores, int64_t N, int Q, int64_t ld, const int32_t* h_columns, const int64_t* h_ks,
+                              int n_slots, float* d_v_k, float* d_v_next, int64_t* d_count_lt, int64_t* d_count_le, int64_t* d_nan_count,
+                              void* ws, size_t ws_bytes, void* stream);
+/* One pass over the same matrix (N >= 0) against d_thresholds (Q,) float64: d_bits (N, ceil(Q / 64)) uint64, bit c % 64 of word
+ * c / 64 of row r set iff (double)d_scores[r * ld + c] > d_thresholds[c] (NaN on either side: not set; bits past column Q - 1 are 0);
+ * d_counts (Q,) int64 = the set bits of every column; d_mask (N,) uint8 = column mask_column's bits as the
+ * 0 / 1 voxel mask the other entry points take, or NULL with mask_column = -1.  Asynchronous.  Replaces map/clip_map.py:62-75
+ * (mask = column > threshold, per category, on the host). */
+AVL_API int avl_cols_above_f32(const float* d_scores, int64_t N, int Q, int64_t ld, const double* d_thresholds, int mask_column,
+                               uint64_t* d_bits, int64_t* d_counts, uint8_t* d_mask, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
