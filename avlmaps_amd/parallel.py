@@ -814,7 +814,10 @@ def plan_merge_directory(cell: "torch.Tensor", first_key: "torch.Tensor", group=
         m4r = torch.empty(R, dtype=torch.uint8, device=dev)
         cnt_dir = torch.empty(2 * ws + 1, dtype=i64, device=dev)
         work, wb = _merge_work(hip, R, dev)
-        _lib.check(hip.avl_merge_dir_scan(R, recv.data_ptr(), allh_d[:, rank].contiguous().data_ptr(), ws, 31, perm.data_ptr(), first.data_ptr(),
+        # (a column of allh_d is a copy: it has a name so that it lives until the launch is queued -- the pointer of a temporary is
+        # that of a block the allocator may already have handed to another thread of the process)
+        rc_d = allh_d[:, rank].contiguous()
+        _lib.check(hip.avl_merge_dir_scan(R, recv.data_ptr(), rc_d.data_ptr(), ws, 31, perm.data_ptr(), first.data_ptr(),
                                           prev_r.data_ptr(), next_r.data_ptr(), reply.data_ptr(), m3r.data_ptr(), m4r.data_ptr(),
                                           cnt_dir.data_ptr(), work.data_ptr(), wb, st), "avl_merge_dir_scan")
         first, m3r, m4r = first.view(torch.bool), m3r.view(torch.bool), m4r.view(torch.bool)

@@ -20,35 +20,8 @@ def ops():
     return ops
 
 
+from merge_worlds import build_shards  # noqa: E402,F401 -- (tools/fuzz_merge2.py reaches it through this module too)
 from thread_world import run_ranks  # noqa: E402
-
-
-def build_shards(ops, ws, D=64, nfr=24, seed=7, rate=5, cs=0.1, gs=400, replay=True):
-    from oracle import avl_oracle as O
-    from test_builder_gpu import synth_scene
-    rng = np.random.default_rng(seed)
-    H, W, Hf, Wf = 120, 160, 58, 77
-    cam_h = 1.5
-    calib = np.array([W / 2, 0, W / 2, 0, W / 2, H / 2, 0, 0, 1.0])
-    depths, rgbs, feats, poses = synth_scene(rng, nfr, H, W, Hf, Wf, D)
-    b2c, bt = O.setup_transforms([1, 0, 0, 0, -1, 0, 0, 0, -1], cam_h, [0, 0, -1], [-1, 0, 0], [0, 1, 0])
-    Ts = O.pc_transforms(poses, bt, b2c)
-    rs = np.random.RandomState(3)
-    samples = [O.sample_indices(rs, H * W, rate) for _ in range(nfr)]
-    fs = [np.ascontiguousarray(np.transpose(f, (1, 2, 0))) for f in feats]
-    vh = int(cam_h / cs)
-    from avlmaps_amd import parallel
-
-    def build(lo, hi):
-        acc = ops.VoxelAccumulator(gs, cs, vh, D, capacity=1 << 16)
-        if replay:
-            acc.enable_replay_log(max(1, (hi - lo) * len(samples[0])))
-        for i in range(lo, hi):
-            acc.integrate_frame(depths[i], calib, Ts[i], samples[i], fs[i], rgbs[i], frame_idx=i)
-        return acc
-    whole = build(0, nfr)
-    shards = [build(*parallel.shard_frames(nfr, r, ws)) for r in range(ws)]
-    return whole, shards, gs, vh
 
 
 @pytest.mark.parametrize("ws,D", [(1, 64), (2, 64), (3, 30), (8, 64), (8, 5)])

@@ -183,8 +183,10 @@ def test_argsort_bits_is_torchs_stable_argsort(env):
 
 def test_merge_plan_kernels_equal_the_tensor_code(env, monkeypatch):
     """csrc/avl_merge.hip (avl_merge_partition / _dir_scan / _classify) against the tensor code of plan_merge_directory on the same
-    device tensors: every output of the plan identical -- one rank here; the N-rank builds of test_api_gpu run the kernels with
-    real neighbours and compare the merged map with the single-rank one"""
+    device tensors: every output of the plan identical -- one rank here, so every cell has one contributor.  With real neighbours
+    (2, 3 and 8 ranks as threads) the kernels run in tests/test_merge_plans_gpu.py: the plan alone against a brute-force oracle in
+    test_plan_kernels_with_neighbours_equal_the_oracle_and_the_tensor_code, the whole directory plan against the single-process map
+    in test_directory_plan_through_the_product.  (The N-rank builds of test_api_gpu take the gather plan.)"""
     import torch
     from avlmaps_amd import parallel
     g = torch.Generator(device="cpu").manual_seed(3)

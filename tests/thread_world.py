@@ -1,10 +1,19 @@
 """parallel._Coll's interface over the threads of ONE process: the merge's choreography runs for several ranks without process groups
-(CPU tensors with the NumPy twin of the kernels, or device tensors with the HIP kernels on one GPU)."""
+(CPU tensors with the NumPy twin of the kernels, or device tensors with the HIP kernels on one GPU).
+
+thread_groups() makes every parallel.* function accept such a stand-in as its `group`, so the directory and general plans
+(plan_merge_directory, merge_raw_sharded, merge_accumulator_sharded, ...) run unchanged for several ranks of one process."""
+import contextlib
+import os
+import queue
 import threading
 
 
 class _NoLock:
     wait_s, held = 0.0, False
+
+
+_ABORT = object()       # what a failing rank leaves in every point-to-point queue: a rank blocked in recv raises instead of waiting
 
 
 class ThreadWorld:
@@ -14,6 +23,14 @@ class ThreadWorld:
         # inside collectives incl. waiting for the lock is booked to comm_s -- a rank's wall time minus comm_s is then what it computes
         # on a GPU of its own (tools/probe_merge2.py)
         self.lock = threading.Lock() if exclusive else None
+        # point-to-point: one FIFO per ordered (source, destination) pair
+        self.fifo = {(s, d): queue.SimpleQueue() for s in range(ws) for d in range(ws)}
+
+    def abort(self):
+        """a rank failed: nobody may stay inside a collective or a recv"""
+        self.barrier.abort()
+        for q in self.fifo.values():
+            q.put(_ABORT)
 
 
 class ThreadColl:
@@ -21,7 +38,7 @@ class ThreadColl:
 
     class _Dist:
         class ReduceOp:
-            MAX = "max"
+            MIN, MAX, SUM = "min", "max", "sum"
 
         @staticmethod
         def get_backend(group):
@@ -85,9 +102,83 @@ class ThreadColl:
     def all_to_all_finish(self, handle):
         return handle[1]
 
-    def all_reduce(self, t, op):
+    @staticmethod
+    def _op_name(op):
+        """"min" / "max" / "sum" from a member of _Dist.ReduceOp or of torch.distributed.ReduceOp"""
+        if isinstance(op, str):
+            name = op
+        else:
+            import torch.distributed as dist
+            name = next((k.lower() for k in ("MIN", "MAX", "SUM") if op == getattr(dist.ReduceOp, k)), None)
+        if name not in ("min", "max", "sum"):
+            raise ValueError(f"ThreadColl: reduce op {op!r} is not MIN, MAX or SUM")
+        return name
+
+    @staticmethod
+    def _reduced(parts, name):
+        """the ranks' tensors folded in rank order into a NEW tensor (a sum of floats is then the same on every rank and in every run)"""
         import torch
-        return self._round(t, lambda s: torch.stack([x for x in s]).max(0).values)
+        acc = parts[0].clone()
+        for x in parts[1:]:
+            acc = torch.minimum(acc, x) if name == "min" else torch.maximum(acc, x) if name == "max" else acc + x
+        return acc
+
+    def all_reduce(self, t, op):
+        """in place, like parallel._Coll.all_reduce; returns t"""
+        name = self._op_name(op)
+        res = self._round(t, lambda s: self._reduced(s, name))      # (the peers read t until the round's second barrier: copy after it)
+        t.copy_(res)
+        return t
+
+    def reduce(self, t, dst, op):
+        """in place on rank dst; the other ranks' tensors stay as they are.  Returns t"""
+        name = self._op_name(op)
+        res = self._round(t, lambda s: self._reduced(s, name) if self.rank == dst else t)
+        if self.rank == dst:
+            t.copy_(res)
+        else:
+            self.bytes_out += t.numel() * t.element_size()
+        return t
+
+    def broadcast(self, t, src):
+        res = self._round(t, lambda s: t if self.rank == src else s[src].clone())
+        if self.rank == src:
+            self.bytes_out += t.numel() * t.element_size()
+        else:
+            t.copy_(res)
+        return t
+
+    def send(self, t, dst):
+        """a copy of t joins the FIFO of (this rank -> dst); does not wait for the receiver"""
+        import time
+        t0 = time.perf_counter()
+        c = t.clone()
+        self._sync(c)
+        self.w.fifo[(self.rank, dst)].put(c)
+        self.comm_s += time.perf_counter() - t0
+        self.bytes_out += t.numel() * t.element_size()
+        self.calls += 1
+
+    def recv(self, t, src):
+        """blocks until rank src's next send to this rank arrives and copies it INTO t (which may be a slice of a larger tensor)"""
+        import time
+        t0 = time.perf_counter()
+        self._sync(t)
+        if self.w.lock is not None:
+            self.w.lock.release()
+        q = self.w.fifo[(src, self.rank)]
+        got = q.get()
+        if self.w.lock is not None:
+            self.w.lock.acquire()
+        if got is _ABORT:
+            q.put(_ABORT)                       # (for this rank's later recvs, should it catch the error and go on)
+            raise threading.BrokenBarrierError(f"rank {self.rank}: recv from rank {src} -- another rank failed")
+        assert got.shape == t.shape and got.dtype == t.dtype, (self.rank, src, tuple(got.shape), tuple(t.shape), got.dtype, t.dtype)
+        t.copy_(got)
+        self._sync(t)
+        self.comm_s += time.perf_counter() - t0
+        self.calls += 1
+        return t
 
 
 def run_ranks(ws, fn, exclusive=False):
@@ -109,12 +200,45 @@ def run_ranks(ws, fn, exclusive=False):
                         world.lock.release()
                     except RuntimeError:
                         pass
-        except BaseException as e:      # noqa: BLE001 -- a failing rank must not leave the others in a barrier
+        except BaseException as e:      # noqa: BLE001 -- a failing rank must not leave the others in a barrier or a recv
             errs.append(e)
-            world.barrier.abort()
+            world.abort()
     th = [threading.Thread(target=body, args=(r,)) for r in range(ws)]
     [t.start() for t in th]
     [t.join() for t in th]
     if errs:
-        raise errs[0]
+        # the rank that failed first, not one of those it released (they only report the broken barrier)
+        first = [e for e in errs if not isinstance(e, threading.BrokenBarrierError)]
+        raise (first or errs)[0]
     return out
+
+
+@contextlib.contextmanager
+def thread_groups(**env):
+    """While this context is open, `group=<ThreadColl>` carries a rank's collectives into every avlmaps_amd.parallel function
+    unchanged: parallel._Coll(group) hands the stand-in back and parallel._dist_on(group) is true for it (and false without a
+    group, as in a process without torch.distributed).  Keyword arguments are environment variables of the merge
+    (AVLMAPS_MERGE_PLAN="directory", AVLMAPS_MERGE_KERNELS="0", ...; None removes one): the threads of a world share the process
+    environment, so they are set HERE, around run_ranks, never inside a rank, and put back on the way out.
+
+        with thread_groups(AVLMAPS_MERGE_PLAN="directory"):
+            outs = run_ranks(ws, lambda r, coll: parallel.merge_accumulator_sharded(shards[r], group=coll))"""
+    from avlmaps_amd import parallel
+    saved = parallel._Coll, parallel._dist_on
+    old = {k: os.environ.get(k) for k in env}
+    parallel._Coll = lambda g=None: g
+    parallel._dist_on = lambda g=None: g is not None
+    try:
+        for k, v in env.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = str(v)
+        yield
+    finally:
+        parallel._Coll, parallel._dist_on = saved
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
