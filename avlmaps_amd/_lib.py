@@ -216,6 +216,12 @@ _SIGS = {
     "avl_colselect_workspace_bytes": (C.c_int, [C.c_int, C.POINTER(_sz)]),
     "avl_colselect_f32": (C.c_int, [_vp, _i64, C.c_int, _i64, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "avl_cols_above_f32": (C.c_int, [_vp, _i64, C.c_int, _i64, _vp, C.c_int, _vp, _vp, _vp, _vp]),
+    # the visibility audit (csrc/avl_audit.hip): upstream has no counterpart, its maps are static
+    "avl_cell_index_work_bytes": (C.c_int, [_i64, C.c_int, C.c_int, C.POINTER(_sz)]),
+    "avl_cell_index_build": (C.c_int, [_vp, _i64, C.c_int, C.c_int, _vp, _sz, _vp]),
+    "avl_cell_index_lookup": (C.c_int, [_vp, _sz, _i64, C.c_int, C.c_int, _vp, _i64, _vp, _vp]),
+    "avl_audit_rays": (C.c_int, [_vp, _sz, _i64, C.c_int, C.c_int, _vp, C.c_int, _f64, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _f64,
+                                 C.c_int, _f64, _f64, _f64, _f64, C.c_int, _vp, _vp, _vp, _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

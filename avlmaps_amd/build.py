@@ -42,6 +42,7 @@ SOURCES = {
     "avl_resize.hip": ["-ffp-contract=off"],       # integer kernels; the flag keeps the file in line with the other 2-D sources
     "avl_instances.hip": ["-ffp-contract=off"],    # integer kernels; the flag keeps the file in line with the other integer sources
     "avl_colselect.hip": ["-ffp-contract=off"],    # integer kernels and one float64 comparison; nothing to fuse, and it stays so
+    "avl_audit.hip": ["-ffp-contract=off"],        # a ray's points, slab and end points are avl_explore.hip's, operation for operation
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fvisibility=hidden", "-Wall",
           "-Wno-unused-function", "-munsafe-fp-atomics"]

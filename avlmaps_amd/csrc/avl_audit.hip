@@ -1,0 +1,381 @@
+// The visibility audit of a voxel map for gfx950: for every voxel the last frame whose depth rays ended in it, and how many rays of
+// later frames passed through its cell on their way to something further away.  The 3-D half of the free-space carver
+// (avl_explore.hip): the same rays, walked through (row, col, height) cells and probed against the map's voxel list.
+//
+// Upstream has no counterpart: its maps are static (avlmaps/map/vlmap.py only ever loads what the builder wrote).  Everything
+// below is this project's own definition, written out in DESIGN.md 4.21; every output is an integer maximum or an integer sum, so a
+// scalar restatement (tests/_audit_ref.py) is compared with np.array_equal.
+//
+// THE CELL INDEX.  A lookup from cell (row, col, h) of a gs x gs x vh grid to the voxel row that owns it, in one caller-owned
+// buffer laid out by ci_layout():
+//   bits    one bit per cell, uint32 words, linear cell (row * gs + col) * vh + h; set with atomicOr
+//   prefix  per word, the number of set bits in the words before it (count per 1024 words, avl_scan.h's scan_counts_kernel over the
+//           counts, one more pass that writes the words' own exclusive prefix)
+//   perm    perm[rank] = the voxel row of the rank-th set bit; several rows of one cell fold with atomicMax: the largest row owns it
+//   counts  the per-block counts of the scan
+// 4 bytes per 32 cells twice over plus 4 bytes per voxel: 15.5 MB at gs = 1000, vh = 30 and 2 M voxels, where a dense int32 id
+// grid is 120 MB.  A probe is one bit test; on a set bit rank = prefix[w] + popc(word & below) and the row is perm[rank].  Rows
+// outside the grid set no bit: no probe finds them.
+//
+// ONE RAY.  Steps 1 - 8 are the carver's (pixel lattice, depth, bp_backproject, validity, far / hit, bp_transform, the height slab
+// with its t0 and t1), RESTATED here rather than shared through a header so that avl_explore.hip and its code object stay as they
+// are; the file is compiled with the same -ffp-contract=off.  Then
+//    9  X(t) = O + t * (P - O) per coordinate for all three (X(0) = O, X(1) = P exactly); row and col as the carver's, hu =
+//       int(z / cs) truncating, h = min(max(hu, 0), vh - 1); a = cell(X(t0)), b = cell(X(t1))
+//   10  skipped whole: O, P or an end point not finite; a outside [0, gs)^2; |b.row| or |b.col| above 2^28
+//   11  has_end = !far && t1 == 1;  is_hit = has_end && 0 <= hu(P) < vh && b inside [0, gs)^2  (the builder's in-range rule)
+//   12  the walk: d = |b - a| per axis, s the signs, n = max(d); cells k = 0 .. n; between two cells every axis x with error
+//       e_x (starting at 2 d_x - n) does `if e_x > 0: x += s_x, e_x -= 2 n`, then `e_x += 2 d_x`.  DESIGN states this with a driving
+//       axis that always steps; an axis with d_x == n has e_x == n > 0 before every step and -n + 2 n after it, so the one rule
+//       steps it every time and the kernel needs no per-axis case (the steps of one move commute: the cell is their sum).  The
+//       walk stops at the first cell outside [0, gs)^2; h cannot leave [0, vh).
+//   13  a visit of a cell that voxel i owns:  k == n && is_hit: last_hit[i] = max(last_hit[i], id).  !has_end, or has_end and
+//       k < n - end_margin: through[i] += 1, unless `after` is given and id <= after[i].
+// Both folds commute: rays, frames, launches and calls may come in any order and continue each other.
+//
+// Launch shape: the carver's.  A thread owns a ray, lanes run along an image row, blockIdx.y is the frame, up to kAuditFrames poses
+// travel in the kernel arguments, nothing is allocated per call.  The through-add is pre-aggregated once per wave (audit_add: the
+// lanes on the first adding lane's voxel share one atomic, 2.15 -> 0.85 ms for pass B of 64 frames); last_hit is
+// read first and the atomicMax issued only when it would change it.
+#include <algorithm>
+#include <climits>
+#include <cmath>
+
+#include "avl_pinhole.h"
+#include "avl_scan.h"
+
+namespace avl {
+
+constexpr int kAuditThreads = 256;
+constexpr int kAuditFrames = 16;                // frames per launch: 16 * 104 bytes of kernel arguments
+constexpr int kAuditMaxSide = 16384;            // gs, as the carver's
+constexpr int kAuditMaxCell = 1 << 28;          // |b.row|, |b.col|: 2 d and 2 n stay inside int32
+constexpr int kCiThreads = 256;
+constexpr int kCiPer = 4;                       // words per thread of the prefix passes: a block owns 1024 words
+
+struct CellIndexView {
+    uint32_t* bits;
+    int32_t* prefix;
+    int32_t* perm;
+    int32_t* counts;
+    int64_t nwords, nblocks;
+    size_t total;
+};
+
+// the ONE layout of the index buffer (the size query passes a null base)
+static CellIndexView ci_layout(void* base, int64_t N, int gs, int vh) {
+    CellIndexView v{};
+    const int64_t cells = (int64_t)gs * gs * vh;
+    v.nwords = (cells + 31) / 32;
+    v.nblocks = (v.nwords + kCiThreads * kCiPer - 1) / (kCiThreads * kCiPer);
+    Carver c(base ? align256_ptr(base) : nullptr);
+    v.bits = c.ptr<uint32_t>((size_t)v.nwords * 4);
+    v.prefix = c.ptr<int32_t>((size_t)v.nwords * 4);
+    v.perm = c.ptr<int32_t>((size_t)std::max<int64_t>(N, 1) * 4);
+    v.counts = c.ptr<int32_t>((size_t)v.nblocks * 4);
+    v.total = c.total() + 256;                  // the slack of a base that is not 256-aligned
+    return v;
+}
+
+__device__ __forceinline__ int64_t ci_linear(int r, int c, int h, int gs, int vh) {
+    const bool in = r >= 0 && r < gs && c >= 0 && c < gs && h >= 0 && h < vh;
+    return in ? ((int64_t)r * gs + c) * vh + h : -1;    // < 2^31 (checked by the entry points)
+}
+
+// the voxel row that owns linear cell `lin` (inside the grid), -1 when it is empty
+__device__ __forceinline__ int ci_probe(const uint32_t* __restrict__ bits, const int32_t* __restrict__ prefix,
+                                        const int32_t* __restrict__ perm, int lin) {
+    const uint32_t w = bits[lin >> 5], b = (uint32_t)lin & 31u;
+    if (!(w >> b & 1u)) return -1;
+    return perm[prefix[lin >> 5] + __popc(w & ((1u << b) - 1u))];
+}
+
+__global__ __launch_bounds__(256) void ci_set_kernel(const int32_t* __restrict__ pos, int64_t N, int gs, int vh, uint32_t* __restrict__ bits) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < N; i += (int64_t)gridDim.x * 256) {
+        const int64_t lin = ci_linear(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], gs, vh);
+        if (lin >= 0) atomicOr(bits + (lin >> 5), 1u << (lin & 31));
+    }
+}
+
+// a thread's kCiPer consecutive words: their popcounts summed, the block's exclusive scan of the sums
+__device__ __forceinline__ int ci_block_scan(const uint32_t* __restrict__ bits, int64_t nwords, int* lds, int64_t* w0, int* total) {
+    *w0 = (int64_t)blockIdx.x * (kCiThreads * kCiPer) + threadIdx.x * kCiPer;
+    int s = 0;
+#pragma unroll
+    for (int k = 0; k < kCiPer; ++k)
+        if (*w0 + k < nwords) s += __popc(bits[*w0 + k]);
+    return block_excl_scan<kCiThreads / kWave>(s, OpSum{}, 0, lds, total);
+}
+
+__global__ __launch_bounds__(kCiThreads) void ci_count_kernel(const uint32_t* __restrict__ bits, int64_t nwords, int32_t* __restrict__ counts) {
+    __shared__ int s_w[kCiThreads / kWave];
+    int64_t w0;
+    int total;
+    ci_block_scan(bits, nwords, s_w, &w0, &total);
+    if (threadIdx.x == 0) counts[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(kCiThreads) void ci_prefix_kernel(const uint32_t* __restrict__ bits, int64_t nwords, const int32_t* __restrict__ offsets,
+                                                               int32_t* __restrict__ prefix) {
+    __shared__ int s_w[kCiThreads / kWave];
+    int64_t w0;
+    int total;
+    int run = offsets[blockIdx.x] + ci_block_scan(bits, nwords, s_w, &w0, &total);
+#pragma unroll
+    for (int k = 0; k < kCiPer; ++k)
+        if (w0 + k < nwords) {
+            prefix[w0 + k] = run;
+            run += __popc(bits[w0 + k]);
+        }
+}
+
+__global__ __launch_bounds__(256) void ci_perm_kernel(const int32_t* __restrict__ pos, int64_t N, int gs, int vh, const uint32_t* __restrict__ bits,
+                                                      const int32_t* __restrict__ prefix, int32_t* __restrict__ perm) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < N; i += (int64_t)gridDim.x * 256) {
+        const int64_t lin = ci_linear(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], gs, vh);
+        if (lin < 0) continue;
+        const uint32_t w = bits[lin >> 5], b = (uint32_t)lin & 31u;
+        atomicMax(perm + prefix[lin >> 5] + __popc(w & ((1u << b) - 1u)), (int32_t)i);        // the largest row of a cell owns it
+    }
+}
+
+__global__ __launch_bounds__(256) void ci_lookup_kernel(const int32_t* __restrict__ cells, int64_t M, int gs, int vh, const uint32_t* __restrict__ bits,
+                                                        const int32_t* __restrict__ prefix, const int32_t* __restrict__ perm, int32_t* __restrict__ out) {
+    for (int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x; m < M; m += (int64_t)gridDim.x * 256) {
+        const int64_t lin = ci_linear(cells[3 * m], cells[3 * m + 1], cells[3 * m + 2], gs, vh);
+        out[m] = lin < 0 ? -1 : ci_probe(bits, prefix, perm, (int)lin);
+    }
+}
+
+__device__ __forceinline__ void audit_add(unsigned* __restrict__ through, int i) {
+#ifdef AVL_AUDIT_PLAIN_ADD
+    atomicAdd(through + i, 1u);     // the B side of tools/probe_audit.py's A/B (tools/build_variant.py), never in the shipped library
+#else
+    // The lanes that add to the voxel of the wave's first adding lane share one atomic -- near the camera neighbouring rays all
+    // cross the same few voxels -- and every other lane adds for itself: one round, no loop over the wave's distinct voxels, which
+    // far from the camera are as many as its lanes.  The same integer either way.  Called from divergent code: the builtin and the
+    // ballot see the lanes that are adding in this step
+    const int lead = __builtin_amdgcn_readfirstlane(i);
+    const unsigned long long same = __ballot(i == lead);
+    if (i != lead) atomicAdd(through + i, 1u);
+    else if ((same & ((1ull << (threadIdx.x & (kWave - 1))) - 1ull)) == 0) atomicAdd(through + lead, (unsigned)__popcll(same));
+#endif
+}
+
+struct AuditFrame {
+    double t[12];                               // the first three rows of the frame's camera -> map transform
+    int32_t id, pad;
+};
+struct AuditBatch {
+    AuditFrame f[kAuditFrames];
+};
+struct AuditParams {
+    double kinv[9];
+    double cs, half_gs, h_min, h_max, min_depth, max_depth, depth_div;
+    int H, W, gs, vh, stride, nv, nu, depth_u16, end_margin;
+    const uint32_t* bits;
+    const int32_t* prefix;
+    const int32_t* perm;
+};
+
+__global__ __launch_bounds__(kAuditThreads) void audit_kernel(AuditParams p, AuditBatch batch, const void* __restrict__ depth,
+                                                             int32_t* __restrict__ last_hit, unsigned* __restrict__ through,
+                                                             const int32_t* __restrict__ after) {
+    const AuditFrame& fr = batch.f[blockIdx.y];
+    const int id = fr.id;
+    const int ray = blockIdx.x * kAuditThreads + threadIdx.x;
+    if (ray >= p.nv * p.nu) return;
+    const double ox = fr.t[3], oy = fr.t[7], oz = fr.t[11];
+    const int v = p.stride / 2 + (ray / p.nu) * p.stride, u = p.stride / 2 + (ray % p.nu) * p.stride;
+    const size_t pix = (size_t)blockIdx.y * p.H * p.W + (size_t)v * p.W + u;
+    const double z = p.depth_u16 ? (double)reinterpret_cast<const uint16_t*>(depth)[pix] / p.depth_div
+                                 : (double)reinterpret_cast<const float*>(depth)[pix];
+    double p0, p1, p2;
+    bp_backproject(p.kinv, (double)u + 0.5, (double)v + 0.5, z, p0, p1, p2);
+    if (!(p2 > p.min_depth)) return;                                            // (3)
+    const bool far = p2 >= p.max_depth;                                         // (4)
+    if (far) {
+        const double s = p.max_depth / p2;
+        p0 = p0 * s;
+        p1 = p1 * s;
+        p2 = p2 * s;
+    }
+    double gx, gy, gz;
+    bp_transform(fr.t, p0, p1, p2, gx, gy, gz);                                 // (5)
+    if (!(isfinite(ox) && isfinite(oy) && isfinite(oz) && isfinite(gx) && isfinite(gy) && isfinite(gz))) return;
+    double t0 = 0.0, t1 = 1.0;                                                  // (8) the height slab
+    const double dz = gz - oz;
+    if (dz == 0.0) {
+        if (!(oz >= p.h_min && oz <= p.h_max)) return;
+    } else {
+        const double ta = (p.h_min - oz) / dz, tb = (p.h_max - oz) / dz;
+        t0 = fmax(0.0, fmin(ta, tb));
+        t1 = fmin(1.0, fmax(ta, tb));
+        if (!(t0 <= t1)) return;
+    }
+    const double dx = gx - ox, dy = gy - oy;                                    // (9)
+    const double ax = t0 == 0.0 ? ox : ox + t0 * dx, ay = t0 == 0.0 ? oy : oy + t0 * dy, az = t0 == 0.0 ? oz : oz + t0 * dz;
+    const double bx = t1 == 1.0 ? gx : ox + t1 * dx, by = t1 == 1.0 ? gy : oy + t1 * dy, bz = t1 == 1.0 ? gz : oz + t1 * dz;
+    if (!(isfinite(ax) && isfinite(ay) && isfinite(az) && isfinite(bx) && isfinite(by) && isfinite(bz))) return;
+    int r = py_int(p.half_gs - (double)py_int(ax / p.cs)), c = py_int(p.half_gs - (double)py_int(ay / p.cs));
+    int h = min(max(py_int(az / p.cs), 0), p.vh - 1);
+    const int br = py_int(p.half_gs - (double)py_int(bx / p.cs)), bc = py_int(p.half_gs - (double)py_int(by / p.cs));
+    const int bhu = py_int(bz / p.cs), bh = min(max(bhu, 0), p.vh - 1);
+    const int gs = p.gs;
+    if (!(r >= 0 && r < gs && c >= 0 && c < gs)) return;                        // (10)
+    if (br > kAuditMaxCell || br < -kAuditMaxCell || bc > kAuditMaxCell || bc < -kAuditMaxCell) return;
+    const bool has_end = !far && t1 == 1.0;                                     // (11)
+    const bool is_hit = has_end && bhu >= 0 && bhu < p.vh && br >= 0 && br < gs && bc >= 0 && bc < gs;
+    const int dr = abs(br - r), dc = abs(bc - c), dh = abs(bh - h);             // (12)
+    const int sr = br > r ? 1 : -1, sc = bc > c ? 1 : -1, sh = bh > h ? 1 : -1;
+    const int n = max(dr, max(dc, dh));
+    int er = 2 * dr - n, ec = 2 * dc - n, eh = 2 * dh - n;
+    const int through_below = has_end ? n - p.end_margin : INT_MAX;            // k < this counts as through (k <= n < INT_MAX)
+    for (int k = 0; k <= n; ++k) {
+        if (!(r >= 0 && r < gs && c >= 0 && c < gs)) break;
+        const int i = ci_probe(p.bits, p.prefix, p.perm, (r * gs + c) * p.vh + h);
+        if (i >= 0) {                                                           // (13)
+            if (last_hit && k == n && is_hit) {
+                if (id > __hip_atomic_load(last_hit + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(last_hit + i, id);
+            }
+            if (through && k < through_below && (!after || id > after[i])) audit_add(through, i);
+        }
+        if (er > 0) {
+            r += sr;
+            er -= 2 * n;
+        }
+        er += 2 * dr;
+        if (ec > 0) {
+            c += sc;
+            ec -= 2 * n;
+        }
+        ec += 2 * dc;
+        if (eh > 0) {
+            h += sh;
+            eh -= 2 * n;
+        }
+        eh += 2 * dh;
+    }
+}
+
+static int ci_check_grid(const char* who, int64_t N, int gs, int vh) {
+    AVL_REQUIRE(N >= 0 && N < INT_MAX, "%s: %lld voxels (0 .. 2^31 - 2)", who, (long long)N);
+    AVL_REQUIRE(gs >= 1 && gs <= kAuditMaxSide && vh >= 1 && (int64_t)gs * gs * vh < INT_MAX, "%s: grid %d x %d x %d (gs 1 .. %d, vh >= 1, gs * gs * vh < 2^31)",
+                who, gs, gs, vh, kAuditMaxSide);
+    return AVL_OK;
+}
+
+}  // namespace avl
+
+using namespace avl;
+
+extern "C" {
+
+int avl_cell_index_work_bytes(int64_t N, int gs, int vh, size_t* bytes) {
+    AVL_REQUIRE(bytes, "avl_cell_index_work_bytes: null output");
+    const int rc = ci_check_grid("avl_cell_index_work_bytes", N, gs, vh);
+    if (rc != AVL_OK) return rc;
+    *bytes = ci_layout(nullptr, N, gs, vh).total;
+    return AVL_OK;
+}
+
+int avl_cell_index_build(const int32_t* d_grid_pos, int64_t N, int gs, int vh, void* d_index, size_t index_bytes, void* stream) {
+    const int rc = ci_check_grid("avl_cell_index_build", N, gs, vh);
+    if (rc != AVL_OK) return rc;
+    AVL_REQUIRE(d_index && (d_grid_pos || N == 0), "avl_cell_index_build: null pointer");
+    const CellIndexView v = ci_layout(d_index, N, gs, vh);
+    AVL_REQUIRE(index_bytes >= v.total, "avl_cell_index_build: the index buffer has %zu bytes, needs %zu", index_bytes, v.total);
+    hipStream_t st = as_stream(stream);
+    AVL_HIP_CHECK(hipMemsetAsync(v.bits, 0, (size_t)v.nwords * 4, st));
+    AVL_HIP_CHECK(hipMemsetAsync(v.perm, 0xFF, (size_t)std::max<int64_t>(N, 1) * 4, st));          // -1 below every row: atomicMax's identity
+    if (N) hipLaunchKernelGGL(ci_set_kernel, dim3(stride_blocks(N)), dim3(256), 0, st, d_grid_pos, N, gs, vh, v.bits);
+    hipLaunchKernelGGL(ci_count_kernel, dim3((unsigned)v.nblocks), dim3(kCiThreads), 0, st, (const uint32_t*)v.bits, v.nwords, v.counts);
+    hipLaunchKernelGGL((scan_counts_kernel<1024, int, int, OpSum>), dim3(1), dim3(1024), 0, st, (const int*)v.counts, v.nblocks, v.counts,
+                       (int*)nullptr, OpSum{}, 0);
+    hipLaunchKernelGGL(ci_prefix_kernel, dim3((unsigned)v.nblocks), dim3(kCiThreads), 0, st, (const uint32_t*)v.bits, v.nwords, (const int32_t*)v.counts,
+                       v.prefix);
+    if (N)
+        hipLaunchKernelGGL(ci_perm_kernel, dim3(stride_blocks(N)), dim3(256), 0, st, d_grid_pos, N, gs, vh, (const uint32_t*)v.bits,
+                           (const int32_t*)v.prefix, v.perm);
+    AVL_HIP_CHECK(hipGetLastError());
+    return AVL_OK;
+}
+
+int avl_cell_index_lookup(const void* d_index, size_t index_bytes, int64_t N, int gs, int vh, const int32_t* d_cells, int64_t M, int32_t* d_out,
+                          void* stream) {
+    const int rc = ci_check_grid("avl_cell_index_lookup", N, gs, vh);
+    if (rc != AVL_OK) return rc;
+    AVL_REQUIRE(M >= 0 && M < INT_MAX, "avl_cell_index_lookup: %lld cells (0 .. 2^31 - 2)", (long long)M);
+    AVL_REQUIRE(d_index, "avl_cell_index_lookup: null index");
+    const CellIndexView v = ci_layout(const_cast<void*>(d_index), N, gs, vh);
+    AVL_REQUIRE(index_bytes >= v.total, "avl_cell_index_lookup: the index buffer has %zu bytes, needs %zu", index_bytes, v.total);
+    if (M == 0) return AVL_OK;
+    AVL_REQUIRE(d_cells && d_out, "avl_cell_index_lookup: null pointer");
+    hipLaunchKernelGGL(ci_lookup_kernel, dim3(stride_blocks(M)), dim3(256), 0, as_stream(stream), d_cells, M, gs, vh, (const uint32_t*)v.bits,
+                       (const int32_t*)v.prefix, (const int32_t*)v.perm, d_out);
+    AVL_HIP_CHECK(hipGetLastError());
+    return AVL_OK;
+}
+
+int avl_audit_rays(const void* d_index, size_t index_bytes, int64_t N, int gs, int vh, const void* d_depth, int depth_is_u16, double depth_div,
+                   int F, int H, int W, const double* h_calib_inv, const double* h_transforms, const int32_t* h_frame_ids, double cs, int stride,
+                   double h_min, double h_max, double min_depth, double max_depth, int end_margin, int32_t* d_last_hit, uint32_t* d_through,
+                   const int32_t* d_after, void* stream) {
+    const int rc = ci_check_grid("avl_audit_rays", N, gs, vh);
+    if (rc != AVL_OK) return rc;
+    AVL_REQUIRE(F >= 0 && H > 0 && W > 0 && (int64_t)H * W < INT_MAX, "avl_audit_rays: bad batch of %d frames of %d x %d", F, H, W);
+    AVL_REQUIRE(std::isfinite(cs) && cs > 0, "avl_audit_rays: cell size must be finite and positive");
+    AVL_REQUIRE(stride >= 1, "avl_audit_rays: stride %d < 1", stride);
+    AVL_REQUIRE(end_margin >= 0, "avl_audit_rays: end_margin %d < 0", end_margin);
+    AVL_REQUIRE(std::isfinite(h_min) && std::isfinite(h_max) && h_min <= h_max, "avl_audit_rays: height band [%g, %g]", h_min, h_max);
+    AVL_REQUIRE(std::isfinite(min_depth) && std::isfinite(max_depth) && min_depth >= 0 && max_depth > min_depth,
+                "avl_audit_rays: depth range (%g, %g)", min_depth, max_depth);
+    AVL_REQUIRE(!depth_is_u16 || (std::isfinite(depth_div) && depth_div > 0), "avl_audit_rays: depth_div must be positive");
+    AVL_REQUIRE(d_index, "avl_audit_rays: null index");
+    const CellIndexView v = ci_layout(const_cast<void*>(d_index), N, gs, vh);
+    AVL_REQUIRE(index_bytes >= v.total, "avl_audit_rays: the index buffer has %zu bytes, needs %zu", index_bytes, v.total);
+    if (F == 0 || (!d_last_hit && !d_through)) return AVL_OK;
+    AVL_REQUIRE(d_depth && h_calib_inv && h_transforms && h_frame_ids, "avl_audit_rays: null pointer");
+    for (int f = 0; f < F; ++f) AVL_REQUIRE(h_frame_ids[f] >= 0, "avl_audit_rays: frame id %d is negative", h_frame_ids[f]);
+    AuditParams p{};
+    for (int i = 0; i < 9; ++i) p.kinv[i] = h_calib_inv[i];
+    p.cs = cs;
+    p.half_gs = (double)gs / 2.0;
+    p.h_min = h_min;
+    p.h_max = h_max;
+    p.min_depth = min_depth;
+    p.max_depth = max_depth;
+    p.depth_div = depth_is_u16 ? depth_div : 1.0;
+    p.H = H;
+    p.W = W;
+    p.gs = gs;
+    p.vh = vh;
+    p.stride = stride;
+    const int off = stride / 2;
+    p.nv = off < H ? (H - off + stride - 1) / stride : 0;
+    p.nu = off < W ? (W - off + stride - 1) / stride : 0;
+    p.depth_u16 = depth_is_u16 ? 1 : 0;
+    p.end_margin = end_margin;
+    p.bits = v.bits;
+    p.prefix = v.prefix;
+    p.perm = v.perm;
+    const int rays = p.nv * p.nu;                                               // < H * W < 2^31
+    if (rays == 0) return AVL_OK;
+    const unsigned blocks = (unsigned)((rays + kAuditThreads - 1) / kAuditThreads);
+    const size_t frame_bytes = (size_t)H * W * (depth_is_u16 ? sizeof(uint16_t) : sizeof(float));
+    hipStream_t st = as_stream(stream);
+    for (int f0 = 0; f0 < F; f0 += kAuditFrames) {
+        const int n = std::min(kAuditFrames, F - f0);
+        AuditBatch b{};
+        for (int k = 0; k < n; ++k) {
+            for (int i = 0; i < 12; ++i) b.f[k].t[i] = h_transforms[(size_t)(f0 + k) * 16 + i];
+            b.f[k].id = h_frame_ids[f0 + k];
+        }
+        hipLaunchKernelGGL(audit_kernel, dim3(blocks, (unsigned)n), dim3(kAuditThreads), 0, st, p, b,
+                           (const void*)((const char*)d_depth + (size_t)f0 * frame_bytes), d_last_hit, (unsigned*)d_through, d_after);
+    }
+    AVL_HIP_CHECK(hipGetLastError());
+    return AVL_OK;
+}
+
+}  // extern "C"

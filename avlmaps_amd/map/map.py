@@ -22,6 +22,41 @@ def cfg_get(cfg, key):
         return cfg[key]
 
 
+class VisibilityAudit:
+    """Map.audit_visibility's result.  last_hit (N,) int32: the last frame whose depth ray ended in the voxel, -1 = none;
+    through (N,) uint32: the rays of frames after that which passed through its cell; params: gs, cs, vh, stride, end_margin,
+    n_frames; frame_counts: the frames of every audited directory, in order."""
+
+    def __init__(self, last_hit, through, params, frame_counts):
+        self.last_hit = np.ascontiguousarray(last_hit, dtype=np.int32)
+        self.through = np.ascontiguousarray(through, dtype=np.uint32)
+        if self.last_hit.ndim != 1 or self.through.shape != self.last_hit.shape:
+            raise ValueError(f"VisibilityAudit: last_hit {self.last_hit.shape} and through {self.through.shape} must be (N,) both")
+        self.params = dict(params)
+        self.frame_counts = [int(c) for c in frame_counts]
+
+    @property
+    def N(self) -> int:
+        return int(self.last_hit.shape[0])
+
+    def stale(self, min_rays: int = 3) -> np.ndarray:
+        """(N,) bool: through >= min_rays.  min_rays = 3 (and the audit's end_margin = 2) are defaults chosen by argument -- a
+        sparse ray lattice, grazing rays -- not by measurement."""
+        if int(min_rays) < 1:
+            raise ValueError(f"stale: min_rays {min_rays} < 1")
+        return self.through >= np.uint32(min(int(min_rays), 2 ** 32 - 1))
+
+    def save(self, path) -> None:
+        np.savez_compressed(path, last_hit=self.last_hit, through=self.through, frame_counts=np.asarray(self.frame_counts, np.int64),
+                            **self.params)
+
+    @classmethod
+    def load(cls, path) -> "VisibilityAudit":
+        with np.load(path, allow_pickle=False) as z:
+            params = {k: z[k].item() for k in z.files if k not in ("last_hit", "through", "frame_counts")}
+            return cls(z["last_hit"], z["through"], params, z["frame_counts"].tolist())
+
+
 class Map:
     def __init__(self, map_config, data_dir: str = ""):
         self.map_config = map_config
@@ -37,6 +72,7 @@ class Map:
         self.obstacles_cropped = None
         self.first_seen = None            # (gs, gs) int32, the first frame that saw a cell, -1 = never (create_explored_map / load_explored_map)
         self.explored_params = None
+        self.visibility = None            # VisibilityAudit of the voxels (audit_visibility / load_visibility)
         self._setup_transforms()
         if data_dir:
             self._setup_paths(data_dir)
@@ -259,6 +295,129 @@ class Map:
             d2 = np.sum((cells - cells.mean(axis=0)) ** 2, axis=1)
             centres[i] = cells[int(np.argmin(d2))] + (int(self.rmin), int(self.cmin))
         return centres, (areas[keep] if keep else np.zeros((0,), np.int64))
+
+    # ------------------------------------------------------------------------ stale voxels (csrc/avl_audit.hip)
+    # The builder only adds voxels: what a later visit saw through stays in the map.  The audit walks the sight rays of the frames
+    # through the voxel list in 3-D and records, per voxel, the last frame that hit it and the rays of later frames that passed
+    # through it.  Upstream has no counterpart (its maps are static).  DESIGN.md 4.21.
+    VISIBILITY_FILE = "visibility.npz"
+
+    def _audit_frames(self, data_dir, first_pose=None):
+        """(depth paths, (n, 4, 4) transforms, min_depth, max_depth, the directory's first pose) of one scene directory, read as
+        create_explored_map reads its own.  The map's frame is the first pose of the scene it was built from: first_pose, when
+        given, takes the place of this directory's own first pose in the builder's frame_transforms, so that a revisit (whose
+        poses.txt is in the same world frame) lands in the map's frame."""
+        from .vlmap_builder import VLMapBuilder
+        data_dir = Path(data_dir)
+        depth_paths = sorted((data_dir / "depth").glob("*.npy"))
+        pose_path = data_dir / "poses.txt"
+        builder = VLMapBuilder(data_dir, self.map_config, pose_path, sorted((data_dir / "rgb").glob("*.png")), depth_paths,
+                               self.base2cam_tf, self.base_transform)
+        poses = np.loadtxt(pose_path).reshape((-1, 7))
+        own_first = poses[0].copy() if len(poses) else None
+        if len(poses) and first_pose is not None:
+            transforms = np.stack(builder.frame_transforms(np.concatenate([np.reshape(first_pose, (1, 7)), poses])))[1:]
+        else:
+            transforms = np.stack(builder.frame_transforms(poses)) if len(poses) else np.zeros((0, 4, 4))
+        n = min(len(depth_paths), len(poses))
+        return depth_paths[:n], transforms[:n], float(builder.min_depth), float(builder.max_depth), own_first
+
+    def audit_visibility(self, data_dirs=None, stride: int = 4, end_margin: int = 2, batch: int = 16) -> "VisibilityAudit":
+        """Audit the map's voxels against the depth frames of `data_dirs` (default: the map's own scene; a revisit is a second
+        directory; frame ids run on consecutively across directories).  Pass A folds every frame's hits into last_hit (N,) int32,
+        pass B counts in through (N,) uint32 the rays of frames AFTER a voxel's last hit that passed through its cell
+        (ops.audit_rays with after = last_hit).  Reads poses.txt and depth/*.npy as create_explored_map does, in batches of
+        `batch` frames, one loader thread ahead of the GPU.  The result is kept as self.visibility and written to
+        <data_dir>/vlmap/visibility.npz."""
+        import queue
+        import threading
+        from .. import ops
+        from ..device import DeviceArray
+        from ..utils.mapping_utils import load_depth_npy
+        if self.grid_pos is None or self.occupied_ids is None:
+            raise ValueError("audit_visibility: no map loaded")
+        if int(batch) < 1:
+            raise ValueError(f"audit_visibility: batch {batch} < 1")
+        if int(stride) < 1 or int(end_margin) < 0:
+            raise ValueError(f"audit_visibility: stride {stride} (>= 1), end_margin {end_margin} (>= 0)")
+        if data_dirs is None:
+            if not hasattr(self, "data_dir"):
+                raise ValueError("audit_visibility: no scene directory (pass data_dirs)")
+            data_dirs = [self.data_dir]
+        elif isinstance(data_dirs, (str, Path)):
+            data_dirs = [data_dirs]
+        calib = np.array(list(cfg_get(self.map_config, "cam_calib_mat")), dtype=np.float64).reshape((3, 3))
+        # the map's frame: the first pose of its own scene when it has one, else of the first directory
+        first_pose = None
+        own = getattr(self, "pose_path", None)
+        if own is not None and Path(own).exists():
+            own_poses = np.loadtxt(own).reshape((-1, 7))
+            first_pose = own_poses[0] if len(own_poses) else None
+        scenes = []
+        for d in data_dirs:
+            scene = self._audit_frames(d, first_pose)
+            first_pose = scene[4] if first_pose is None else first_pose
+            scenes.append(scene[:4])
+        counts = [len(s[0]) for s in scenes]
+        starts = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        gs, cs, vh = int(self.gs), float(self.cs), int(np.asarray(self.occupied_ids).shape[2])
+        N = len(self.grid_pos)
+
+        def run_pass(index, **outputs):
+            batches = queue.Queue(maxsize=2)
+
+            def load():
+                try:
+                    for (paths, transforms, mn, mx), first in zip(scenes, starts):
+                        for lo in range(0, len(paths), int(batch)):
+                            hi = min(len(paths), lo + int(batch))
+                            depth = np.stack([np.asarray(load_depth_npy(paths[i]), dtype=np.float32) for i in range(lo, hi)])
+                            batches.put((depth, transforms[lo:hi], np.arange(first + lo, first + hi), mn, mx))
+                    batches.put(None)
+                except BaseException as e:          # surfaced on the calling thread
+                    batches.put(e)
+            loader = threading.Thread(target=load, name="avl-audit-load", daemon=True)
+            loader.start()
+            while True:
+                item = batches.get()
+                if item is None:
+                    break
+                if isinstance(item, BaseException):
+                    raise item
+                depth, transforms, ids, mn, mx = item
+                ops.audit_rays(index, DeviceArray.from_numpy(depth), calib, transforms, ids, cs, stride=int(stride), min_depth=mn,
+                               max_depth=mx, end_margin=int(end_margin), **outputs)
+            loader.join()
+
+        last_hit = DeviceArray.from_numpy(np.full((N,), ops.NEVER_HIT, np.int32))
+        through = DeviceArray((N,), np.uint32).zero_()
+        try:
+            with ops.cell_index(np.ascontiguousarray(self.grid_pos, dtype=np.int32), gs, vh) as index:
+                run_pass(index, last_hit=last_hit)                                  # pass A
+                run_pass(index, through=through, after=last_hit)                    # pass B
+            params = dict(gs=gs, cs=cs, vh=vh, stride=int(stride), end_margin=int(end_margin), n_frames=int(starts[-1]))
+            audit = VisibilityAudit(last_hit.numpy(), through.numpy(), params, counts)
+        finally:
+            last_hit.free()
+            through.free()
+        self.visibility = audit
+        out_dir = Path(getattr(self, "data_dir", data_dirs[0])) / "vlmap"
+        out_dir.mkdir(parents=True, exist_ok=True)
+        audit.save(out_dir / self.VISIBILITY_FILE)
+        return audit
+
+    def load_visibility(self, data_dir=None) -> bool:
+        """Read <data_dir>/vlmap/visibility.npz into self.visibility; False (and no audit) when the file does not exist or was made
+        for a map of another voxel count -- a pruned or rebuilt map simply has no audit yet."""
+        self.visibility = None
+        path = Path(data_dir if data_dir is not None else self.data_dir) / "vlmap" / self.VISIBILITY_FILE
+        if not path.exists() or self.grid_pos is None:
+            return False
+        audit = VisibilityAudit.load(path)
+        if audit.N != len(self.grid_pos):
+            return False
+        self.visibility = audit
+        return True
 
     @staticmethod
     def _dilate_map(binary_map: np.ndarray, dilate_iter: int = 0, gaussian_sigma: float = 1.0):

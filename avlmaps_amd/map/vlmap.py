@@ -74,6 +74,7 @@ class VLMap(Map):
          self.grid_rgb) = load_3d_map(self.map_save_path)[:6]
         self._dev_feat = None
         self.load_explored_map(data_dir)                 # vlmap/explored.npz when it exists; a map without it behaves as ever
+        self.load_visibility(data_dir)                   # vlmap/visibility.npz when it exists and is this map's (same voxel count)
         # straight after a multi-GPU build in this process the merged map already lies row-sharded in the ranks' HBM
         # (VLMapBuilder.map_shard): take this rank's block as the resident copy instead of uploading it again from the file
         shard = getattr(getattr(self, "map_builder", None), "map_shard", None)
@@ -107,6 +108,57 @@ class VLMap(Map):
         th.start()
         _UPLOADS.append(th)
         del _UPLOADS[:-8]
+
+    def prune_voxels(self, mask) -> int:
+        """Remove the voxels of `mask` (N,) bool -- VisibilityAudit.stale(), say -- from the map; returns how many went.  Host NumPy:
+        the rows leave grid_feat, grid_pos, weight, grid_rgb and scores_mat (when set), occupied_ids is renumbered (-1 where a cell
+        was emptied), and every device copy derived from the old arrays is dropped (the resident features, positions, colours, the
+        heat plan, the scores, the instances, the audit itself), so that queries afterwards equal those of a freshly loaded pruned
+        map.  Saving goes through utils.mapping_utils.save_3d_map as ever.  Upstream has no counterpart (its maps are static)."""
+        if self.grid_pos is None or self.grid_feat is None:
+            raise ValueError("prune_voxels: no map loaded")
+        n = len(self.grid_pos)
+        mask = np.asarray(mask)
+        if mask.dtype != np.dtype(bool) or mask.shape != (n,):
+            raise ValueError(f"prune_voxels: expected a bool mask of shape ({n},), got {mask.dtype} {mask.shape}")
+        removed = int(np.count_nonzero(mask))
+        if removed == 0:
+            return 0
+        keep = ~mask
+        new_id = np.full((n,), -1, dtype=np.int64)
+        new_id[keep] = np.arange(n - removed)
+        with self._dev_lock:
+            self.grid_feat = np.ascontiguousarray(np.asarray(self.grid_feat)[keep])
+            self.grid_pos = np.ascontiguousarray(np.asarray(self.grid_pos)[keep])
+            self.weight = np.ascontiguousarray(np.asarray(self.weight)[keep])
+            if self.grid_rgb is not None:
+                self.grid_rgb = np.ascontiguousarray(np.asarray(self.grid_rgb)[keep])
+            if self.occupied_ids is not None:
+                occ = np.asarray(self.occupied_ids)
+                out = np.full(occ.shape, -1, dtype=occ.dtype)
+                held = (occ >= 0) & (occ < n)
+                out[held] = new_id[occ[held]].astype(occ.dtype)
+                self.occupied_ids = out
+            if self.scores_mat is not None:
+                self.scores_mat = np.ascontiguousarray(np.asarray(self.scores_mat)[keep])
+            # everything that mirrors the old arrays on the device, or was computed from them
+            self._dev_feat = self._dev_feat_src = None
+            self._dev_pos = self._dev_pos_src = None
+            self._dev_rgb = self._dev_rgb_src = None
+            plan = getattr(self, "_heat_plan_obj", None)
+            if plan is not None:
+                plan.close()
+            self._heat_plan_obj = self._heat_plan_src = None
+            self._dev_scores = self._dev_scores_src = None
+            self._quantile_cache = {}
+            self._argmax = self._argmax_src = None
+            self._dev_argmax = self._dev_argmax_src = None
+            cached = getattr(self, "_instances_cache", None)
+            if cached is not None:
+                cached[1].close()
+            self._instances_cache = None
+            self.visibility = None
+        return removed
 
     def _init_clip(self, clip_version="ViT-B/32"):
         """Reference: vlmap.py:67-90."""

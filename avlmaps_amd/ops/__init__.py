@@ -63,6 +63,9 @@ from .instances import (  # noqa: F401
 from .select import (  # noqa: F401
     cols_above, COLSELECT_SLOTS, column_order_stats, column_quantiles, ColumnOrderStats, quantile_index, quantile_lerp,
 )
+from .audit import (  # noqa: F401
+    AUDIT_MAX_SIDE, audit_rays, cell_index, CellIndex, lookup_cells, NEVER_HIT,
+)
 # the shared marshalling layer; its one device predicate keeps both of the names it had here
 from ._args import (  # noqa: F401
     _dev_u8, _image_any, _image_shape, _image_u8, _is_dev, _is_dev as _on_device, _result,

@@ -1181,6 +1181,41 @@ AVL_API int avl_colselect_f32(const float* d_scores, int64_t N, int Q, int64_t l
 AVL_API int avl_cols_above_f32(const float* d_scores, int64_t N, int Q, int64_t ld, const double* d_thresholds, int mask_column,
                                uint64_t* d_bits, int64_t* d_counts, uint8_t* d_mask, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * (20) the visibility audit of a voxel map: a device cell index of the voxel list, and the 3-D sight-ray pass that records for
+ *     every voxel the last frame that hit it and the rays that passed through it (csrc/avl_audit.hip).
+ *     Upstream has no counterpart: its maps are static (avlmaps/map/vlmap.py loads what the builder wrote and never revises it).
+ *     The grid is gs x gs x vh cells with 1 <= gs <= 16384, vh >= 1 and gs * gs * vh < 2^31; 0 <= N < 2^31 - 1 voxels.  Every
+ *     result is an integer maximum or an integer sum: the bytes do not depend on the order of rays, frames, launches or calls.
+ *     All calls are asynchronous on `stream`, check their arguments before any device work and allocate nothing.
+ * ------------------------------------------------------------------------------------------------ */
+/* The size of the index buffer of avl_cell_index_build: an occupancy bitmap (one bit per cell), the exclusive prefix of its words'
+ * popcounts, a rank -> voxel permutation and the scan's block counts -- 8 bytes per 32 cells and 4 per voxel.  Upstream has no
+ * counterpart. */
+AVL_API int avl_cell_index_work_bytes(int64_t N, int gs, int vh, size_t* bytes);
+/* Builds the lookup cell (row, col, h) -> voxel row of d_grid_pos (N, 3) int32 into d_index (index_bytes >= the size above).  Rows
+ * outside the grid are ignored; of several rows in one cell the largest row index owns it.  N = 0 gives an empty index.  The
+ * buffer is read by the two calls below with the same N, gs and vh.  Upstream has no counterpart. */
+AVL_API int avl_cell_index_build(const int32_t* d_grid_pos, int64_t N, int gs, int vh, void* d_index, size_t index_bytes, void* stream);
+/* d_out (M,) int32: the voxel row that owns each of the M cells of d_cells (M, 3) int32, -1 where the cell is empty or outside the
+ * grid.  0 <= M < 2^31 - 1; M = 0 does nothing.  Upstream has no counterpart. */
+AVL_API int avl_cell_index_lookup(const void* d_index, size_t index_bytes, int64_t N, int gs, int vh, const int32_t* d_cells, int64_t M,
+                                  int32_t* d_out, void* stream);
+/* Folds the sight rays of F depth frames into d_last_hit (N,) int32 (-1 = never) and d_through (N,) uint32; each may be NULL.
+ * Depth, calibration, transforms, frame ids, stride, height band and depth range are avl_carve_free_space's, and so is a ray up to
+ * its segment inside the band; from there it is walked through (row, col, h) cells (h = int(z / cs) clamped to [0, vh)) by the
+ * integer walk written out at the top of csrc/avl_audit.hip, from the cell of its start to the cell of its end, stopping at the
+ * first cell outside [0, gs)^2.  With i the voxel that owns a visited cell: the END cell of a ray that ends on a surface which
+ * the builder would fuse (not far, not cut by the band, 0 <= int(z / cs) < vh, inside the grid) does d_last_hit[i] =
+ * max(d_last_hit[i], id); a cell more than end_margin steps before such an end, or any cell of a ray without a surface at its
+ * end, does d_through[i] += 1 -- only where id > d_after[i] when d_after (N,) int32 is given.  d_through does not saturate (it
+ * would take 2^32 rays through one voxel).  Both folds commute: calls continue each other in any order.  F = 0, or both outputs
+ * NULL, does nothing.  end_margin >= 0.  Upstream has no counterpart. */
+AVL_API int avl_audit_rays(const void* d_index, size_t index_bytes, int64_t N, int gs, int vh, const void* d_depth, int depth_is_u16,
+                           double depth_div, int F, int H, int W, const double* h_calib_inv, const double* h_transforms,
+                           const int32_t* h_frame_ids, double cs, int stride, double h_min, double h_max, double min_depth, double max_depth,
+                           int end_margin, int32_t* d_last_hit, uint32_t* d_through, const int32_t* d_after, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,204 @@
+"""Scalar restatement of the visibility audit (csrc/avl_audit.hip) for the tests: the cell index as a dict, the ray
+and its 3-D walk as a Python loop in the order DESIGN writes them down.
+
+A ray's points come from the oracle's pinned depth2pc_pixels, transform_points and base_pos2grid_id_3d (oracle/avl_oracle.py), as
+in _explore_ref.py, whose scene helpers are re-exported here.  `stats`, when given, counts what the rays of a call did, so that a
+test can assert that its scene really contains the cases it claims to cover."""
+import numpy as np
+
+from oracle import avl_oracle as O
+
+from _explore_ref import _bump, calib, camera, rot_x, rot_y, rot_z, walk as walk2d  # noqa: F401
+
+NEVER = -1
+MAX_CELL = 1 << 28
+
+
+def cell_dict(grid_pos, gs, vh):
+    """{(row, col, h): voxel row}: rows outside the grid are left out, the largest row of a cell owns it"""
+    index = {}
+    for i, (r, c, h) in enumerate(np.asarray(grid_pos).reshape(-1, 3).tolist()):
+        if 0 <= r < gs and 0 <= c < gs and 0 <= h < vh:
+            index[(r, c, h)] = i            # rows come in increasing order: the last one written is the largest
+    return index
+
+
+def lookup_ref(grid_pos, gs, vh, cells):
+    index = cell_dict(grid_pos, gs, vh)
+    return np.array([index.get(tuple(c), -1) for c in np.asarray(cells).reshape(-1, 3).tolist()], dtype=np.int32).reshape(-1)
+
+
+def walk3(a, b):
+    """the n + 1 cells of the driving-axis walk from a to b, not clipped to any grid"""
+    x = list(a)
+    d = [abs(b[k] - a[k]) for k in range(3)]
+    s = [1 if b[k] > a[k] else -1 for k in range(3)]
+    n = max(d)
+    drive = d.index(n)                      # the first of (row, col, h) with d == n
+    e = [2 * d[k] - n for k in range(3)]
+    out = []
+    for _ in range(n + 1):
+        out.append(tuple(x))
+        for k in range(3):
+            if k == drive:
+                continue
+            if e[k] > 0:
+                x[k] += s[k]
+                e[k] -= 2 * n
+            e[k] += 2 * d[k]
+        x[drive] += s[drive]
+    return out
+
+
+def ray(z_f32, u, v, Kinv, T, gs, vh, cs, h_min, h_max, min_depth, max_depth, stats=None):
+    """-> None for a ray that is skipped whole, else (cells, n, has_end, is_hit): the cells the walk visits inside the grid, in
+    order (cells[k] is step k), the walk's length n, and the ray's kind"""
+    depth = np.zeros((v + 1, u + 1), np.float32)        # depth2pc_pixels takes pixel v * W + u of an image: one just large enough
+    depth[v, u] = z_f32
+    pc, _ = O.depth2pc_pixels(depth, Kinv, [v * (u + 1) + u], min_depth, max_depth)
+    p = pc[0]
+    if not p[2] > min_depth:
+        _bump(stats, "dropped")
+        return None
+    far = bool(p[2] >= max_depth)
+    if far:
+        with np.errstate(invalid="ignore"):                 # an infinite depth gives inf * 0: not finite, skipped below
+            s = max_depth / p[2]
+            p = np.array([p[0] * s, p[1] * s, p[2] * s])
+    Ov = np.array([T[0, 3], T[1, 3], T[2, 3]], dtype=np.float64)
+    P = O.transform_points(T, p[None])[0]
+    if not (np.all(np.isfinite(Ov)) and np.all(np.isfinite(P))):
+        _bump(stats, "not_finite")
+        return None
+    t0, t1 = 0.0, 1.0
+    dz = P[2] - Ov[2]
+    if Ov[2] == h_max:
+        _bump(stats, "camera_at_h_max")
+    if dz == 0.0:
+        if not (h_min <= Ov[2] <= h_max):
+            _bump(stats, "level_outside")
+            return None
+        _bump(stats, "level_inside")
+    else:
+        ta, tb = (h_min - Ov[2]) / dz, (h_max - Ov[2]) / dz
+        t0, t1 = max(0.0, min(ta, tb)), min(1.0, max(ta, tb))
+        if not t0 <= t1:
+            _bump(stats, "slab_empty")
+            return None
+        if t0 > 0.0:
+            _bump(stats, "enters_from_above" if Ov[2] > h_max else "enters_from_below")
+        if t1 < 1.0:
+            _bump(stats, "slab_leaves")
+    dx, dy = P[0] - Ov[0], P[1] - Ov[1]
+    A = tuple(Ov) if t0 == 0.0 else (Ov[0] + t0 * dx, Ov[1] + t0 * dy, Ov[2] + t0 * dz)
+    B = tuple(P) if t1 == 1.0 else (Ov[0] + t1 * dx, Ov[1] + t1 * dy, Ov[2] + t1 * dz)
+    if not all(np.isfinite(w) for w in A + B):
+        _bump(stats, "not_finite")
+        return None
+
+    def cell(X):
+        row, col, _ = O.base_pos2grid_id_3d(gs, cs, X[0], X[1], 0.0)
+        hu = int(X[2] / cs)                                 # truncating: the builder's base_pos2grid_id_3d
+        assert hu == O.base_pos2grid_id_3d(gs, cs, 0.0, 0.0, X[2])[2]
+        return (int(row), int(col), min(max(hu, 0), vh - 1)), hu
+    (a, _), (b, bhu) = cell(A), cell(B)
+    if not (0 <= a[0] < gs and 0 <= a[1] < gs):
+        _bump(stats, "starts_outside")
+        return None
+    if abs(b[0]) > MAX_CELL or abs(b[1]) > MAX_CELL:
+        _bump(stats, "too_far")
+        return None
+    has_end = (not far) and t1 == 1.0
+    b_in = 0 <= b[0] < gs and 0 <= b[1] < gs
+    is_hit = has_end and 0 <= bhu < vh and b_in
+    _bump(stats, "far" if far else "has_end" if has_end else "cut")
+    if is_hit:
+        _bump(stats, "hit")
+        if -cs < P[2] < 0.0:
+            _bump(stats, "hit_below_zero")
+    if has_end and b_in and bhu >= vh:
+        _bump(stats, "end_above_grid")
+    d = [abs(b[k] - a[k]) for k in range(3)]
+    n = max(d)
+    if n == 0:
+        _bump(stats, "point")
+    elif sorted(d)[1] == 0:
+        _bump(stats, "axis_aligned", d.index(n))
+    elif sorted(d)[1] == n:
+        _bump(stats, "diagonal")
+    if min(d) > 0:
+        _bump(stats, "octants", (d.index(n), b[0] > a[0], b[1] > a[1], b[2] > a[2]))
+    cells = []
+    for x in walk3(a, b):
+        if not (0 <= x[0] < gs and 0 <= x[1] < gs):
+            _bump(stats, "leaves_grid")
+            break
+        assert 0 <= x[2] < vh
+        cells.append(x)
+    else:
+        assert cells[-1] == b and len(cells) == n + 1
+    return cells, n, has_end, is_hit
+
+
+def lattice(H, W, stride):
+    return [(v, u) for v in range(stride // 2, H, stride) for u in range(stride // 2, W, stride)]
+
+
+def hit_cells(rays):
+    """the end cells of the hit rays of a trace, a sorted list without repeats (a hit ray starts and ends inside the grid, and a
+    walk between two cells of a box never leaves the box: its last cell is its end cell)"""
+    return sorted({cells[-1] for _, cells, n, has_end, is_hit in rays if is_hit})
+
+
+def trace(gs, vh, depth, calib_mat, transforms, frame_ids, cs, stride=4, h_min=None, h_max=None, min_depth=0.1, max_depth=6.0,
+          stats=None):
+    """the rays of the frames that are not skipped, in frame and lattice order: a list of (frame id, cells, n, has_end, is_hit).
+    It does not depend on the voxels: a test traces a scene once and folds it as often as it likes."""
+    h_min = -cs if h_min is None else h_min
+    h_max = vh * cs if h_max is None else h_max
+    depth = np.asarray(depth, dtype=np.float32)
+    depth = depth[None] if depth.ndim == 2 else depth
+    Kinv = np.linalg.inv(np.asarray(calib_mat, dtype=np.float64).reshape(3, 3))
+    Ts = np.asarray(transforms, dtype=np.float64).reshape(-1, 4, 4)
+    out = []
+    for f in range(depth.shape[0]):
+        for v, u in lattice(depth.shape[1], depth.shape[2], stride):
+            got = ray(depth[f, v, u], u, v, Kinv, Ts[f], gs, vh, cs, h_min, h_max, min_depth, max_depth, stats)
+            if got is not None:
+                out.append((int(frame_ids[f]),) + got)
+    return out
+
+
+def fold(rays, grid_pos, gs, vh, end_margin=2, last_hit=None, through=None, after=None, stats=None):
+    """-> (last_hit, through): copies of the given arrays with the traced rays folded in, None where None was given"""
+    index = cell_dict(grid_pos, gs, vh)
+    last_hit = None if last_hit is None else np.array(last_hit, dtype=np.int32)
+    through = None if through is None else np.array(through, dtype=np.uint32)
+    for fid, cells, n, has_end, is_hit in rays:
+        for k, x in enumerate(cells):
+            i = index.get(x)
+            if i is None:
+                continue
+            if k == n and is_hit:
+                _bump(stats, "hit_recorded")
+                if last_hit is not None:
+                    last_hit[i] = max(int(last_hit[i]), fid)
+            if (not has_end) or k < n - end_margin:
+                if after is None or fid > int(after[i]):
+                    _bump(stats, "through_counted")
+                    if after is not None:
+                        _bump(stats, "after_never" if int(after[i]) == NEVER else "after_next" if fid == int(after[i]) + 1 else "after_later")
+                    if through is not None:
+                        through[i] += np.uint32(1)
+                else:
+                    _bump(stats, "after_equal" if fid == int(after[i]) else "after_earlier")
+            elif k < n:
+                _bump(stats, "inside_margin")
+    return last_hit, through
+
+
+def audit_ref(grid_pos, gs, vh, depth, calib_mat, transforms, frame_ids, cs, stride=4, h_min=None, h_max=None, min_depth=0.1,
+              max_depth=6.0, end_margin=2, last_hit=None, through=None, after=None, stats=None):
+    """ops.audit_rays restated: trace, then fold"""
+    rays = trace(gs, vh, depth, calib_mat, transforms, frame_ids, cs, stride, h_min, h_max, min_depth, max_depth, stats)
+    return fold(rays, grid_pos, gs, vh, end_margin, last_hit, through, after, stats)
