@@ -37,12 +37,12 @@ SOURCES = {
     "avl_pnp.hip": ["-ffp-contract=off"],          # the inlier test and the lift are NumPy's float64 expressions, operation for operation
     "avl_audio.hip": ["-ffp-contract=off"],        # compares, one product and one division per sample: nothing to fuse, and it stays so
     "avl_resample.hip": ["-ffp-contract=off"],     # a filter term is a float64 product, then a float64 add: SciPy's upfirdn, unfused
-    "avl_explore.hip": ["-ffp-contract=off"],      # a ray's points are K1's (the explicit fma chain), its slab and end points plain float64 operations
-    "avl_gtmap.hip": ["-ffp-contract=off"],        # a vote's voxel is K1's point and cell (the explicit fma chain); everything after it is integer
+    "avl_explore.hip": ["-ffp-contract=off"],      # avl_sightray.h: a ray's points are K1's (the explicit fma chain), its slab and end points plain float64 operations
+    "avl_gtmap.hip": ["-ffp-contract=off"],        # avl_sightray.h's pixel, K1's point and cell (the explicit fma chain); everything after it is integer
     "avl_resize.hip": ["-ffp-contract=off"],       # integer kernels; the flag keeps the file in line with the other 2-D sources
     "avl_instances.hip": ["-ffp-contract=off"],    # integer kernels; the flag keeps the file in line with the other integer sources
     "avl_colselect.hip": ["-ffp-contract=off"],    # integer kernels and one float64 comparison; nothing to fuse, and it stays so
-    "avl_audit.hip": ["-ffp-contract=off"],        # a ray's points, slab and end points are avl_explore.hip's, operation for operation
+    "avl_audit.hip": ["-ffp-contract=off"],        # avl_sightray.h: the ray's points, slab and end points are the carver's by one definition
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fvisibility=hidden", "-Wall",
           "-Wno-unused-function", "-munsafe-fp-atomics"]

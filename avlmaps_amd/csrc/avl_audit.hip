@@ -17,12 +17,12 @@
 // grid is 120 MB.  A probe is one bit test; on a set bit rank = prefix[w] + popc(word & below) and the row is perm[rank].  Rows
 // outside the grid set no bit: no probe finds them.
 //
-// ONE RAY.  Steps 1 - 8 are the carver's (pixel lattice, depth, bp_backproject, validity, far / hit, bp_transform, the height slab
-// with its t0 and t1), RESTATED here rather than shared through a header so that avl_explore.hip and its code object stay as they
-// are; the file is compiled with the same -ffp-contract=off.  Then
-//    9  X(t) = O + t * (P - O) per coordinate for all three (X(0) = O, X(1) = P exactly); row and col as the carver's, hu =
-//       int(z / cs) truncating, h = min(max(hu, 0), vh - 1); a = cell(X(t0)), b = cell(X(t1))
-//   10  skipped whole: O, P or an end point not finite; a outside [0, gs)^2; |b.row| or |b.col| above 2^28
+// ONE RAY.  Steps 1 - 8 are the sight ray of avl_sightray.h, the carver's: the pixel lattice, the depth, bp_backproject, validity,
+// far / hit, bp_transform, the height slab with its t0 and t1, the end points A = X(t0) and B = X(t1) in all three coordinates
+// (X(0) = O, X(1) = P exactly) and the finiteness of their x and y.  Then
+//    9  the cell of a point: row and col as the carver's (ray_cell_rc), hu = int(z / cs) truncating, h = min(max(hu, 0), vh - 1);
+//       a = cell(A), b = cell(B)
+//   10  also skipped whole: the z of A or B not finite; a outside [0, gs)^2; |b.row| or |b.col| above 2^28
 //   11  has_end = !far && t1 == 1;  is_hit = has_end && 0 <= hu(P) < vh && b inside [0, gs)^2  (the builder's in-range rule)
 //   12  the walk: d = |b - a| per axis, s the signs, n = max(d); cells k = 0 .. n; between two cells every axis x with error
 //       e_x (starting at 2 d_x - n) does `if e_x > 0: x += s_x, e_x -= 2 n`, then `e_x += 2 d_x`.  DESIGN states this with a driving
@@ -33,7 +33,7 @@
 //       k < n - end_margin: through[i] += 1, unless `after` is given and id <= after[i].
 // Both folds commute: rays, frames, launches and calls may come in any order and continue each other.
 //
-// Launch shape: the carver's.  A thread owns a ray, lanes run along an image row, blockIdx.y is the frame, up to kAuditFrames poses
+// Launch shape: the carver's.  A thread owns a ray, lanes run along an image row, blockIdx.y is the frame, up to kRayFrames poses
 // travel in the kernel arguments, nothing is allocated per call.  The through-add is pre-aggregated once per wave (audit_add: the
 // lanes on the first adding lane's voxel share one atomic, 2.15 -> 0.85 ms for pass B of 64 frames); last_hit is
 // read first and the atomicMax issued only when it would change it.
@@ -41,13 +41,12 @@
 #include <climits>
 #include <cmath>
 
-#include "avl_pinhole.h"
 #include "avl_scan.h"
+#include "avl_sightray.h"
 
 namespace avl {
 
 constexpr int kAuditThreads = 256;
-constexpr int kAuditFrames = 16;                // frames per launch: 16 * 104 bytes of kernel arguments
 constexpr int kAuditMaxSide = 16384;            // gs, as the carver's
 constexpr int kAuditMaxCell = 1 << 28;          // |b.row|, |b.col|: 2 d and 2 n stay inside int32
 constexpr int kCiThreads = 256;
@@ -162,69 +161,35 @@ __device__ __forceinline__ void audit_add(unsigned* __restrict__ through, int i)
 #endif
 }
 
-struct AuditFrame {
-    double t[12];                               // the first three rows of the frame's camera -> map transform
-    int32_t id, pad;
-};
-struct AuditBatch {
-    AuditFrame f[kAuditFrames];
-};
 struct AuditParams {
-    double kinv[9];
-    double cs, half_gs, h_min, h_max, min_depth, max_depth, depth_div;
-    int H, W, gs, vh, stride, nv, nu, depth_u16, end_margin;
+    RayParams ray;
+    int vh, end_margin;
     const uint32_t* bits;
     const int32_t* prefix;
     const int32_t* perm;
 };
 
-__global__ __launch_bounds__(kAuditThreads) void audit_kernel(AuditParams p, AuditBatch batch, const void* __restrict__ depth,
+__global__ __launch_bounds__(kAuditThreads) void audit_kernel(AuditParams p, RayBatch batch, const void* __restrict__ depth,
                                                              int32_t* __restrict__ last_hit, unsigned* __restrict__ through,
                                                              const int32_t* __restrict__ after) {
-    const AuditFrame& fr = batch.f[blockIdx.y];
+    const RayFrame& fr = batch.f[blockIdx.y];
     const int id = fr.id;
     const int ray = blockIdx.x * kAuditThreads + threadIdx.x;
-    if (ray >= p.nv * p.nu) return;
-    const double ox = fr.t[3], oy = fr.t[7], oz = fr.t[11];
-    const int v = p.stride / 2 + (ray / p.nu) * p.stride, u = p.stride / 2 + (ray % p.nu) * p.stride;
-    const size_t pix = (size_t)blockIdx.y * p.H * p.W + (size_t)v * p.W + u;
-    const double z = p.depth_u16 ? (double)reinterpret_cast<const uint16_t*>(depth)[pix] / p.depth_div
-                                 : (double)reinterpret_cast<const float*>(depth)[pix];
+    if (ray >= p.ray.nv * p.ray.nu) return;
+    SightRay s;
+    ray_origin(fr, s);
+    size_t pix;
     double p0, p1, p2;
-    bp_backproject(p.kinv, (double)u + 0.5, (double)v + 0.5, z, p0, p1, p2);
-    if (!(p2 > p.min_depth)) return;                                            // (3)
-    const bool far = p2 >= p.max_depth;                                         // (4)
-    if (far) {
-        const double s = p.max_depth / p2;
-        p0 = p0 * s;
-        p1 = p1 * s;
-        p2 = p2 * s;
-    }
-    double gx, gy, gz;
-    bp_transform(fr.t, p0, p1, p2, gx, gy, gz);                                 // (5)
-    if (!(isfinite(ox) && isfinite(oy) && isfinite(oz) && isfinite(gx) && isfinite(gy) && isfinite(gz))) return;
-    double t0 = 0.0, t1 = 1.0;                                                  // (8) the height slab
-    const double dz = gz - oz;
-    if (dz == 0.0) {
-        if (!(oz >= p.h_min && oz <= p.h_max)) return;
-    } else {
-        const double ta = (p.h_min - oz) / dz, tb = (p.h_max - oz) / dz;
-        t0 = fmax(0.0, fmin(ta, tb));
-        t1 = fmin(1.0, fmax(ta, tb));
-        if (!(t0 <= t1)) return;
-    }
-    const double dx = gx - ox, dy = gy - oy;                                    // (9)
-    const double ax = t0 == 0.0 ? ox : ox + t0 * dx, ay = t0 == 0.0 ? oy : oy + t0 * dy, az = t0 == 0.0 ? oz : oz + t0 * dz;
-    const double bx = t1 == 1.0 ? gx : ox + t1 * dx, by = t1 == 1.0 ? gy : oy + t1 * dy, bz = t1 == 1.0 ? gz : oz + t1 * dz;
-    if (!(isfinite(ax) && isfinite(ay) && isfinite(az) && isfinite(bx) && isfinite(by) && isfinite(bz))) return;
-    int r = py_int(p.half_gs - (double)py_int(ax / p.cs)), c = py_int(p.half_gs - (double)py_int(ay / p.cs));
-    int h = min(max(py_int(az / p.cs), 0), p.vh - 1);
-    const int br = py_int(p.half_gs - (double)py_int(bx / p.cs)), bc = py_int(p.half_gs - (double)py_int(by / p.cs));
-    const int bhu = py_int(bz / p.cs), bh = min(max(bhu, 0), p.vh - 1);
-    const int gs = p.gs;
+    ray_pixel(p.ray, depth, ray, blockIdx.y, pix, p0, p1, p2);                  // (1 - 2)
+    if (!(sight_ray(p.ray, fr, p0, p1, p2, s) && isfinite(s.az) && isfinite(s.bz))) return;       // (3 - 8)
+    int r = ray_cell_rc(p.ray, s.ax), c = ray_cell_rc(p.ray, s.ay);             // (9)
+    int h = min(max(py_int(s.az / p.ray.cs), 0), p.vh - 1);
+    const int br = ray_cell_rc(p.ray, s.bx), bc = ray_cell_rc(p.ray, s.by);
+    const int bhu = py_int(s.bz / p.ray.cs), bh = min(max(bhu, 0), p.vh - 1);
+    const int gs = p.ray.gs;
     if (!(r >= 0 && r < gs && c >= 0 && c < gs)) return;                        // (10)
     if (br > kAuditMaxCell || br < -kAuditMaxCell || bc > kAuditMaxCell || bc < -kAuditMaxCell) return;
-    const bool has_end = !far && t1 == 1.0;                                     // (11)
+    const bool has_end = !s.far && s.ends;                                      // (11)
     const bool is_hit = has_end && bhu >= 0 && bhu < p.vh && br >= 0 && br < gs && bc >= 0 && bc < gs;
     const int dr = abs(br - r), dc = abs(bc - c), dh = abs(bh - h);             // (12)
     const int sr = br > r ? 1 : -1, sc = bc > c ? 1 : -1, sh = bh > h ? 1 : -1;
@@ -321,59 +286,33 @@ int avl_audit_rays(const void* d_index, size_t index_bytes, int64_t N, int gs, i
                    int F, int H, int W, const double* h_calib_inv, const double* h_transforms, const int32_t* h_frame_ids, double cs, int stride,
                    double h_min, double h_max, double min_depth, double max_depth, int end_margin, int32_t* d_last_hit, uint32_t* d_through,
                    const int32_t* d_after, void* stream) {
-    const int rc = ci_check_grid("avl_audit_rays", N, gs, vh);
+    int rc = ci_check_grid("avl_audit_rays", N, gs, vh);
     if (rc != AVL_OK) return rc;
-    AVL_REQUIRE(F >= 0 && H > 0 && W > 0 && (int64_t)H * W < INT_MAX, "avl_audit_rays: bad batch of %d frames of %d x %d", F, H, W);
-    AVL_REQUIRE(std::isfinite(cs) && cs > 0, "avl_audit_rays: cell size must be finite and positive");
-    AVL_REQUIRE(stride >= 1, "avl_audit_rays: stride %d < 1", stride);
+    const double h_band[2] = {h_min, h_max};
+    AuditParams p{};
+    rc = ray_params("avl_audit_rays", depth_is_u16, depth_div, F, H, W, h_calib_inv, gs, 0, cs, stride, h_band, min_depth, max_depth, &p.ray);
+    if (rc != AVL_OK) return rc;
     AVL_REQUIRE(end_margin >= 0, "avl_audit_rays: end_margin %d < 0", end_margin);
-    AVL_REQUIRE(std::isfinite(h_min) && std::isfinite(h_max) && h_min <= h_max, "avl_audit_rays: height band [%g, %g]", h_min, h_max);
-    AVL_REQUIRE(std::isfinite(min_depth) && std::isfinite(max_depth) && min_depth >= 0 && max_depth > min_depth,
-                "avl_audit_rays: depth range (%g, %g)", min_depth, max_depth);
-    AVL_REQUIRE(!depth_is_u16 || (std::isfinite(depth_div) && depth_div > 0), "avl_audit_rays: depth_div must be positive");
     AVL_REQUIRE(d_index, "avl_audit_rays: null index");
     const CellIndexView v = ci_layout(const_cast<void*>(d_index), N, gs, vh);
     AVL_REQUIRE(index_bytes >= v.total, "avl_audit_rays: the index buffer has %zu bytes, needs %zu", index_bytes, v.total);
     if (F == 0 || (!d_last_hit && !d_through)) return AVL_OK;
     AVL_REQUIRE(d_depth && h_calib_inv && h_transforms && h_frame_ids, "avl_audit_rays: null pointer");
-    for (int f = 0; f < F; ++f) AVL_REQUIRE(h_frame_ids[f] >= 0, "avl_audit_rays: frame id %d is negative", h_frame_ids[f]);
-    AuditParams p{};
-    for (int i = 0; i < 9; ++i) p.kinv[i] = h_calib_inv[i];
-    p.cs = cs;
-    p.half_gs = (double)gs / 2.0;
-    p.h_min = h_min;
-    p.h_max = h_max;
-    p.min_depth = min_depth;
-    p.max_depth = max_depth;
-    p.depth_div = depth_is_u16 ? depth_div : 1.0;
-    p.H = H;
-    p.W = W;
-    p.gs = gs;
+    if ((rc = ray_frame_ids("avl_audit_rays", h_frame_ids, F)) != AVL_OK) return rc;
     p.vh = vh;
-    p.stride = stride;
-    const int off = stride / 2;
-    p.nv = off < H ? (H - off + stride - 1) / stride : 0;
-    p.nu = off < W ? (W - off + stride - 1) / stride : 0;
-    p.depth_u16 = depth_is_u16 ? 1 : 0;
     p.end_margin = end_margin;
     p.bits = v.bits;
     p.prefix = v.prefix;
     p.perm = v.perm;
-    const int rays = p.nv * p.nu;                                               // < H * W < 2^31
+    const int rays = p.ray.nv * p.ray.nu;
     if (rays == 0) return AVL_OK;
     const unsigned blocks = (unsigned)((rays + kAuditThreads - 1) / kAuditThreads);
     const size_t frame_bytes = (size_t)H * W * (depth_is_u16 ? sizeof(uint16_t) : sizeof(float));
     hipStream_t st = as_stream(stream);
-    for (int f0 = 0; f0 < F; f0 += kAuditFrames) {
-        const int n = std::min(kAuditFrames, F - f0);
-        AuditBatch b{};
-        for (int k = 0; k < n; ++k) {
-            for (int i = 0; i < 12; ++i) b.f[k].t[i] = h_transforms[(size_t)(f0 + k) * 16 + i];
-            b.f[k].id = h_frame_ids[f0 + k];
-        }
+    ray_launches(F, h_transforms, h_frame_ids, [&](const RayBatch& b, int n, int f0) {
         hipLaunchKernelGGL(audit_kernel, dim3(blocks, (unsigned)n), dim3(kAuditThreads), 0, st, p, b,
                            (const void*)((const char*)d_depth + (size_t)f0 * frame_bytes), d_last_hit, (unsigned*)d_through, d_after);
-    }
+    });
     AVL_HIP_CHECK(hipGetLastError());
     return AVL_OK;
 }

@@ -12,7 +12,8 @@
 //
 // avl_gt_vote, per pixel of the lattice stride / 2, stride / 2 + stride, ... in both image directions, in this order (float64,
 // unfused: the file is compiled with -ffp-contract=off, the only fma() are bp_backproject's and bp_transform's, K1's own code):
-//    1  z = depth[v, u] (float32 metres, or uint16 / depth_div); p = bp_backproject(Kinv, u + 0.5, v + 0.5, z); dropped unless
+//    1  z = depth[v, u] (float32 metres, or uint16 / depth_div); p = bp_backproject(Kinv, u + 0.5, v + 0.5, z) (avl_sightray.h's
+//       ray_pixel, the carver's and the audit's); dropped unless
 //       p.z > min_depth && p.z < max_depth                          (the builder's rule, oracle/avl_oracle.c:63; drops NaN and inf)
 //    2  g = bp_transform(T, p); row = int(gs / 2 - int(g.x / cs)), col = int(gs / 2 - int(g.y / cs)), h = int(g.z / cs), all
 //       truncating toward zero (base_pos2grid_id_3d); dropped outside [0, gs) x [0, gs) x [0, vh)       1 - 2 count in stats[0]
@@ -27,7 +28,7 @@
 // not guarded.  Every fold is an integer sum: nothing depends on the order of pixels, frames, launches or calls.
 //
 // Launch shape (the carver's, avl_explore.hip): a thread owns a pixel, lanes run along an image row, blockIdx.y is the frame, the
-// pose is wave-uniform and comes from the kernel arguments (up to kVoteFrames frames per launch; a longer batch takes several
+// pose is wave-uniform and comes from the kernel arguments (up to kRayFrames frames per launch; a longer batch takes several
 // launches).  A block walks tiles of 256 pixels in a grid-stride loop (about 8 blocks per CU over the launch's frames).  The vote is
 // one vector atomic whose result is not used.  The four statistics are counted per wave with ballots (scalar adds, once per tile),
 // per block in LDS, and added with one 64-bit atomic per block and non-zero count: every block of every frame adds to the same four
@@ -48,13 +49,12 @@
 #include <climits>
 #include <cmath>
 
-#include "avl_pinhole.h"
+#include "avl_sightray.h"
 #include "avl_wave.h"
 
 namespace avl {
 
 constexpr int kVoteThreads = 256;
-constexpr int kVoteFrames = 16;                 // frames per launch: 16 * 96 bytes of kernel arguments
 constexpr int kVoteBlocksPerCu = 8;             // blocks of a launch per CU, all frames together
 constexpr int kGtMaxSide = 16384;               // gs
 constexpr int kGtMaxClasses = 4096;             // C of avl_gt_vote / avl_gt_labels
@@ -64,49 +64,44 @@ constexpr int kConfMaxClasses = 65536;
 constexpr int64_t kConfMaxCounters = (int64_t)1 << 28;
 constexpr int64_t kConfBlockItems = (int64_t)1 << 30;  // a block's LDS counters are uint32: it takes fewer than 2^32 pairs
 
-struct VoteBatch {
-    double t[kVoteFrames][12];                  // the first three rows of each frame's camera -> map transform
-};
 struct VoteParams {
-    double kinv[9];
-    double cs, half_gs, min_depth, max_depth, depth_div;
+    RayParams ray;
     long long n_voxels;
-    int H, W, gs, vh, stride, nv, nu, depth_u16, n_obj, n_classes;
+    int vh, n_obj, n_classes;
 };
 
-__global__ __launch_bounds__(kVoteThreads) void gt_vote_kernel(VoteParams p, VoteBatch batch, const void* __restrict__ depth,
+// (the poses travel as avl_sightray.h's RayBatch, 16 * 104 bytes of kernel arguments: 8 more per frame than the 96 of a bare pose,
+// for a frame id that the vote does not read)
+__global__ __launch_bounds__(kVoteThreads) void gt_vote_kernel(VoteParams p, RayBatch batch, const void* __restrict__ depth,
                                                                const int32_t* __restrict__ semantic, const int32_t* __restrict__ obj2cls,
                                                                const int32_t* __restrict__ occupied, uint32_t* __restrict__ votes,
                                                                unsigned long long* __restrict__ stats, int* __restrict__ err_flag) {
     __shared__ unsigned block_counts[4];
     if (threadIdx.x < 4) block_counts[threadIdx.x] = 0;
     __syncthreads();
-    const double* T = batch.t[blockIdx.y];
-    const int pixels = p.nv * p.nu, tiles = (pixels + kVoteThreads - 1) / kVoteThreads;
+    const double* T = batch.f[blockIdx.y].t;
+    const int pixels = p.ray.nv * p.ray.nu, tiles = (pixels + kVoteThreads - 1) / kVoteThreads;
     unsigned n0 = 0, n1 = 0, n2 = 0, n3 = 0;                                   // wave-uniform: what this wave's pixels came to
     for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {              // (block-uniform trip count: the ballots below see whole waves)
         const int pixel = tile * kVoteThreads + threadIdx.x;
         int outcome = -1;                                                       // 0 .. 3: the statistic this pixel counts in
         if (pixel < pixels) {
-            const int v = p.stride / 2 + (pixel / p.nu) * p.stride, u = p.stride / 2 + (pixel % p.nu) * p.stride;
-            const size_t pix = (size_t)blockIdx.y * p.H * p.W + (size_t)v * p.W + u;
-            const double z = p.depth_u16 ? (double)reinterpret_cast<const uint16_t*>(depth)[pix] / p.depth_div
-                                         : (double)reinterpret_cast<const float*>(depth)[pix];
+            size_t pix;
             double p0, p1, p2;
-            bp_backproject(p.kinv, (double)u + 0.5, (double)v + 0.5, z, p0, p1, p2);
+            ray_pixel(p.ray, depth, pixel, blockIdx.y, pix, p0, p1, p2);
             outcome = 0;
-            if (p2 > p.min_depth && p2 < p.max_depth) {                         // (1)
+            if (p2 > p.ray.min_depth && p2 < p.ray.max_depth) {                 // (1)
                 double g0, g1, g2;
                 bp_transform(T, p0, p1, p2, g0, g1, g2);                        // (2)
-                const int row = py_int(p.half_gs - (double)py_int(g0 / p.cs)), col = py_int(p.half_gs - (double)py_int(g1 / p.cs));
-                const int h = py_int(g2 / p.cs);
-                if (row >= 0 && row < p.gs && col >= 0 && col < p.gs && h >= 0 && h < p.vh) {
+                const int row = ray_cell_rc(p.ray, g0), col = ray_cell_rc(p.ray, g1);
+                const int h = py_int(g2 / p.ray.cs);
+                if (row >= 0 && row < p.ray.gs && col >= 0 && col < p.ray.gs && h >= 0 && h < p.vh) {
                     outcome = 1;
                     int c = semantic[pix];                                      // (3)
                     if (obj2cls) c = (c >= 0 && c < p.n_obj) ? obj2cls[c] : -1;
                     if (c >= 0 && c < p.n_classes) {
                         outcome = 2;
-                        const int r = occupied[((size_t)row * p.gs + col) * p.vh + h];      // (4)
+                        const int r = occupied[((size_t)row * p.ray.gs + col) * p.vh + h];  // (4)
                         if (r >= p.n_voxels) {
                             outcome = -1;
                             if (err_flag) atomicOr(err_flag, 1);
@@ -242,14 +237,11 @@ int avl_gt_vote(const void* d_depth, int depth_is_u16, double depth_div, const i
                 const double* h_calib_inv, const double* h_transforms, int gs, double cs, int vh, int stride, double min_depth,
                 double max_depth, const int32_t* d_obj2cls, int n_obj, int n_classes, const int32_t* d_occupied_ids, int64_t n_voxels,
                 uint32_t* d_votes, uint64_t* d_stats, int32_t* d_err_flag, void* stream) {
-    AVL_REQUIRE(F >= 0 && H > 0 && W > 0 && (int64_t)H * W < INT_MAX, "avl_gt_vote: bad batch of %d frames of %d x %d", F, H, W);
-    AVL_REQUIRE(gs >= 1 && gs <= kGtMaxSide, "avl_gt_vote: grid size %d (1 .. %d)", gs, kGtMaxSide);
+    VoteParams p{};
+    const int rc = ray_params("avl_gt_vote", depth_is_u16, depth_div, F, H, W, h_calib_inv, gs, kGtMaxSide, cs, stride, nullptr, min_depth,
+                              max_depth, &p.ray);
+    if (rc != AVL_OK) return rc;
     AVL_REQUIRE(vh >= 1 && (int64_t)gs * gs * vh < kGtMaxVotes, "avl_gt_vote: voxel height %d (>= 1, gs * gs * vh < 2^40)", vh);
-    AVL_REQUIRE(std::isfinite(cs) && cs > 0, "avl_gt_vote: cell size must be finite and positive");
-    AVL_REQUIRE(stride >= 1, "avl_gt_vote: stride %d < 1", stride);
-    AVL_REQUIRE(std::isfinite(min_depth) && std::isfinite(max_depth) && min_depth >= 0 && max_depth > min_depth,
-                "avl_gt_vote: depth range (%g, %g)", min_depth, max_depth);
-    AVL_REQUIRE(!depth_is_u16 || (std::isfinite(depth_div) && depth_div > 0), "avl_gt_vote: depth_div must be positive");
     AVL_REQUIRE(n_classes >= 1 && n_classes <= kGtMaxClasses, "avl_gt_vote: %d classes (1 .. %d)", n_classes, kGtMaxClasses);
     AVL_REQUIRE(n_voxels >= 0 && n_voxels * n_classes < kGtMaxVotes, "avl_gt_vote: %lld voxels x %d classes (N * C < 2^40)",
                 (long long)n_voxels, n_classes);
@@ -257,41 +249,22 @@ int avl_gt_vote(const void* d_depth, int depth_is_u16, double depth_div, const i
     if (F == 0) return AVL_OK;
     AVL_REQUIRE(d_depth && d_semantic && h_calib_inv && h_transforms && d_occupied_ids && d_stats && (d_votes || n_voxels == 0),
                 "avl_gt_vote: null pointer");
-    VoteParams p{};
-    for (int i = 0; i < 9; ++i) p.kinv[i] = h_calib_inv[i];
-    p.cs = cs;
-    p.half_gs = (double)gs / 2.0;
-    p.min_depth = min_depth;
-    p.max_depth = max_depth;
-    p.depth_div = depth_is_u16 ? depth_div : 1.0;
     p.n_voxels = n_voxels;
-    p.H = H;
-    p.W = W;
-    p.gs = gs;
     p.vh = vh;
-    p.stride = stride;
-    const int off = stride / 2;
-    p.nv = off < H ? (H - off + stride - 1) / stride : 0;
-    p.nu = off < W ? (W - off + stride - 1) / stride : 0;
-    p.depth_u16 = depth_is_u16 ? 1 : 0;
     p.n_obj = n_obj;
     p.n_classes = n_classes;
-    const int pixels = p.nv * p.nu;                                             // <= H * W < 2^31
+    const int pixels = p.ray.nv * p.ray.nu;
     if (pixels == 0) return AVL_OK;
     const int tiles = (pixels + kVoteThreads - 1) / kVoteThreads;
     const size_t frame_px = (size_t)H * W, depth_bytes = frame_px * (depth_is_u16 ? sizeof(uint16_t) : sizeof(float));
     hipStream_t st = as_stream(stream);
-    for (int f0 = 0; f0 < F; f0 += kVoteFrames) {
-        const int n = std::min(kVoteFrames, F - f0);
+    ray_launches(F, h_transforms, nullptr, [&](const RayBatch& b, int n, int f0) {
         // about kVoteBlocksPerCu blocks per CU over the launch's frames: a block walks several tiles and adds its statistics once
         const unsigned blocks = (unsigned)std::max(1, std::min(tiles, (num_cus() * kVoteBlocksPerCu + n - 1) / n));
-        VoteBatch b{};
-        for (int k = 0; k < n; ++k)
-            for (int i = 0; i < 12; ++i) b.t[k][i] = h_transforms[(size_t)(f0 + k) * 16 + i];
         hipLaunchKernelGGL(gt_vote_kernel, dim3(blocks, (unsigned)n), dim3(kVoteThreads), 0, st, p, b,
                            (const void*)((const char*)d_depth + (size_t)f0 * depth_bytes), d_semantic + (size_t)f0 * frame_px, d_obj2cls,
                            d_occupied_ids, d_votes, (unsigned long long*)d_stats, (int*)d_err_flag);
-    }
+    });
     AVL_HIP_CHECK(hipGetLastError());
     return AVL_OK;
 }

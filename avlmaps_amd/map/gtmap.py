@@ -84,11 +84,9 @@ class GTMap(Map):
         exists, else the frames hold class ids.  categories: names whose index is the class id; their number is the number of
         classes (without them: the table's largest class + 1).  One vote per stride-th pixel in both directions;
         frames go up in batches of `batch`, one loader thread ahead of the GPU."""
-        import queue
-        import threading
         from .. import ops
         from ..device import DeviceArray
-        from ..utils.mapping_utils import load_depth_npy
+        from ._frames import batch_ranges, depth_batch, prefetch
         from .vlmap_builder import VLMapBuilder
         self._setup_paths(data_dir)
         if not self.semantic_paths:
@@ -122,36 +120,21 @@ class GTMap(Map):
         n = min(len(self.depth_paths), len(self.semantic_paths), len(poses))
         N = int(len(self.grid_pos))
         params = dict(cs=float(self.cs), stride=int(stride), min_depth=float(builder.min_depth), max_depth=float(builder.max_depth))
-        batches = queue.Queue(maxsize=2)
 
-        def load():
-            try:
-                for lo in range(0, n, int(batch)):
-                    hi = min(n, lo + int(batch))
-                    depth = np.stack([np.asarray(load_depth_npy(self.depth_paths[i]), dtype=np.float32) for i in range(lo, hi)])
-                    sem = ops._ids_i32(np.stack([load_semantic_npy(self.semantic_paths[i]) for i in range(lo, hi)]), "semantic")
-                    batches.put((lo, hi, depth.reshape(sem.shape), sem))
-                batches.put(None)
-            except BaseException as e:          # surfaced on the calling thread
-                batches.put(e)
-        loader = threading.Thread(target=load, name="avl-gtmap-load", daemon=True)
-        loader.start()
+        def load(lo, hi):
+            depth = depth_batch(self.depth_paths, lo, hi)
+            sem = ops._ids_i32(np.stack([load_semantic_npy(self.semantic_paths[i]) for i in range(lo, hi)]), "semantic")
+            return lo, hi, depth.reshape(sem.shape), sem
+        frames = prefetch(load, batch_ranges(n, batch), "avl-gtmap-load")
         occ = self._device_occupied()
         votes = DeviceArray((N, C), np.uint32).zero_()
         stats = DeviceArray((4,), np.uint64).zero_()
         flag = DeviceArray((1,), np.int32).zero_()
         table_dev = None if table is None else DeviceArray.from_numpy(table)
         try:
-            while True:
-                item = batches.get()
-                if item is None:
-                    break
-                if isinstance(item, BaseException):
-                    raise item
-                lo, hi, depth, sem = item
+            for lo, hi, depth, sem in frames:
                 ops.gt_vote(votes, DeviceArray.from_numpy(depth), DeviceArray.from_numpy(sem), calib, transforms[lo:hi], occ, N, C,
                             obj2cls=table_dev, stats=stats, err_flag=flag, device=True, **params)
-            loader.join()
             labels, support = ops.gt_labels(votes, device=True)
             grid_gt = ops.pool_labels_2d(labels, occ, err_flag=flag, device=True)
             ops.check_label_flag(flag, "GTMap.create_map")

@@ -174,11 +174,9 @@ class Map:
         cell inside the height band, -1 = never -- and write <data_dir>/vlmap/explored.npz.  Reads poses.txt and depth/*.npy as the
         builder does: its frame_transforms, cam_calib_mat, min_depth and max_depth.  Frames go up in batches of `batch`, one
         loader thread ahead of the GPU; one ray per stride-th pixel in both directions."""
-        import queue
-        import threading
         from .. import ops
         from ..device import DeviceArray
-        from ..utils.mapping_utils import load_depth_npy
+        from ._frames import batch_ranges, depth_batch, prefetch
         from .vlmap_builder import VLMapBuilder
         if data_dir is not None:
             self._setup_paths(data_dir)
@@ -195,30 +193,12 @@ class Map:
         gs, cs = int(self.gs), float(self.cs)
         params = dict(gs=gs, cs=cs, stride=int(stride), h_min=float(h_min), h_max=float(h_max), min_depth=float(builder.min_depth),
                       max_depth=float(builder.max_depth))
-        batches = queue.Queue(maxsize=2)
-
-        def load():
-            try:
-                for lo in range(0, n, int(batch)):
-                    hi = min(n, lo + int(batch))
-                    batches.put((lo, hi, np.stack([np.asarray(load_depth_npy(self.depth_paths[i]), dtype=np.float32) for i in range(lo, hi)])))
-                batches.put(None)
-            except BaseException as e:          # surfaced on the calling thread
-                batches.put(e)
-        loader = threading.Thread(target=load, name="avl-explore-load", daemon=True)
-        loader.start()
+        frames = prefetch(lambda lo, hi: (lo, hi, depth_batch(self.depth_paths, lo, hi)), batch_ranges(n, batch), "avl-explore-load")
         first_seen = DeviceArray.from_numpy(np.full((gs, gs), ops.NEVER_SEEN, np.int32))
         try:
-            while True:
-                item = batches.get()
-                if item is None:
-                    break
-                if isinstance(item, BaseException):
-                    raise item
-                lo, hi, depth = item
+            for lo, hi, depth in frames:
                 ops.carve_free_space(first_seen, DeviceArray.from_numpy(depth), calib, transforms[lo:hi], np.arange(lo, hi), device=True,
                                      **params)
-            loader.join()
             self.first_seen = first_seen.numpy()
         finally:
             first_seen.free()
@@ -329,11 +309,9 @@ class Map:
         (ops.audit_rays with after = last_hit).  Reads poses.txt and depth/*.npy as create_explored_map does, in batches of
         `batch` frames, one loader thread ahead of the GPU.  The result is kept as self.visibility and written to
         <data_dir>/vlmap/visibility.npz."""
-        import queue
-        import threading
         from .. import ops
         from ..device import DeviceArray
-        from ..utils.mapping_utils import load_depth_npy
+        from ._frames import batch_ranges, depth_batch, prefetch
         if self.grid_pos is None or self.occupied_ids is None:
             raise ValueError("audit_visibility: no map loaded")
         if int(batch) < 1:
@@ -363,31 +341,16 @@ class Map:
         gs, cs, vh = int(self.gs), float(self.cs), int(np.asarray(self.occupied_ids).shape[2])
         N = len(self.grid_pos)
 
-        def run_pass(index, **outputs):
-            batches = queue.Queue(maxsize=2)
+        ranges = [(s, lo, hi) for s, count in enumerate(counts) for lo, hi in batch_ranges(count, batch)]      # (no batch spans two directories)
 
-            def load():
-                try:
-                    for (paths, transforms, mn, mx), first in zip(scenes, starts):
-                        for lo in range(0, len(paths), int(batch)):
-                            hi = min(len(paths), lo + int(batch))
-                            depth = np.stack([np.asarray(load_depth_npy(paths[i]), dtype=np.float32) for i in range(lo, hi)])
-                            batches.put((depth, transforms[lo:hi], np.arange(first + lo, first + hi), mn, mx))
-                    batches.put(None)
-                except BaseException as e:          # surfaced on the calling thread
-                    batches.put(e)
-            loader = threading.Thread(target=load, name="avl-audit-load", daemon=True)
-            loader.start()
-            while True:
-                item = batches.get()
-                if item is None:
-                    break
-                if isinstance(item, BaseException):
-                    raise item
-                depth, transforms, ids, mn, mx = item
+        def load(s, lo, hi):
+            paths, transforms, mn, mx = scenes[s]
+            return depth_batch(paths, lo, hi), transforms[lo:hi], np.arange(starts[s] + lo, starts[s] + hi), mn, mx
+
+        def run_pass(index, **outputs):
+            for depth, transforms, ids, mn, mx in prefetch(load, ranges, "avl-audit-load"):
                 ops.audit_rays(index, DeviceArray.from_numpy(depth), calib, transforms, ids, cs, stride=int(stride), min_depth=mn,
                                max_depth=mx, end_margin=int(end_margin), **outputs)
-            loader.join()
 
         last_hit = DeviceArray.from_numpy(np.full((N,), ops.NEVER_HIT, np.int32))
         through = DeviceArray((N,), np.uint32).zero_()

@@ -7,6 +7,7 @@ import numpy as np
 from .. import _lib
 from ..device import DeviceArray, DeviceView, as_device, _is_torch
 from ._args import _image_shape, _workspace
+from ._rays import frame_args
 from .builder import _global_depth
 
 AUDIT_MAX_SIDE = 16384
@@ -137,41 +138,13 @@ def audit_rays(index: CellIndex, depth, calib, transforms, frame_ids, cs, stride
         raise TypeError(f"audit_rays: expected a CellIndex, got {type(index).__name__}")
     gs, vh, N = index.gs, index.vh, index.N
     stride, end_margin = int(stride), int(end_margin)
-    if stride < 1:
-        raise ValueError(f"audit_rays: stride {stride} < 1")
     if end_margin < 0:
         raise ValueError(f"audit_rays: end_margin {end_margin} < 0")
-    if not (np.isfinite(cs) and cs > 0):
-        raise ValueError(f"audit_rays: cell size {cs}")
-    h_min = -float(cs) if h_min is None else h_min
-    h_max = vh * float(cs) if h_max is None else h_max
-    if not (np.isfinite(h_min) and np.isfinite(h_max) and h_min <= h_max):
-        raise ValueError(f"audit_rays: height band [{h_min}, {h_max}]")
-    if not (np.isfinite(min_depth) and np.isfinite(max_depth) and 0 <= min_depth < max_depth):
-        raise ValueError(f"audit_rays: depth range ({min_depth}, {max_depth})")
-    ddt = str(depth.dtype) if _is_torch(depth) else np.dtype(getattr(depth, "dtype", object))
-    if ddt not in ("torch.uint16", "torch.int16", "torch.float32", np.dtype(np.uint16), np.dtype(np.float32)):
-        raise TypeError(f"depth must be uint16 (value / depth_div metres) or float32 metres, got {ddt}")
-    if ddt in ("torch.uint16", "torch.int16", np.dtype(np.uint16)) and not (np.isfinite(depth_div) and depth_div > 0):
-        raise ValueError(f"audit_rays: depth_div {depth_div}")
-    dshape = tuple(int(s) for s in depth.shape)
-    if len(dshape) == 2:
-        dshape = (1,) + dshape
-    if len(dshape) != 3 or dshape[1] < 1 or dshape[2] < 1:
-        raise ValueError(f"audit_rays: depth must be (F, H, W) or (H, W), got shape {tuple(depth.shape)}")
-    F, H, W = dshape
-    K = np.asarray(calib, dtype=np.float64)
-    if K.size != 9:
-        raise ValueError(f"audit_rays: calib must be 3 x 3, got shape {K.shape}")
-    T = np.ascontiguousarray(transforms, dtype=np.float64)
-    if T.shape not in ((F, 4, 4), (4, 4)) or T.size != F * 16:
-        raise ValueError(f"audit_rays: {F} frames but transforms of shape {T.shape}")
-    ids = np.ascontiguousarray(np.asarray(frame_ids).reshape(-1))
-    if ids.shape[0] != F:
-        raise ValueError(f"audit_rays: {F} frames but {ids.shape[0]} frame ids")
-    if F and (ids.dtype.kind not in "iu" or ids.min() < 0 or ids.max() > 2 ** 31 - 2):
-        raise ValueError("audit_rays: frame ids are integers in [0, 2^31 - 2]")
-    ids = ids.astype(np.int32)
+    if np.isfinite(cs):                                 # (any other cell size is refused below, before the band is looked at)
+        h_min = -float(cs) if h_min is None else h_min
+        h_max = vh * float(cs) if h_max is None else h_max
+    F, H, W, Kinv, T, ids = frame_args("audit_rays", depth, calib, transforms, frame_ids, stride, cs, min_depth, max_depth,
+                                       h_band=(h_min, h_max), depth_div=depth_div)
     last_hit = _per_voxel(last_hit, "last_hit", np.int32, N)
     through = _per_voxel(through, "through", np.uint32, N)
     after = _per_voxel(after, "after", np.int32, N)
@@ -181,7 +154,6 @@ def audit_rays(index: CellIndex, depth, calib, transforms, frame_ids, cs, stride
     lp, ld, lhost = _stage(last_hit, np.int32, stream)
     tp, td, thost = _stage(through, np.uint32, stream)
     ap, ad, _ = _stage(after, np.int32, stream)
-    Kinv = np.ascontiguousarray(np.linalg.inv(K.reshape(3, 3)))
     if F and (lp or tp):
         dp, _, keep_d, is_u16 = _global_depth(depth, stream)
         _lib.check(lib.avl_audit_rays(ip, index.nbytes, N, gs, vh, dp, int(is_u16), float(depth_div), F, H, W, Kinv.ctypes.data,

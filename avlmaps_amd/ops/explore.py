@@ -6,6 +6,7 @@ import numpy as np
 from .. import _lib
 from ..device import DeviceArray, as_device, _is_torch
 from ._args import _image_shape, _image_u8, _result
+from ._rays import frame_args
 from .builder import _global_depth
 
 EXPLORE_MAX_SIDE = 16384
@@ -34,35 +35,8 @@ def carve_free_space(first_seen, depth, calib, transforms, frame_ids, gs, cs, st
     gs, stride = int(gs), int(stride)
     if not 1 <= gs <= EXPLORE_MAX_SIDE:
         raise ValueError(f"carve_free_space: grid size {gs} (1 .. {EXPLORE_MAX_SIDE})")
-    if stride < 1:
-        raise ValueError(f"carve_free_space: stride {stride} < 1")
-    if not (np.isfinite(h_min) and np.isfinite(h_max) and h_min <= h_max):
-        raise ValueError(f"carve_free_space: height band [{h_min}, {h_max}]")
-    if not (np.isfinite(cs) and cs > 0):
-        raise ValueError(f"carve_free_space: cell size {cs}")
-    if not (np.isfinite(min_depth) and np.isfinite(max_depth) and 0 <= min_depth < max_depth):
-        raise ValueError(f"carve_free_space: depth range ({min_depth}, {max_depth})")
-    ddt = str(depth.dtype) if _is_torch(depth) else np.dtype(getattr(depth, "dtype", object))
-    if ddt not in ("torch.uint16", "torch.int16", "torch.float32", np.dtype(np.uint16), np.dtype(np.float32)):
-        raise TypeError(f"depth must be uint16 (value / depth_div metres) or float32 metres, got {ddt}")
-    dshape = tuple(int(s) for s in depth.shape)
-    if len(dshape) == 2:
-        dshape = (1,) + dshape
-    if len(dshape) != 3 or dshape[1] < 1 or dshape[2] < 1:
-        raise ValueError(f"carve_free_space: depth must be (F, H, W) or (H, W), got shape {tuple(depth.shape)}")
-    F, H, W = dshape
-    K = np.asarray(calib, dtype=np.float64)
-    if K.size != 9:
-        raise ValueError(f"carve_free_space: calib must be 3 x 3, got shape {K.shape}")
-    T = np.ascontiguousarray(transforms, dtype=np.float64)
-    if T.shape not in ((F, 4, 4), (4, 4)) or T.size != F * 16:
-        raise ValueError(f"carve_free_space: {F} frames but transforms of shape {T.shape}")
-    ids = np.ascontiguousarray(np.asarray(frame_ids).reshape(-1))
-    if ids.shape[0] != F:
-        raise ValueError(f"carve_free_space: {F} frames but {ids.shape[0]} frame ids")
-    if F and (ids.dtype.kind not in "iu" or ids.min() < 0 or ids.max() > 2 ** 31 - 2):
-        raise ValueError("carve_free_space: frame ids are integers in [0, 2^31 - 2]")
-    ids = ids.astype(np.int32)
+    F, H, W, Kinv, T, ids = frame_args("carve_free_space", depth, calib, transforms, frame_ids, stride, cs, min_depth, max_depth,
+                                       h_band=(h_min, h_max))
     host_map = None
     if first_seen is not None:
         fdt = str(first_seen.dtype) if _is_torch(first_seen) else np.dtype(getattr(first_seen, "dtype", object))
@@ -83,7 +57,6 @@ def carve_free_space(first_seen, depth, calib, transforms, frame_ids, gs, cs, st
         fp = fs.ptr
     else:
         fp, fs = as_device(first_seen, np.int32, stream)[0], first_seen
-    Kinv = np.ascontiguousarray(np.linalg.inv(K.reshape(3, 3)))
     keep_d = None
     if F:
         dp, _, keep_d, is_u16 = _global_depth(depth, stream)

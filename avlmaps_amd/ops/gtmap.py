@@ -9,6 +9,7 @@ import numpy as np
 from .. import _lib
 from ..device import DeviceArray, DeviceView, as_device, _is_torch
 from ._args import _is_dev, _result
+from ._rays import frame_args
 from .builder import _global_depth
 from .explore import EXPLORE_MAX_SIDE
 
@@ -122,35 +123,15 @@ def gt_vote(votes, depth, semantic, calib, transforms, occupied_ids, n_voxels, n
     of several calls (check it with check_label_flag); None: this call checks its own, which waits for the launch.  TypeError on
     other dtypes, ValueError on bad shapes or parameters, before any device work."""
     stride, n_voxels, n_classes = int(stride), int(n_voxels), int(n_classes)
-    if stride < 1:
-        raise ValueError(f"gt_vote: stride {stride} < 1")
     if not 1 <= n_classes <= GT_MAX_CLASSES:
         raise ValueError(f"gt_vote: {n_classes} classes (1 .. {GT_MAX_CLASSES})")
     if n_voxels < 0 or n_voxels * n_classes >= GT_MAX_VOTES:
         raise ValueError(f"gt_vote: {n_voxels} voxels x {n_classes} classes (N * C < 2^40)")
-    if not (np.isfinite(cs) and cs > 0):
-        raise ValueError(f"gt_vote: cell size {cs}")
-    if not (np.isfinite(min_depth) and np.isfinite(max_depth) and 0 <= min_depth < max_depth):
-        raise ValueError(f"gt_vote: depth range ({min_depth}, {max_depth})")
-    ddt = _dtype_of(depth)
-    if ddt not in ("torch.uint16", "torch.int16", "torch.float32", np.dtype(np.uint16), np.dtype(np.float32)):
-        raise TypeError(f"depth must be uint16 (value / depth_div metres) or float32 metres, got {ddt}")
-    dshape = tuple(int(s) for s in depth.shape)
-    if len(dshape) == 2:
-        dshape = (1,) + dshape
-    if len(dshape) != 3 or dshape[1] < 1 or dshape[2] < 1:
-        raise ValueError(f"gt_vote: depth must be (F, H, W) or (H, W), got shape {tuple(depth.shape)}")
-    F, H, W = dshape
+    F, H, W, Kinv, T, _ = frame_args("gt_vote", depth, calib, transforms, None, stride, cs, min_depth, max_depth)
     semantic = _ids_i32(semantic, "semantic")
     sshape = tuple(int(s) for s in semantic.shape)
-    if (sshape if len(sshape) == 3 else (1,) + sshape) != dshape:
-        raise ValueError(f"gt_vote: depth frames of shape {dshape} but semantic frames of shape {sshape}")
-    K = np.asarray(calib, dtype=np.float64)
-    if K.size != 9:
-        raise ValueError(f"gt_vote: calib must be 3 x 3, got shape {K.shape}")
-    T = np.ascontiguousarray(transforms, dtype=np.float64)
-    if T.shape not in ((F, 4, 4), (4, 4)) or T.size != F * 16:
-        raise ValueError(f"gt_vote: {F} frames but transforms of shape {T.shape}")
+    if (sshape if len(sshape) == 3 else (1,) + sshape) != (F, H, W):
+        raise ValueError(f"gt_vote: depth frames of shape {(F, H, W)} but semantic frames of shape {sshape}")
     if _dtype_of(occupied_ids) not in ("torch.int32", np.dtype(np.int32)):
         raise TypeError(f"occupied_ids must be int32, got {_dtype_of(occupied_ids)}")
     oshape = tuple(int(s) for s in occupied_ids.shape)
@@ -172,7 +153,6 @@ def gt_vote(votes, depth, semantic, calib, transforms, occupied_ids, n_voxels, n
         err_flag = DeviceArray((1,), np.int32).zero_(stream)
     keep = []
     if F:
-        Kinv = np.ascontiguousarray(np.linalg.inv(K.reshape(3, 3)))
         dp, _, k1, is_u16 = _global_depth(depth, stream)
         mp, _, k2 = as_device(semantic, np.int32, stream)
         op, _, k3 = as_device(occupied_ids, np.int32, stream)

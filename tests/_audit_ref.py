@@ -1,14 +1,15 @@
 """Scalar restatement of the visibility audit (csrc/avl_audit.hip) for the tests: the cell index as a dict, the ray
 and its 3-D walk as a Python loop in the order DESIGN writes them down.
 
-A ray's points come from the oracle's pinned depth2pc_pixels, transform_points and base_pos2grid_id_3d (oracle/avl_oracle.py), as
-in _explore_ref.py, whose scene helpers are re-exported here.  `stats`, when given, counts what the rays of a call did, so that a
-test can assert that its scene really contains the cases it claims to cover."""
+A ray up to its end points is _ray_ref.ray_segment, the one _explore_ref.py starts from; its cells come from the oracle's pinned
+base_pos2grid_id_3d (oracle/avl_oracle.py).  The scene helpers of _ray_ref.py are re-exported here.  `stats`, when given, counts
+what the rays of a call did, so that a test can assert that its scene really contains the cases it claims to cover."""
 import numpy as np
 
 from oracle import avl_oracle as O
 
-from _explore_ref import _bump, calib, camera, rot_x, rot_y, rot_z, walk as walk2d  # noqa: F401
+from _explore_ref import walk as walk2d  # noqa: F401
+from _ray_ref import _bump, calib, camera, ray_segment, rot_x, rot_y, rot_z  # noqa: F401
 
 NEVER = -1
 MAX_CELL = 1 << 28
@@ -53,46 +54,11 @@ def walk3(a, b):
 def ray(z_f32, u, v, Kinv, T, gs, vh, cs, h_min, h_max, min_depth, max_depth, stats=None):
     """-> None for a ray that is skipped whole, else (cells, n, has_end, is_hit): the cells the walk visits inside the grid, in
     order (cells[k] is step k), the walk's length n, and the ray's kind"""
-    depth = np.zeros((v + 1, u + 1), np.float32)        # depth2pc_pixels takes pixel v * W + u of an image: one just large enough
-    depth[v, u] = z_f32
-    pc, _ = O.depth2pc_pixels(depth, Kinv, [v * (u + 1) + u], min_depth, max_depth)
-    p = pc[0]
-    if not p[2] > min_depth:
-        _bump(stats, "dropped")
+    seg = ray_segment(z_f32, u, v, Kinv, T, h_min, h_max, min_depth, max_depth, stats)
+    if isinstance(seg, str):
         return None
-    far = bool(p[2] >= max_depth)
-    if far:
-        with np.errstate(invalid="ignore"):                 # an infinite depth gives inf * 0: not finite, skipped below
-            s = max_depth / p[2]
-            p = np.array([p[0] * s, p[1] * s, p[2] * s])
-    Ov = np.array([T[0, 3], T[1, 3], T[2, 3]], dtype=np.float64)
-    P = O.transform_points(T, p[None])[0]
-    if not (np.all(np.isfinite(Ov)) and np.all(np.isfinite(P))):
-        _bump(stats, "not_finite")
-        return None
-    t0, t1 = 0.0, 1.0
-    dz = P[2] - Ov[2]
-    if Ov[2] == h_max:
-        _bump(stats, "camera_at_h_max")
-    if dz == 0.0:
-        if not (h_min <= Ov[2] <= h_max):
-            _bump(stats, "level_outside")
-            return None
-        _bump(stats, "level_inside")
-    else:
-        ta, tb = (h_min - Ov[2]) / dz, (h_max - Ov[2]) / dz
-        t0, t1 = max(0.0, min(ta, tb)), min(1.0, max(ta, tb))
-        if not t0 <= t1:
-            _bump(stats, "slab_empty")
-            return None
-        if t0 > 0.0:
-            _bump(stats, "enters_from_above" if Ov[2] > h_max else "enters_from_below")
-        if t1 < 1.0:
-            _bump(stats, "slab_leaves")
-    dx, dy = P[0] - Ov[0], P[1] - Ov[1]
-    A = tuple(Ov) if t0 == 0.0 else (Ov[0] + t0 * dx, Ov[1] + t0 * dy, Ov[2] + t0 * dz)
-    B = tuple(P) if t1 == 1.0 else (Ov[0] + t1 * dx, Ov[1] + t1 * dy, Ov[2] + t1 * dz)
-    if not all(np.isfinite(w) for w in A + B):
+    far, _, t1, _, P, A, B = seg
+    if not (np.isfinite(A[2]) and np.isfinite(B[2])):
         _bump(stats, "not_finite")
         return None
 

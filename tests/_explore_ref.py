@@ -1,11 +1,14 @@
 """NumPy / scalar restatement of the free-space carver (csrc/avl_explore.hip) and of the frontier mask, for the tests.
 
-A ray's points come from the oracle's pinned depth2pc_pixels, transform_points and base_pos2grid_id_3d (oracle/avl_oracle.py); the
-slab and the walk are a scalar Python loop in the order DESIGN.md 4.14 writes them down.  `stats`, when given, counts what the rays
-of a call did, so that a test can assert that its scene really contains the cases it claims to cover."""
+A ray up to its end points is _ray_ref.ray_segment (the oracle's pinned depth2pc_pixels and transform_points, the slab in scalar
+Python), shared with _audit_ref.py; its cells come from the oracle's base_pos2grid_id_3d and the walk is a scalar Python loop in the
+order DESIGN.md 4.14 writes it down.  `stats`, when given, counts what the rays of a call did, so that a test can assert that its
+scene really contains the cases it claims to cover.  The scene helpers of _ray_ref.py are re-exported here."""
 import numpy as np
 
 from oracle import avl_oracle as O
+
+from _ray_ref import BASE_FROM_CAM, _bump, calib, camera, ray_segment, rot_x, rot_y, rot_z  # noqa: F401
 
 NEVER = -1
 MAX_CELL = 1 << 29
@@ -41,60 +44,13 @@ def walk(a, b, gs, mark_end):
     return out
 
 
-def _bump(stats, key, value=None):
-    if stats is None:
-        return
-    if value is None:
-        stats[key] = stats.get(key, 0) + 1
-    else:
-        stats.setdefault(key, set()).add(value)
-
-
 def ray_cells(z_f32, u, v, Kinv, T, gs, cs, h_min, h_max, min_depth, max_depth, stats=None):
     """the cells one ray marks (the camera cell not included)"""
-    depth = np.zeros((v + 1, u + 1), np.float32)        # depth2pc_pixels takes pixel v * W + u of an image: one just large enough
-    depth[v, u] = z_f32
-    pc, _ = O.depth2pc_pixels(depth, Kinv, [v * (u + 1) + u], min_depth, max_depth)
-    p = pc[0]
-    if not p[2] > min_depth:
-        _bump(stats, "dropped")
+    seg = ray_segment(z_f32, u, v, Kinv, T, h_min, h_max, min_depth, max_depth, stats)
+    if isinstance(seg, str):
         return []
-    far = bool(p[2] >= max_depth)
-    if far:
-        with np.errstate(invalid="ignore"):                 # an infinite depth gives inf * 0: not finite, skipped below
-            s = max_depth / p[2]
-            p = np.array([p[0] * s, p[1] * s, p[2] * s])
-    Ov = np.array([T[0, 3], T[1, 3], T[2, 3]], dtype=np.float64)
-    P = O.transform_points(T, p[None])[0]
-    if not (np.all(np.isfinite(Ov)) and np.all(np.isfinite(P))):
-        _bump(stats, "not_finite")
-        return []
-    t0, t1 = 0.0, 1.0
-    dz = P[2] - Ov[2]
-    if dz == 0.0:
-        if not (h_min <= Ov[2] <= h_max):
-            _bump(stats, "level_outside")
-            return []
-        _bump(stats, "level_inside")
-    else:
-        ta, tb = (h_min - Ov[2]) / dz, (h_max - Ov[2]) / dz
-        t0, t1 = max(0.0, min(ta, tb)), min(1.0, max(ta, tb))
-        if not t0 <= t1:
-            _bump(stats, "slab_empty")
-            return []
-        if t0 > 0.0:
-            _bump(stats, "slab_enters")
-        if t1 < 1.0:
-            _bump(stats, "slab_leaves")
-        if t0 == 0.0 and t1 == 1.0:
-            _bump(stats, "slab_inside")
-    dx, dy = P[0] - Ov[0], P[1] - Ov[1]
-    ax, ay = (Ov[0], Ov[1]) if t0 == 0.0 else (Ov[0] + t0 * dx, Ov[1] + t0 * dy)
-    bx, by = (P[0], P[1]) if t1 == 1.0 else (Ov[0] + t1 * dx, Ov[1] + t1 * dy)
-    if not all(np.isfinite(w) for w in (ax, ay, bx, by)):
-        _bump(stats, "not_finite")
-        return []
-    a, b = cell(gs, cs, ax, ay), cell(gs, cs, bx, by)
+    far, _, t1, _, _, A, B = seg
+    a, b = cell(gs, cs, A[0], A[1]), cell(gs, cs, B[0], B[1])
     if not (0 <= a[0] < gs and 0 <= a[1] < gs):
         _bump(stats, "starts_outside")
         return []
@@ -145,41 +101,3 @@ def frontier_ref(free, explored):
     unknown = np.pad(~explored & free, 1)
     near = unknown[:-2, 1:-1] | unknown[2:, 1:-1] | unknown[1:-1, :-2] | unknown[1:-1, 2:]
     return (free & explored & near).astype(np.uint8)
-
-
-# ------------------------------------------------------------------ scene helpers
-BASE_FROM_CAM = np.array([[0.0, 0.0, 1.0], [-1.0, 0.0, 0.0], [0.0, -1.0, 0.0]])     # camera x right, y down, z forward -> base x forward, y left, z up
-
-
-def rot_z(deg):
-    q = {0: (1.0, 0.0), 90: (0.0, 1.0), 180: (-1.0, 0.0), 270: (0.0, -1.0)}.get(deg % 360 if float(deg).is_integer() else None)
-    c, s = q if q else (np.cos(np.deg2rad(deg)), np.sin(np.deg2rad(deg)))
-    return np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
-
-
-def rot_y(deg):
-    c, s = np.cos(np.deg2rad(deg)), np.sin(np.deg2rad(deg))
-    return np.array([[c, 0.0, s], [0.0, 1.0, 0.0], [-s, 0.0, c]])
-
-
-def rot_x(deg):
-    c, s = np.cos(np.deg2rad(deg)), np.sin(np.deg2rad(deg))
-    return np.array([[1.0, 0.0, 0.0], [0.0, c, -s], [0.0, s, c]])
-
-
-def camera(origin, yaw=0, pitch=0.0, roll=0.0):
-    """camera -> map transform of a camera at `origin` (base frame, metres) looking along the base x axis turned by yaw (about z, to the
-    left), pitch (about y, positive = down) and roll (about x).  Quarter-turn yaws are exact."""
-    T = np.eye(4)
-    R = rot_z(yaw)
-    if pitch:
-        R = R @ rot_y(pitch)
-    if roll:
-        R = R @ rot_x(roll)
-    T[:3, :3] = R @ BASE_FROM_CAM
-    T[:3, 3] = origin
-    return T
-
-
-def calib(f, cx, cy):
-    return np.array([[f, 0.0, cx], [0.0, f, cy], [0.0, 0.0, 1.0]])

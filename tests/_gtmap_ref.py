@@ -9,7 +9,7 @@ import numpy as np
 
 from oracle import avl_oracle as O
 
-from _explore_ref import _bump, calib, camera  # noqa: F401  (the scene helpers, re-exported)
+from _ray_ref import _bump, calib, camera  # noqa: F401  (the scene helpers, re-exported)
 
 UNLABELLED = -1
 
