@@ -7,6 +7,7 @@ setup_scene + move_to (robot/habitat_lang_robot.py:88-104, 432-461) without the 
                                          [--dilate-iter N] [--gaussian-sigma S]]
                                         [--relation left|right|between|north|south|east|west|face --heading DEG [--query-b NAME]]
                                         [--nearest euclid|path] [--known-free] [--goal object|frontier] [--render PNG]
+                                        [--view [--view-range METRES] [--view-fraction F]]
 
 Loads <scene>/vlmap/vlmaps.h5df (with --text-model hash a missing map is first created with the model-free feature stand-in, as
 apps.create_map --features hash does), builds the obstacle map (Map.generate_obstacle_map), takes the goal from
@@ -47,6 +48,15 @@ With --known-free the path is planned on Map.get_known_free_cropped(): the obsta
 next: the frontier of the explored area with the shortest travel distance from --start (Map.get_frontiers,
 Navigator.plan_to_nearest_frontier), planned on the known-free map; --query is not needed, and the JSON line has "frontiers", the
 number of frontier islands, and "frontier_cells", the size of the chosen one.
+
+With --view the goal is not the object's contour point but a cell the object can be SEEN from (Map.get_viewpoints: 3-D sight lines
+from a camera at the map config's camera height to the object's voxels, through the voxel map; csrc/avl_sight.hip): among the free
+cells of the map the path is planned on (the customised one with --customize-obstacles, the known-free one with --known-free)
+within --view-range metres (default 3) of the object that see at least --view-fraction (default 0.5) of what the best cell sees,
+the one nearest to --start as the crow flies, or by travel distance with --nearest path (Map.get_viewpoint_pos).  The JSON line
+then has "goal_kind": "viewpoint", "visible" (the object's voxels seen from the goal), "view_targets" (the voxels tested) and
+"view_cells" (the cells that see any); --render tints those cells.  The robot's heading and field of view are not modelled.  An
+object that no free cell in range sees ends with a message and exit status 1.
 
 With --render the plan is also drawn: the top-down colour map of the obstacle crop (Map.generate_rgb_topdown_map) with the
 obstacle cells the planner used darkened, the path as a polyline, the start in green and the goal in red, as a PNG.  The JSON line
@@ -93,6 +103,10 @@ def parse_args(argv=None):
     ap.add_argument("--goal", choices=["object", "frontier"], default="object",
                     help="object = go to --query (default); frontier = go to the nearest frontier of the explored area")
     ap.add_argument("--render", default=None, metavar="PNG", help="draw the crop, its obstacles, the path, start and goal")
+    ap.add_argument("--view", action="store_true", help="go to a cell --query can be seen from (Map.get_viewpoint_pos), not to its contour")
+    ap.add_argument("--view-range", type=float, default=None, metavar="METRES", help="how far from the object a viewpoint may be (default 3.0)")
+    ap.add_argument("--view-fraction", type=float, default=None, metavar="F",
+                    help="a viewpoint sees at least this fraction of what the best cell sees (default 0.5)")
     args = ap.parse_args(argv)
     if args.goal == "frontier":
         if args.query is not None or args.relation is not None or args.area or args.sound or args.image or args.goal_2d or args.nearest == "path":
@@ -100,6 +114,15 @@ def parse_args(argv=None):
         args.known_free = True
     elif args.query is None:
         ap.error("--query is required (or --goal frontier)")
+    if args.view:
+        if args.goal == "frontier" or args.relation is not None or args.area or args.sound or args.image or args.goal_2d:
+            ap.error("--view looks at the --query object: no --goal frontier, --relation, --area, --sound, --image or --goal-2d")
+        args.view_range = 3.0 if args.view_range is None else args.view_range
+        args.view_fraction = 0.5 if args.view_fraction is None else args.view_fraction
+        if not (args.view_range > 0.0 and args.view_range < float("inf")) or not 0.0 <= args.view_fraction <= 1.0:
+            ap.error("--view-range is a positive number of metres, --view-fraction lies in [0, 1]")
+    elif args.view_range is not None or args.view_fraction is not None:
+        ap.error("--view-range and --view-fraction belong to --view")
     if args.render and args.relation == "face":
         ap.error("--relation face plans no path: nothing to --render")
     if args.nearest == "path" and (args.relation is not None or args.area or args.sound or args.image or args.goal_2d):
@@ -160,9 +183,10 @@ def clamp_cell(cell, rmin, cmin, shape):
             min(max(int(cell[1]), int(cmin)), int(cmin) + int(shape[1]) - 1)]
 
 
-def render_plan(vm, obstacles, start, goal, path):
+def render_plan(vm, obstacles, start, goal, path, view=None):
     """(H, W, 3) uint8: the crop of the top-down colour map, obstacle cells (obstacles == 0) at a third of their brightness, the
-    path in yellow, the start green, the goal red.  Host drawing on the small image (utils.visualize_utils: integer Bresenham)."""
+    cells of `view` (a crop-shaped bool, Viewpoints.mask(): where the object can be seen from) half-way to cyan, the path in
+    yellow, the start green, the goal red.  Host drawing on the small image (utils.visualize_utils: integer Bresenham)."""
     import numpy as np
     from avlmaps_amd.utils.visualize_utils import draw_marker, draw_polyline
     r0, c0 = int(vm.rmin), int(vm.cmin)
@@ -170,6 +194,9 @@ def render_plan(vm, obstacles, start, goal, path):
     img = np.ascontiguousarray(vm.generate_rgb_topdown_map()[r0:r0 + H, c0:c0 + W])
     blocked = np.asarray(obstacles) == 0
     img[blocked] = img[blocked] // 3
+    if view is not None:
+        seen = np.asarray(view, dtype=bool)
+        img[seen] = ((img[seen].astype(np.uint16) + np.array([0, 255, 255], np.uint16)) // 2).astype(np.uint8)
     local = [(float(p[0]) - r0, float(p[1]) - c0) for p in path]
     draw_polyline(img, local, (255, 255, 0))
     draw_marker(img, (float(start[0]) - r0, float(start[1]) - c0), (0, 255, 0))
@@ -241,6 +268,13 @@ def main(argv=None):
         if len(frontiers[0]) == 0:
             raise SystemExit("--goal frontier: the explored area has no frontier (of at least 5 cells) left")
         goal = None
+    elif args.view:
+        import numpy as np
+        viewpoints = vm.get_viewpoints(args.query, max_range=args.view_range, free=np.asarray(obstacles) != 0,
+                                       customized=args.customize_obstacles)
+        if len(viewpoints.select(args.view_fraction)) == 0:
+            raise SystemExit(f"--view: no free cell within {args.view_range} m sees {args.query!r} ({viewpoints.n_targets} voxels tested)")
+        goal = None
     elif avlmap is None:
         goal = None if args.nearest == "path" else vm.get_nearest_pos(start, args.query)
     elif args.goal_2d:
@@ -266,6 +300,13 @@ def main(argv=None):
             k, path = nav.plan_to_nearest_frontier(start, frontiers)
             goal = [int(frontiers[0][k, 0]), int(frontiers[0][k, 1])]
             extra = {"goal_kind": "frontier", "frontiers": int(len(frontiers[0])), "frontier_cells": int(frontiers[1][k])}
+        elif args.view:
+            goal, path = vm.get_viewpoint_pos(start, viewpoints, nav if args.nearest == "path" else None, args.view_fraction)
+            if args.nearest != "path":
+                path = nav.plan_to(start, goal)
+            at = int(np.flatnonzero((viewpoints.cells == np.asarray(goal)).all(axis=1))[0])
+            extra = {"goal_kind": "viewpoint", "visible": int(viewpoints.visible[at]), "view_targets": viewpoints.n_targets,
+                     "view_cells": int(np.count_nonzero(viewpoints.visible))}
         elif args.nearest == "path":
             goal, path = vm.get_nearest_reachable_pos(start, args.query, nav)
         else:
@@ -277,7 +318,8 @@ def main(argv=None):
     out.update(extra)
     if args.render:
         from PIL import Image
-        Image.fromarray(render_plan(vm, obstacles, start, goal, path)).save(args.render)
+        view = viewpoints.mask() if args.view else None
+        Image.fromarray(render_plan(vm, obstacles, start, goal, path, view)).save(args.render)
         out["render"] = args.render
     print(json.dumps(out))
     return out

@@ -7,7 +7,7 @@
 // scalar restatement (tests/_audit_ref.py) is compared with np.array_equal.
 //
 // THE CELL INDEX.  A lookup from cell (row, col, h) of a gs x gs x vh grid to the voxel row that owns it, in one caller-owned
-// buffer laid out by ci_layout():
+// buffer laid out by ci_layout() (avl_cellindex.h, with the probe; avl_sight.hip reads the same index):
 //   bits    one bit per cell, uint32 words, linear cell (row * gs + col) * vh + h; set with atomicOr
 //   prefix  per word, the number of set bits in the words before it (count per 1024 words, avl_scan.h's scan_counts_kernel over the
 //           counts, one more pass that writes the words' own exclusive prefix)
@@ -41,53 +41,14 @@
 #include <climits>
 #include <cmath>
 
+#include "avl_cellindex.h"
 #include "avl_scan.h"
 #include "avl_sightray.h"
 
 namespace avl {
 
 constexpr int kAuditThreads = 256;
-constexpr int kAuditMaxSide = 16384;            // gs, as the carver's
 constexpr int kAuditMaxCell = 1 << 28;          // |b.row|, |b.col|: 2 d and 2 n stay inside int32
-constexpr int kCiThreads = 256;
-constexpr int kCiPer = 4;                       // words per thread of the prefix passes: a block owns 1024 words
-
-struct CellIndexView {
-    uint32_t* bits;
-    int32_t* prefix;
-    int32_t* perm;
-    int32_t* counts;
-    int64_t nwords, nblocks;
-    size_t total;
-};
-
-// the ONE layout of the index buffer (the size query passes a null base)
-static CellIndexView ci_layout(void* base, int64_t N, int gs, int vh) {
-    CellIndexView v{};
-    const int64_t cells = (int64_t)gs * gs * vh;
-    v.nwords = (cells + 31) / 32;
-    v.nblocks = (v.nwords + kCiThreads * kCiPer - 1) / (kCiThreads * kCiPer);
-    Carver c(base ? align256_ptr(base) : nullptr);
-    v.bits = c.ptr<uint32_t>((size_t)v.nwords * 4);
-    v.prefix = c.ptr<int32_t>((size_t)v.nwords * 4);
-    v.perm = c.ptr<int32_t>((size_t)std::max<int64_t>(N, 1) * 4);
-    v.counts = c.ptr<int32_t>((size_t)v.nblocks * 4);
-    v.total = c.total() + 256;                  // the slack of a base that is not 256-aligned
-    return v;
-}
-
-__device__ __forceinline__ int64_t ci_linear(int r, int c, int h, int gs, int vh) {
-    const bool in = r >= 0 && r < gs && c >= 0 && c < gs && h >= 0 && h < vh;
-    return in ? ((int64_t)r * gs + c) * vh + h : -1;    // < 2^31 (checked by the entry points)
-}
-
-// the voxel row that owns linear cell `lin` (inside the grid), -1 when it is empty
-__device__ __forceinline__ int ci_probe(const uint32_t* __restrict__ bits, const int32_t* __restrict__ prefix,
-                                        const int32_t* __restrict__ perm, int lin) {
-    const uint32_t w = bits[lin >> 5], b = (uint32_t)lin & 31u;
-    if (!(w >> b & 1u)) return -1;
-    return perm[prefix[lin >> 5] + __popc(w & ((1u << b) - 1u))];
-}
 
 __global__ __launch_bounds__(256) void ci_set_kernel(const int32_t* __restrict__ pos, int64_t N, int gs, int vh, uint32_t* __restrict__ bits) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < N; i += (int64_t)gridDim.x * 256) {
@@ -221,13 +182,6 @@ __global__ __launch_bounds__(kAuditThreads) void audit_kernel(AuditParams p, Ray
         }
         eh += 2 * dh;
     }
-}
-
-static int ci_check_grid(const char* who, int64_t N, int gs, int vh) {
-    AVL_REQUIRE(N >= 0 && N < INT_MAX, "%s: %lld voxels (0 .. 2^31 - 2)", who, (long long)N);
-    AVL_REQUIRE(gs >= 1 && gs <= kAuditMaxSide && vh >= 1 && (int64_t)gs * gs * vh < INT_MAX, "%s: grid %d x %d x %d (gs 1 .. %d, vh >= 1, gs * gs * vh < 2^31)",
-                who, gs, gs, vh, kAuditMaxSide);
-    return AVL_OK;
 }
 
 }  // namespace avl

@@ -57,6 +57,52 @@ class VisibilityAudit:
             return cls(z["last_hit"], z["through"], params, z["frame_counts"].tolist())
 
 
+class Viewpoints:
+    """Map.get_viewpoints' result: the candidate eye cells of one target and what each of them sees.  cells (E, 2) int64 full-map
+    (row, col) in raster order; visible (E,) uint32, the target voxels with a free sight line from the cell; first (E,) int32, the
+    first of them (an index into the target rows that were used), -1 = none; n_targets, how many target voxels were tested;
+    eye_h, the height cell of every eye; window = (rmin, cmin, H, W), the obstacle crop the cells were taken from."""
+
+    def __init__(self, cells, visible, first, n_targets, eye_h, window):
+        self.cells = np.ascontiguousarray(cells, dtype=np.int64).reshape(-1, 2)
+        self.visible = np.ascontiguousarray(visible, dtype=np.uint32).reshape(-1)
+        self.first = np.ascontiguousarray(first, dtype=np.int32).reshape(-1)
+        if not len(self.cells) == len(self.visible) == len(self.first):
+            raise ValueError(f"Viewpoints: {len(self.cells)} cells, {len(self.visible)} counts, {len(self.first)} first targets")
+        self.n_targets, self.eye_h = int(n_targets), int(eye_h)
+        self.window = tuple(int(v) for v in window)
+
+    def __len__(self) -> int:
+        return len(self.cells)
+
+    def best(self, k: int = 1) -> np.ndarray:
+        """(<= k,) indices into cells of the cells that see the most, most first, equal counts in raster order; only cells that see
+        something"""
+        if int(k) < 0:
+            raise ValueError(f"best: k {k} < 0")
+        order = np.argsort(-self.visible.astype(np.int64), kind="stable")
+        return order[:min(int(k), int(np.count_nonzero(self.visible)))]
+
+    def select(self, min_fraction: float = 0.5) -> np.ndarray:
+        """indices (in raster order) of the cells with visible >= max(1, ceil(min_fraction * max(visible))); none when nothing is
+        visible from anywhere"""
+        f = float(min_fraction)
+        if not 0.0 <= f <= 1.0:
+            raise ValueError(f"select: min_fraction {min_fraction} outside [0, 1]")
+        if len(self.visible) == 0 or int(self.visible.max()) == 0:
+            return np.zeros((0,), np.int64)
+        need = max(1, int(np.ceil(f * int(self.visible.max()))))
+        return np.flatnonzero(self.visible >= need)
+
+    def mask(self) -> np.ndarray:
+        """(H, W) bool over the obstacle crop: True where visible > 0"""
+        r0, c0, H, W = self.window
+        out = np.zeros((H, W), dtype=bool)
+        seen = self.cells[self.visible > 0]
+        out[seen[:, 0] - r0, seen[:, 1] - c0] = True
+        return out
+
+
 class Map:
     def __init__(self, map_config, data_dir: str = ""):
         self.map_config = map_config
@@ -381,6 +427,93 @@ class Map:
             return False
         self.visibility = audit
         return True
+
+    # ------------------------------------------------------------------------ viewpoints (csrc/avl_sight.hip)
+    # get_nearest_reachable_pos ends on a contour point, which may lie under the table or behind a half-height partition: whether an
+    # object can be SEEN from a cell is a 3-D property of the voxels.  A sight line runs from the eye's cell to a target voxel's cell
+    # (that direction: the walk is not symmetric) between cell centres; the robot's field of view and heading are not modelled.
+    # Upstream has no counterpart.  DESIGN.md 4.22.
+    def get_viewpoints(self, target, eye_height: float = None, max_range: float = 3.0, max_targets: int = 1024, free=None,
+                       customized: bool = False, end_margin: int = 0) -> "Viewpoints":
+        """From which free cells can `target` be seen?  target: a category name (self.index_map(name)) or an (N,) bool / uint8 voxel
+        mask (index_map's, get_quantile_predict_mask's, an Instance3D's).  The targets are the mask's rows in row order, every
+        ceil(n / max_targets)-th of them when there are more than max_targets; the mask itself is `transparent`, so an object does not
+        hide itself.  The candidate eyes are the True cells of `free` -- a bool array over the obstacle crop, default
+        get_obstacle_cropped() != 0 (customized: the customized crop), e.g. get_known_free_cropped() -- inside the 2-D bounding box
+        of the target cells grown by ceil(max_range / cs) cells, at height cell min(max(int(eye_height / cs), 0), vh - 1)
+        (eye_height in metres, default the map config's pose_info.camera_height).  The exact 3-D range, max_range / cs cells,
+        is applied on the device.  One ops.cell_index and one ops.visible_counts call."""
+        from .. import ops
+        if self.grid_pos is None or self.occupied_ids is None:
+            raise ValueError("get_viewpoints: no map loaded")
+        max_range = float(max_range)
+        if not (np.isfinite(max_range) and max_range > 0.0):
+            raise ValueError(f"get_viewpoints: max_range {max_range} (metres; finite and > 0)")
+        max_targets = int(max_targets)
+        if not 1 <= max_targets <= ops.LOS_MAX_TARGETS:
+            raise ValueError(f"get_viewpoints: max_targets {max_targets} (1 .. {ops.LOS_MAX_TARGETS})")
+        if int(end_margin) < 0:
+            raise ValueError(f"get_viewpoints: end_margin {end_margin} < 0")
+        gs, cs, vh = int(self.gs), float(self.cs), int(np.asarray(self.occupied_ids).shape[2])
+        N = len(self.grid_pos)
+        mask = self.index_map(target) if isinstance(target, str) else target
+        mask = np.asarray(mask)
+        if mask.dtype not in (np.dtype(bool), np.dtype(np.uint8)) or mask.shape != (N,):
+            raise ValueError(f"get_viewpoints: the target mask must be ({N},) bool or uint8, got {mask.dtype} {mask.shape}")
+        mask = mask != 0
+        if eye_height is None:
+            eye_height = cfg_get(cfg_get(self.map_config, "pose_info"), "camera_height")
+        eye_h = min(max(int(float(eye_height) / cs), 0), vh - 1)
+        if self.obstacles_cropped is None:
+            self.generate_obstacle_map()
+        base = self.get_customized_obstacle_cropped() if customized else self.get_obstacle_cropped()
+        free = np.asarray(base) != 0 if free is None else np.asarray(free)
+        if free.dtype != np.dtype(bool) or free.shape != np.asarray(base).shape:
+            raise ValueError(f"get_viewpoints: free must be a bool array over the obstacle crop {np.asarray(base).shape}, got "
+                             f"{free.dtype} {free.shape}")
+        rmin, cmin = int(self.rmin), int(self.cmin)
+        window = (rmin, cmin, free.shape[0], free.shape[1])
+        rows = np.flatnonzero(mask)
+        if len(rows) > max_targets:
+            rows = rows[::-(-len(rows) // max_targets)]
+        targets = np.ascontiguousarray(np.asarray(self.grid_pos)[rows], dtype=np.int32).reshape(-1, 3)
+        empty = Viewpoints(np.zeros((0, 2)), np.zeros(0), np.zeros(0), len(rows), eye_h, window)
+        if len(rows) == 0:
+            return empty
+        grow = int(np.ceil(max_range / cs))
+        r0 = max(int(targets[:, 0].min()) - grow, rmin)
+        r1 = min(int(targets[:, 0].max()) + grow, rmin + free.shape[0] - 1)
+        c0 = max(int(targets[:, 1].min()) - grow, cmin)
+        c1 = min(int(targets[:, 1].max()) + grow, cmin + free.shape[1] - 1)
+        if r0 > r1 or c0 > c1:
+            return empty
+        cells = np.argwhere(free[r0 - rmin:r1 - rmin + 1, c0 - cmin:c1 - cmin + 1]) + (r0, c0)      # raster order
+        if len(cells) == 0:
+            return empty
+        eyes = np.concatenate([cells, np.full((len(cells), 1), eye_h)], axis=1).astype(np.int32)
+        with ops.cell_index(np.ascontiguousarray(self.grid_pos, dtype=np.int32), gs, vh) as index:
+            visible, first = ops.visible_counts(index, eyes, targets, transparent=mask.astype(np.uint8), end_margin=int(end_margin),
+                                                max_range=max_range / cs)
+        return Viewpoints(cells, visible, first, len(rows), eye_h, window)
+
+    def get_viewpoint_pos(self, curr_pos: List[float], target, navigator=None, min_fraction: float = 0.5, **kw):
+        """-> (pos, path): a cell `target` can be seen from (get_viewpoints(target, **kw)), among the cells that see at least
+        max(1, ceil(min_fraction * the best cell's count)) of its voxels (Viewpoints.select): with a navigator the one with the
+        shortest TRAVEL distance from curr_pos and the path to it (Navigator.plan_to_viewpoint; NoPathError when none can be
+        reached), without one the nearest in the plane (the first in raster order among equals) and the path [curr_pos, pos].
+        (curr_pos, [curr_pos]) when nothing is visible from anywhere, as get_nearest_reachable_pos without islands.  A Viewpoints
+        that get_viewpoints has already returned may be passed as `target`."""
+        vp = target if isinstance(target, Viewpoints) else self.get_viewpoints(target, **kw)
+        keep = vp.select(min_fraction)
+        if len(keep) == 0:
+            return curr_pos, [curr_pos]
+        if navigator is not None:
+            k, path = navigator.plan_to_viewpoint(curr_pos, vp, min_fraction)
+            return [int(vp.cells[k, 0]), int(vp.cells[k, 1])], path
+        cand = vp.cells[keep]
+        d2 = np.sum((cand.astype(np.float64) - np.asarray(curr_pos, dtype=np.float64).reshape(1, 2)) ** 2, axis=1)
+        pos = [int(v) for v in cand[int(np.argmin(d2))]]
+        return pos, [curr_pos, pos]
 
     @staticmethod
     def _dilate_map(binary_map: np.ndarray, dilate_iter: int = 0, gaussian_sigma: float = 1.0):

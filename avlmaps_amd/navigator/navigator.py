@@ -65,6 +65,16 @@ class Navigator:
             raise ValueError("plan_to_nearest_frontier: no frontier to go to")
         return self.plan_to_nearest(start_full_map, centres)
 
+    def plan_to_viewpoint(self, start_full_map: Tuple[float, float], viewpoints, min_fraction: float = 0.5):
+        """-> (index, path): plan_to_nearest over the cells of a Map.get_viewpoints result that see at least
+        max(1, ceil(min_fraction * the best cell's count)) target voxels (Viewpoints.select); index is the chosen cell's row in
+        viewpoints.cells.  ValueError when the target is visible from nowhere, NoPathError when no such cell can be reached."""
+        keep = viewpoints.select(min_fraction)
+        if len(keep) == 0:
+            raise ValueError("plan_to_viewpoint: the target is visible from no candidate cell")
+        k, path = self.plan_to_nearest(start_full_map, np.asarray(viewpoints.cells, dtype=np.float64)[keep])
+        return int(keep[k]), path
+
     def _goals_to_cropped(self, goals_full_map) -> np.ndarray:
         goals = np.asarray(goals_full_map, dtype=np.float64).reshape(-1, 2)
         return goals - np.array([self.rowmin, self.colmin], np.float64)

@@ -66,6 +66,9 @@ from .select import (  # noqa: F401
 from .audit import (  # noqa: F401
     AUDIT_MAX_SIDE, audit_rays, cell_index, CellIndex, lookup_cells, NEVER_HIT,
 )
+from .sight import (  # noqa: F401
+    line_of_sight, LOS_INVALID, LOS_MAX_TARGETS, LOS_VISIBLE, visible_counts,
+)
 # the shared marshalling layer; its one device predicate keeps both of the names it had here
 from ._args import (  # noqa: F401
     _dev_u8, _image_any, _image_shape, _image_u8, _is_dev, _is_dev as _on_device, _result,

@@ -1216,6 +1216,29 @@ AVL_API int avl_audit_rays(const void* d_index, size_t index_bytes, int64_t N, i
                            const int32_t* h_frame_ids, double cs, int stride, double h_min, double h_max, double min_depth, double max_depth,
                            int end_margin, int32_t* d_last_hit, uint32_t* d_through, const int32_t* d_after, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * (21) cell-to-cell line of sight through a voxel map (csrc/avl_sight.hip), on the cell index of (20).  Cells are
+ *     (row, col, h) int32.  The sight line from eye cell e to target cell t is the integer walk written out at the top of
+ *     csrc/avl_audit.hip (step 12) from e to t, cells k = 0 .. n with n = max |t - e| over the axes.  It is NOT symmetric:
+ *     (0,0,0) -> (2,1,0) passes (1,0,0), the reverse passes (1,1,0); the direction is always eye -> target.  Cell k is a blocker
+ *     when 1 <= k < n - end_margin, the index has an owner row for it, and d_transparent (N,) uint8 is NULL or 0 at that row.  The
+ *     eye's own cell never blocks and the target cell is never tested.  A pair is visible when it has no blocker and invalid when
+ *     either end lies outside [0, gs)^2 x [0, vh).  Lines run between cell centres: there is no sub-cell geometry, and no field
+ *     of view or heading of a camera.  Both calls are asynchronous on `stream`, check their arguments before any device work and
+ *     allocate nothing; every result is an integer and does not depend on the launch geometry.  Upstream has no counterpart.
+ * ------------------------------------------------------------------------------------------------ */
+/* d_blocker (M,) int32 of the M pairs d_eyes[m] -> d_targets[m] (both (M, 3) int32): -1 visible, -2 invalid, else the voxel row of
+ * the first blocker along the walk (the one with the smallest k).  0 <= M < 2^31 - 1; M = 0 does nothing.  end_margin >= 0. */
+AVL_API int avl_los_pairs(const void* d_index, size_t index_bytes, int64_t N, int gs, int vh, const int32_t* d_eyes, const int32_t* d_targets,
+                          int64_t M, const uint8_t* d_transparent, int end_margin, int32_t* d_blocker, void* stream);
+/* Every eye of d_eyes (E, 3) against every target of d_targets (T, 3): d_visible[e] (E,) uint32 = the number of targets that are
+ * valid, in range -- dr^2 + dc^2 + dh^2 <= max_range2 in int64, equality included; max_range2 < 0: unlimited -- and visible from
+ * eye e; d_first[e] (E,) int32, or NULL, = the smallest such target index, -1 when there is none.  An eye outside the grid gets 0
+ * and -1.  0 <= E < 2^31, 0 <= T <= 65536; E = 0 does nothing, T = 0 writes zeros and -1s. */
+AVL_API int avl_los_count(const void* d_index, size_t index_bytes, int64_t N, int gs, int vh, const int32_t* d_eyes, int64_t E,
+                          const int32_t* d_targets, int64_t T, const uint8_t* d_transparent, int end_margin, int64_t max_range2,
+                          uint32_t* d_visible, int32_t* d_first, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
