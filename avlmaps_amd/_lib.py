@@ -225,6 +225,11 @@ _SIGS = {
     # cell-to-cell line of sight on the same index (csrc/avl_sight.hip): upstream has no counterpart
     "avl_los_pairs": (C.c_int, [_vp, _sz, _i64, C.c_int, C.c_int, _vp, _vp, _i64, _vp, C.c_int, _vp, _vp]),
     "avl_los_count": (C.c_int, [_vp, _sz, _i64, C.c_int, C.c_int, _vp, _i64, _vp, _i64, _vp, C.c_int, _i64, _vp, _vp, _vp]),
+    # registration of depth frames to the map on the same index (csrc/avl_match.hip): upstream has no counterpart
+    "avl_match_ws_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_sz)]),
+    "avl_match_frames": (C.c_int, [_vp, _sz, _i64, C.c_int, C.c_int, _vp, C.c_int, _f64, C.c_int, C.c_int, C.c_int, _vp, _vp, _f64, C.c_int,
+                                   _f64, _f64, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f64, _f64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _sz,
+                                   _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -1,5 +1,6 @@
 // The sight ray of a depth pixel: the ONE front end of the kernels that walk or bin the rays of a depth frame -- the free-space
-// carver (avl_explore.hip), the visibility audit (avl_audit.hip) and the ground-truth vote (avl_gtmap.hip).  Like avl_pinhole.h,
+// carver (avl_explore.hip), the visibility audit (avl_audit.hip), the ground-truth vote (avl_gtmap.hip) and the pose search
+// (avl_match.hip).  Like avl_pinhole.h,
 // which it includes, it holds arithmetic that several files must round alike; the files that include it are
 // compiled with -ffp-contract=off.
 //
@@ -23,9 +24,9 @@
 //       (the audit does; the carver does not, and the compiler then drops that arithmetic from carve_kernel)
 // ray_pixel is steps 1 - 2, sight_ray steps 3 - 8 (with ray_origin, the O of step 5, read ahead of them).  The carver and the audit take both and go on with their own cells, limits and
 // walks.  The vote takes ray_pixel, its own range test (open at both ends, no far rays: the builder's rule), bp_transform and
-// ray_cell_rc.
+// ray_cell_rc; the pose search takes the same four and rotates the point before its cell.
 //
-// Launch shape of all three.  A thread owns a ray, lanes run along an image row, blockIdx.y is the frame's slot in the launch, so
+// Launch shape of all four (the pose search's rasterise kernel; its angles travel beside the poses).  A thread owns a ray, lanes run along an image row, blockIdx.y is the frame's slot in the launch, so
 // the pose is wave-uniform and comes from the kernel arguments through scalar loads: up to kRayFrames frames per launch, a longer
 // batch takes several launches (ray_launches).  Nothing is staged, nothing allocated.
 #pragma once
@@ -107,7 +108,7 @@ __device__ __forceinline__ bool sight_ray(const RayParams& p, const RayFrame& fr
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host
-// The requirements that the three entry points share, with `who` in their messages, and the RayParams they allow.  h_band: {h_min,
+// The requirements that the four entry points share, with `who` in their messages, and the RayParams they allow.  h_band: {h_min,
 // h_max}, or null for an entry point without a height band.  max_side: the largest gs, or 0 when the caller has checked its grid.
 // kinv is copied when h_calib_inv is given: a missing one is refused by the entry point's own null-pointer check, which comes after
 // its F == 0 return.

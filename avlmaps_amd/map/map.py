@@ -103,6 +103,34 @@ class Viewpoints:
         return out
 
 
+class Registration:
+    """Map.register_frames' result.  corrections (V, 4, 4) float64, V = 1 (joint) or one per frame: to be left-multiplied onto the
+    recording's transforms (audit_visibility(corrections=[..., reg.correction])).  transforms (n, 4, 4): the corrected camera -> map
+    transforms of every frame of the directory.  best (V, 4) int32 = (angle index, di, dj, score) of each winner; valid (V,) uint32,
+    the points that took part; fraction = score / valid (0 without a point); angle_deg and shift_cells (V, 2) spell the winners
+    out.  frames: the indices of the frames that were matched; pivots (V, 2); params: the grid and the search window.  The shift
+    is a whole number of cells: the translation is accurate to one cell, and pitch, roll and height are not searched."""
+
+    def __init__(self, corrections, transforms, best, valid, angles, frames, pivots, joint, params):
+        self.corrections, self.transforms = np.asarray(corrections, dtype=np.float64), np.asarray(transforms, dtype=np.float64)
+        self.best, self.valid = np.asarray(best, dtype=np.int32).reshape(-1, 4), np.asarray(valid, dtype=np.uint32).reshape(-1)
+        self.angles, self.frames, self.pivots = np.asarray(angles, dtype=np.float64), np.asarray(frames, dtype=np.int64), np.asarray(pivots)
+        self.joint, self.params = bool(joint), dict(params)
+        self.score = self.best[:, 3].copy()
+        v = self.valid.astype(np.float64)
+        self.fraction = np.divide(self.score.astype(np.float64), v, out=np.zeros(len(v)), where=v > 0)
+        a = self.angles[self.best[:, 0]]
+        self.angle_deg = np.degrees(np.arctan2(a[:, 1], a[:, 0]))
+        self.shift_cells = self.best[:, 1:3].copy()
+
+    @property
+    def correction(self) -> np.ndarray:
+        """the one 4 x 4 correction of a joint registration"""
+        if not self.joint:
+            raise ValueError("Registration.correction: a per-frame registration has one correction per frame (corrections)")
+        return self.corrections[0]
+
+
 class Map:
     def __init__(self, map_config, data_dir: str = ""):
         self.map_config = map_config
@@ -328,6 +356,14 @@ class Map:
     # through it.  Upstream has no counterpart (its maps are static).  DESIGN.md 4.21.
     VISIBILITY_FILE = "visibility.npz"
 
+    def _own_first_pose(self):
+        """the first pose of the scene the map was built from, which defines the map's frame; None for a map without a scene"""
+        own = getattr(self, "pose_path", None)
+        if own is None or not Path(own).exists():
+            return None
+        poses = np.loadtxt(own).reshape((-1, 7))
+        return poses[0] if len(poses) else None
+
     def _audit_frames(self, data_dir, first_pose=None):
         """(depth paths, (n, 4, 4) transforms, min_depth, max_depth, the directory's first pose) of one scene directory, read as
         create_explored_map reads its own.  The map's frame is the first pose of the scene it was built from: first_pose, when
@@ -348,12 +384,14 @@ class Map:
         n = min(len(depth_paths), len(poses))
         return depth_paths[:n], transforms[:n], float(builder.min_depth), float(builder.max_depth), own_first
 
-    def audit_visibility(self, data_dirs=None, stride: int = 4, end_margin: int = 2, batch: int = 16) -> "VisibilityAudit":
+    def audit_visibility(self, data_dirs=None, stride: int = 4, end_margin: int = 2, batch: int = 16, corrections=None) -> "VisibilityAudit":
         """Audit the map's voxels against the depth frames of `data_dirs` (default: the map's own scene; a revisit is a second
         directory; frame ids run on consecutively across directories).  Pass A folds every frame's hits into last_hit (N,) int32,
         pass B counts in through (N,) uint32 the rays of frames AFTER a voxel's last hit that passed through its cell
         (ops.audit_rays with after = last_hit).  Reads poses.txt and depth/*.npy as create_explored_map does, in batches of
-        `batch` frames, one loader thread ahead of the GPU.  The result is kept as self.visibility and written to
+        `batch` frames, one loader thread ahead of the GPU.  corrections: None, or a sequence with one entry per directory, each
+        None or a 4 x 4 matrix that is left-multiplied onto that directory's transforms (register_frames's correction of a
+        recording that was not made in the map's frame).  The result is kept as self.visibility and written to
         <data_dir>/vlmap/visibility.npz."""
         from .. import ops
         from ..device import DeviceArray
@@ -371,16 +409,17 @@ class Map:
         elif isinstance(data_dirs, (str, Path)):
             data_dirs = [data_dirs]
         calib = np.array(list(cfg_get(self.map_config, "cam_calib_mat")), dtype=np.float64).reshape((3, 3))
-        # the map's frame: the first pose of its own scene when it has one, else of the first directory
-        first_pose = None
-        own = getattr(self, "pose_path", None)
-        if own is not None and Path(own).exists():
-            own_poses = np.loadtxt(own).reshape((-1, 7))
-            first_pose = own_poses[0] if len(own_poses) else None
+        first_pose = self._own_first_pose()             # the map's frame: its own scene's when it has one, else the first directory's
+        if corrections is not None:
+            corrections = [None if c is None else np.asarray(c, dtype=np.float64) for c in corrections]
+            if len(corrections) != len(data_dirs) or any(c is not None and c.shape != (4, 4) for c in corrections):
+                raise ValueError(f"audit_visibility: corrections must hold one 4 x 4 matrix or None for each of the {len(data_dirs)} directories")
         scenes = []
-        for d in data_dirs:
+        for i, d in enumerate(data_dirs):
             scene = self._audit_frames(d, first_pose)
             first_pose = scene[4] if first_pose is None else first_pose
+            if corrections is not None and corrections[i] is not None and len(scene[1]):
+                scene = (scene[0], corrections[i] @ scene[1]) + scene[2:]
             scenes.append(scene[:4])
         counts = [len(s[0]) for s in scenes]
         starts = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
@@ -427,6 +466,63 @@ class Map:
             return False
         self.visibility = audit
         return True
+
+    # ------------------------------------------------------------------------ registration (csrc/avl_match.hip)
+    # The audit, the explored map and the GT vote take a recording's poses as they come.  A second recording of the same rooms starts
+    # from another odometry origin and drifts: a few centimetres or one degree move every sight ray by a cell or more at range.
+    # register_frames slides the recording's depth points over the map's own voxels, every planar rotation of a table and every
+    # whole-cell shift of a window, and returns the correction under which most points land on occupied cells.  Upstream has no
+    # counterpart.  DESIGN.md 4.23.
+    def register_frames(self, data_dir, max_angle_deg: float = 10.0, angle_step_deg: float = 0.5, radius_m: float = 0.5, joint: bool = True,
+                        max_frames: int = 32, stride: int = 4, h_band_m=(0.1, None), batch: int = 16) -> "Registration":
+        """Register the depth frames of `data_dir` to the map (ops.match_frames): read the directory as audit_visibility reads a
+        revisit -- its poses.txt taken relative to the map's first pose -- and search rotations of -max_angle_deg .. max_angle_deg
+        in steps of angle_step_deg about z and shifts of up to radius_m in whole cells.  joint=True: one correction for the
+        recording, from up to max_frames evenly spaced frames in one call, rotated about the first frame's origin.  joint=False: a
+        correction per frame, about the frame's own origin, every frame of the directory in batches of `batch`.  Only points whose
+        height lies in h_band_m (metres, inclusive in cells; None = the top of the grid) take part: the default leaves the floor
+        out.  The search is planar (no pitch, roll or height), a shift is a whole number of cells -- the translation is accurate to
+        one cell -- and only occupied cells count.  Writes nothing."""
+        from .. import ops
+        from ._frames import batch_ranges, depth_batch
+        if self.grid_pos is None or self.occupied_ids is None:
+            raise ValueError("register_frames: no map loaded")
+        if int(batch) < 1 or int(max_frames) < 1 or int(stride) < 1:
+            raise ValueError(f"register_frames: batch {batch}, max_frames {max_frames}, stride {stride} (all >= 1)")
+        gs, cs, vh = int(self.gs), float(self.cs), int(np.asarray(self.occupied_ids).shape[2])
+        radius = int(round(float(radius_m) / cs))
+        if not 0 <= radius <= ops.MATCH_MAX_RADIUS:
+            raise ValueError(f"register_frames: radius_m {radius_m} is {radius} cells (0 .. {ops.MATCH_MAX_RADIUS})")
+        angles = ops.match_angles(max_angle_deg, angle_step_deg)
+        k0 = len(angles) // 2
+        h_lo = 0 if h_band_m[0] is None else min(max(int(float(h_band_m[0]) / cs), 0), vh - 1)
+        h_hi = vh - 1 if h_band_m[1] is None else min(max(int(float(h_band_m[1]) / cs), 0), vh - 1)
+        if h_lo > h_hi:
+            raise ValueError(f"register_frames: height band {tuple(h_band_m)} m is empty")
+        calib = np.array(list(cfg_get(self.map_config, "cam_calib_mat")), dtype=np.float64).reshape((3, 3))
+        paths, transforms, mn, mx, _ = self._audit_frames(data_dir, self._own_first_pose())
+        n = len(paths)
+        if n == 0:
+            raise ValueError(f"register_frames: no frames under {data_dir}")
+        kw = dict(stride=int(stride), min_depth=mn, max_depth=mx, h_band=(h_lo, h_hi), k0=k0)
+        with ops.cell_index(np.ascontiguousarray(self.grid_pos, dtype=np.int32), gs, vh) as index:
+            if joint:
+                frames = np.unique(np.round(np.linspace(0, n - 1, min(n, int(max_frames)))).astype(np.int64))
+                pivots = transforms[frames[0], :2, 3][None].copy()
+                depth = np.stack([depth_batch(paths, int(i), int(i) + 1)[0] for i in frames])
+                res = ops.match_frames(index, depth, calib, transforms[frames], cs, angles, radius, joint=True, pivot=pivots[0], **kw)
+                best, valid = np.asarray(res.best), np.asarray(res.valid)
+            else:
+                frames = np.arange(n, dtype=np.int64)
+                pivots = transforms[:, :2, 3].copy()
+                parts = [ops.match_frames(index, depth_batch(paths, lo, hi), calib, transforms[lo:hi], cs, angles, radius, joint=False, **kw)
+                         for lo, hi in batch_ranges(n, batch)]
+                best = np.concatenate([np.asarray(r.best) for r in parts])
+                valid = np.concatenate([np.asarray(r.valid) for r in parts])
+        corrections = ops.MatchResult(None, best, valid, radius).corrections(cs, angles, pivots)
+        return Registration(corrections, (corrections if not joint else corrections[:1]) @ transforms, best, valid, angles, frames, pivots,
+                            bool(joint), dict(gs=gs, cs=cs, vh=vh, radius=radius, stride=int(stride), h_band=(h_lo, h_hi),
+                                              max_angle_deg=float(max_angle_deg), angle_step_deg=float(angle_step_deg)))
 
     # ------------------------------------------------------------------------ viewpoints (csrc/avl_sight.hip)
     # get_nearest_reachable_pos ends on a contour point, which may lie under the table or behind a half-height partition: whether an

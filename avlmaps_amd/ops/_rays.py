@@ -1,5 +1,5 @@
-"""The frame arguments of the ops that take the sight rays of depth frames -- carve_free_space, audit_rays, gt_vote (csrc/avl_sightray.h)
--- checked and normalised in one place."""
+"""The frame arguments of the ops that take the sight rays of depth frames -- carve_free_space, audit_rays, gt_vote, match_frames
+(csrc/avl_sightray.h) -- checked and normalised in one place."""
 from __future__ import annotations
 
 import numpy as np
@@ -10,10 +10,10 @@ from ..device import _is_torch
 def frame_args(who, depth, calib, transforms, frame_ids, stride, cs, min_depth, max_depth, h_band=None, depth_div=None):
     """-> (F, H, W, Kinv, T, ids): the frame count and size of depth ((F, H, W) or (H, W), uint16 or float32, host or device), the
     inverse of the 3 x 3 calib, the (F, 4, 4) float64 transforms and the (F,) int32 frame ids (None when frame_ids is None: the
-    vote has none).  h_band: (h_min, h_max), or None for an op without a height band.  TypeError on another depth dtype,
+    vote and the pose search have none).  h_band: (h_min, h_max), or None for an op without a height band.  TypeError on another depth dtype,
     ValueError on bad shapes or parameters, with `who` in the messages; nothing here touches the device.
 
-    depth_div is checked only where one is passed, and only audit_rays passes it: carve_free_space and gt_vote leave a bad
+    depth_div is checked only where one is passed, and only audit_rays and match_frames pass it: carve_free_space and gt_vote leave a bad
     divisor of uint16 depths to the library's AvlError, as they always have.  Kept as it is on purpose, not unified here."""
     if stride < 1:
         raise ValueError(f"{who}: stride {stride} < 1")

@@ -1239,6 +1239,34 @@ AVL_API int avl_los_count(const void* d_index, size_t index_bytes, int64_t N, in
                           const int32_t* d_targets, int64_t T, const uint8_t* d_transparent, int end_margin, int64_t max_range2,
                           uint32_t* d_visible, int32_t* d_first, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * (22) registration of depth frames to a voxel map: correlative scan matching on the cell index of (20) (csrc/avl_match.hip,
+ *     DESIGN.md 4.23).  The hit points of F depth frames (min_depth < z < max_depth, the builder's rule) are turned into map cells
+ *     (row, col, h) under their prior transforms, once per angle of a table of K planar rotations (cos, sin) about a pivot, and
+ *     score[v, k, di + R, dj + R] counts the points of volume v whose cell shifted by (di, dj) is occupied, for every shift of the
+ *     window [-R, R]^2.  joint != 0: one volume (V = 1) of all frames, rotated about (pivot_x, pivot_y); joint == 0: a volume per
+ *     frame (V = F), each rotated about its own origin (T[0, 3], T[1, 3]).  Only points with h_lo <= h <= h_hi (cells) take part.
+ *     The definition, operation by operation, is written out at the top of csrc/avl_match.hip.  Planar only: no pitch, roll or
+ *     height is searched, and a shift is a whole number of cells.  1 <= K <= 1024, 0 <= R <= 64, V * K * (2R + 1)^2 < 2^31,
+ *     fewer than 2^31 - 1 lattice pixels per volume, (gs + 2R)^2 * vh < 2^32.  Both calls check their arguments before any device
+ *     work; avl_match_frames is asynchronous on `stream` and allocates nothing.  Upstream has no counterpart.
+ * ------------------------------------------------------------------------------------------------ */
+/* The size of the workspace of avl_match_frames for F frames of H x W pixels sampled every `stride`: the K point lists of every
+ * volume, 4 bytes per lattice pixel, frame and angle.  Upstream has no counterpart. */
+AVL_API int avl_match_ws_bytes(int F, int H, int W, int stride, int K, int R, int joint, size_t* bytes);
+/* d_scores (V, K, 2R + 1, 2R + 1) uint32, d_valid (V,) uint32 = the points of a volume inside the depth range and the height band,
+ * d_best (V, 4) int32 = (k, di, dj, score) of the winner: the largest score, then the smallest di^2 + dj^2, then the smallest
+ * |k - k0|, then the smallest k, di, dj; (k0, 0, 0, 0) for a volume without a valid point.  Depth, calibration and transforms are
+ * avl_audit_rays's; h_angles (K, 2) float64 on the host.  split: over how many blocks at most a volume's list of points is spread
+ * in the scoring kernel, 1 .. 65536, or 0 to have it chosen (from the arguments alone, not from the device); it changes the
+ * launch, never a byte of the results.  d_ws: ws_bytes >= the size above.  F = 0 does nothing and touches no pointer.  Upstream
+ * has no counterpart. */
+AVL_API int avl_match_frames(const void* d_index, size_t index_bytes, int64_t N, int gs, int vh, const void* d_depth, int depth_is_u16,
+                             double depth_div, int F, int H, int W, const double* h_calib_inv, const double* h_transforms, double cs,
+                             int stride, double min_depth, double max_depth, const double* h_angles, int K, int R, int h_lo, int h_hi,
+                             int joint, double pivot_x, double pivot_y, int k0, int split, uint32_t* d_scores, int32_t* d_best,
+                             uint32_t* d_valid, void* d_ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
