@@ -230,6 +230,12 @@ _SIGS = {
     "avl_match_frames": (C.c_int, [_vp, _sz, _i64, C.c_int, C.c_int, _vp, C.c_int, _f64, C.c_int, C.c_int, C.c_int, _vp, _vp, _f64, C.c_int,
                                    _f64, _f64, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f64, _f64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _sz,
                                    _vp]),
+    # the scene inventory (csrc/avl_objects.hip): upstream has no counterpart, map/map.py:146-151 stops at one category's mask
+    "avl_label_classes_work_bytes": (C.c_int, [_i64, C.POINTER(_sz)]),
+    "avl_label_classes": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp, _vp, _vp, _sz, _vp]),
+    "avl_pick_columns": (C.c_int, [_vp, _i64, C.c_int, _i64, _vp, _vp, _vp]),
+    "avl_pool_rows_work_bytes": (C.c_int, [_i64, C.c_int, _i32, C.POINTER(_sz)]),
+    "avl_pool_rows": (C.c_int, [_vp, _i64, C.c_int, _i64, _vp, _i32, _vp, _vp, _sz, _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

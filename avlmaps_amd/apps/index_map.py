@@ -7,6 +7,7 @@ and image branches, :23-142; the Open3D viewer and the habitat branches are not 
                                          [--image PNG] [--object-decay R] [--area-decay R] [--sound-decay R] [--image-decay R]
     ... --modality object --categories A,B,...   [--instances] [--instance K] [--min-voxels M] [--connectivity 6|18|26]
     ... --modality object --categories A,B,...   --quantile P [--instances]
+    ... --modality object --categories A,B,...   [--inventory] [--inventory-json PATH] [--min-voxels M] [--connectivity 6|18|26]
     ... any modality ...                 [--render PNG [--view topdown|frame:<i>|orbit] [--render-size W H]] [--save-ply PLY]
 
 object (default): the VLMap text query; area: the area map's frame embeddings (area_map/clip_sparse_map.h5df); sound: the sound
@@ -23,6 +24,11 @@ alone (AVLMap.index_object_instance).  Both need --categories; --min-voxels and 
 of the category's own score column (VLMap.index_map_quantile; upstream's map/clip_map.py:45-75 uses 95), not those whose row
 maximum it is, so the answer does not depend on the other names in --categories.  The heat, --save, --render and --save-ply follow
 that mask, and --instances lists its connected components.  Needs --categories.
+
+--inventory lists what is in the scene (VLMap.get_objects: the objects of ALL of --categories in one labelling), one line each:
+label, category, the category with the largest mean score over the object's voxels when it differs, voxels, box, centre, best
+score and the margin between the two largest mean scores.  --inventory-json writes the same objects as JSON
+(SceneObjects.to_json).  Both need --categories and reuse --min-voxels and --connectivity.
 
 --render writes the picture the reference shows in a window (visualize_heatmap_3d, application/index_map.py): the heat in JET
 colours over the map's own, rendered on the GPU (AVLMap.render_heat).  --view topdown (default) is the map from above, frame:<i>
@@ -56,6 +62,8 @@ def parse_args(argv=None):
     ap.add_argument("--quantile", type=float, default=None, metavar="P",
                     help="object: the voxels above the P-th percentile of the category's own scores instead of the row maximum "
                          "(needs --categories)")
+    ap.add_argument("--inventory", action="store_true", help="object: list the objects of all categories in 3-D (needs --categories)")
+    ap.add_argument("--inventory-json", default=None, metavar="PATH", help="object: write the inventory as JSON (needs --categories)")
     ap.add_argument("--image", default=None, help="query image (PNG) of --modality image and fused")
     ap.add_argument("--image-pose", type=int, default=0, help="row of poses.txt the model-free localiser places the image at")
     ap.add_argument("--object", action="append", default=[], help="fused: an object name (repeatable)")
@@ -92,6 +100,9 @@ def parse_args(argv=None):
             ap.error(f"--quantile {args.quantile}: a percentile lies in 0 .. 100")
         if args.instance is not None:
             ap.error("--instance picks an object of the row-maximum mask; with --quantile use --instances")
+    if args.inventory or args.inventory_json:
+        if args.modality != "object" or not args.categories:
+            ap.error("--inventory and --inventory-json need --modality object and --categories")
     return args
 
 
@@ -122,6 +133,16 @@ def print_instances(instances, name: str) -> None:
         r0, r1, c0, c1, h0, h1 = it.bbox
         print(f"  instance {it.label}: {it.count} voxels, rows {r0}..{r1}, cols {c0}..{c1}, heights {h0}..{h1}, "
               f"centre ({it.center[0]:.2f}, {it.center[1]:.2f}, {it.center[2]:.2f}), best score {it.best_score:.4f} at voxel {it.best_voxel}")
+
+
+def print_inventory(scene) -> None:
+    """--inventory: one line per object of VLMap.get_objects"""
+    print(f"{len(scene.objects)} objects of at least {scene.min_voxels} voxels ({scene.n} in all)")
+    for it in scene.objects:
+        r0, r1, c0, c1, h0, h1 = it.bbox
+        voted = "" if it.voted == it.category else f" (voted {it.voted_name!r})"
+        print(f"  object {it.label}: {it.name!r}{voted}, {it.count} voxels, rows {r0}..{r1}, cols {c0}..{c1}, heights {h0}..{h1}, "
+              f"centre ({it.center[0]:.2f}, {it.center[1]:.2f}, {it.center[2]:.2f}), best score {it.best_score:.4f}, margin {it.margin:.4f}")
 
 
 def quantile_query(avlmap, args, cats, decay):
@@ -203,6 +224,14 @@ def main(argv=None):
         if args.instances and args.quantile is None:
             print()
             print_instances(vm.get_instances_3d(args.query, args.min_voxels, args.connectivity), args.query)
+        if args.inventory or args.inventory_json:
+            scene = vm.get_objects(args.min_voxels, args.connectivity)      # the query above has run init_categories
+            if args.inventory:
+                print()
+                print_inventory(scene)
+            if args.inventory_json:
+                scene.save(args.inventory_json)
+                print(f"\nwrote {args.inventory_json}: {len(scene.objects)} objects")
         if args.instance is not None:
             try:
                 heat = avlmap.index_object_instance(args.query, args.instance, decay_rate=decay, min_voxels=args.min_voxels,

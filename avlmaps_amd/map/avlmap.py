@@ -147,6 +147,20 @@ class AVLMap:
             raise IndexError(f"instance {k} of {object_name!r} has {int(inst.table[int(k) - 1, 0])} voxels, fewer than min_voxels = {min_voxels}")
         return vm.heatmap_from_mask(inst.mask_of(int(k)), cs, decay_rate).numpy()
 
+    def index_scene_object(self, label: int, decay_rate: float = 0.1, min_voxels: int = 50, connectivity: int = 26) -> np.ndarray:
+        """(N,) float32 heat of ONE object of the scene: object `label` of VLMap.get_objects(min_voxels, connectivity), 1 on its voxels
+        and decaying from them alone -- index_object_instance without naming the category.  Upstream has no counterpart
+        (avlmap.py:67-76 heats every voxel of a category).  Needs vlmap.init_categories.  IndexError when `label` is no object of the
+        scene or the object has fewer than min_voxels voxels.  The heat can go into index_goal(extra=[...]) as it stands."""
+        cs = cfg_get(cfg_get(self.config, "params"), "cs")
+        vm = self.vlmap
+        vo = vm.get_objects(min_voxels=min_voxels, connectivity=connectivity).voxel_objects
+        if not 1 <= int(label) <= vo.n:
+            raise IndexError(f"the scene has {vo.n} objects, asked for {label}")
+        if vo.table[int(label) - 1, 0] < int(min_voxels):
+            raise IndexError(f"object {label} has {int(vo.table[int(label) - 1, 0])} voxels, fewer than min_voxels = {min_voxels}")
+        return vm.heatmap_from_mask(vo.mask_of(int(label)), cs, decay_rate).numpy()
+
     # ------------------------------------------------------------------ area
     def _require_area(self):
         if not self._area_loaded:

@@ -157,6 +157,10 @@ class VLMap(Map):
             if cached is not None:
                 cached[1].close()
             self._instances_cache = None
+            cached = getattr(self, "_objects_cache", None)
+            if cached is not None:
+                cached[1].close()
+            self._objects_cache = None
             self.visibility = None
         return removed
 
@@ -502,6 +506,53 @@ class VLMap(Map):
         _, inst = self._instances_3d(name, connectivity)
         table, best = inst.table, inst.best_score
         return [ops.Instance3D.from_row(k + 1, table[k], best[k]) for k in range(inst.n) if table[k, 0] >= int(min_voxels)]
+
+    def get_objects(self, min_voxels: int = 50, connectivity: int = 26, exclude=("other",)):
+        """What is in this scene: a SceneObjects (map/scene_objects.py) of ALL objects of ALL categories.  A voxel's class is its row
+        argmax over scores_mat; the categories named in `exclude` get class -1 and take part in nothing (scores_mat's columns are
+        the init_categories names plus the "other" that init_categories appends).  One labelling by class (ops.label_voxel_classes:
+        get_instances_3d's components of every category at once, numbered 1 .. n by (first cell, category)), one table, with every
+        voxel's score of its own class (ops.pick_columns), and one pooling of the resident scores_mat (ops.pool_rows) give
+        mean_scores, voted and margin per object.  `objects` lists those of at least min_voxels voxels; they keep their scene-wide
+        labels, which are what AVLMap.index_scene_object takes.  Needs init_categories.  The labelling stays on the map until the
+        categories, the connectivity or `exclude` change.  NotImplementedError when the rows are sharded over ranks, like the
+        quantile queries.  Upstream has no counterpart: vlmap_3d.py:75-100 stops at one category's mask."""
+        from .. import ops, parallel
+        from ..device import DeviceArray
+        from .scene_objects import SceneObjects
+        if self.scores_mat is not None and self.categories is not None and parallel.rank_world()[1] > 1 and self.shard_index_rows:
+            raise NotImplementedError("get_objects on rows sharded over ranks: an object's voxels lie in several ranks' blocks")
+        scores = self._scores_device()                   # raises when init_categories has not run
+        am = self._argmax_device()
+        Q = int(self.scores_mat.shape[1])
+        names = list(self.categories)[:Q] + ["other"] * (Q - len(self.categories))
+        exclude = tuple(exclude or ())
+        key = (self.scores_mat, self.grid_pos, int(connectivity), exclude)
+        cached = getattr(self, "_objects_cache", None)
+        if cached is not None:
+            (scores_mat, grid_pos, *rest), scene = cached
+            if scores_mat is self.scores_mat and grid_pos is self.grid_pos and tuple(rest) == key[2:]:
+                if scene.min_voxels != int(min_voxels):  # the same labelling, listed again
+                    scene = SceneObjects(scene.voxel_objects, scene.mean_scores, self._argmax, names, min_voxels, connectivity, exclude)
+                    self._objects_cache = (key, scene)
+                return scene
+            scene.close()
+            self._objects_cache = None
+        classes = am
+        out = [c for c, name in enumerate(names) if name in exclude]
+        if out:                                          # the excluded columns' voxels leave on the host's copy of the argmax
+            host = np.array(self._argmax, dtype=np.int32, copy=True)
+            host[np.isin(host, out)] = -1
+            classes = DeviceArray.from_numpy(host)
+        own = ops.pick_columns(scores, am, device=True)
+        vo = ops.label_voxel_classes(self._device_pos(), classes, connectivity=connectivity, scores=own, device=True)
+        vo.classes = self._argmax                        # classes_of from the host's copy: an object's first voxel is not excluded
+        sums = ops.pool_rows(scores, vo.labels_dev, vo.n)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mean = sums / vo.table[:, 0:1].astype(np.float64)
+        scene = SceneObjects(vo, mean, self._argmax, names, min_voxels, connectivity, exclude)
+        self._objects_cache = (key, scene)
+        return scene
 
     def _distribution_map_device(self, name: str, decay_rate: float = 0.1):
         from .. import ops

@@ -72,6 +72,9 @@ from .sight import (  # noqa: F401
 from .match import (  # noqa: F401
     match_angles, match_frames, MATCH_MAX_ANGLES, MATCH_MAX_RADIUS, MATCH_MAX_SPLIT, MatchResult,
 )
+from .objects import (  # noqa: F401
+    label_voxel_classes, Object3D, pick_columns, POOL_CHUNK, pool_rows, vote_rows, VoxelObjects,
+)
 # the shared marshalling layer; its one device predicate keeps both of the names it had here
 from ._args import (  # noqa: F401
     _dev_u8, _image_any, _image_shape, _image_u8, _is_dev, _is_dev as _on_device, _result,

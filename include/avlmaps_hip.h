@@ -1267,6 +1267,47 @@ AVL_API int avl_match_frames(const void* d_index, size_t index_bytes, int64_t N,
                              int joint, double pivot_x, double pivot_y, int k0, int split, uint32_t* d_scores, int32_t* d_best,
                              uint32_t* d_valid, void* d_ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * (23) the scene inventory: the objects of ALL categories in one labelling, the score of every voxel's own class, and the score
+ *     rows pooled per object (csrc/avl_objects.hip).  Upstream has no counterpart: avlmaps/map/map.py:146-151 and
+ *     avlmaps/map/vlmap_3d.py:75-100, the nearest lines, stop at ONE category's voxel mask.  The table of the objects is (18)'s
+ *     avl_voxel_instance_table, called with these labels.  Arguments are checked before any device work.
+ * ------------------------------------------------------------------------------------------------ */
+/* The workspace of avl_label_classes, a function of N alone:
+ *     256 + 2 * align256(8 N) + 3 * align256(4 N) + align256(4 * ceil(N / 1024)) bytes, align256(b) = b rounded up to 256
+ * (a header, the cell keys and their sorted copy, two index arrays, the parents, the scan's block counts): 28 bytes per voxel,
+ * whatever the bounding box and the class ids.  Upstream has no counterpart (nearest: map/map.py:146-151). */
+AVL_API int avl_label_classes_work_bytes(int64_t N, size_t* bytes);
+/* avl_label_voxels for all classes at once.  d_classes (N,) int32: a voxel with a negative class takes part in nothing; two others
+ * are adjacent when their cells are (as in avl_label_voxels, connectivity 6 / 18 / 26) AND their classes are equal; voxels of one
+ * cell with the same class belong together, with different classes they do not.  d_labels (N,) int32: 0 or the voxel's object,
+ * 1 .. n in lexicographic order of (first cell (row, col, height), class); *d_n (1 int32, device) = n.  That is
+ * scipy.ndimage.label run once per class on the class's dense array, all components then sorted by (first cell, class); with one
+ * class it is avl_label_voxels on the mask d_classes >= 0, byte for byte.  Class ids are any int32 >= 0.  Every side of the
+ * participating voxels' bounding box is at most 2^20 cells: the box is read back after its pass (the call synchronises `stream`
+ * once) and a larger one returns AVL_ERR_INVALID.  Every output is an integer that does not depend on the order in which atomics
+ * land.  Upstream has no counterpart (nearest: map/vlmap_3d.py:75-100, one category's 3-D index). */
+AVL_API int avl_label_classes(const int32_t* d_grid_pos, const int32_t* d_classes, int64_t N, int connectivity, int32_t* d_labels,
+                              int32_t* d_n, void* ws, size_t ws_bytes, void* stream);
+/* d_out[i] = (float)d_rows[i * ld + d_cols[i]] for the row-major float32 matrix d_rows (N, C) with row stride ld >= C elements, and
+ * 0.0f where d_cols[i] lies outside 0 .. C - 1: with d_cols the row argmax, every voxel's score of its own class.  0 <= N < 2^31,
+ * C >= 1; N = 0 does nothing.  Asynchronous.  Upstream has no counterpart (nearest: map/vlmap.py:123, np.argmax of the rows). */
+AVL_API int avl_pick_columns(const float* d_rows, int64_t N, int C, int64_t ld, const int32_t* d_cols, float* d_out, void* stream);
+/* The workspace of avl_pool_rows for N rows of C columns and n objects:
+ *     4 * align256(4 N) + 2 * align256(4 (n + 1)) + align256(8 C * (floor(N / 256) + n)) bytes
+ * (labels as sort keys and their sorted copy, the row indices and their sorted copy, the objects' first members and first chunks,
+ * one float64 row per chunk).  Upstream has no counterpart (nearest: map/map.py:146-151). */
+AVL_API int avl_pool_rows_work_bytes(int64_t N, int C, int32_t n, size_t* bytes);
+/* d_sums (n, C) float64, row k - 1 = the sum of the rows of d_rows (N, C) float32 (row stride ld >= C) whose d_labels (N,) int32 is
+ * k; labels outside 1 .. n take part in nothing, an object without a member gets zeros.  The order of the additions is pinned, so
+ * the bytes are the same on every run: the members of an object in ascending row index, cut into chunks of 256 consecutive
+ * members; a chunk's partial is the sequential float64 sum of its rows in that order, starting from 0.0; the object's sum is the
+ * sequential float64 sum of its partials in chunk order, starting from 0.0.  No floating-point atomics.  0 <= N < 2^31,
+ * 0 <= n < 2^31 - 1, C >= 1; n = 0 does nothing.  Asynchronous.  Upstream has no counterpart (nearest: map/vlmap.py:92-102, the
+ * score matrix itself). */
+AVL_API int avl_pool_rows(const float* d_rows, int64_t N, int C, int64_t ld, const int32_t* d_labels, int32_t n, double* d_sums,
+                          void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
