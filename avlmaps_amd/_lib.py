@@ -236,6 +236,9 @@ _SIGS = {
     "avl_pick_columns": (C.c_int, [_vp, _i64, C.c_int, _i64, _vp, _vp, _vp]),
     "avl_pool_rows_work_bytes": (C.c_int, [_i64, C.c_int, _i32, C.POINTER(_sz)]),
     "avl_pool_rows": (C.c_int, [_vp, _i64, C.c_int, _i64, _vp, _i32, _vp, _vp, _sz, _vp]),
+    # object relations on the cell index and the inventory's labels (csrc/avl_relations.hip): upstream has no counterpart
+    "avl_object_relations_work_bytes": (C.c_int, [_i64, C.POINTER(_sz)]),
+    "avl_object_relations": (C.c_int, [_vp, _sz, _i64, C.c_int, C.c_int, _vp, _vp, _i32, C.c_int, _i64, _vp, _vp, _vp, _sz, _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

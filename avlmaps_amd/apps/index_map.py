@@ -8,6 +8,8 @@ and image branches, :23-142; the Open3D viewer and the habitat branches are not 
     ... --modality object --categories A,B,...   [--instances] [--instance K] [--min-voxels M] [--connectivity 6|18|26]
     ... --modality object --categories A,B,...   --quantile P [--instances]
     ... --modality object --categories A,B,...   [--inventory] [--inventory-json PATH] [--min-voxels M] [--connectivity 6|18|26]
+    ... --modality object --categories A,B,...   --inventory --relations [--relation-radius M] [--relations-json PATH]
+    ... --modality object --categories A,B,...   --related "SUBJECT near|on|under|touching ANCHOR" [--relation-radius M]
     ... any modality ...                 [--render PNG [--view topdown|frame:<i>|orbit] [--render-size W H]] [--save-ply PLY]
 
 object (default): the VLMap text query; area: the area map's frame embeddings (area_map/clip_sparse_map.h5df); sound: the sound
@@ -29,6 +31,12 @@ that mask, and --instances lists its connected components.  Needs --categories.
 label, category, the category with the largest mean score over the object's voxels when it differs, voxels, box, centre, best
 score and the margin between the two largest mean scores.  --inventory-json writes the same objects as JSON
 (SceneObjects.to_json).  Both need --categories and reuse --min-voxels and --connectivity.
+
+--relations, after --inventory, lists how the listed objects stand to one another (VLMap.get_scene_graph: every pair within
+--relation-radius metres, at most 15 cells), one line each: the nearest gap and its two voxels, the touching voxel pairs, the voxels
+of each lying directly on the other and who rests on whom.  --relations-json writes the same edges as JSON (SceneGraph.to_json).
+--related "mug on table" makes --save, --render and --save-ply use the heat of the first such object alone
+(AVLMap.index_related_object).  They need --categories and reuse --min-voxels and --connectivity.
 
 --render writes the picture the reference shows in a window (visualize_heatmap_3d, application/index_map.py): the heat in JET
 colours over the map's own, rendered on the GPU (AVLMap.render_heat).  --view topdown (default) is the map from above, frame:<i>
@@ -64,6 +72,13 @@ def parse_args(argv=None):
                          "(needs --categories)")
     ap.add_argument("--inventory", action="store_true", help="object: list the objects of all categories in 3-D (needs --categories)")
     ap.add_argument("--inventory-json", default=None, metavar="PATH", help="object: write the inventory as JSON (needs --categories)")
+    ap.add_argument("--relations", action="store_true", help="object: after --inventory, list how the listed objects stand to one another")
+    ap.add_argument("--relation-radius", type=float, default=0.25, metavar="M",
+                    help="--relations / --relations-json / --related: objects within M metres are related (default 0.25; at most 15 cells)")
+    ap.add_argument("--relations-json", default=None, metavar="PATH", help="object: write the relations as JSON (needs --categories)")
+    ap.add_argument("--related", default=None, metavar="\"SUBJECT REL ANCHOR\"",
+                    help="object: --save / --render / --save-ply use the heat of the first SUBJECT that is REL (near, on, under, "
+                         "touching) an ANCHOR, e.g. \"mug on table\" (needs --categories)")
     ap.add_argument("--image", default=None, help="query image (PNG) of --modality image and fused")
     ap.add_argument("--image-pose", type=int, default=0, help="row of poses.txt the model-free localiser places the image at")
     ap.add_argument("--object", action="append", default=[], help="fused: an object name (repeatable)")
@@ -103,6 +118,20 @@ def parse_args(argv=None):
     if args.inventory or args.inventory_json:
         if args.modality != "object" or not args.categories:
             ap.error("--inventory and --inventory-json need --modality object and --categories")
+    if args.relations and not args.inventory:
+        ap.error("--relations lists the edges of the inventory: it needs --inventory")
+    if args.relations_json or args.related is not None:
+        if args.modality != "object" or not args.categories:
+            ap.error("--relations-json and --related need --modality object and --categories")
+    if not (np.isfinite(args.relation_radius) and args.relation_radius > 0.0):
+        ap.error(f"--relation-radius {args.relation_radius}: metres, finite and > 0")
+    if args.related is not None:
+        parts = args.related.split()
+        if len(parts) != 3 or parts[1] not in ("near", "on", "under", "touching"):
+            ap.error(f"--related {args.related!r}: expected \"SUBJECT REL ANCHOR\" with REL one of near, on, under, touching")
+        if args.instance is not None:
+            ap.error("--related and --instance both choose the heat: give one of them")
+        args.related = tuple(parts)
     return args
 
 
@@ -143,6 +172,16 @@ def print_inventory(scene) -> None:
         voted = "" if it.voted == it.category else f" (voted {it.voted_name!r})"
         print(f"  object {it.label}: {it.name!r}{voted}, {it.count} voxels, rows {r0}..{r1}, cols {c0}..{c1}, heights {h0}..{h1}, "
               f"centre ({it.center[0]:.2f}, {it.center[1]:.2f}, {it.center[2]:.2f}), best score {it.best_score:.4f}, margin {it.margin:.4f}")
+
+
+def print_relations(graph) -> None:
+    """--relations: one line per pair of listed objects of VLMap.get_scene_graph"""
+    print(f"{len(graph.edges)} relations among the listed objects within {graph.R} cells ({graph.relations.P} pairs in all)")
+    names = {it.label: it.voted_name for it in graph.objects.objects}
+    for e in graph.edges:
+        how = f"{e.a} on {e.b}" if e.rests() else (f"{e.b} on {e.a}" if e.mirrored().rests() else "side by side")
+        print(f"  relation {e.a} {names[e.a]!r} - {e.b} {names[e.b]!r}: gap {e.distance:.3f} m (d2 {e.d2}) between voxels {e.voxel_a} and "
+              f"{e.voxel_b}, {e.contacts} contacts, {e.a_on_b} / {e.b_on_a} voxels on top, {how}")
 
 
 def quantile_query(avlmap, args, cats, decay):
@@ -232,6 +271,21 @@ def main(argv=None):
             if args.inventory_json:
                 scene.save(args.inventory_json)
                 print(f"\nwrote {args.inventory_json}: {len(scene.objects)} objects")
+        if args.relations or args.relations_json:
+            graph = vm.get_scene_graph(args.relation_radius, args.min_voxels, args.connectivity)
+            if args.relations:
+                print()
+                print_relations(graph)
+            if args.relations_json:
+                graph.save(args.relations_json)
+                print(f"\nwrote {args.relations_json}: {len(graph.edges)} relations")
+        if args.related is not None:
+            try:
+                heat = avlmap.index_related_object(*args.related, decay_rate=decay, radius=args.relation_radius, min_voxels=args.min_voxels,
+                                                   connectivity=args.connectivity)
+            except LookupError as e:
+                raise SystemExit(f"--related: {e}")
+            print(f"related {' '.join(args.related)!r}: ", end="")
         if args.instance is not None:
             try:
                 heat = avlmap.index_object_instance(args.query, args.instance, decay_rate=decay, min_voxels=args.min_voxels,

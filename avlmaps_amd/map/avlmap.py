@@ -161,6 +161,22 @@ class AVLMap:
             raise IndexError(f"object {label} has {int(vo.table[int(label) - 1, 0])} voxels, fewer than min_voxels = {min_voxels}")
         return vm.heatmap_from_mask(vo.mask_of(int(label)), cs, decay_rate).numpy()
 
+    def index_related_object(self, subject: str, relation: str, anchor: str, decay_rate: float = 0.1, radius: float = 0.25,
+                             **kwargs) -> np.ndarray:
+        """(N,) float32 heat of "the mug on the table": index_scene_object's heat of the subject of the FIRST hit of
+        VLMap.get_scene_graph(radius, **kwargs).find(subject, relation, anchor) -- relation one of "near", "on", "under",
+        "touching", the names matched against the objects' voted categories, the hits in find's documented order; kwargs are
+        get_objects' min_voxels, connectivity and exclude.  LookupError when no pair of listed objects stands in that relation.
+        Upstream has no counterpart.  Needs vlmap.init_categories.  The heat can go into index_goal(extra=[...]) as it stands."""
+        cs = cfg_get(cfg_get(self.config, "params"), "cs")
+        vm = self.vlmap
+        graph = vm.get_scene_graph(radius=radius, **kwargs)
+        hits = graph.find(subject, relation, anchor)
+        if not hits:
+            raise LookupError(f"no {subject!r} {relation} a {anchor!r} among the {len(graph.objects.objects)} listed objects "
+                              f"within {graph.R} cells")
+        return vm.heatmap_from_mask(graph.objects.voxel_objects.mask_of(hits[0][0].label), cs, decay_rate).numpy()
+
     # ------------------------------------------------------------------ area
     def _require_area(self):
         if not self._area_loaded:

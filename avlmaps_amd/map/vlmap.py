@@ -554,6 +554,32 @@ class VLMap(Map):
         self._objects_cache = (key, scene)
         return scene
 
+    def get_scene_graph(self, radius: float = 0.25, min_voxels: int = 50, connectivity: int = 26, exclude=("other",)):
+        """How the objects of this scene stand to one another: a SceneGraph (map/scene_graph.py) of get_objects(min_voxels,
+        connectivity, exclude) -- its cache, its errors -- and of every pair of objects that come within `radius` metres of each
+        other: the nearest gap and its two voxels, how many voxels of one lie directly on the other, and how many touch.  The
+        radius in cells is R = min(max(round(radius / cs), 1), 15).  One ops.cell_index over the resident cells and one
+        ops.object_relations on the resident labels; the grid is gs x gs x vh with vh the height of occupied_ids, or the largest
+        height of grid_pos plus one on a map without it.  Upstream has no counterpart: map.py:183-240 relates one category's 2-D
+        islands."""
+        from .. import ops
+        from .scene_graph import SceneGraph
+        scene = self.get_objects(min_voxels=min_voxels, connectivity=connectivity, exclude=exclude)
+        cs = float(self.cs)
+        radius = float(radius)
+        if not (np.isfinite(radius) and radius > 0.0 and np.isfinite(cs) and cs > 0.0):
+            raise ValueError(f"get_scene_graph: radius {radius} m at a cell size of {cs} m (both finite and > 0)")
+        R = min(max(int(round(radius / cs)), 1), ops.RELATIONS_MAX_RADIUS)
+        if getattr(self, "occupied_ids", None) is not None:
+            vh = int(np.asarray(self.occupied_ids).shape[2])
+        else:
+            vh = max(int(np.asarray(self.grid_pos)[:, 2].max()) + 1, 1) if len(self.grid_pos) else 1
+        vo = scene.voxel_objects
+        pos = self._device_pos()
+        with ops.cell_index(pos, int(self.gs), vh) as index:
+            relations = ops.object_relations(index, pos, vo.labels_dev, vo.n, R)
+        return SceneGraph(scene, relations, cs, R)
+
     def _distribution_map_device(self, name: str, decay_rate: float = 0.1):
         from .. import ops
         window = self._crop_window()

@@ -75,6 +75,9 @@ from .match import (  # noqa: F401
 from .objects import (  # noqa: F401
     label_voxel_classes, Object3D, pick_columns, POOL_CHUNK, pool_rows, vote_rows, VoxelObjects,
 )
+from .relations import (  # noqa: F401
+    object_relations, ObjectRelations, RELATION_TABLE_COLS, RELATIONS_MAX_PAIRS, RELATIONS_MAX_RADIUS,
+)
 # the shared marshalling layer; its one device predicate keeps both of the names it had here
 from ._args import (  # noqa: F401
     _dev_u8, _image_any, _image_shape, _image_u8, _is_dev, _is_dev as _on_device, _result,

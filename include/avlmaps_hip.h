@@ -1308,6 +1308,48 @@ AVL_API int avl_pool_rows_work_bytes(int64_t N, int C, int32_t n, size_t* bytes)
 AVL_API int avl_pool_rows(const float* d_rows, int64_t N, int C, int64_t ld, const int32_t* d_labels, int32_t n, double* d_sums,
                           void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * (24) object relations: for every pair of objects of a labelled voxel list that come within `radius` cells of each other, their
+ *     nearest gap, where it is, who rests on whom and how much they touch (csrc/avl_relations.hip), on the cell
+ *     index of (20) and the labels of (23) or (18).  Upstream has no counterpart: avlmaps/map/map.py:183-240, the nearest lines,
+ *     relate the 2-D islands of ONE category's top-down mask.  Arguments are checked before any device work.  Every result is an
+ *     integer minimum or an integer sum: nothing depends on the order in which atomics land, and the bytes are the same on
+ *     every run.
+ * ------------------------------------------------------------------------------------------------ */
+/* The workspace of avl_object_relations, a function of max_pairs alone (1 <= max_pairs <= 2^28).  With H the smallest power of two
+ * >= 2 * max_pairs (at least 2) and align256(b) = b rounded up to 256:
+ *     256 + 2 * align256(8 H) + align256(24 H) + align256(4 * ceil(H / 1024)) + 2 * align256(8 max_pairs) + 2 * align256(4 max_pairs)
+ * bytes (a header, the keys and the packed minima of the pair table's H slots, their three counters, the scan's block counts, the
+ * claimed keys and their sorted copy, their slots and their sorted copy).  Upstream has no counterpart (nearest: map/map.py:183). */
+AVL_API int avl_object_relations_work_bytes(int64_t max_pairs, size_t* bytes);
+/* d_index: the avl_cell_index_build index of the same d_grid_pos (N, 3) int32 on the gs x gs x vh grid; d_labels (N,) int32, a value
+ * outside 1 .. n takes part in nothing; R = radius, 1 <= R <= 15.  Every voxel row i with label a in 1 .. n and its cell inside
+ * the grid scans every offset d = (dr, dc, dh) with dr^2 + dc^2 + dh^2 <= R^2, d = 0 included; an offset whose cell
+ * cell(i) + d lies outside the grid is skipped (each of row, col and height is checked, not the linear cell).  With j the owner of
+ * that cell in the index (the largest row of the cell; an empty cell gives no event) and b = d_labels[j]: when b lies in 1 .. n and
+ * b != a, the unordered pair (min(a, b), max(a, b)) exists and the event (i, d, j) belongs to it.  A pair collects
+ *     d2        the minimum of |d|^2 over its events;
+ *     i, j      the witness: among the events with |d|^2 = d2 the one with the smallest scanning row i, then the smallest offset
+ *               code ((dr + R)(2R + 1) + (dc + R))(2R + 1) + (dh + R); i scans, j is seen;
+ *     lo_on_hi  the events with d = (0, 0, -1) whose scanning voxel has the lower label: a voxel of the lower-numbered object with
+ *               a cell of the higher-numbered one directly beneath it (larger height is up);
+ *     hi_on_lo  the same with the roles exchanged;
+ *     contacts  the events with 0 < |d|^2 <= 3 (the 26-neighbourhood), from either side.
+ * Several rows in one cell make the scan ASYMMETRIC: a row that does not own its cell scans but is never seen; two rows of
+ * different objects in one cell give d2 = 0.  d_table (max_pairs, 8) int64: its first P rows are
+ * [lo, hi, d2, i, j, lo_on_hi, hi_on_lo, contacts], sorted by (lo, hi); d_count[0] (1 int64, device) = P, exact when
+ * P <= max_pairs.  With more pairs d_count[0] is some value above max_pairs and the table's content is unspecified: that is not
+ * an error code, the caller looks at the count.  Rows P .. max_pairs - 1 are not written.  Pairs live in a hash table of the
+ * workspace (64-bit keys lo * (n + 1) + hi claimed by compare-and-swap; d2, i and the code packed as d2 << 46 | i << 15 | code
+ * under one 64-bit atomic minimum, which is why R stops at 15 and N at 2^31 - 2); integer minima and sums only, so nothing depends
+ * on the order in which atomics land.  0 <= N <= 2^31 - 2, the grid as in (20), index_bytes >= avl_cell_index_work_bytes(N, gs, vh),
+ * n >= 0, ws_bytes >= the size above; N = 0 or n = 0 writes P = 0.  Asynchronous on `stream`; the sort's temporary storage comes
+ * from the stream's memory pool.  Upstream has no counterpart (nearest: map/map.py:183-240, get_nearest_pos and the left / right /
+ * between helpers on one category's 2-D islands). */
+AVL_API int avl_object_relations(const void* d_index, size_t index_bytes, int64_t N, int gs, int vh, const int32_t* d_grid_pos,
+                                 const int32_t* d_labels, int32_t n, int radius, int64_t max_pairs, int64_t* d_table, int64_t* d_count,
+                                 void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
