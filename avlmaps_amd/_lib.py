@@ -239,6 +239,10 @@ _SIGS = {
     # object relations on the cell index and the inventory's labels (csrc/avl_relations.hip): upstream has no counterpart
     "avl_object_relations_work_bytes": (C.c_int, [_i64, C.POINTER(_sz)]),
     "avl_object_relations": (C.c_int, [_vp, _sz, _i64, C.c_int, C.c_int, _vp, _vp, _i32, C.c_int, _i64, _vp, _vp, _vp, _sz, _vp]),
+    # travel-distance fields on the free space of a 2-D map (csrc/avl_travel.hip): upstream has no counterpart
+    "avl_travel2d_workspace_bytes": (C.c_int, [C.c_int, C.c_int, C.POINTER(_sz)]),
+    "avl_travel2d": (C.c_int, [_vp, _i64, _vp, _i64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "avl_travel_decay_2d": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _f64, _f64, C.c_int, _vp, _vp, _vp, _sz, _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

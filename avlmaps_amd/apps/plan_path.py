@@ -2,7 +2,7 @@
 setup_scene + move_to (robot/habitat_lang_robot.py:88-104, 432-461) without the simulator.
 
     python -m avlmaps_amd.apps.plan_path --data-dir <scene> --query sofa --start ROW COL [--text-model clip|hash]
-                                        [--area NAME]... [--sound NAME]... [--image PNG] [--goal-2d]
+                                        [--area NAME]... [--sound NAME]... [--image PNG] [--goal-2d [--travel [--travel-from-start]]]
                                         [--customize-obstacles [--potential-obstacles a,b,c --obstacles a,b]
                                          [--dilate-iter N] [--gaussian-sigma S]]
                                         [--relation left|right|between|north|south|east|west|face --heading DEG [--query-b NAME]]
@@ -24,7 +24,10 @@ that far.
 With --goal-2d the goal is taken on the planner's own grid instead: the cell of AVLMap.index_goal_2d(obj=--query, area=..,
 sound=..), the first maximum of the product of the 2-D distribution maps over the obstacle crop (habitat_lang_robot.py:357-375,
 419-425).  The JSON line then has "goal_value" and "goal_cell"; the cell lies inside the crop, so "goal" equals it.  --image has no
-2-D map and is rejected.
+2-D map and is rejected.  With --goal-2d --travel the object factor decays with the travel distance on the obstacle crop instead
+of the straight line (AVLMap.index_goal_2d_travel, csrc/avl_travel.hip): the goal cell is near the object by the way the robot has
+to walk, not through a wall; --travel-from-start multiplies in the travel decay from --start, which prefers the nearest of
+several objects by that way.  Area and sound factors stay Euclidean.
 
 With --customize-obstacles the path is planned on Map.get_customized_obstacle_cropped() as upstream's robot does
 (habitat_lang_robot.py:89-104): VLMap.customize_obstacle_map keeps only the obstacles whose class is one of --obstacles among
@@ -87,6 +90,10 @@ def parse_args(argv=None):
     ap.add_argument("--image-pose", type=int, default=0, help="row of poses.txt the model-free localiser places the image at")
     ap.add_argument("--goal-2d", action="store_true",
                     help="take the goal from the 2-D distribution maps over the obstacle crop (AVLMap.index_goal_2d)")
+    ap.add_argument("--travel", action="store_true",
+                    help="with --goal-2d: object factors decay with the travel distance around walls (AVLMap.index_goal_2d_travel)")
+    ap.add_argument("--travel-from-start", action="store_true",
+                    help="with --goal-2d --travel: one more factor, the travel decay from --start")
     ap.add_argument("--customize-obstacles", action="store_true",
                     help="plan on the customised obstacle map (VLMap.customize_obstacle_map) instead of the raw one")
     ap.add_argument("--potential-obstacles", default=None, help="comma separated class list the voxels are scored against")
@@ -141,6 +148,10 @@ def parse_args(argv=None):
         ap.error("--potential-obstacles, --obstacles, --dilate-iter and --gaussian-sigma belong to --customize-obstacles")
     if args.goal_2d and args.image:
         ap.error("--goal-2d takes --query, --area and --sound: an image query has no 2-D map")
+    if args.travel and not args.goal_2d:
+        ap.error("--travel belongs to --goal-2d")
+    if args.travel_from_start and not args.travel:
+        ap.error("--travel-from-start belongs to --goal-2d --travel")
     return args
 
 
@@ -278,7 +289,11 @@ def main(argv=None):
     elif avlmap is None:
         goal = None if args.nearest == "path" else vm.get_nearest_pos(start, args.query)
     elif args.goal_2d:
-        g = avlmap.index_goal_2d(obj=args.query, area=args.area or None, sound=args.sound or None, want_heat=False)
+        if args.travel:
+            g = avlmap.index_goal_2d_travel(obj=args.query, area=args.area or None, sound=args.sound or None, want_heat=False,
+                                            start=start if args.travel_from_start else None)
+        else:
+            g = avlmap.index_goal_2d(obj=args.query, area=args.area or None, sound=args.sound or None, want_heat=False)
         goal = [int(g.cell[0]), int(g.cell[1])]
         extra = {"goal_value": g.value, "goal_cell": [float(g.cell[0]), float(g.cell[1])]}
     else:

@@ -47,6 +47,7 @@ SOURCES = {
     "avl_match.hip": ["-ffp-contract=off"],        # avl_sightray.h's pixel and K1's point; the rotation is plain float64 products and sums, unfused
     "avl_objects.hip": ["-ffp-contract=off"],      # integer kernels and float64 additions in a pinned order: nothing to fuse, and it stays so
     "avl_relations.hip": ["-ffp-contract=off"],    # integer kernels; the flag keeps the file in line with the other integer sources
+    "avl_travel.hip": ["-ffp-contract=off"],       # the field is integer; a + b * sqrt(2), the decay and the normalisation round like NumPy, unfused
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fvisibility=hidden", "-Wall",
           "-Wno-unused-function", "-munsafe-fp-atomics"]

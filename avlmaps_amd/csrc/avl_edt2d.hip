@@ -27,6 +27,7 @@
 #include <cmath>
 
 #include "avl_common.h"
+#include "avl_decay2d.h"
 #include "avl_wave.h"
 
 namespace avl {
@@ -88,14 +89,8 @@ __global__ __launch_bounds__(kEdtCols* kEdtSegs) void edt_column_kernel(const ui
     }
 }
 
-// NumPy: t = 1 - (d / cell_size) * decay_rate, t < 0 -> 0
-__device__ __forceinline__ double edt_decay(double d, double cell_size, double decay_rate) {
-    const double t = 1.0 - __ddiv_rn(d, cell_size) * decay_rate;
-    return t < 0.0 ? 0.0 : t;
-}
-
-// One workgroup per row.  DECAY = false: out = sqrt(min d^2); true: out = edt_decay(that), and (minmax != nullptr) the minimum and
-// maximum of the image by bit pattern (the values are >= +0: their IEEE patterns order like the values).
+// One workgroup per row.  DECAY = false: out = sqrt(min d^2); true: out = decay_value(that) (avl_decay2d.h), and (minmax != nullptr)
+// the minimum and maximum of the image by bit pattern (the values are >= +0: their IEEE patterns order like the values).
 template <bool DECAY>
 __global__ __launch_bounds__(kEdtRowThreads) void edt_row_kernel(const int32_t* __restrict__ g, int H, int W, double cell_size,
                                                                  double decay_rate, double* __restrict__ out,
@@ -153,20 +148,13 @@ __global__ __launch_bounds__(kEdtRowThreads) void edt_row_kernel(const int32_t* 
         }
         double v = sqrt((double)best);
         if (DECAY) {
-            v = edt_decay(v, cell_size, decay_rate);
+            v = decay_value(v, cell_size, decay_rate);
             mn = fmin(mn, v);
             mx = fmax(mx, v);
         }
         out[(int64_t)r * W + c] = v;
     }
     if (DECAY && minmax) block_minmax_atomic<kEdtRowThreads>(mn, mx, minmax, s_red);
-}
-
-// NumPy: (t - min) / (max - min), in place (field_normalize_kernel's expression on an (H, W) image)
-__global__ __launch_bounds__(256) void edt_normalize_kernel(double* __restrict__ t, const double* __restrict__ minmax, int64_t n) {
-    const double mn = minmax[0], span = minmax[1] - minmax[0];
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        t[i] = __ddiv_rn(t[i] - mn, span);
 }
 
 static int edt_check_shape(const char* what, int H, int W) {
@@ -180,8 +168,8 @@ static int edt_launch(const uint8_t* img, int64_t ld, int H, int W, int invert, 
     int32_t* g = (int32_t*)ws;
     AVL_HIP_CHECK(hipMemsetAsync(found, 0, sizeof(int32_t), st));
     if (minmax) {
-        AVL_HIP_CHECK(hipMemsetAsync(minmax, 0xFF, sizeof(double), st));    // min: all ones = above every non-negative value
-        AVL_HIP_CHECK(hipMemsetAsync(minmax + 1, 0, sizeof(double), st));   // max: +0
+        const int rc = decay_minmax_reset(minmax, st);
+        if (rc != AVL_OK) return rc;
     }
     hipLaunchKernelGGL(edt_column_kernel, dim3((unsigned)((W + kEdtCols - 1) / kEdtCols)), dim3(kEdtCols * kEdtSegs), 0, st, img, ld, H, W,
                        invert, g, (int*)found);
@@ -240,11 +228,7 @@ int avl_mask_decay_2d(const uint8_t* d_mask_u8, int64_t ld, int H, int W, double
     hipStream_t st = as_stream(stream);
     rc = edt_launch(d_mask_u8, ld, H, W, 1, true, cell_size, decay_rate, d_out_f64, d_minmax, d_found, ws, st);
     if (rc != AVL_OK || !normalize) return rc;
-    const int64_t n = (int64_t)H * W;
-    const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, (int64_t)num_cus() * 8));
-    hipLaunchKernelGGL(edt_normalize_kernel, dim3(blocks), dim3(256), 0, st, d_out_f64, (const double*)d_minmax, n);
-    AVL_HIP_CHECK(hipGetLastError());
-    return AVL_OK;
+    return decay_normalize(d_out_f64, d_minmax, (int64_t)H * W, nullptr, st);
 }
 
 }  // extern "C"

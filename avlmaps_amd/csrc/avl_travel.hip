@@ -1,0 +1,386 @@
+// Multi-source travel-distance field on the free space of a 2-D obstacle map for gfx950, and the decay map built on it.
+//
+// Upstream has no counterpart: avlmaps/robot/habitat_lang_robot.py:229-240 decays with the Euclidean distance transform of the
+// category mask (csrc/avl_edt2d.hip reproduces that chain), which does not know about walls.  This file is its counterpart on
+// the free space of the obstacle crop.
+//
+// Definition.  free (H, W) uint8, nonzero = free; sources (H, W) uint8, nonzero = source, a source may lie on an
+// obstacle cell.  A step u -> v between 8-neighbours is legal when v is free, u is free or a source, and -- for a diagonal step --
+// both cells that share an edge with u and with v are free (no corner cutting).  A walk of a straight and b diagonal steps has
+// length a + b * sqrt(2); the field of a cell is the pair (a, b) of the shortest legal walk from any source to it, (0, 0) on a
+// source, (-1, -1) where no walk ends.  sqrt(2) is irrational, so different pairs differ in length: the minimum is unique.
+//
+// Order.  Pairs are compared exactly in integers (travel_less): the sign cases of da against db, then da^2 against 2 db^2 in
+// int64.  With a, b <= H * W <= 2^28 both squares stay below 2^57.  No floating-point key is involved.
+//
+// State.  One 64-bit word per cell, a in the high half and b in the low half; all ones = unreached, which unpacks to (-1, -1).
+// A candidate is "neighbour + step", a plain 64-bit addition: b never carries into a.
+//
+// Work.  The grid is cut into 32 x 32 tiles, one 256-thread workgroup each, four cells per thread.  A round is one plain launch
+// over all tiles; a tile that is not marked active returns at once.  An active tile loads its cells and a one-cell halo of state
+// and passability into LDS, turns passability into one byte per cell of legal incoming directions (registers), and sweeps
+// pull-relaxations over its cells: every thread reads the neighbours of its cells, a barrier, every thread writes what got
+// smaller, a barrier that also ORs "something changed".  The sweeps end when one changes nothing or after kTravelSweeps of them.
+// The tile writes the cells that changed back, marks each of its eight neighbours active for the next round when a cell they
+// see as halo changed, and marks itself when it ran into the sweep cap.  The host launches kTravelRoundBatch rounds, reads how
+// many tiles each round activated, and stops when the last round of a batch activated none (rounds after an empty round find
+// no active tile and return at once).
+//
+// One state buffer, read and written in place with single aligned 64-bit accesses (relaxed atomics of device scope, so the
+// compiler can neither split nor duplicate them).  Only the workgroup that owns a cell writes it.  A neighbour that reads the
+// cell as halo in the same round sees the old or the new word, never a mixture; both are lengths of real walks.  If it saw the
+// old one, the owner has marked it active for the next round, whose launch boundary makes the new word visible.
+//
+// Convergence.  Every stored word is (0, 0) on a source or was produced as "a stored neighbour + a legal step": by induction the
+// length of a real legal walk from a source, so never below the definition's minimum.  Words only decrease.  A cell whose word
+// changes wakes every tile that can read it (its own through the sweep loop or the cap mark, the neighbours through the halo
+// mark), so when no tile is active every cell equals the minimum over its legal incoming steps: the Bellman fixed point, which
+// with strictly positive step lengths is the shortest-walk field itself, whatever order the tiles ran in.  The optimal pair of
+// a cell whose shortest walk has k steps is in place after at most k rounds, and a walk without repeated cells has fewer than
+// H * W steps: the host gives up with an error after H * W + 1 rounds, which cannot happen unless the device misbehaves.
+//
+// No grid-wide barrier, no wait on another workgroup; every device loop has a compile-time bound or is a grid-stride loop over
+// the cells.
+#include <algorithm>
+#include <cmath>
+
+#include "avl_common.h"
+#include "avl_decay2d.h"
+#include "avl_wave.h"
+
+namespace avl {
+
+constexpr int kTravelMaxSide = 16384;            // avl_edt2d.hip's kEdtMaxSide: the decay maps of both families cover the same crops
+constexpr int kTravelTile = 32;                  // cells per tile side
+constexpr int kTravelThreads = 256;
+constexpr int kTravelCells = kTravelTile * kTravelTile / kTravelThreads;   // cells per thread: 4, rows ty, ty + 8, ty + 16, ty + 24
+constexpr int kTravelSweeps = 64;                // in-tile sweep cap: an open tile converges in ~33, a corridor maze continues next round
+constexpr int kTravelHalo = kTravelTile + 2;
+constexpr int kTravelRoundBatch = 8;             // rounds launched between two convergence checks
+constexpr unsigned long long kTravelUnreached = ~0ull;
+constexpr unsigned long long kTravelStraight = 1ull << 32, kTravelDiagonal = 1ull;
+constexpr uint8_t kTravelFree = 1, kTravelSource = 2;
+
+// header words of the workspace (uint32)
+constexpr int kTravelHdrAny = 0;                 // a source exists
+constexpr int kTravelHdrInit = 1;                // tiles the initialisation marked active
+constexpr int kTravelHdrRound = 8;               // [kTravelRoundBatch] tiles marked active by each round of the current batch
+constexpr int kTravelHdrWords = 64;
+
+// a1 + b1 sqrt(2) < a2 + b2 sqrt(2) for two reached words, exactly
+__device__ __forceinline__ bool travel_less(unsigned long long p, unsigned long long q) {
+    const int da = (int)(unsigned)(p >> 32) - (int)(unsigned)(q >> 32);
+    const int db = (int)(unsigned)p - (int)(unsigned)q;
+    if (da <= 0 && db <= 0) return (da | db) != 0;
+    if (da >= 0 && db >= 0) return false;
+    const long long a2 = (long long)da * da, b2 = 2ll * ((long long)db * db);
+    return da < 0 ? a2 > b2 : a2 < b2;               // da < 0 < db: |da| > db sqrt(2);  db < 0 < da: da < |db| sqrt(2)
+}
+
+__device__ __forceinline__ unsigned long long travel_load(const unsigned long long* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void travel_store(unsigned long long* p, unsigned long long v) {
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// marks tile t active for the coming round; *count counts the tiles that were not marked yet
+__device__ __forceinline__ void travel_mark(unsigned* __restrict__ flags, int t, unsigned* __restrict__ count) {
+    if (atomicExch(&flags[t], 1u) == 0u) atomicAdd(count, 1u);
+}
+
+// pass = free | source << 1 per cell, state = (0, 0) on sources and unreached elsewhere; the tile of every source and its eight
+// neighbours (a source on a tile border is their halo) start active
+__global__ __launch_bounds__(256) void travel_init_kernel(const uint8_t* __restrict__ free_u8, int64_t ld_free,
+                                                          const uint8_t* __restrict__ src_u8, int64_t ld_src, int H, int W,
+                                                          uint8_t* __restrict__ pass, unsigned long long* __restrict__ state,
+                                                          unsigned* __restrict__ flags, unsigned* __restrict__ hdr) {
+    const int tw = (W + kTravelTile - 1) / kTravelTile, th = (H + kTravelTile - 1) / kTravelTile;
+    const int64_t n = (int64_t)H * W;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int r = (int)(i / W), c = (int)(i - (int64_t)r * W);
+        const bool fr = free_u8[(int64_t)r * ld_free + c] != 0, sr = src_u8[(int64_t)r * ld_src + c] != 0;
+        pass[i] = (uint8_t)((fr ? kTravelFree : 0) | (sr ? kTravelSource : 0));
+        state[i] = sr ? 0ull : kTravelUnreached;
+        if (sr) {
+            if (hdr[kTravelHdrAny] == 0u) atomicExch(&hdr[kTravelHdrAny], 1u);
+            const int tr = r / kTravelTile, tc = c / kTravelTile;
+#pragma unroll
+            for (int dr = -1; dr <= 1; ++dr) {
+#pragma unroll
+                for (int dc = -1; dc <= 1; ++dc) {
+                    const int ur = tr + dr, uc = tc + dc;
+                    if (ur < 0 || ur >= th || uc < 0 || uc >= tw) continue;
+                    if (flags[ur * tw + uc] == 0u) travel_mark(flags, ur * tw + uc, &hdr[kTravelHdrInit]);
+                }
+            }
+        }
+    }
+}
+
+// the eight directions in 45 degree steps, E first (avl_nav.hip's order): odd = diagonal
+__device__ __forceinline__ constexpr int travel_dr(int k) { return k == 0 || k == 4 ? 0 : (k < 4 ? -1 : 1); }
+__device__ __forceinline__ constexpr int travel_dc(int k) { return k == 2 || k == 6 ? 0 : (k == 3 || k == 4 || k == 5 ? -1 : 1); }
+
+// One round: see the head of the file.  cur / next: the active marks of this round and of the coming one.
+__global__ __launch_bounds__(kTravelThreads) void travel_round_kernel(const uint8_t* __restrict__ pass, unsigned long long* state, int H,
+                                                                      int W, unsigned* __restrict__ cur, unsigned* __restrict__ next,
+                                                                      unsigned* __restrict__ activated) {
+    __shared__ unsigned long long s_state[kTravelHalo * kTravelHalo];
+    __shared__ uint8_t s_pass[kTravelHalo * kTravelHalo];
+    __shared__ unsigned s_active, s_dirty;
+    const int tw = (W + kTravelTile - 1) / kTravelTile, th = (H + kTravelTile - 1) / kTravelTile;
+    const int tile_r = blockIdx.x / tw, tile_c = blockIdx.x - tile_r * tw;
+    if (threadIdx.x == 0) {
+        s_active = cur[blockIdx.x];
+        s_dirty = 0u;
+        if (s_active) cur[blockIdx.x] = 0u;           // this buffer takes the marks of the round after the next
+    }
+    __syncthreads();
+    if (s_active == 0u) return;
+    const int r0 = tile_r * kTravelTile - 1, c0 = tile_c * kTravelTile - 1;    // the halo's origin
+#pragma unroll
+    for (int k = 0; k < (kTravelHalo * kTravelHalo + kTravelThreads - 1) / kTravelThreads; ++k) {
+        const int i = k * kTravelThreads + threadIdx.x;
+        if (i < kTravelHalo * kTravelHalo) {
+            const int r = r0 + i / kTravelHalo, c = c0 + i % kTravelHalo;
+            const bool in = r >= 0 && r < H && c >= 0 && c < W;
+            s_state[i] = in ? travel_load(&state[(int64_t)r * W + c]) : kTravelUnreached;
+            s_pass[i] = in ? pass[(int64_t)r * W + c] : (uint8_t)0;
+        }
+    }
+    __syncthreads();
+    const int tx = threadIdx.x % kTravelTile, ty = threadIdx.x / kTravelTile;
+    unsigned long long first[kTravelCells], mine[kTravelCells];
+    unsigned legal[kTravelCells];                     // bit k: the step from the neighbour in direction k to this cell is legal
+#pragma unroll
+    for (int j = 0; j < kTravelCells; ++j) {
+        const int at = (ty + 8 * j + 1) * kTravelHalo + tx + 1;
+        first[j] = mine[j] = s_state[at];
+        unsigned m = 0;
+        const uint8_t pv = s_pass[at];
+        if ((pv & kTravelFree) && !(pv & kTravelSource)) {          // a source keeps (0, 0); a blocked cell is never entered
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                bool ok = s_pass[at + travel_dr(k) * kTravelHalo + travel_dc(k)] != 0;      // u is free or a source
+                if (k & 1)
+                    ok = ok && (s_pass[at + travel_dr(k) * kTravelHalo] & kTravelFree) && (s_pass[at + travel_dc(k)] & kTravelFree);
+                m |= ok ? 1u << k : 0u;
+            }
+        }
+        legal[j] = m;
+    }
+    bool more = true;
+    for (int sweep = 0; sweep < kTravelSweeps && more; ++sweep) {
+        unsigned long long best[kTravelCells];
+#pragma unroll
+        for (int j = 0; j < kTravelCells; ++j) {
+            const int at = (ty + 8 * j + 1) * kTravelHalo + tx + 1;
+            unsigned long long b = mine[j];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                if (!(legal[j] >> k & 1u)) continue;
+                const unsigned long long s = s_state[at + travel_dr(k) * kTravelHalo + travel_dc(k)];
+                if (s == kTravelUnreached) continue;
+                const unsigned long long cand = s + ((k & 1) ? kTravelDiagonal : kTravelStraight);
+                if (b == kTravelUnreached || travel_less(cand, b)) b = cand;
+            }
+            best[j] = b;
+        }
+        __syncthreads();                               // every read of this sweep is done
+        int changed = 0;
+#pragma unroll
+        for (int j = 0; j < kTravelCells; ++j) {
+            if (best[j] != mine[j]) {
+                mine[j] = best[j];
+                s_state[(ty + 8 * j + 1) * kTravelHalo + tx + 1] = best[j];
+                changed = 1;
+            }
+        }
+        more = __syncthreads_or(changed) != 0;
+    }
+    // write back; bit k of dirty: the neighbour tile in direction k reads a changed cell as halo
+    unsigned dirty = 0;
+#pragma unroll
+    for (int j = 0; j < kTravelCells; ++j) {
+        if (mine[j] == first[j]) continue;
+        const int lr = ty + 8 * j, lc = tx;
+        travel_store(&state[(int64_t)(r0 + 1 + lr) * W + (c0 + 1 + lc)], mine[j]);     // changed cells lie inside the map
+        const bool n = lr == 0, s = lr == kTravelTile - 1, w = lc == 0, e = lc == kTravelTile - 1;
+        dirty |= (e ? 1u << 0 : 0u) | (n && e ? 1u << 1 : 0u) | (n ? 1u << 2 : 0u) | (n && w ? 1u << 3 : 0u) | (w ? 1u << 4 : 0u) |
+                 (s && w ? 1u << 5 : 0u) | (s ? 1u << 6 : 0u) | (s && e ? 1u << 7 : 0u);
+    }
+    if (dirty) atomicOr(&s_dirty, dirty);
+    __syncthreads();
+    if (threadIdx.x < 8) {
+        const int k = threadIdx.x;
+        const int ur = tile_r + travel_dr(k), uc = tile_c + travel_dc(k);
+        if ((s_dirty >> k & 1u) && ur >= 0 && ur < th && uc >= 0 && uc < tw) travel_mark(next, ur * tw + uc, activated);
+    } else if (threadIdx.x == 8 && more) {
+        travel_mark(next, blockIdx.x, activated);      // the sweep cap: go on in the next round
+    }
+}
+
+// the two int32 planes, the number of reached cells, and the host's counters into d_stats = [rounds, tile runs, reached, any source]
+__global__ __launch_bounds__(256) void travel_unpack_kernel(const unsigned long long* __restrict__ state, int64_t n,
+                                                            int32_t* __restrict__ straight, int32_t* __restrict__ diagonal,
+                                                            long long rounds, long long tile_runs, int any_source,
+                                                            unsigned long long* __restrict__ stats) {
+    unsigned long long reached = 0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const unsigned long long s = state[i];
+        straight[i] = (int32_t)(unsigned)(s >> 32);
+        diagonal[i] = (int32_t)(unsigned)s;
+        reached += s != kTravelUnreached;
+    }
+    reached = wave_sum(reached);
+    if ((threadIdx.x & (kWave - 1)) == 0 && reached) atomicAdd(&stats[2], reached);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        stats[0] = (unsigned long long)rounds;
+        stats[1] = (unsigned long long)tile_runs;
+        stats[3] = (unsigned long long)any_source;
+    }
+}
+
+// d = double(a) + double(b) * sqrt(2), unfused; t = decay_value(d), 0 on unreached cells; [min, max] of the window by bit pattern
+__global__ __launch_bounds__(256) void travel_decay_kernel(const int32_t* __restrict__ straight, const int32_t* __restrict__ diagonal,
+                                                           int64_t n, double cell_size, double decay_rate, double* __restrict__ out,
+                                                           unsigned long long* __restrict__ minmax) {
+    __shared__ double s_red[2 * 256 / kWave];
+    double mn = INFINITY, mx = -INFINITY;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t a = straight[i], b = diagonal[i];
+        double v = 0.0;
+        if (a >= 0 && b >= 0) v = decay_value((double)a + (double)b * 1.4142135623730951, cell_size, decay_rate);
+        out[i] = v;
+        mn = fmin(mn, v);
+        mx = fmax(mx, v);
+    }
+    block_minmax_atomic<256>(mn, mx, minmax, s_red);
+}
+
+static int travel_check_shape(const char* what, int H, int W) {
+    AVL_REQUIRE(H > 0 && W > 0 && H <= kTravelMaxSide && W <= kTravelMaxSide, "%s: bad shape %d x %d (sides 1 .. %d)", what, H, W,
+                kTravelMaxSide);
+    return AVL_OK;
+}
+
+struct TravelLayout {
+    size_t hdr, flags, pass, state, total;
+};
+
+static TravelLayout travel_layout(int H, int W) {
+    const size_t tiles = (size_t)((H + kTravelTile - 1) / kTravelTile) * (size_t)((W + kTravelTile - 1) / kTravelTile);
+    Carver c;
+    TravelLayout l;
+    l.hdr = c.take(kTravelHdrWords * sizeof(unsigned));
+    l.flags = c.take(2 * tiles * sizeof(unsigned));
+    l.pass = c.take((size_t)H * W);
+    l.state = c.take((size_t)H * W * sizeof(unsigned long long));
+    l.total = c.total() + 256;                        // the entry point aligns the base itself
+    return l;
+}
+
+}  // namespace avl
+
+using namespace avl;
+
+extern "C" {
+
+int avl_travel2d_workspace_bytes(int H, int W, size_t* bytes) {
+    AVL_REQUIRE(bytes, "avl_travel2d_workspace_bytes: null output");
+    int rc = travel_check_shape("avl_travel2d_workspace_bytes", H, W);
+    if (rc != AVL_OK) return rc;
+    *bytes = travel_layout(H, W).total;
+    return AVL_OK;
+}
+
+int avl_travel2d(const uint8_t* d_free, int64_t ld_free, const uint8_t* d_sources, int64_t ld_src, int H, int W, int32_t* d_straight,
+                 int32_t* d_diagonal, int64_t* d_stats, void* ws, size_t ws_bytes, void* stream) {
+    int rc = travel_check_shape("avl_travel2d", H, W);
+    if (rc != AVL_OK) return rc;
+    AVL_REQUIRE(d_free && d_sources, "avl_travel2d: null free or source image");
+    AVL_REQUIRE(d_straight && d_diagonal && d_stats, "avl_travel2d: null output plane or stats pointer");
+    AVL_REQUIRE(ld_free >= W, "avl_travel2d: free rows of %lld cells cannot hold %d columns", (long long)ld_free, W);
+    AVL_REQUIRE(ld_src >= W, "avl_travel2d: source rows of %lld cells cannot hold %d columns", (long long)ld_src, W);
+    const TravelLayout l = travel_layout(H, W);
+    AVL_REQUIRE(ws && ws_bytes >= l.total, "avl_travel2d: workspace of %zu bytes, need %zu", ws_bytes, l.total);
+    hipStream_t st = as_stream(stream);
+    char* base = (char*)align256_ptr(ws);
+    unsigned* hdr = (unsigned*)(base + l.hdr);
+    unsigned* flags = (unsigned*)(base + l.flags);
+    uint8_t* pass = (uint8_t*)(base + l.pass);
+    unsigned long long* state = (unsigned long long*)(base + l.state);
+    const int tw = (W + kTravelTile - 1) / kTravelTile, th = (H + kTravelTile - 1) / kTravelTile;
+    const unsigned tiles = (unsigned)(tw * th);        // at most 512 * 512
+    const int64_t n = (int64_t)H * W;
+
+    AVL_HIP_CHECK(hipMemsetAsync(hdr, 0, l.pass - l.hdr, st));              // the header and both mark buffers
+    AVL_HIP_CHECK(hipMemsetAsync(d_stats, 0, 4 * sizeof(int64_t), st));
+    hipLaunchKernelGGL(travel_init_kernel, dim3(stride_blocks(n)), dim3(256), 0, st, d_free, ld_free, d_sources, ld_src, H, W, pass, state,
+                       flags, hdr);
+    AVL_HIP_CHECK(hipGetLastError());
+
+    // a shortest walk has fewer than H * W steps and every round moves every pending walk on by a step or more
+    const int64_t max_rounds = n + 1;
+    int64_t k = 0, rounds = 0, tile_runs = 0;
+    unsigned host[kTravelHdrWords];
+    unsigned carry = 0;                                 // tiles active in the first round of the batch
+    bool first_batch = true, converged = false;
+    while (k < max_rounds && !converged) {
+        const int64_t k0 = k, k1 = std::min<int64_t>(k + kTravelRoundBatch, max_rounds);
+        if (!first_batch) AVL_HIP_CHECK(hipMemsetAsync(hdr + kTravelHdrRound, 0, kTravelRoundBatch * sizeof(unsigned), st));
+        for (; k < k1; ++k) {
+            unsigned* cur = flags + (size_t)(k & 1) * tiles;
+            unsigned* next = flags + (size_t)((k + 1) & 1) * tiles;
+            hipLaunchKernelGGL(travel_round_kernel, dim3(tiles), dim3(kTravelThreads), 0, st, (const uint8_t*)pass, state, H, W, cur, next,
+                               hdr + kTravelHdrRound + (int)(k - k0));
+        }
+        AVL_HIP_CHECK(hipGetLastError());
+        AVL_HIP_CHECK(hipMemcpyAsync(host, hdr, sizeof(host), hipMemcpyDeviceToHost, st));
+        AVL_HIP_CHECK(hipStreamSynchronize(st));
+        if (first_batch) {
+            carry = host[kTravelHdrInit];
+            first_batch = false;
+        }
+        for (int64_t j = 0; j < k1 - k0; ++j) {
+            rounds += carry != 0;
+            tile_runs += carry;
+            carry = host[kTravelHdrRound + j];
+        }
+        converged = carry == 0;
+    }
+    if (!converged) {
+        set_error("avl_travel2d: did not converge in %lld rounds", (long long)max_rounds);
+        return AVL_ERR_STATE;
+    }
+    hipLaunchKernelGGL(travel_unpack_kernel, dim3(stride_blocks(n)), dim3(256), 0, st, (const unsigned long long*)state, n, d_straight,
+                       d_diagonal, (long long)rounds, (long long)tile_runs, (int)(host[kTravelHdrAny] != 0),
+                       reinterpret_cast<unsigned long long*>(d_stats));
+    AVL_HIP_CHECK(hipGetLastError());
+    return AVL_OK;
+}
+
+int avl_travel_decay_2d(const int32_t* d_straight, const int32_t* d_diagonal, int H, int W, double cell_size, double decay_rate,
+                        int normalize, double* d_out_f64, int32_t* d_flags, void* ws, size_t ws_bytes, void* stream) {
+    int rc = travel_check_shape("avl_travel_decay_2d", H, W);
+    if (rc != AVL_OK) return rc;
+    AVL_REQUIRE(d_straight && d_diagonal && d_out_f64 && d_flags, "avl_travel_decay_2d: null plane, output or flag pointer");
+    AVL_REQUIRE(std::isfinite(decay_rate) && decay_rate >= 0.0, "avl_travel_decay_2d: decay_rate must be finite and >= 0");
+    AVL_REQUIRE(std::isfinite(cell_size) && cell_size > 0.0, "avl_travel_decay_2d: cell_size must be finite and > 0");
+    AVL_REQUIRE(ws && ws_bytes >= 256 + 2 * sizeof(double), "avl_travel_decay_2d: workspace of %zu bytes, need %zu", ws_bytes,
+                256 + 2 * sizeof(double));
+    hipStream_t st = as_stream(stream);
+    double* minmax = (double*)align256_ptr(ws);
+    AVL_HIP_CHECK(hipMemsetAsync(d_flags, 0, sizeof(int32_t), st));
+    rc = decay_minmax_reset(minmax, st);
+    if (rc != AVL_OK) return rc;
+    const int64_t n = (int64_t)H * W;
+    hipLaunchKernelGGL(travel_decay_kernel, dim3(stride_blocks(n)), dim3(256), 0, st, d_straight, d_diagonal, n, cell_size, decay_rate,
+                       d_out_f64, reinterpret_cast<unsigned long long*>(minmax));
+    AVL_HIP_CHECK(hipGetLastError());
+    if (!normalize) return AVL_OK;
+    return decay_normalize(d_out_f64, minmax, n, d_flags, st);
+}
+
+}  // extern "C"

@@ -393,6 +393,42 @@ class AVLMap:
         res = ops.product_argmax_2d(terms, want_heat=want_heat)
         return Goal2D(res.heat.numpy() if want_heat else None, res.value, (res.cell[0] + r0, res.cell[1] + c0))
 
+    def index_goal_2d_travel(self, obj=None, area=None, sound=None, decay_rates=None, want_heat: bool = True, start=None,
+                             start_decay_rate=None) -> "Goal2D":
+        """index_goal_2d whose object factors decay around walls: an object factor is vlmap.get_travel_distribution_map(name, rate)
+        (csrc/avl_travel.hip), so the goal cell is near the object by the way the robot has to walk, not through the wall behind it.
+        Area and sound factors are exactly those of index_goal_2d and stay Euclidean: their fields are maxima over weighted peaks,
+        which one distance transform cannot give.
+
+        start: the robot's full-map (row, col); it adds one more factor after the others, the UN-normalised travel decay
+        ops.travel_decay_2d(get_travel_field([start]), start_decay_rate) from the robot's cell ("the nearest sofa by the way I have
+        to walk"); start_decay_rate defaults to 0.01 and is required to be finite and >= 0.  The product and its first maximum go
+        through ops.product_argmax_2d like index_goal_2d's: the definition is the NumPy product of the stand-alone public calls, bit
+        for bit.  Raises what those calls raise; ValueError without obj, area and sound."""
+        from .. import ops
+        specs = self._goal_specs(obj, area, sound, None, (), decay_rates)
+        if not specs:
+            raise ValueError("index_goal_2d_travel needs at least one of obj, area, sound")
+        if start is None and start_decay_rate is not None:
+            raise ValueError("start_decay_rate belongs to start")
+        if len(specs) + (start is not None) > ops.GOAL_MAX_TERMS:
+            raise ValueError(f"a goal is the product of 1 to {ops.GOAL_MAX_TERMS} terms, got {len(specs) + (start is not None)}")
+        vm = self.vlmap
+        r0, r1, c0, c1 = vm._crop_window()
+        terms = []
+        for kind, what, rate in specs:
+            if kind == "obj":
+                terms.append(vm._travel_distribution_map_device(what, rate))
+            else:
+                gf = self._area_field(what, rate) if kind == "area" else self._sound_field(what, rate)
+                self._check_bounds(gf, f"{kind} {what!r}")
+                terms.append(ops.Window(ops.field_normalize(gf), r0, r1, c0, c1))
+        if start is not None:
+            field = vm.get_travel_field([start], device=True)
+            terms.append(ops.travel_decay_2d(field, 0.01 if start_decay_rate is None else start_decay_rate, device=True))
+        res = ops.product_argmax_2d(terms, want_heat=want_heat)
+        return Goal2D(res.heat.numpy() if want_heat else None, res.value, (res.cell[0] + r0, res.cell[1] + c0))
+
     def get_max_pos_3d(self, heat: np.ndarray) -> np.ndarray:
         """grid_pos of the first maximum of a host (N,) float32 / float64 heat.  Reference: habitat_lang_robot.py:427-430."""
         from .. import ops

@@ -611,6 +611,44 @@ class Map:
         pos = [int(v) for v in cand[int(np.argmin(d2))]]
         return pos, [curr_pos, pos]
 
+    # ------------------------------------------------------------------------ travel-distance fields (csrc/avl_travel.hip)
+    # "near" that goes around walls: per free cell of a crop the length of the shortest 8-connected walk from the nearest source
+    # that stays on free cells and cuts no corner (the 8-neighbour chamfer metric, not the Navigator's visibility-graph length).
+    # Upstream has no counterpart.  DESIGN.md 4.26.
+    def _travel_free(self, customized: bool = False, known_free: bool = False) -> np.ndarray:
+        """the (h, w) bool free map a travel field runs on: the obstacle crop, the customised one, or either AND-ed with the
+        explored crop"""
+        if self.obstacles_cropped is None:
+            self.generate_obstacle_map()
+        if known_free:
+            return self.get_known_free_cropped(customized)
+        base = self.get_customized_obstacle_cropped() if customized else self.get_obstacle_cropped()
+        if base is None:
+            raise ValueError("get_travel_field: no customised obstacle map (call customize_obstacle_map first)")
+        return np.asarray(base) != 0
+
+    def get_travel_field(self, sources, customized: bool = False, known_free: bool = False, device: bool = False):
+        """ops.travel_field over the obstacle crop (customized: the customised crop; known_free: get_known_free_cropped).
+        sources: (M, 2) full-map (row, col) points -- their int() cells, which must lie inside the crop -- or a mask of the crop's
+        shape (nonzero = source; a source may lie on an obstacle cell, as the cells of a sofa do).  -> ops.TravelField over the
+        crop: cell (r, c) of its planes is full-map cell (r + rmin, c + cmin)."""
+        from .. import ops
+        free = self._travel_free(customized, known_free)
+        src = sources if ops._is_dev(sources) else np.asarray(sources)
+        if not ops._is_dev(src) and src.shape != free.shape:
+            pts = np.asarray(src, dtype=np.float64).reshape(-1, 2)
+            cells = pts.astype(np.int64) - np.array([int(self.rmin), int(self.cmin)])
+            if len(cells) and (cells.min() < 0 or cells[:, 0].max() >= free.shape[0] or cells[:, 1].max() >= free.shape[1]):
+                raise ValueError(f"get_travel_field: a source lies outside the obstacle crop [{self.rmin}:{self.rmax + 1}, "
+                                 f"{self.cmin}:{self.cmax + 1}]")
+            src = cells
+        return ops.travel_field(free, src, device=device)
+
+    def get_reachable_cropped(self, curr_pos: List[float], customized: bool = False, known_free: bool = False) -> np.ndarray:
+        """(h, w) bool over the obstacle crop: the cells the robot can walk to from curr_pos (full-map (row, col)), its own cell
+        included -- even when that cell is an obstacle, from which it may step onto a free neighbour"""
+        return self.get_travel_field([curr_pos], customized, known_free).reachable()
+
     @staticmethod
     def _dilate_map(binary_map: np.ndarray, dilate_iter: int = 0, gaussian_sigma: float = 1.0):
         """2x bilinear upsample -> gaussian -> threshold -> dilation -> downsample, (h, w) float64.  Reference: map.py:169-181

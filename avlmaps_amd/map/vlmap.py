@@ -594,6 +594,27 @@ class VLMap(Map):
         map is constant."""
         return self._distribution_map_device(name, decay_rate).numpy()
 
+    def _travel_distribution_map_device(self, name: str, decay_rate: float = 0.1, customized: bool = False):
+        from .. import ops
+        window = self._crop_window()
+        mask = ops.mask_smooth_2d(self._predict_mask_device(name), 1, window=window, device=True)
+        try:
+            field = ops.travel_field(self._travel_free(customized), mask, device=True)
+        except ValueError as e:
+            if "no source" not in str(e):
+                raise
+            raise ValueError("get_travel_distribution_map: the mask has no target cell after the smoothing") from None
+        return ops.travel_decay_2d(field, decay_rate, cell_size=1.0, normalize=True, device=True)
+
+    def get_travel_distribution_map(self, name: str, decay_rate: float = 0.1, customized: bool = False) -> np.ndarray:
+        """get_distribution_map with the travel distance in place of the straight line: (h, w) float64 over the obstacle crop.  The
+        mask chain is get_distribution_map's (predicted mask -> gaussian_filter(float32, sigma=1) > 0.5); its cells are the sources
+        of ops.travel_field on the obstacle crop (customized: the customised crop), then 1 - d * decay_rate, negative and unreached
+        cells 0, min-max normalisation (ops.travel_decay_2d) -- all on the device.  The heat no longer passes through walls: a cell
+        behind one is as cold as the walk around it is long, and a cell no walk reaches is 0.  ValueError when no cell survives the
+        smoothing or the map is constant, as get_distribution_map."""
+        return self._travel_distribution_map_device(name, decay_rate, customized).numpy()
+
     def customize_obstacle_map(self, potential_obstacle_names: List[str], obstacle_names: List[str], vis: bool = False):
         """Reference: vlmap.py:127-156 (like upstream the class lists and the smoothing parameters come from map_config, not from
         the arguments).  The class scoring and the scatter run on the GPU (avl_obstacle_scatter), and so does the 2-D smoothing

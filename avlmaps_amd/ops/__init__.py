@@ -20,8 +20,8 @@ from .render import (  # noqa: F401
 )
 from .image2d import (  # noqa: F401
     binary_morph, dilate_map, distance_transform_edt, EDT_MAX_SIDE, _edt_workspace, gaussian_filter2d,
-    gaussian_filter2d_f32, gaussian_weights, mask_decay_2d, mask_foreground, _MORPH_OPS, _MORPH_STRUCTURES,
-    product_argmax_2d, ProductResult, resize2x_down, resize2x_up, Window, _WindowTermC,
+    gaussian_filter2d_f32, gaussian_weights, mask_decay_2d, mask_foreground, mask_smooth_2d, _MORPH_OPS, _MORPH_STRUCTURES,
+    product_argmax_2d, ProductResult, resize2x_down, resize2x_up, _smooth_mask_window, Window, _WindowTermC,
 )
 from .fields import (  # noqa: F401
     area_field, _check_decay, field_lift, field_normalize, GOAL_CONES, GOAL_DENSE_F32, GOAL_DENSE_F64, GOAL_FIELD_F32,
@@ -77,6 +77,9 @@ from .objects import (  # noqa: F401
 )
 from .relations import (  # noqa: F401
     object_relations, ObjectRelations, RELATION_TABLE_COLS, RELATIONS_MAX_PAIRS, RELATIONS_MAX_RADIUS,
+)
+from .travel import (  # noqa: F401
+    travel_decay_2d, travel_field, TRAVEL_MAX_SIDE, TRAVEL_NEIGHBOURS, TRAVEL_SWEEPS, TRAVEL_TILE, TravelField, UNREACHED,
 )
 # the shared marshalling layer; its one device predicate keeps both of the names it had here
 from ._args import (  # noqa: F401

@@ -146,6 +146,33 @@ def distance_transform_edt(image, device=False, stream=None):
     return _result(out, device, stream, keep=(keep, ws))
 
 
+def _smooth_mask_window(lib, mp, ld, H, W, sigma, stream):
+    """gaussian_filter(mask.astype(np.float32), sigma) > 0.5 in float32 storage (habitat_lang_robot.py:231-232) of the (H, W) window
+    at device pointer mp with rows of ld cells -> (the (H, W) uint8 mask, the float32 temporary it must outlive the launch with)"""
+    w, radius = gaussian_weights(sigma)
+    gt, tmp = DeviceArray((H, W), np.uint8), DeviceArray((H, W), np.float32)
+    _lib.check(lib.avl_gauss2d_f32(mp, 1, ld, H, W, w.ctypes.data, radius, None, gt.ptr, 0.5, tmp.ptr, stream), "avl_gauss2d_f32")
+    return gt, tmp
+
+
+def mask_smooth_2d(mask, sigma=1, window=None, device=False, stream=None):
+    """The mask step of mask_decay_2d(smooth_sigma=sigma) on its own: gaussian_filter(mask.astype(np.float32), sigma) > 0.5 of
+    mask[r0:r1, c0:c1] (window, default the whole mask) -> (H, W) bool, or the uint8 DeviceArray."""
+    lib = _lib.load()
+    shape = _image_shape(mask)
+    if len(shape) != 2 or shape[0] < 1 or shape[1] < 1:
+        raise ValueError(f"expected a non-empty 2-D mask, got shape {shape}")
+    r0, r1, c0, c1 = (0, shape[0], 0, shape[1]) if window is None else (int(v) for v in window)
+    if not (0 <= r0 < r1 <= shape[0] and 0 <= c0 < c1 <= shape[1]):
+        raise ValueError(f"window [{r0}:{r1}, {c0}:{c1}] is not inside the {shape} mask")
+    _lib.require_gpu()
+    if isinstance(mask, np.ndarray) and mask.dtype not in (np.dtype(bool), np.dtype(np.uint8)):
+        mask = mask != 0
+    mp, _, keep = _image_u8(mask, stream)
+    gt, tmp = _smooth_mask_window(lib, mp + r0 * shape[1] + c0, shape[1], r1 - r0, c1 - c0, sigma, stream)
+    return _result(gt, device, stream, as_bool=True, keep=(keep, tmp))
+
+
 def mask_decay_2d(mask, decay_rate, cell_size=1.0, normalize=False, smooth_sigma=None, device=False, stream=None, window=None):
     """The decay map of a 2-D mask (nonzero = target), NumPy's float64 bits:
         d = distance_transform_edt(mask == 0);  t = 1 - (d / cell_size) * decay_rate;  t[t < 0] = 0
@@ -173,9 +200,7 @@ def mask_decay_2d(mask, decay_rate, cell_size=1.0, normalize=False, smooth_sigma
     mp += r0 * ld + c0
     keep = [keep, ws]
     if smooth_sigma is not None:
-        w, radius = gaussian_weights(smooth_sigma)
-        gt, tmp = DeviceArray((H, W), np.uint8), DeviceArray((H, W), np.float32)
-        _lib.check(lib.avl_gauss2d_f32(mp, 1, ld, H, W, w.ctypes.data, radius, None, gt.ptr, 0.5, tmp.ptr, stream), "avl_gauss2d_f32")
+        gt, tmp = _smooth_mask_window(lib, mp, ld, H, W, smooth_sigma, stream)
         keep += [gt, tmp]
         mp, ld = gt.ptr, W
     out, mm = DeviceArray((H, W), np.float64), DeviceArray((2,), np.float64)

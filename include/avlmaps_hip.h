@@ -1350,6 +1350,34 @@ AVL_API int avl_object_relations(const void* d_index, size_t index_bytes, int64_
                                  const int32_t* d_labels, int32_t n, int radius, int64_t max_pairs, int64_t* d_table, int64_t* d_count,
                                  void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * (25) travel-distance fields on the free space of a 2-D obstacle map and their decay maps (csrc/avl_travel.hip).
+ *     Upstream has no counterpart: avlmaps/robot/habitat_lang_robot.py:229-240 decays with the Euclidean distance of (10).
+ *     d_free (H, W) uint8, nonzero = free; d_sources (H, W) uint8, nonzero = source (a source may lie on an obstacle cell); rows of
+ *     ld_free / ld_src cells (a window of a larger image: ld > W).  A step u -> v between 8-neighbours is legal when v is free, u is
+ *     free or a source and, for a diagonal step, both cells that share an edge with u and with v are free.  The field of a cell is
+ *     the pair (a, b) of straight and diagonal steps of the shortest legal walk (length a + b sqrt(2)) from any source: (0, 0) on a
+ *     source, (-1, -1) where no walk ends.  Pairs are compared exactly in integers, so the planes are the same on every run.
+ *     1 <= H, W <= 16384, the sides of (10); every argument is checked before any device work.
+ * ------------------------------------------------------------------------------------------------ */
+/* 256 + align256(256) + align256(8 T) + align256(H W) + align256(8 H W) bytes with T = ceil(H / 32) * ceil(W / 32) tiles (a header,
+ * two mark words per tile, a passability byte and a 64-bit state word per cell). */
+AVL_API int avl_travel2d_workspace_bytes(int H, int W, size_t* bytes);
+/* d_straight, d_diagonal: (H, W) int32, contiguous.  d_stats: 4 int64 on the device = [rounds that had an active tile, tile runs,
+ * reached cells, 1 when a source exists else 0]; without a source both planes are -1 everywhere, which is not an error code.  The
+ * call launches rounds in batches of 8 and SYNCHRONISES the stream after each batch to read how many tiles are still active; the
+ * last launch (the planes and the stats) is asynchronous.  AVL_ERR_STATE ("did not converge") after H * W + 1 rounds. */
+AVL_API int avl_travel2d(const uint8_t* d_free, int64_t ld_free, const uint8_t* d_sources, int64_t ld_src, int H, int W,
+                         int32_t* d_straight, int32_t* d_diagonal, int64_t* d_stats, void* ws, size_t ws_bytes, void* stream);
+/* The decay map of a travel field, NumPy's float64 operation order of avl_mask_decay_2d:
+ *   d = double(a) + double(b) * 1.4142135623730951 (unfused);  t = 1 - (d / cell_size) * decay_rate;  t < 0 -> 0;  unreached -> 0;
+ *   normalize != 0:  (t - min t) / (max t - min t) over the whole (H, W) window.
+ * d_flags (1 int32, device): 1 when normalize was asked for and max t > min t does not hold (the output is then NaN or inf as in
+ * NumPy, the caller reports it), else 0.  ws: at least 272 bytes of device memory (an avl_travel2d workspace serves).
+ * decay_rate finite and >= 0, cell_size finite and > 0.  Asynchronous. */
+AVL_API int avl_travel_decay_2d(const int32_t* d_straight, const int32_t* d_diagonal, int H, int W, double cell_size, double decay_rate,
+                                int normalize, double* d_out_f64, int32_t* d_flags, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
