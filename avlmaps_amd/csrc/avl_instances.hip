@@ -12,23 +12,7 @@
 // Every output follows uniquely from these definitions and is a minimum, a maximum or a sum of integers: the bytes do not depend
 // on the order in which the atomics land.
 //
-// Labelling.  The work is done on the masked voxels in CELL order, on their ranks t = 0 .. M - 1:
-//   box      bounding box and number M of the masked voxels (one pass, read back: the sort needs M, the key the box).  A side
-//            beyond 2^20 cells is refused here: three sides of 20 bits make a key of at most 60 bits
-//   compact  the masked voxels in index order (avl_scan.h: count_flagged_kernel per 1024 voxels, scan_counts_kernel, then one
-//            write): key = ((row - rmin) * ny + (col - cmin)) * nz + (height - hmin) as uint64, value = the voxel index
-//   sort     rocPRIM's stable radix sort over the key's bits: equal cells keep index order, so the smallest rank of a cell is its
-//            smallest voxel index
-//   merge    union-find on one int32 parent per rank (uf_unite; avl_unionfind.h states the invariant, an element being a rank).
-//            A voxel looks at the 13 cells that precede it in raster order: the height neighbour and a second voxel of its own
-//            cell are the previous rank; the three cells of each of the four preceding columns (row - 1, col - 1 .. col + 1) and
-//            (row, col - 1) are consecutive ranks, found by ONE binary search per column among the ranks before t
-//   flatten  parent = root (uf_flatten_kernel)
-//   number   the roots counted per 1024 ranks, scanned, every root receives 1 + the number of roots before it (count_flagged_kernel,
-//            scan_counts_kernel, number_flagged_kernel).  Roots are first cells and ranks are in cell order, which is the
-//            lexicographic order of (row, col, height)
-//   scatter  labels[voxel of rank t] = label of t's root; the unmasked voxels keep the 0 of the memset
-// The workspace is 28 bytes per voxel of the list whatever the box (no grid over the box is kept, not even one of bits).
+// Labelling.  avl_voxel_label.h's labeller under its mask policy (VlMask): the pipeline is described there.
 //
 // Table.  avl_voxel_instance_table reads pos, labels and scores in voxel order, three passes: (1) count, box, coordinate sums and
 // the largest score key; (2) among the voxels of an instance's first row the smallest (col, height), and among the voxels with the
@@ -39,160 +23,15 @@
 #include <algorithm>
 #include <climits>
 
-#include <rocprim/device/device_radix_sort.hpp>
-
 #include "avl_common.h"
-#include "avl_scan.h"
-#include "avl_unionfind.h"
+#include "avl_voxel_label.h"
 
 namespace avl {
 
-constexpr int kVxMaxSide = 1 << 20;
-constexpr int64_t kVxMaxVoxels = ((int64_t)1 << 31) - 1;
 constexpr int kVxTableCols = 12;                // count, rmin, rmax, cmin, cmax, hmin, hmax, sum_row, sum_col, sum_height, first, best
-constexpr int kVxScanThreads = 256;
-constexpr int kVxScanPer = 4;
-constexpr int kVxScanBlock = kVxScanThreads * kVxScanPer;
 constexpr int kVxSlots = 256;                   // labels a workgroup of the table's first pass keeps in LDS (a power of two)
 constexpr int kVxProbe = 8;
 constexpr int kVxTablePer = 8192;               // voxels per workgroup of that pass, at least
-
-struct VxHeader {
-    int mn[3], mx[3];
-    int count;                                  // masked voxels
-    int pad;
-};
-
-// the masked voxels, for avl_scan.h's counting kernel and the compaction
-struct VxMasked {
-    const uint8_t* mask;
-    __device__ __forceinline__ bool operator()(int64_t i) const { return mask[i] != 0; }
-};
-
-__global__ void vx_header_init_kernel(VxHeader* __restrict__ h) {
-    if (threadIdx.x < 3) {
-        h->mn[threadIdx.x] = INT_MAX;
-        h->mx[threadIdx.x] = INT_MIN;
-    }
-    if (threadIdx.x == 3) h->count = h->pad = 0;
-}
-
-__global__ __launch_bounds__(256) void vx_box_kernel(const int32_t* __restrict__ pos, const uint8_t* __restrict__ mask, int64_t N,
-                                                     VxHeader* __restrict__ h) {
-    __shared__ int red[7][4];
-    int mn[3] = {INT_MAX, INT_MAX, INT_MAX}, mx[3] = {INT_MIN, INT_MIN, INT_MIN}, cnt = 0;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
-        if (!mask[i]) continue;
-        ++cnt;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const int v = pos[i * 3 + c];
-            mn[c] = min(mn[c], v);
-            mx[c] = max(mx[c], v);
-        }
-    }
-    const int w = threadIdx.x / kWave;
-    cnt = wave_sum(cnt);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        mn[c] = wave_min(mn[c]);
-        mx[c] = wave_max(mx[c]);
-        if ((threadIdx.x & (kWave - 1)) == 0) {
-            red[c][w] = mn[c];
-            red[3 + c][w] = mx[c];
-        }
-    }
-    if ((threadIdx.x & (kWave - 1)) == 0) red[6][w] = cnt;
-    __syncthreads();
-    if (threadIdx.x < 7) {
-        const int c = threadIdx.x;
-        int v = red[c][0];
-        for (int k = 1; k < 4; ++k) v = c < 3 ? min(v, red[c][k]) : (c < 6 ? max(v, red[c][k]) : v + red[c][k]);
-        if (c == 6) {
-            if (v) atomicAdd(&h->count, v);
-        } else if (red[6][0] + red[6][1] + red[6][2] + red[6][3]) {         // a workgroup without a masked voxel offers nothing
-            if (c < 3) atomicMin(&h->mn[c], v);
-            else atomicMax(&h->mx[c - 3], v);
-        }
-    }
-}
-
-// the masked voxels in index order: key, voxel index and the rank's own parent.  M is the count of the box pass: nothing is
-// written at or past it, whatever the mask holds by now
-__global__ __launch_bounds__(kVxScanThreads) void vx_compact_kernel(const int32_t* __restrict__ pos, const uint8_t* __restrict__ mask, int64_t N,
-                                                                    const int* __restrict__ offsets, int ox, int oy, int oz, int ny, int nz,
-                                                                    int64_t M, unsigned long long* __restrict__ keys, int* __restrict__ idx,
-                                                                    int* __restrict__ parent) {
-    __shared__ int s_w[kVxScanThreads / kWave];
-    const int64_t base = offsets[blockIdx.x];
-    int64_t i0;
-    int before, total;
-    const int f = block_flags<kVxScanThreads, kVxScanPer>(N, VxMasked{mask}, s_w, &i0, &before, &total);
-    int64_t t = base + before;
-#pragma unroll
-    for (int k = 0; k < kVxScanPer; ++k) {
-        if (!(f >> k & 1) || t >= M) continue;
-        const int64_t i = i0 + k;
-        const unsigned long long x = (unsigned)(pos[i * 3] - ox), y = (unsigned)(pos[i * 3 + 1] - oy), z = (unsigned)(pos[i * 3 + 2] - oz);
-        keys[t] = (x * (unsigned long long)ny + y) * (unsigned long long)nz + z;
-        idx[t] = (int)i;
-        parent[t] = (int)t;
-        ++t;
-    }
-}
-
-// the first rank in [0, hi) whose key is >= k
-__device__ __forceinline__ int vx_lower_bound(const unsigned long long* __restrict__ keys, int hi, unsigned long long k) {
-    int lo = 0;
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (keys[mid] < k) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
-// axes: 1, 2 or 3 = the number of axes on which adjacent cells may differ
-__global__ __launch_bounds__(256) void vx_merge_kernel(const unsigned long long* __restrict__ keys, int M, int ny, int nz, int axes,
-                                                       int* __restrict__ parent) {
-    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < M; t += gridDim.x * blockDim.x) {
-        if (t == 0) continue;
-        const unsigned long long key = keys[t], prev = keys[t - 1];
-        if (prev == key) {                                            // a second voxel of the cell: the cell's first one does the rest
-            uf_unite(parent, t, t - 1);
-            continue;
-        }
-        const int z = (int)(key % (unsigned long long)nz);
-        const unsigned long long col = key / (unsigned long long)nz;
-        const int y = (int)(col % (unsigned long long)ny), x = (int)(col / (unsigned long long)ny);
-        if (z > 0 && prev == key - 1) uf_unite(parent, t, t - 1);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int dx = k < 3 ? -1 : 0, dy = k < 3 ? k - 1 : -1;   // (-1, -1) (-1, 0) (-1, +1) (0, -1)
-            const int dz = min(axes - (dy != 0) - (dx != 0), 1);      // the height may differ by dz (0 or 1); < 0: no such neighbour
-            const int a = x + dx, b = y + dy;
-            if (dz < 0 || a < 0 || b < 0 || b >= ny) continue;
-            const unsigned long long base = ((unsigned long long)a * (unsigned long long)ny + (unsigned long long)b) * (unsigned long long)nz;
-            const unsigned long long lo = base + (unsigned long long)max(z - dz, 0), hi = base + (unsigned long long)min(z + dz, nz - 1);
-            unsigned long long last = ~0ull;                          // no key: a key has at most 60 bits
-            for (int s = vx_lower_bound(keys, t, lo); s < t; ++s) {
-                const unsigned long long ks = keys[s];
-                if (ks > hi) break;
-                if (ks != last) uf_unite(parent, t, s);               // the first voxel of each neighbouring cell
-                last = ks;
-            }
-        }
-    }
-}
-
-// idx[t] < N by construction (vx_compact_kernel wrote it); the comparison only keeps a foreign workspace from writing out of bounds
-__global__ __launch_bounds__(256) void vx_scatter_labels_kernel(const int* __restrict__ parent, const int* __restrict__ rank_label,
-                                                                const int* __restrict__ idx, int M, int64_t N, int* __restrict__ labels) {
-    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < M; t += gridDim.x * blockDim.x) {
-        const int p = parent[t], i = idx[t];
-        if (p >= 0 && p < M && i >= 0 && i < N) labels[i] = rank_label[p];
-    }
-}
 
 // ---------------------------------------------------------------------------------------------------------------- the table
 __device__ __forceinline__ long long vx_load64(const long long* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -340,35 +179,6 @@ __global__ __launch_bounds__(256) void vx_table_finish_kernel(const float* __res
     best_score[k] = scores && b >= 0 && b < N ? scores[b] : 0.f;
 }
 
-static int vx_check_n(const char* what, int64_t N) {
-    AVL_REQUIRE(N >= 0 && N <= kVxMaxVoxels, "%s: N = %lld voxels (0 .. %lld)", what, (long long)N, (long long)kVxMaxVoxels);
-    return AVL_OK;
-}
-
-// workspace of avl_label_voxels: header | keys, sorted keys | voxel indices, sorted | parents | one count per scan block.  After the
-// sort the unsorted indices are dead: their piece takes the labels of the roots
-struct VxWork {
-    int nblocks;
-    VxHeader* header;
-    unsigned long long *keys_in, *keys;
-    int *idx_in, *idx, *parent, *counts;
-    size_t total;
-};
-static VxWork vx_work(int64_t N, void* ws) {
-    Carver c(ws);
-    VxWork w;
-    w.nblocks = (int)((N + kVxScanBlock - 1) / kVxScanBlock);
-    w.header = c.ptr<VxHeader>(sizeof(VxHeader));
-    w.keys_in = c.ptr<unsigned long long>((size_t)N * sizeof(uint64_t));
-    w.keys = c.ptr<unsigned long long>((size_t)N * sizeof(uint64_t));
-    w.idx_in = c.ptr<int>((size_t)N * sizeof(int32_t));
-    w.idx = c.ptr<int>((size_t)N * sizeof(int32_t));
-    w.parent = c.ptr<int>((size_t)N * sizeof(int32_t));
-    w.counts = c.ptr<int>((size_t)w.nblocks * sizeof(int32_t));
-    w.total = c.total();
-    return w;
-}
-
 }  // namespace avl
 
 using namespace avl;
@@ -377,79 +187,27 @@ extern "C" {
 
 int avl_label_voxels_work_bytes(int64_t N, size_t* bytes) {
     AVL_REQUIRE(bytes, "avl_label_voxels_work_bytes: null output");
-    int rc = vx_check_n("avl_label_voxels_work_bytes", N);
+    int rc = vl_check_n("avl_label_voxels_work_bytes", N);
     if (rc != AVL_OK) return rc;
-    *bytes = vx_work(N, nullptr).total;
+    *bytes = vl_work(N, nullptr).total;
     return AVL_OK;
 }
 
 int avl_label_voxels(const int32_t* d_grid_pos, const uint8_t* d_mask, int64_t N, int connectivity, int32_t* d_labels, int32_t* d_n, void* ws,
                      size_t ws_bytes, void* stream) {
-    int rc = vx_check_n("avl_label_voxels", N);
+    int rc = vl_check_n("avl_label_voxels", N);
     if (rc != AVL_OK) return rc;
     AVL_REQUIRE(connectivity == 6 || connectivity == 18 || connectivity == 26, "avl_label_voxels: connectivity %d (6, 18 or 26)", connectivity);
     AVL_REQUIRE(d_grid_pos, "avl_label_voxels: null d_grid_pos");
     AVL_REQUIRE(d_mask, "avl_label_voxels: null d_mask");
     AVL_REQUIRE(d_labels, "avl_label_voxels: null d_labels");
     AVL_REQUIRE(d_n, "avl_label_voxels: null d_n");
-    const VxWork w = vx_work(N, ws);
-    AVL_REQUIRE(ws && ws_bytes >= w.total, "avl_label_voxels: workspace (ws) of %zu bytes, need %zu", ws_bytes, w.total);
-    hipStream_t st = as_stream(stream);
-    AVL_HIP_CHECK(hipMemsetAsync(d_n, 0, sizeof(int32_t), st));
-    if (N == 0) return AVL_OK;
-    keep_mempool_once();
-    AVL_HIP_CHECK(hipMemsetAsync(d_labels, 0, (size_t)N * sizeof(int32_t), st));
-    hipLaunchKernelGGL(vx_header_init_kernel, dim3(1), dim3(64), 0, st, w.header);
-    hipLaunchKernelGGL(vx_box_kernel, dim3(std::min(stride_blocks(N), 512u)), dim3(256), 0, st, d_grid_pos, d_mask, N, w.header);
-    VxHeader h;
-    AVL_HIP_CHECK(hipMemcpyAsync(&h, w.header, sizeof(h), hipMemcpyDeviceToHost, st));
-    AVL_HIP_CHECK(hipStreamSynchronize(st));
-    const int64_t M = h.count;
-    if (M == 0) return AVL_OK;
-    AVL_REQUIRE(M > 0 && M <= N, "avl_label_voxels: %lld masked voxels among %lld", (long long)M, (long long)N);
-    const int64_t sx = (int64_t)h.mx[0] - h.mn[0] + 1, sy = (int64_t)h.mx[1] - h.mn[1] + 1, sz = (int64_t)h.mx[2] - h.mn[2] + 1;
-    AVL_REQUIRE(sx >= 1 && sy >= 1 && sz >= 1 && sx <= kVxMaxSide && sy <= kVxMaxSide && sz <= kVxMaxSide,
-                "avl_label_voxels: the masked voxels' bounding box is %lld x %lld x %lld cells (at most %d a side)", (long long)sx, (long long)sy,
-                (long long)sz, kVxMaxSide);
-    const int ny = (int)sy, nz = (int)sz;
-    const unsigned long long cells = (unsigned long long)sx * (unsigned long long)sy * (unsigned long long)sz;       // at most 2^60
-    int bits = 1;
-    while (bits < 60 && (1ull << bits) < cells) ++bits;
-    const dim3 scan_n((unsigned)w.nblocks), scan_t(kVxScanThreads);
-    hipLaunchKernelGGL((count_flagged_kernel<kVxScanThreads, kVxScanPer, VxMasked>), scan_n, scan_t, 0, st, N, VxMasked{d_mask}, w.counts);
-    hipLaunchKernelGGL((scan_counts_kernel<1024, int, int, OpSum>), dim3(1), dim3(1024), 0, st, (const int*)w.counts, (int64_t)w.nblocks, w.counts,
-                       (int*)nullptr, OpSum{}, 0);
-    hipLaunchKernelGGL(vx_compact_kernel, scan_n, scan_t, 0, st, d_grid_pos, d_mask, N, (const int*)w.counts, h.mn[0], h.mn[1], h.mn[2], ny, nz, M,
-                       w.keys_in, w.idx_in, w.parent);
-    AVL_HIP_CHECK(hipGetLastError());
-    void* tmp = nullptr;
-    size_t tmp_bytes = 0;
-    AVL_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, w.keys_in, w.keys, w.idx_in, w.idx, (size_t)M, 0, bits, st));
-    AVL_HIP_CHECK(hipMallocAsync(&tmp, tmp_bytes ? tmp_bytes : 16, st));
-    const hipError_t e = rocprim::radix_sort_pairs(tmp, tmp_bytes, w.keys_in, w.keys, w.idx_in, w.idx, (size_t)M, 0, bits, st);
-    (void)hipFreeAsync(tmp, st);
-    AVL_HIP_CHECK(e);
-    const unsigned sb = stride_blocks(M);
-    const int mblocks = (int)((M + kVxScanBlock - 1) / kVxScanBlock);
-    int* rank_label = w.idx_in;
-    const int axes = connectivity == 6 ? 1 : (connectivity == 18 ? 2 : 3);
-    hipLaunchKernelGGL(vx_merge_kernel, dim3(sb), dim3(256), 0, st, (const unsigned long long*)w.keys, (int)M, ny, nz, axes, w.parent);
-    const dim3 scan_m((unsigned)mblocks);
-    const UfIsRoot roots{w.parent};
-    hipLaunchKernelGGL((uf_flatten_kernel<256>), dim3(sb), dim3(256), 0, st, w.parent, M);
-    hipLaunchKernelGGL((count_flagged_kernel<kVxScanThreads, kVxScanPer, UfIsRoot>), scan_m, scan_t, 0, st, M, roots, w.counts);
-    hipLaunchKernelGGL((scan_counts_kernel<1024, int, int, OpSum>), dim3(1), dim3(1024), 0, st, (const int*)w.counts, (int64_t)mblocks, w.counts,
-                       (int*)d_n, OpSum{}, 0);
-    hipLaunchKernelGGL((number_flagged_kernel<kVxScanThreads, kVxScanPer, UfIsRoot>), scan_m, scan_t, 0, st, M, roots, (const int*)w.counts, rank_label);
-    hipLaunchKernelGGL(vx_scatter_labels_kernel, dim3(sb), dim3(256), 0, st, (const int*)w.parent, (const int*)rank_label, (const int*)w.idx, (int)M, N,
-                       (int*)d_labels);
-    AVL_HIP_CHECK(hipGetLastError());
-    return AVL_OK;
+    return label_sparse_voxels("avl_label_voxels", "masked", VlMask{d_mask}, d_grid_pos, N, connectivity, d_labels, d_n, ws, ws_bytes, stream);
 }
 
 int avl_voxel_instance_table(const int32_t* d_grid_pos, const int32_t* d_labels, const float* d_scores, int64_t N, int32_t n, int64_t* d_table,
                              float* d_best_score, void* stream) {
-    int rc = vx_check_n("avl_voxel_instance_table", N);
+    int rc = vl_check_n("avl_voxel_instance_table", N);
     if (rc != AVL_OK) return rc;
     AVL_REQUIRE(n >= 0 && (int64_t)n <= N, "avl_voxel_instance_table: n = %d instances among %lld voxels", n, (long long)N);
     if (n == 0) return AVL_OK;

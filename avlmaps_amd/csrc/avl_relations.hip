@@ -41,10 +41,9 @@
 #include <algorithm>
 #include <climits>
 
-#include <rocprim/device/device_radix_sort.hpp>
-
 #include "avl_cellindex.h"
 #include "avl_scan.h"
+#include "avl_sort.h"
 
 namespace avl {
 
@@ -351,20 +350,9 @@ int avl_object_relations(const void* d_index, size_t index_bytes, int64_t N, int
                        w.slots_in);
     AVL_HIP_CHECK(hipGetLastError());
     // every key is below (n + 1)^2 <= 2^bits, and the low `bits` bits of the padding are all ones: it sorts behind every pair
-    int bits = 1;
-    while (bits < 64 && (1ull << bits) < ((unsigned long long)n + 1ull) * ((unsigned long long)n + 1ull)) ++bits;
-    void* tmp = nullptr;
-    size_t tmp_bytes = 0;
-    hipError_t e = rocprim::radix_sort_pairs(nullptr, tmp_bytes, w.keys_in, w.keys_out, w.slots_in, w.slots_out, (size_t)max_pairs, 0, bits, st);
-    if (e == hipSuccess) e = hipMallocAsync(&tmp, tmp_bytes ? tmp_bytes : 16, st);
-    if (e == hipSuccess) {
-        e = rocprim::radix_sort_pairs(tmp, tmp_bytes, w.keys_in, w.keys_out, w.slots_in, w.slots_out, (size_t)max_pairs, 0, bits, st);
-        (void)hipFreeAsync(tmp, st);
-    }
-    if (e != hipSuccess) {
-        set_error("%s: the radix sort failed: %s", who, hipGetErrorString(e));
-        return AVL_ERR_HIP;
-    }
+    const int bits = bits_for(((unsigned long long)n + 1ull) * ((unsigned long long)n + 1ull), 64);
+    rc = sort_pairs_pooled(who, w.keys_in, w.keys_out, w.slots_in, w.slots_out, max_pairs, bits, st);
+    if (rc != AVL_OK) return rc;
     hipLaunchKernelGGL(rel_rows_kernel, dim3(stride_blocks(max_pairs)), dim3(256), 0, st, p, (const unsigned long long*)w.keys_out,
                        (const int*)w.slots_out, d_table, d_count);
     AVL_HIP_CHECK(hipGetLastError());

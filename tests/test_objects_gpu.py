@@ -144,6 +144,43 @@ def test_many_waves_and_workgroups(ops):
         assert got.best_score.tobytes() == one.best_score.tobytes() and (got.classes_of == 3).all()
 
 
+@functools.lru_cache(maxsize=None)
+def shared_cells_and_mask(n_vox):
+    """n_vox voxels dealt unevenly among a quarter of the cells of a 9 x 9 x 5 box at (-3, 40, 2), and a random 60 % mask.  A
+    quarter of the cells, because a box in which every cell is masked is one component at every connectivity"""
+    rng = np.random.default_rng(1)
+    cells = np.argwhere(rng.random((9, 9, 5)) < 0.25)
+    weight = rng.random(len(cells)) ** 3                         # a few voxels in some cells, dozens in others
+    pos = (cells[rng.choice(len(cells), n_vox, p=weight / weight.sum())] + np.array([-3, 40, 2])).astype(np.int32)
+    mask = rng.random(n_vox) < 0.6
+    for a in (pos, mask):
+        a.setflags(write=False)
+    return pos, mask
+
+
+@pytest.mark.parametrize("connectivity", [6, 18, 26])
+@pytest.mark.parametrize("n_vox", [1500, 1025 + 1024])           # two and three scan blocks of the compaction
+def test_label_voxels_is_label_classes_with_one_class(ops, n_vox, connectivity):
+    """avl_label_voxels and avl_label_classes are one labeller (csrc/avl_voxel_label.h) under two policies: a mask is one class,
+    whichever id the class has (7 goes through class - smallest class), also where cells hold several voxels"""
+    pos, mask = shared_cells_and_mask(n_vox)
+    _, per_cell = np.unique(pos, axis=0, return_counts=True)
+    assert (per_cell >= 2).sum() >= 50 and (per_cell >= 3).sum() >= 10 and 0.55 < mask.mean() < 0.65
+    q = pos[mask] - pos[mask].min(0)
+    dense = np.zeros(q.max(0) + 1, np.uint8)
+    dense[q[:, 0], q[:, 1], q[:, 2]] = 1
+    assert ndimage.label(dense, ndimage.generate_binary_structure(3, 3))[1] >= 2
+    with ops.label_voxels(pos, mask, connectivity=connectivity) as one:
+        labels, n = one.labels.copy(), one.n
+    assert labels.dtype == np.int32 and n >= 2 and labels.max() == n and not labels[~mask].any()
+    for cls in (0, 7):
+        classes = np.where(mask, cls, -1).astype(np.int32)
+        with ops.label_voxel_classes(pos, classes, connectivity=connectivity) as got:
+            assert np.array_equal(got.n, n) and got.labels.dtype == np.int32 and np.array_equal(got.labels, labels), cls
+    want, want_n = oracle_labels(pos, np.where(mask, 0, -1), connectivity)
+    assert n == want_n and np.array_equal(labels, want)
+
+
 # ------------------------------------------------------------------ 3 .. 7. shapes whose answer is known
 def test_two_slabs_face_to_face(ops):
     cells = np.argwhere(np.ones((4, 6, 3), bool))
