@@ -243,6 +243,16 @@ _SIGS = {
     "avl_travel2d_workspace_bytes": (C.c_int, [C.c_int, C.c_int, C.POINTER(_sz)]),
     "avl_travel2d": (C.c_int, [_vp, _i64, _vp, _i64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _sz, _vp]),
     "avl_travel_decay_2d": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _f64, _f64, C.c_int, _vp, _vp, _vp, _sz, _vp]),
+    # rooms and doorways: label growth along the travel field, seeds, tables and the voxel lift (csrc/avl_rooms.hip): no upstream counterpart
+    "avl_grow_labels_workspace_bytes": (C.c_int, [C.c_int, C.c_int, C.POINTER(_sz)]),
+    "avl_grow_labels": (C.c_int, [_vp, _i64, _vp, _i64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "avl_room_seeds_workspace_bytes": (C.c_int, [C.c_int, C.c_int, C.POINTER(_sz)]),
+    "avl_room_seeds": (C.c_int, [_vp, C.c_int, C.c_int, _f64, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "avl_room_table": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _i32, _vp, _vp]),
+    "avl_room_doors_workspace_bytes": (C.c_int, [_i32, C.POINTER(_sz)]),
+    "avl_room_doors": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _i32, _vp, _vp, _sz, _vp]),
+    "avl_room_door_table": (C.c_int, [_vp, _sz, _i32, C.c_int, _i64, _vp, _vp]),
+    "avl_lift_labels_2d": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _i64, C.c_int, C.c_int, _vp, _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -3,7 +3,7 @@ application/generate_obstacle_map.py (:19-33), with PNG files where upstream ope
 
     python -m avlmaps_amd.apps.generate_obstacle_map --data-dir <scene> [--out-dir DIR] [--text-model clip|hash]
                                                      [--potential-obstacles a,b,c --obstacles a,b] [--dilate-iter N] [--gaussian-sigma S]
-                                                     [--known-free]
+                                                     [--known-free] [--rooms [--door-width M] [--min-core-area M2]]
 
 Loads <scene>/vlmap/vlmaps.h5df, builds the obstacle map from the occupancy between --h-min and --h-max
 (Map.generate_obstacle_map), then keeps only the obstacles of the classes --obstacles and smooths the map
@@ -11,7 +11,9 @@ Loads <scene>/vlmap/vlmaps.h5df, builds the obstacle map from the occupancy betw
 and obstacles_customized.png (white = free, the cropped maps) under --out-dir (default <scene>/vlmap) and prints one JSON line with
 the crop and the number of obstacle cells of both maps.  With --known-free it also writes obstacles_known_free.png: the obstacle map
 AND-ed with the explored map (Map.get_known_free_cropped; needs <scene>/vlmap/explored.npz, apps.create_map --explored), in which a
-cell no camera ever looked at is not free."""
+cell no camera ever looked at is not free.  With --rooms it also writes rooms.png: the rooms of the customised map (Map.get_rooms with
+customized=True, DESIGN.md 4.27), room k of n in the colour (255 k) // n of the heat maps' colour table (ops.jet_table), cells of
+no room black; the JSON line then has "rooms", the number of rooms, and "doors", the door table's (i, j, door row, door col)."""
 from __future__ import annotations
 
 import argparse
@@ -33,7 +35,21 @@ def parse_args(argv=None):
     ap.add_argument("--dilate-iter", type=int, default=None)
     ap.add_argument("--gaussian-sigma", type=float, default=None)
     ap.add_argument("--known-free", action="store_true", help="also write obstacles_known_free.png (free AND observed)")
-    return ap.parse_args(argv)
+    ap.add_argument("--rooms", action="store_true", help="also write rooms.png (Map.get_rooms on the customised map)")
+    ap.add_argument("--door-width", type=float, default=None, metavar="M", help="--rooms: openings up to M metres separate rooms (default 0.9)")
+    ap.add_argument("--min-core-area", type=float, default=None, metavar="M2", help="--rooms: the smallest room core in square metres (default 0.25)")
+    args = ap.parse_args(argv)
+    if not args.rooms and (args.door_width is not None or args.min_core_area is not None):
+        ap.error("--door-width and --min-core-area belong to --rooms")
+    return args
+
+
+def room_colours(labels, n):
+    """(H, W, 3) uint8: room k of n in entry (255 k) // n of ops.jet_table, label 0 black"""
+    import numpy as np
+    from avlmaps_amd import ops
+    table = np.concatenate([np.zeros((1, 3), np.uint8), ops.jet_table()[(255 * np.arange(1, n + 1)) // max(n, 1)]])
+    return table[np.asarray(labels)]
 
 
 def save_mask_png(path, mask) -> None:
@@ -75,6 +91,14 @@ def main(argv=None):
         save_mask_png(out_dir / "obstacles_known_free.png", known)
         out["known_free_blocked_cells"] = int((known == 0).sum())
         out["files"].append(str(out_dir / "obstacles_known_free.png"))
+    if args.rooms:
+        from PIL import Image
+        rooms = vm.get_rooms(0.9 if args.door_width is None else args.door_width, 0.25 if args.min_core_area is None else args.min_core_area,
+                            customized=True)
+        Image.fromarray(room_colours(rooms.labels, rooms.n)).save(str(out_dir / "rooms.png"))
+        out["rooms"] = rooms.n
+        out["doors"] = rooms.doors[:, [0, 1, 7, 8]].tolist()
+        out["files"].append(str(out_dir / "rooms.png"))
     print(json.dumps(out))
     return out
 

@@ -9,6 +9,7 @@ and image branches, :23-142; the Open3D viewer and the habitat branches are not 
     ... --modality object --categories A,B,...   --quantile P [--instances]
     ... --modality object --categories A,B,...   [--inventory] [--inventory-json PATH] [--min-voxels M] [--connectivity 6|18|26]
     ... --modality object --categories A,B,...   --inventory --relations [--relation-radius M] [--relations-json PATH]
+    ... --modality object --categories A,B,...   --inventory --rooms [--door-width M]
     ... --modality object --categories A,B,...   --related "SUBJECT near|on|under|touching ANCHOR" [--relation-radius M]
     ... any modality ...                 [--render PNG [--view topdown|frame:<i>|orbit] [--render-size W H]] [--save-ply PLY]
 
@@ -73,6 +74,8 @@ def parse_args(argv=None):
     ap.add_argument("--inventory", action="store_true", help="object: list the objects of all categories in 3-D (needs --categories)")
     ap.add_argument("--inventory-json", default=None, metavar="PATH", help="object: write the inventory as JSON (needs --categories)")
     ap.add_argument("--relations", action="store_true", help="object: after --inventory, list how the listed objects stand to one another")
+    ap.add_argument("--rooms", action="store_true", help="object: print the --inventory grouped by room (Map.get_rooms, SceneObjects.assign_rooms)")
+    ap.add_argument("--door-width", type=float, default=None, metavar="M", help="--rooms: openings up to M metres separate rooms (default 0.9)")
     ap.add_argument("--relation-radius", type=float, default=0.25, metavar="M",
                     help="--relations / --relations-json / --related: objects within M metres are related (default 0.25; at most 15 cells)")
     ap.add_argument("--relations-json", default=None, metavar="PATH", help="object: write the relations as JSON (needs --categories)")
@@ -120,6 +123,10 @@ def parse_args(argv=None):
             ap.error("--inventory and --inventory-json need --modality object and --categories")
     if args.relations and not args.inventory:
         ap.error("--relations lists the edges of the inventory: it needs --inventory")
+    if args.rooms and not args.inventory:
+        ap.error("--rooms groups the inventory by room: it needs --inventory")
+    if args.door_width is not None and not args.rooms:
+        ap.error("--door-width belongs to --rooms")
     if args.relations_json or args.related is not None:
         if args.modality != "object" or not args.categories:
             ap.error("--relations-json and --related need --modality object and --categories")
@@ -172,6 +179,20 @@ def print_inventory(scene) -> None:
         voted = "" if it.voted == it.category else f" (voted {it.voted_name!r})"
         print(f"  object {it.label}: {it.name!r}{voted}, {it.count} voxels, rows {r0}..{r1}, cols {c0}..{c1}, heights {h0}..{h1}, "
               f"centre ({it.center[0]:.2f}, {it.center[1]:.2f}, {it.center[2]:.2f}), best score {it.best_score:.4f}, margin {it.margin:.4f}")
+
+
+def print_rooms(scene, rooms) -> None:
+    """--inventory --rooms: the listed objects under the room that holds most of their voxels, room 0 = in no room"""
+    scene.assign_rooms(rooms)
+    print(f"{rooms.n} rooms, {len(rooms.door_table)} doors")
+    for k in list(range(1, rooms.n + 1)) + [0]:
+        inside = scene.in_room(k)
+        if k == 0 and not inside:
+            continue
+        head = f"room {k}: {rooms.area_m2(k):.2f} m^2, centre {rooms.centre(k)}, next to {rooms.neighbours(k)}" if k else "in no room"
+        print(f"  {head}: {len(inside)} objects")
+        for it in inside:
+            print(f"    object {it.label}: {it.voted_name!r}, {it.count} voxels")
 
 
 def print_relations(graph) -> None:
@@ -271,6 +292,9 @@ def main(argv=None):
             if args.inventory_json:
                 scene.save(args.inventory_json)
                 print(f"\nwrote {args.inventory_json}: {len(scene.objects)} objects")
+            if args.rooms:
+                print()
+                print_rooms(scene, vm.get_rooms(0.9 if args.door_width is None else args.door_width))
         if args.relations or args.relations_json:
             graph = vm.get_scene_graph(args.relation_radius, args.min_voxels, args.connectivity)
             if args.relations:

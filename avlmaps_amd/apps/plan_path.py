@@ -8,6 +8,7 @@ setup_scene + move_to (robot/habitat_lang_robot.py:88-104, 432-461) without the 
                                         [--relation left|right|between|north|south|east|west|face --heading DEG [--query-b NAME]]
                                         [--nearest euclid|path] [--known-free] [--goal object|frontier] [--render PNG]
                                         [--view [--view-range METRES] [--view-fraction F]]
+                                        [--room NAME|ID [--door-width M] [--room-names a,b,c]]
 
 Loads <scene>/vlmap/vlmaps.h5df (with --text-model hash a missing map is first created with the model-free feature stand-in, as
 apps.create_map --features hash does), builds the obstacle map (Map.generate_obstacle_map), takes the goal from
@@ -60,6 +61,13 @@ the one nearest to --start as the crow flies, or by travel distance with --neare
 then has "goal_kind": "viewpoint", "visible" (the object's voxels seen from the goal), "view_targets" (the voxels tested) and
 "view_cells" (the cells that see any); --render tints those cells.  The robot's heading and field of view are not modelled.  An
 object that no free cell in range sees ends with a message and exit status 1.
+
+With --room the goal is a room, not an object: the centre of room ID of Map.get_rooms (on the customised map with
+--customize-obstacles, which is what keeps furniture from splitting rooms), the room's cell farthest from every obstacle.  A NAME
+is resolved through AVLMap.name_rooms over --room-names (default: the name alone): among the rooms that get the name, the one with
+the highest mean frame score.  --door-width (default 0.9 m) is the widest opening that still separates rooms.  --query is not
+needed; the JSON line has "goal_kind": "room", "room", "rooms" and "route", the rooms from --start's to the goal's through the
+fewest doors (null when --start lies in no room or the two are not connected).
 
 With --render the plan is also drawn: the top-down colour map of the obstacle crop (Map.generate_rgb_topdown_map) with the
 obstacle cells the planner used darkened, the path as a polyline, the start in green and the goal in red, as a PNG.  The JSON line
@@ -114,13 +122,28 @@ def parse_args(argv=None):
     ap.add_argument("--view-range", type=float, default=None, metavar="METRES", help="how far from the object a viewpoint may be (default 3.0)")
     ap.add_argument("--view-fraction", type=float, default=None, metavar="F",
                     help="a viewpoint sees at least this fraction of what the best cell sees (default 0.5)")
+    ap.add_argument("--room", default=None, metavar="NAME|ID", help="go to the centre of a room (Map.get_rooms): its id, or a name for AVLMap.name_rooms")
+    ap.add_argument("--door-width", type=float, default=None, metavar="M", help="--room: openings up to M metres separate rooms (default 0.9)")
+    ap.add_argument("--room-names", default=None, help="--room NAME: the comma separated names the rooms are named from (default: NAME alone)")
     args = ap.parse_args(argv)
+    if args.room is not None:
+        if (args.query is not None or args.goal == "frontier" or args.relation is not None or args.area or args.sound or args.image
+                or args.goal_2d or args.view or args.nearest == "path"):
+            ap.error("--room goes to a room's centre: no --query, --goal frontier, --relation, --area, --sound, --image, --goal-2d, --view or "
+                     "--nearest path")
+        if args.door_width is not None and not (0.0 <= args.door_width < float("inf")):
+            ap.error("--door-width is a number of metres >= 0")
+        args.room = int(args.room) if args.room.lstrip("+").isdigit() else args.room
+        if args.room_names is not None and isinstance(args.room, int):
+            ap.error("--room-names belongs to --room NAME")
+    elif args.door_width is not None or args.room_names is not None:
+        ap.error("--door-width and --room-names belong to --room")
     if args.goal == "frontier":
         if args.query is not None or args.relation is not None or args.area or args.sound or args.image or args.goal_2d or args.nearest == "path":
             ap.error("--goal frontier takes its goal from the explored map: no --query, --relation, --area, --sound, --image, --goal-2d or --nearest path")
         args.known_free = True
-    elif args.query is None:
-        ap.error("--query is required (or --goal frontier)")
+    elif args.query is None and args.room is None:
+        ap.error("--query is required (or --goal frontier, or --room)")
     if args.view:
         if args.goal == "frontier" or args.relation is not None or args.area or args.sound or args.image or args.goal_2d:
             ap.error("--view looks at the --query object: no --goal frontier, --relation, --area, --sound, --image or --goal-2d")
@@ -185,7 +208,32 @@ def obstacle_overrides(args) -> dict:
 
 
 def is_cross_modal(args) -> bool:
-    return bool(args.area or args.sound or args.image or args.goal_2d)
+    return bool(args.area or args.sound or args.image or args.goal_2d or isinstance(getattr(args, "room", None), str))
+
+
+def room_goal(vm, avlmap, args, start):
+    """--room: (the centre of the room, the JSON extras); SystemExit when there is no such room"""
+    import numpy as np
+    width = 0.9 if args.door_width is None else args.door_width
+    if isinstance(args.room, int):
+        rooms = vm.get_rooms(width, customized=args.customize_obstacles, known_free=args.known_free)
+        if not 1 <= args.room <= rooms.n:
+            raise SystemExit(f"--room {args.room}: the map has rooms 1 .. {rooms.n}")
+        k = args.room
+    else:
+        rooms = avlmap.get_rooms(door_width=width, customized=args.customize_obstacles, known_free=args.known_free)
+        names = [c.strip() for c in args.room_names.split(",") if c.strip()] if args.room_names else [args.room]
+        if args.room not in names:
+            names.append(args.room)
+        named = avlmap.name_rooms(names, rooms)
+        ids = [i + 1 for i, name in enumerate(named) if name == args.room]
+        if not ids:
+            raise SystemExit(f"--room {args.room!r}: no room gets that name (the rooms' names: {named})")
+        scores = avlmap.room_scores[np.array(ids) - 1, names.index(args.room)]
+        k = ids[int(np.argmax(scores))]
+    here = rooms.room_of(start)
+    route = rooms.route(here, k) if here else None
+    return rooms.centre(k), {"goal_kind": "room", "room": k, "rooms": rooms.n, "route": route}
 
 
 def clamp_cell(cell, rmin, cmin, shape):
@@ -243,9 +291,9 @@ def main(argv=None):
     if hashed:
         vm.clip_feat_dim = vm.grid_feat.shape[1]
         vm.clip_model = HashClip(vm.clip_feat_dim)
-    elif args.goal != "frontier" or args.customize_obstacles:          # a frontier goal asks the text tower nothing
+    elif (args.goal != "frontier" and args.room is None) or args.customize_obstacles:          # a frontier or room goal asks the text tower nothing
         vm._init_clip()
-    if args.goal != "frontier":
+    if args.goal != "frontier" and args.room is None:
         cats = ([c.strip() for c in args.categories.split(",")] if args.categories
                 else [args.query] + ([args.query_b] if args.query_b else []) + ["other"])
         vm.init_categories(cats)
@@ -274,6 +322,8 @@ def main(argv=None):
         extra = {"relation": args.relation, "heading": args.heading, "goal_cell": cell}
         if args.query_b:
             extra["query_b"] = args.query_b
+    elif args.room is not None:
+        goal, extra = room_goal(vm, avlmap, args, start)
     elif args.goal == "frontier":
         frontiers = vm.get_frontiers()
         if len(frontiers[0]) == 0:

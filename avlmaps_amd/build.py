@@ -48,6 +48,7 @@ SOURCES = {
     "avl_objects.hip": ["-ffp-contract=off"],      # integer kernels and float64 additions in a pinned order: nothing to fuse, and it stays so
     "avl_relations.hip": ["-ffp-contract=off"],    # integer kernels; the flag keeps the file in line with the other integer sources
     "avl_travel.hip": ["-ffp-contract=off"],       # the field is integer; a + b * sqrt(2), the decay and the normalisation round like NumPy, unfused
+    "avl_rooms.hip": ["-ffp-contract=off"],        # integer kernels and one float64 comparison; the flag keeps the file in line with avl_travel.hip
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fvisibility=hidden", "-Wall",
           "-Wno-unused-function", "-munsafe-fp-atomics"]

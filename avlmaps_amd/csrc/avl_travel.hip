@@ -46,6 +46,7 @@
 
 #include "avl_common.h"
 #include "avl_decay2d.h"
+#include "avl_travel_tile.h"
 #include "avl_wave.h"
 
 namespace avl {
@@ -56,16 +57,7 @@ constexpr int kTravelThreads = 256;
 constexpr int kTravelCells = kTravelTile * kTravelTile / kTravelThreads;   // cells per thread: 4, rows ty, ty + 8, ty + 16, ty + 24
 constexpr int kTravelSweeps = 64;                // in-tile sweep cap: an open tile converges in ~33, a corridor maze continues next round
 constexpr int kTravelHalo = kTravelTile + 2;
-constexpr int kTravelRoundBatch = 8;             // rounds launched between two convergence checks
-constexpr unsigned long long kTravelUnreached = ~0ull;
-constexpr unsigned long long kTravelStraight = 1ull << 32, kTravelDiagonal = 1ull;
-constexpr uint8_t kTravelFree = 1, kTravelSource = 2;
-
-// header words of the workspace (uint32)
-constexpr int kTravelHdrAny = 0;                 // a source exists
-constexpr int kTravelHdrInit = 1;                // tiles the initialisation marked active
-constexpr int kTravelHdrRound = 8;               // [kTravelRoundBatch] tiles marked active by each round of the current batch
-constexpr int kTravelHdrWords = 64;
+// (the state word, the passability bits, the header words, the marks and the legal-step rule: avl_travel_tile.h, shared with avl_rooms.hip)
 
 // a1 + b1 sqrt(2) < a2 + b2 sqrt(2) for two reached words, exactly
 __device__ __forceinline__ bool travel_less(unsigned long long p, unsigned long long q) {
@@ -75,18 +67,6 @@ __device__ __forceinline__ bool travel_less(unsigned long long p, unsigned long 
     if (da >= 0 && db >= 0) return false;
     const long long a2 = (long long)da * da, b2 = 2ll * ((long long)db * db);
     return da < 0 ? a2 > b2 : a2 < b2;               // da < 0 < db: |da| > db sqrt(2);  db < 0 < da: da < |db| sqrt(2)
-}
-
-__device__ __forceinline__ unsigned long long travel_load(const unsigned long long* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void travel_store(unsigned long long* p, unsigned long long v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// marks tile t active for the coming round; *count counts the tiles that were not marked yet
-__device__ __forceinline__ void travel_mark(unsigned* __restrict__ flags, int t, unsigned* __restrict__ count) {
-    if (atomicExch(&flags[t], 1u) == 0u) atomicAdd(count, 1u);
 }
 
 // pass = free | source << 1 per cell, state = (0, 0) on sources and unreached elsewhere; the tile of every source and its eight
@@ -104,23 +84,10 @@ __global__ __launch_bounds__(256) void travel_init_kernel(const uint8_t* __restr
         state[i] = sr ? 0ull : kTravelUnreached;
         if (sr) {
             if (hdr[kTravelHdrAny] == 0u) atomicExch(&hdr[kTravelHdrAny], 1u);
-            const int tr = r / kTravelTile, tc = c / kTravelTile;
-#pragma unroll
-            for (int dr = -1; dr <= 1; ++dr) {
-#pragma unroll
-                for (int dc = -1; dc <= 1; ++dc) {
-                    const int ur = tr + dr, uc = tc + dc;
-                    if (ur < 0 || ur >= th || uc < 0 || uc >= tw) continue;
-                    if (flags[ur * tw + uc] == 0u) travel_mark(flags, ur * tw + uc, &hdr[kTravelHdrInit]);
-                }
-            }
+            travel_mark_around<kTravelTile>(flags, r, c, th, tw, &hdr[kTravelHdrInit]);
         }
     }
 }
-
-// the eight directions in 45 degree steps, E first (avl_nav.hip's order): odd = diagonal
-__device__ __forceinline__ constexpr int travel_dr(int k) { return k == 0 || k == 4 ? 0 : (k < 4 ? -1 : 1); }
-__device__ __forceinline__ constexpr int travel_dc(int k) { return k == 2 || k == 6 ? 0 : (k == 3 || k == 4 || k == 5 ? -1 : 1); }
 
 // One round: see the head of the file.  cur / next: the active marks of this round and of the coming one.
 __global__ __launch_bounds__(kTravelThreads) void travel_round_kernel(const uint8_t* __restrict__ pass, unsigned long long* state, int H,
@@ -157,18 +124,7 @@ __global__ __launch_bounds__(kTravelThreads) void travel_round_kernel(const uint
     for (int j = 0; j < kTravelCells; ++j) {
         const int at = (ty + 8 * j + 1) * kTravelHalo + tx + 1;
         first[j] = mine[j] = s_state[at];
-        unsigned m = 0;
-        const uint8_t pv = s_pass[at];
-        if ((pv & kTravelFree) && !(pv & kTravelSource)) {          // a source keeps (0, 0); a blocked cell is never entered
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                bool ok = s_pass[at + travel_dr(k) * kTravelHalo + travel_dc(k)] != 0;      // u is free or a source
-                if (k & 1)
-                    ok = ok && (s_pass[at + travel_dr(k) * kTravelHalo] & kTravelFree) && (s_pass[at + travel_dc(k)] & kTravelFree);
-                m |= ok ? 1u << k : 0u;
-            }
-        }
-        legal[j] = m;
+        legal[j] = travel_legal_in<kTravelHalo>(s_pass, at);
     }
     bool more = true;
     for (int sweep = 0; sweep < kTravelSweeps && more; ++sweep) {
@@ -206,9 +162,7 @@ __global__ __launch_bounds__(kTravelThreads) void travel_round_kernel(const uint
         if (mine[j] == first[j]) continue;
         const int lr = ty + 8 * j, lc = tx;
         travel_store(&state[(int64_t)(r0 + 1 + lr) * W + (c0 + 1 + lc)], mine[j]);     // changed cells lie inside the map
-        const bool n = lr == 0, s = lr == kTravelTile - 1, w = lc == 0, e = lc == kTravelTile - 1;
-        dirty |= (e ? 1u << 0 : 0u) | (n && e ? 1u << 1 : 0u) | (n ? 1u << 2 : 0u) | (n && w ? 1u << 3 : 0u) | (w ? 1u << 4 : 0u) |
-                 (s && w ? 1u << 5 : 0u) | (s ? 1u << 6 : 0u) | (s && e ? 1u << 7 : 0u);
+        dirty |= travel_halo_readers<kTravelTile>(lr, lc);
     }
     if (dirty) atomicOr(&s_dirty, dirty);
     __syncthreads();
@@ -323,37 +277,15 @@ int avl_travel2d(const uint8_t* d_free, int64_t ld_free, const uint8_t* d_source
 
     // a shortest walk has fewer than H * W steps and every round moves every pending walk on by a step or more
     const int64_t max_rounds = n + 1;
-    int64_t k = 0, rounds = 0, tile_runs = 0;
+    int64_t rounds = 0, tile_runs = 0;
     unsigned host[kTravelHdrWords];
-    unsigned carry = 0;                                 // tiles active in the first round of the batch
-    bool first_batch = true, converged = false;
-    while (k < max_rounds && !converged) {
-        const int64_t k0 = k, k1 = std::min<int64_t>(k + kTravelRoundBatch, max_rounds);
-        if (!first_batch) AVL_HIP_CHECK(hipMemsetAsync(hdr + kTravelHdrRound, 0, kTravelRoundBatch * sizeof(unsigned), st));
-        for (; k < k1; ++k) {
-            unsigned* cur = flags + (size_t)(k & 1) * tiles;
-            unsigned* next = flags + (size_t)((k + 1) & 1) * tiles;
-            hipLaunchKernelGGL(travel_round_kernel, dim3(tiles), dim3(kTravelThreads), 0, st, (const uint8_t*)pass, state, H, W, cur, next,
-                               hdr + kTravelHdrRound + (int)(k - k0));
-        }
-        AVL_HIP_CHECK(hipGetLastError());
-        AVL_HIP_CHECK(hipMemcpyAsync(host, hdr, sizeof(host), hipMemcpyDeviceToHost, st));
-        AVL_HIP_CHECK(hipStreamSynchronize(st));
-        if (first_batch) {
-            carry = host[kTravelHdrInit];
-            first_batch = false;
-        }
-        for (int64_t j = 0; j < k1 - k0; ++j) {
-            rounds += carry != 0;
-            tile_runs += carry;
-            carry = host[kTravelHdrRound + j];
-        }
-        converged = carry == 0;
-    }
-    if (!converged) {
-        set_error("avl_travel2d: did not converge in %lld rounds", (long long)max_rounds);
-        return AVL_ERR_STATE;
-    }
+    rc = travel_run_rounds(
+        "avl_travel2d", max_rounds, hdr, flags, tiles, st,
+        [&](int64_t, unsigned* cur, unsigned* next, unsigned* activated) {
+            hipLaunchKernelGGL(travel_round_kernel, dim3(tiles), dim3(kTravelThreads), 0, st, (const uint8_t*)pass, state, H, W, cur, next, activated);
+        },
+        &rounds, &tile_runs, host);
+    if (rc != AVL_OK) return rc;
     hipLaunchKernelGGL(travel_unpack_kernel, dim3(stride_blocks(n)), dim3(256), 0, st, (const unsigned long long*)state, n, d_straight,
                        d_diagonal, (long long)rounds, (long long)tile_runs, (int)(host[kTravelHdrAny] != 0),
                        reinterpret_cast<unsigned long long*>(d_stats));

@@ -6,3 +6,4 @@ from .avlmap import AVLMap, Goal, Goal2D  # noqa: F401
 from .vlmap_builder_multi_floor import VLMapBuilderMultiFloor  # noqa: F401
 from .vlmap_multi_floor import VLMapMultiFloor  # noqa: F401
 from .gtmap import GTMap  # noqa: F401
+from .rooms import Rooms  # noqa: F401

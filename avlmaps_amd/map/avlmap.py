@@ -56,6 +56,7 @@ class AVLMap:
         self._area_loaded = self._sound_loaded = False
         self._dataloader = None
         self._area_cells = self._sound_cells = None
+        self._rooms = self._room_names = None
 
     # ------------------------------------------------------------------ build / load
     def create_map(self, data_dir, feat_extractor=None, area_encoder=None, audio_encoder=None, area_batch_encoder=None) -> bool:
@@ -83,6 +84,7 @@ class AVLMap:
         from .area_map import AreaMap
         self._dataloader = None
         self._area_cells = self._sound_cells = None
+        self._rooms = self._room_names = None
         self._area_loaded = AreaMap.map_exists(data_dir) and self.area_map.load_map(data_dir)
         self._sound_loaded = False
         if self.sound_map is not None and self.sound_map.sound_map_path(data_dir).exists():
@@ -225,6 +227,79 @@ class AVLMap:
         heat = ops.field_lift(gf, self.vlmap._device_pos(), self._vh())
         self._check_bounds(gf, what)
         return heat.numpy()
+
+    # ------------------------------------------------------------------ rooms
+    def get_rooms(self, **kwargs):
+        """the Rooms of the voxel map (Map.get_rooms), kept for name_rooms and index_room until the next call with arguments"""
+        if kwargs or getattr(self, "_rooms", None) is None:
+            self._rooms, self._room_names = self.vlmap.get_rooms(**kwargs), None
+        return self._rooms
+
+    def _frame_cells(self) -> np.ndarray:
+        """(F, 2) int32 full-map cells of the area map's frames, exactly the cells _area_field hands to the kernel"""
+        cells = self.dataloader.habitat_tfs_to_cells(self.area_map.robot_pose_list)
+        return np.clip(cells, -1, np.iinfo(np.int32).max).astype(np.int32)
+
+    def name_rooms(self, names: List[str], rooms=None) -> list:
+        """A name for every room: [name of room 1, .., name of room K].  A room's score for a name is the float64 mean of the area
+        map's frame scores (AreaMap.index_map, as index_area reads them) over the frames whose pose cell lies in the room -- a
+        sequential sum in frame order on the host; the room's name is the first maximum over `names`, None for a room without a
+        frame.  rooms: a Rooms (kept for index_room), by default get_rooms().  The scores stay on self.room_scores (K, len(names))
+        float64, NaN for a room without a frame."""
+        self._require_area()
+        names = [str(s) for s in names]
+        if not names:
+            raise ValueError("name_rooms needs at least one name")
+        if rooms is None:
+            rooms = self.get_rooms()
+        self._rooms = rooms
+        frame_room = np.array([rooms.room_of(cell) for cell in self._frame_cells()], dtype=np.int64)
+        scores = [np.asarray(self.area_map.index_map(name, with_init_cat=False)).reshape(-1) for name in names]
+        table = np.full((rooms.n, len(names)), np.nan, dtype=np.float64)
+        out = []
+        for k in range(1, rooms.n + 1):
+            frames = np.flatnonzero(frame_room == k)
+            if not len(frames):
+                out.append(None)
+                continue
+            for q, s in enumerate(scores):
+                total = 0.0
+                for f in frames:                                  # frame order, one float64 addition per frame
+                    total += float(s[f])
+                table[k - 1, q] = total / len(frames)
+            out.append(names[int(np.argmax(table[k - 1]))])
+        self.room_scores, self._room_names = table, out
+        return out
+
+    def _room_ids(self, room) -> List[int]:
+        rooms = self.get_rooms()
+        if isinstance(room, str):
+            named = getattr(self, "_room_names", None)
+            if named is None:
+                raise ValueError(f"room {room!r}: call name_rooms first")
+            ids = [k + 1 for k, name in enumerate(named) if name == room]
+            if not ids:
+                raise LookupError(f"no room is named {room!r} (the names: {named})")
+            return ids
+        return [rooms._check(room)]
+
+    def index_room_2d(self, room) -> np.ndarray:
+        """(h, w) float64 over the obstacle crop: 1.0 on the cells of the room, 0.0 elsewhere.  room: an id, or a name that
+        name_rooms gave (every room of that name)."""
+        return np.isin(self.get_rooms().labels, self._room_ids(room)).astype(np.float64)
+
+    def index_room(self, room, decay_rate: float = None) -> np.ndarray:
+        """(N,) float64: 1.0 on the voxels of the room and 0.0 elsewhere (VLMap.get_voxel_rooms), a factor for index_goal:
+        index_goal(obj="sofa", extra=[avl.index_room("kitchen")]) is the sofa in the kitchen.  room: an id, or a name that
+        name_rooms gave (every room of that name).  decay_rate: None for the indicator; a number lets the heat decay with the
+        distance from the room's voxels as index_object's does (ValueError when the room holds no voxel)."""
+        inside = np.isin(self.vlmap.get_voxel_rooms(self.get_rooms()), self._room_ids(room))
+        if decay_rate is None:
+            return inside.astype(np.float64)
+        if not inside.any():
+            raise ValueError(f"room {room!r} holds no voxel")
+        cs = cfg_get(cfg_get(self.config, "params"), "cs")
+        return self.vlmap.heatmap_from_mask(inside.astype(np.uint8), cs, decay_rate).numpy().astype(np.float64)
 
     # ------------------------------------------------------------------ sound
     def _require_sound(self):

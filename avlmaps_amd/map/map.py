@@ -649,6 +649,21 @@ class Map:
         included -- even when that cell is an obstacle, from which it may step onto a free neighbour"""
         return self.get_travel_field([curr_pos], customized, known_free).reachable()
 
+    def get_rooms(self, door_width: float = 0.9, min_core_area: float = 0.25, customized: bool = False, known_free: bool = False):
+        """The rooms of this map: a Rooms (map/rooms.py) of ops.segment_rooms over the obstacle crop (customized: the customised
+        crop; known_free: get_known_free_cropped), DESIGN.md 4.27.  The free space is eroded by half a door width -- radius =
+        door_width / (2 cs) cells -- so that rooms fall apart at their doors; the pieces of at least min_core_area square metres
+        (min_seed_cells = ceil(min_core_area / cs^2)) are the seeds, and they grow back along the travel field until they meet in
+        the doorways.  Openings wider than door_width do not separate rooms, and furniture does: call customize_obstacle_map with
+        the walls only and pass customized=True, or a sofa across a room splits it.  Upstream has no counterpart."""
+        from .. import ops
+        from .rooms import Rooms, room_parameters
+        free = self._travel_free(customized, known_free)
+        radius, least = room_parameters(door_width, min_core_area, self.cs)
+        seg = ops.segment_rooms(free, radius, least)
+        params = dict(door_width=float(door_width), min_core_area=float(min_core_area), radius=radius, min_seed_cells=least)
+        return Rooms(seg.labels, seg.rooms, seg.doors, seg.clearance, (int(self.rmin), int(self.cmin)), self.cs, params, seg.field)
+
     @staticmethod
     def _dilate_map(binary_map: np.ndarray, dilate_iter: int = 0, gaussian_sigma: float = 1.0):
         """2x bilinear upsample -> gaussian -> threshold -> dilation -> downsample, (h, w) float64.  Reference: map.py:169-181

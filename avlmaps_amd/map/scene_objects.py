@@ -20,6 +20,7 @@ class SceneObjects:
         self.mean_scores = np.asarray(mean_scores, np.float64).reshape(voxel_objects.n, len(self.names))
         self.min_voxels, self.connectivity, self.exclude = int(min_voxels), int(connectivity), tuple(exclude)
         self._argmax, self._labels = argmax, None
+        self.positions, self.rooms = None, None         # the (N, 3) cells of the voxels (VLMap.get_objects sets them); assign_rooms' result
         self.voted, self.margin = ops.vote_rows(self.mean_scores)
         table, best, classes = voxel_objects.table, voxel_objects.best_score, voxel_objects.classes_of
         self.objects: List[ops.Object3D] = [
@@ -51,6 +52,30 @@ class SceneObjects:
         v = vote_of[labels]
         out[v >= 0] = v[v >= 0]
         return out
+
+    def assign_rooms(self, rooms, positions=None) -> np.ndarray:
+        """(len(objects),) int32: per listed object the room that holds most of its voxels -- the smallest room id among equals,
+        0 when no voxel of the object lies in a room.  rooms: Map.get_rooms' result.  The voxels' rooms are ops.lift_labels_2d of
+        the rooms' labels on `positions` ((N, 3) cells, by default those VLMap.get_objects left here); the votes are one
+        ops.label_confusion over the object labels and the voxels' rooms.  Kept as self.rooms for in_room."""
+        from .. import ops
+        from .rooms import majority_room
+        positions = self.positions if positions is None else positions
+        if positions is None:
+            raise ValueError("assign_rooms: no voxel positions (pass positions=vlmap.grid_pos)")
+        vo = self.voxel_objects
+        voxel_room = ops.lift_labels_2d(rooms.labels, positions, rooms.window, device=True)
+        labels = vo.labels_dev if getattr(vo, "labels_dev", None) is not None else self._host_labels()
+        conf, _ = ops.label_confusion(labels, voxel_room, self.n + 1, rooms.n + 1)
+        listed = np.array([it.label for it in self.objects], dtype=np.int64)
+        self.rooms = majority_room(conf[listed].astype(np.int64)) if len(listed) else np.zeros((0,), np.int32)
+        return self.rooms
+
+    def in_room(self, k) -> list:
+        """the listed objects of room k (0: those in no room), in label order; assign_rooms must have run"""
+        if self.rooms is None:
+            raise ValueError("in_room: call assign_rooms(rooms) first")
+        return [it for it, room in zip(self.objects, self.rooms) if int(room) == int(k)]
 
     def to_json(self) -> str:
         """the listed objects as JSON text; objects_from_json reads them back.  A margin of inf (Q = 1) is written as null"""

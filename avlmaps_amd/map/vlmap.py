@@ -533,7 +533,9 @@ class VLMap(Map):
             (scores_mat, grid_pos, *rest), scene = cached
             if scores_mat is self.scores_mat and grid_pos is self.grid_pos and tuple(rest) == key[2:]:
                 if scene.min_voxels != int(min_voxels):  # the same labelling, listed again
+                    positions = scene.positions
                     scene = SceneObjects(scene.voxel_objects, scene.mean_scores, self._argmax, names, min_voxels, connectivity, exclude)
+                    scene.positions = positions
                     self._objects_cache = (key, scene)
                 return scene
             scene.close()
@@ -551,6 +553,7 @@ class VLMap(Map):
         with np.errstate(invalid="ignore", divide="ignore"):
             mean = sums / vo.table[:, 0:1].astype(np.float64)
         scene = SceneObjects(vo, mean, self._argmax, names, min_voxels, connectivity, exclude)
+        scene.positions = self._device_pos()             # assign_rooms lifts the rooms onto these
         self._objects_cache = (key, scene)
         return scene
 
@@ -614,6 +617,18 @@ class VLMap(Map):
         behind one is as cold as the walk around it is long, and a cell no walk reaches is 0.  ValueError when no cell survives the
         smoothing or the map is constant, as get_distribution_map."""
         return self._travel_distribution_map_device(name, decay_rate, customized).numpy()
+
+    def get_voxel_rooms(self, rooms, device: bool = False):
+        """(N,) int32: the room of every voxel, rooms.labels[row - rmin, col - cmin] of its cell and 0 outside the crop
+        (ops.lift_labels_2d on the resident positions).  rooms: Map.get_rooms' result.  A voxel above an obstacle cell -- the top
+        of a table -- is in no room unless the rooms were made on a walls-only customised map.  NotImplementedError when the rows
+        are sharded over ranks, like get_objects."""
+        from .. import ops, parallel
+        if parallel.rank_world()[1] > 1 and self.shard_index_rows:
+            raise NotImplementedError("get_voxel_rooms on rows sharded over ranks")
+        if self.grid_pos is None or len(self.grid_pos) == 0:
+            return np.zeros((0,), np.int32)
+        return ops.lift_labels_2d(rooms.labels, self._device_pos(), rooms.window, device=device)
 
     def customize_obstacle_map(self, potential_obstacle_names: List[str], obstacle_names: List[str], vis: bool = False):
         """Reference: vlmap.py:127-156 (like upstream the class lists and the smoothing parameters come from map_config, not from

@@ -81,6 +81,10 @@ from .relations import (  # noqa: F401
 from .travel import (  # noqa: F401
     travel_decay_2d, travel_field, TRAVEL_MAX_SIDE, TRAVEL_NEIGHBOURS, TRAVEL_SWEEPS, TRAVEL_TILE, TravelField, UNREACHED,
 )
+from .rooms import (  # noqa: F401
+    DOOR_TABLE_COLS, grow_labels, LabelGrowth, lift_labels_2d, ROOM_TABLE_COLS, room_seeds, room_tables, ROOMS_MAX,
+    RoomSegmentation, _seed_image, segment_rooms,
+)
 # the shared marshalling layer; its one device predicate keeps both of the names it had here
 from ._args import (  # noqa: F401
     _dev_u8, _image_any, _image_shape, _image_u8, _is_dev, _is_dev as _on_device, _result,

@@ -1378,6 +1378,46 @@ AVL_API int avl_travel2d(const uint8_t* d_free, int64_t ld_free, const uint8_t* 
 AVL_API int avl_travel_decay_2d(const int32_t* d_straight, const int32_t* d_diagonal, int H, int W, double cell_size, double decay_rate,
                                 int normalize, double* d_out_f64, int32_t* d_flags, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * (26) rooms and doorways: label growth along the travel field, room seeds, the room and door tables and the lift of a label image
+ *     onto voxels (csrc/avl_rooms.hip).  Upstream has no counterpart.  Images are row-major, 1 <= H, W <= 16384 as in
+ *     (25); every argument is checked before any device work; every result is integers and the same bytes on every run.
+ * ------------------------------------------------------------------------------------------------ */
+AVL_API int avl_grow_labels_workspace_bytes(int H, int W, size_t* bytes);
+/* d_free as in (25); d_seeds (H, W) int32 with rows of ld_seeds cells, a seed is > 0 and is a label, it may lie on an obstacle cell.
+ * First the travel field of (25) from the sources seeds > 0 (avl_travel2d itself: d_straight, d_diagonal, d_stats[0 .. 3]), then the
+ * label rounds on the fixed field: d_owner (H, W) int32 = the seed on a source, 0 where the field does not reach, else the smallest
+ * label over the tight predecessors (the step u -> c is legal and field[u] + step == field[c]).  d_stats: 8 int64 on the device;
+ * [4] label rounds that had an active tile, [5] label tile runs, [6] 1 when a negative seed was seen (it counts as no seed), [7] 0.
+ * SYNCHRONISES the stream after each batch of 8 rounds of either phase; the last launch is asynchronous.  AVL_ERR_STATE after
+ * H * W + 1 rounds of a phase. */
+AVL_API int avl_grow_labels(const uint8_t* d_free, int64_t ld_free, const int32_t* d_seeds, int64_t ld_seeds, int H, int W, int32_t* d_straight,
+                            int32_t* d_diagonal, int32_t* d_owner, int64_t* d_stats, void* ws, size_t ws_bytes, void* stream);
+AVL_API int avl_room_seeds_workspace_bytes(int H, int W, size_t* bytes);
+/* d_clearance (H, W) float64 (avl_edt2d of the free map).  core = clearance > radius; d_seeds (H, W) int32 = the 8-connected islands
+ * of core in avl_label_islands' numbering, those with fewer than min_seed_cells cells dropped and the rest renumbered 1 .. K in their
+ * old order; *d_k (1 int32, device) = K.  H * W <= 2^28 as in (11).  SYNCHRONISES the stream once (the island count). */
+AVL_API int avl_room_seeds(const double* d_clearance, int H, int W, double radius, int64_t min_seed_cells, int32_t* d_seeds, int32_t* d_k,
+                           void* ws, size_t ws_bytes, void* stream);
+/* d_table (K, 10) int64, row k - 1 for label k of d_labels (H, W) int32: cells, rmin, rmax, cmin, cmax, sum of rows, sum of columns,
+ * seed cells (d_seeds == k), centre row, centre col.  The centre is the room's cell with the largest clearance, the smallest raster
+ * index among equals.  A label without a cell: 0 cells, -1 in the box and the centre.  K = 0 does nothing.  Asynchronous. */
+AVL_API int avl_room_table(const int32_t* d_labels, const int32_t* d_seeds, const double* d_clearance, int H, int W, int32_t K,
+                           int64_t* d_table, void* stream);
+AVL_API int avl_room_doors_workspace_bytes(int32_t K, size_t* bytes);
+/* Accumulates the contacts of d_labels per unordered pair of labels 1 .. K and sorts the pairs by (i, j) inside ws.  A contact is a
+ * pair of 4-adjacent cells (u, v), v right of or below u, both labels nonzero and different.  d_count: 2 int64 on the device =
+ * [pairs D, 1 when the pair table overflowed (the result is then incomplete and the caller reports it)].  Asynchronous. */
+AVL_API int avl_room_doors(const int32_t* d_labels, const double* d_clearance, int H, int W, int32_t K, int64_t* d_count, void* ws,
+                           size_t ws_bytes, void* stream);
+/* d_table (D, 10) int64 from the workspace avl_room_doors filled, sorted by (i, j): i, j, contacts, rmin, rmax, cmin, cmax over all
+ * cells of all contacts, door row, door col, 0.  The door cell has the largest clearance among the cells of the pair's contacts, the
+ * smallest raster index among equals.  D = 0 does nothing.  Asynchronous. */
+AVL_API int avl_room_door_table(const void* ws, size_t ws_bytes, int32_t K, int W, int64_t D, int64_t* d_table, void* stream);
+/* d_out[n] = d_labels[row - rmin, col - cmin] for d_grid_pos (N, 3) int32 = (row, col, height), 0 outside the (H, W) crop. */
+AVL_API int avl_lift_labels_2d(const int32_t* d_labels, int H, int W, const int32_t* d_grid_pos, int64_t N, int rmin, int cmin,
+                               int32_t* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
