@@ -253,6 +253,9 @@ _SIGS = {
     "avl_room_doors": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _i32, _vp, _vp, _sz, _vp]),
     "avl_room_door_table": (C.c_int, [_vp, _sz, _i32, C.c_int, _i64, _vp, _vp]),
     "avl_lift_labels_2d": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _i64, C.c_int, C.c_int, _vp, _vp]),
+    # 2-D viewsheds and information gain on the explored map (csrc/avl_viewshed.hip): upstream has no counterpart
+    "avl_viewshed_gain": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _i64, C.c_int, C.c_int, _vp, _vp]),
+    "avl_viewshed_seen": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _i64, C.c_int, C.c_int, C.c_int, _vp, _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -6,7 +6,8 @@ setup_scene + move_to (robot/habitat_lang_robot.py:88-104, 432-461) without the 
                                         [--customize-obstacles [--potential-obstacles a,b,c --obstacles a,b]
                                          [--dilate-iter N] [--gaussian-sigma S]]
                                         [--relation left|right|between|north|south|east|west|face --heading DEG [--query-b NAME]]
-                                        [--nearest euclid|path] [--known-free] [--goal object|frontier] [--render PNG]
+                                        [--nearest euclid|path] [--known-free] [--goal object|frontier|nbv] [--render PNG]
+                                        [--goal nbv [--view-range METRES] [--nbv-count K] [--nbv-conservative]]
                                         [--view [--view-range METRES] [--view-fraction F]]
                                         [--room NAME|ID [--door-width M] [--room-names a,b,c]]
 
@@ -52,6 +53,17 @@ With --known-free the path is planned on Map.get_known_free_cropped(): the obsta
 next: the frontier of the explored area with the shortest travel distance from --start (Map.get_frontiers,
 Navigator.plan_to_nearest_frontier), planned on the known-free map; --query is not needed, and the JSON line has "frontiers", the
 number of frontier islands, and "frontier_cells", the size of the chosen one.
+
+With --goal nbv the goal is the next best view (Map.get_next_best_view; csrc/avl_viewshed.hip): among the known-free
+cells on a lattice and the frontier centres that the robot can reach, those from which at least half as many unknown cells would
+become visible within --view-range metres (default 3) as from the best one, and of these the one with the shortest travel distance
+from --start.  The path is planned on the known-free map.  The JSON line has "goal_kind": "nbv", "gain" (the unknown cells the goal
+would see), "heading_octant" (the first of the two neighbouring 45-degree sectors of atan2(d_row, d_col) that hold the most of
+them) and "views", the tour of Map.plan_exploration with --nbv-count K views (default 1): [{"goal", "heading_octant", "gain"}, ...],
+each chosen on the map as it would be known after the views before it.  --nbv-conservative lets unknown cells block the view, so
+that only the first layer of unknown cells behind known space counts.  --render tints the cells the first view would see and marks
+every view of the tour.  A fully explored map ends with a message and exit status 1.  Sight lines are 2-D, in the explored map's
+height band; the robot's field of view is not modelled beyond the sector sums.
 
 With --view the goal is not the object's contour point but a cell the object can be SEEN from (Map.get_viewpoints: 3-D sight lines
 from a camera at the map config's camera height to the object's voxels, through the voxel map; csrc/avl_sight.hip): among the free
@@ -115,21 +127,24 @@ def parse_args(argv=None):
                     help="which --query object is the goal: euclid = the nearest as the crow flies (Map.get_nearest_pos); "
                          "path = the one with the shortest travel distance (Map.get_nearest_reachable_pos)")
     ap.add_argument("--known-free", action="store_true", help="plan on the obstacle map AND-ed with the explored map (Map.get_known_free_cropped)")
-    ap.add_argument("--goal", choices=["object", "frontier"], default="object",
-                    help="object = go to --query (default); frontier = go to the nearest frontier of the explored area")
+    ap.add_argument("--goal", choices=["object", "frontier", "nbv"], default="object",
+                    help="object = go to --query (default); frontier = go to the nearest frontier of the explored area; "
+                         "nbv = go to the next best view (Map.get_next_best_view)")
     ap.add_argument("--render", default=None, metavar="PNG", help="draw the crop, its obstacles, the path, start and goal")
     ap.add_argument("--view", action="store_true", help="go to a cell --query can be seen from (Map.get_viewpoint_pos), not to its contour")
-    ap.add_argument("--view-range", type=float, default=None, metavar="METRES", help="how far from the object a viewpoint may be (default 3.0)")
+    ap.add_argument("--view-range", type=float, default=None, metavar="METRES", help="how far from the object a viewpoint may be, or with --goal nbv how far the robot sees (default 3.0)")
     ap.add_argument("--view-fraction", type=float, default=None, metavar="F",
                     help="a viewpoint sees at least this fraction of what the best cell sees (default 0.5)")
+    ap.add_argument("--nbv-count", type=int, default=None, metavar="K", help="--goal nbv: the views of the greedy tour (default 1)")
+    ap.add_argument("--nbv-conservative", action="store_true", help="--goal nbv: unknown cells block the view")
     ap.add_argument("--room", default=None, metavar="NAME|ID", help="go to the centre of a room (Map.get_rooms): its id, or a name for AVLMap.name_rooms")
     ap.add_argument("--door-width", type=float, default=None, metavar="M", help="--room: openings up to M metres separate rooms (default 0.9)")
     ap.add_argument("--room-names", default=None, help="--room NAME: the comma separated names the rooms are named from (default: NAME alone)")
     args = ap.parse_args(argv)
     if args.room is not None:
-        if (args.query is not None or args.goal == "frontier" or args.relation is not None or args.area or args.sound or args.image
+        if (args.query is not None or args.goal != "object" or args.relation is not None or args.area or args.sound or args.image
                 or args.goal_2d or args.view or args.nearest == "path"):
-            ap.error("--room goes to a room's centre: no --query, --goal frontier, --relation, --area, --sound, --image, --goal-2d, --view or "
+            ap.error("--room goes to a room's centre: no --query, --goal frontier or nbv, --relation, --area, --sound, --image, --goal-2d, --view or "
                      "--nearest path")
         if args.door_width is not None and not (0.0 <= args.door_width < float("inf")):
             ap.error("--door-width is a number of metres >= 0")
@@ -138,13 +153,22 @@ def parse_args(argv=None):
             ap.error("--room-names belongs to --room NAME")
     elif args.door_width is not None or args.room_names is not None:
         ap.error("--door-width and --room-names belong to --room")
-    if args.goal == "frontier":
+    if args.goal in ("frontier", "nbv"):
         if args.query is not None or args.relation is not None or args.area or args.sound or args.image or args.goal_2d or args.nearest == "path":
-            ap.error("--goal frontier takes its goal from the explored map: no --query, --relation, --area, --sound, --image, --goal-2d or --nearest path")
+            ap.error(f"--goal {args.goal} takes its goal from the explored map: no --query, --relation, --area, --sound, --image, --goal-2d or --nearest path")
         args.known_free = True
     elif args.query is None and args.room is None:
         ap.error("--query is required (or --goal frontier, or --room)")
-    if args.view:
+    if args.goal == "nbv":
+        if args.view or args.view_fraction is not None:
+            ap.error("--goal nbv looks for unknown space, not at an object: no --view or --view-fraction")
+        args.view_range = 3.0 if args.view_range is None else args.view_range
+        args.nbv_count = 1 if args.nbv_count is None else args.nbv_count
+        if not (args.view_range > 0.0 and args.view_range < float("inf")) or args.nbv_count < 1:
+            ap.error("--view-range is a positive number of metres, --nbv-count is at least 1")
+    elif args.nbv_count is not None or args.nbv_conservative:
+        ap.error("--nbv-count and --nbv-conservative belong to --goal nbv")
+    elif args.view:
         if args.goal == "frontier" or args.relation is not None or args.area or args.sound or args.image or args.goal_2d:
             ap.error("--view looks at the --query object: no --goal frontier, --relation, --area, --sound, --image or --goal-2d")
         args.view_range = 3.0 if args.view_range is None else args.view_range
@@ -152,7 +176,7 @@ def parse_args(argv=None):
         if not (args.view_range > 0.0 and args.view_range < float("inf")) or not 0.0 <= args.view_fraction <= 1.0:
             ap.error("--view-range is a positive number of metres, --view-fraction lies in [0, 1]")
     elif args.view_range is not None or args.view_fraction is not None:
-        ap.error("--view-range and --view-fraction belong to --view")
+        ap.error("--view-range and --view-fraction belong to --view (--view-range also to --goal nbv)")
     if args.render and args.relation == "face":
         ap.error("--relation face plans no path: nothing to --render")
     if args.nearest == "path" and (args.relation is not None or args.area or args.sound or args.image or args.goal_2d):
@@ -242,10 +266,11 @@ def clamp_cell(cell, rmin, cmin, shape):
             min(max(int(cell[1]), int(cmin)), int(cmin) + int(shape[1]) - 1)]
 
 
-def render_plan(vm, obstacles, start, goal, path, view=None):
+def render_plan(vm, obstacles, start, goal, path, view=None, marks=()):
     """(H, W, 3) uint8: the crop of the top-down colour map, obstacle cells (obstacles == 0) at a third of their brightness, the
-    cells of `view` (a crop-shaped bool, Viewpoints.mask(): where the object can be seen from) half-way to cyan, the path in
-    yellow, the start green, the goal red.  Host drawing on the small image (utils.visualize_utils: integer Bresenham)."""
+    cells of `view` (a crop-shaped bool: Viewpoints.mask(), where the object can be seen from, or the cells a next best view would
+    see) half-way to cyan, the path in yellow, the start green, the goal red, the full-map cells of `marks` (the later views of a
+    tour) orange.  Host drawing on the small image (utils.visualize_utils: integer Bresenham)."""
     import numpy as np
     from avlmaps_amd.utils.visualize_utils import draw_marker, draw_polyline
     r0, c0 = int(vm.rmin), int(vm.cmin)
@@ -258,6 +283,8 @@ def render_plan(vm, obstacles, start, goal, path, view=None):
         img[seen] = ((img[seen].astype(np.uint16) + np.array([0, 255, 255], np.uint16)) // 2).astype(np.uint8)
     local = [(float(p[0]) - r0, float(p[1]) - c0) for p in path]
     draw_polyline(img, local, (255, 255, 0))
+    for m in marks:
+        draw_marker(img, (float(m[0]) - r0, float(m[1]) - c0), (255, 128, 0))
     draw_marker(img, (float(start[0]) - r0, float(start[1]) - c0), (0, 255, 0))
     draw_marker(img, (float(goal[0]) - r0, float(goal[1]) - c0), (255, 0, 0))
     return img
@@ -291,9 +318,9 @@ def main(argv=None):
     if hashed:
         vm.clip_feat_dim = vm.grid_feat.shape[1]
         vm.clip_model = HashClip(vm.clip_feat_dim)
-    elif (args.goal != "frontier" and args.room is None) or args.customize_obstacles:          # a frontier or room goal asks the text tower nothing
+    elif (args.goal == "object" and args.room is None) or args.customize_obstacles:          # a frontier, view or room goal asks the text tower nothing
         vm._init_clip()
-    if args.goal != "frontier" and args.room is None:
+    if args.goal == "object" and args.room is None:
         cats = ([c.strip() for c in args.categories.split(",")] if args.categories
                 else [args.query] + ([args.query_b] if args.query_b else []) + ["other"])
         vm.init_categories(cats)
@@ -328,6 +355,8 @@ def main(argv=None):
         frontiers = vm.get_frontiers()
         if len(frontiers[0]) == 0:
             raise SystemExit("--goal frontier: the explored area has no frontier (of at least 5 cells) left")
+        goal = None
+    elif args.goal == "nbv":
         goal = None
     elif args.view:
         import numpy as np
@@ -365,6 +394,17 @@ def main(argv=None):
             k, path = nav.plan_to_nearest_frontier(start, frontiers)
             goal = [int(frontiers[0][k, 0]), int(frontiers[0][k, 1])]
             extra = {"goal_kind": "frontier", "frontiers": int(len(frontiers[0])), "frontier_cells": int(frontiers[1][k])}
+        elif args.goal == "nbv":
+            try:
+                tour = vm.plan_exploration(start, args.nbv_count, navigator=nav, max_range=args.view_range,
+                                           customized=args.customize_obstacles, opaque_unknown=args.nbv_conservative)
+            except ValueError as e:
+                raise SystemExit(f"--goal nbv: {e}") from None
+            if not tour:
+                raise SystemExit(f"--goal nbv: no reachable cell would see any unknown cell within {args.view_range} m: the map is explored")
+            goal, path = tour[0][0], tour[0][3]
+            extra = {"goal_kind": "nbv", "gain": tour[0][2], "heading_octant": tour[0][1],
+                     "views": [{"goal": [float(v[0][0]), float(v[0][1])], "heading_octant": v[1], "gain": v[2]} for v in tour]}
         elif args.view:
             goal, path = vm.get_viewpoint_pos(start, viewpoints, nav if args.nearest == "path" else None, args.view_fraction)
             if args.nearest != "path":
@@ -383,8 +423,15 @@ def main(argv=None):
     out.update(extra)
     if args.render:
         from PIL import Image
-        view = viewpoints.mask() if args.view else None
-        Image.fromarray(render_plan(vm, obstacles, start, goal, path, view)).save(args.render)
+        view, marks = viewpoints.mask() if args.view else None, ()
+        if args.goal == "nbv":
+            import numpy as np
+            from avlmaps_amd import ops
+            free = np.asarray(vm.get_customized_obstacle_cropped() if args.customize_obstacles else vm.get_obstacle_cropped()) != 0
+            eye = np.array([[int(goal[0]) - int(vm.rmin), int(goal[1]) - int(vm.cmin)]], np.int32)
+            view = ops.viewshed_seen(free, vm.get_explored_cropped(), eye, int(args.view_range / float(vm.cs)), args.nbv_conservative) != 0
+            marks = [v[0] for v in tour[1:]]
+        Image.fromarray(render_plan(vm, obstacles, start, goal, path, view, marks)).save(args.render)
         out["render"] = args.render
     print(json.dumps(out))
     return out

@@ -103,6 +103,67 @@ class Viewpoints:
         return out
 
 
+class ExplorationViews:
+    """Map.get_exploration_views' result: the candidate cells of the next look and what each of them would add.  cells (n, 2) int64
+    full-map (row, col) in raster order; gain (n, 8) int32, the unknown cells that become visible from the cell per 45-degree
+    sector (ops.viewshed_gain); total (n,) int64 = gain.sum(1); heading (n,) int64, the first sector of the pair of neighbouring
+    sectors with the largest sum (ops.best_heading); distance (n, 2) int32, the travel field's pair (straight, diagonal steps)
+    from the robot, (-1, -1) when no position was given; window = (rmin, cmin, H, W), the obstacle crop; radius, the sensor
+    range in cells; field, the ops.TravelField the distances were read from, or None."""
+
+    def __init__(self, cells, gain, distance, window, radius, field=None):
+        from ..ops.viewshed import best_heading
+        self.cells = np.ascontiguousarray(cells, dtype=np.int64).reshape(-1, 2)
+        self.gain = np.ascontiguousarray(gain, dtype=np.int32).reshape(-1, 8)
+        self.distance = np.ascontiguousarray(distance, dtype=np.int32).reshape(-1, 2)
+        if not len(self.cells) == len(self.gain) == len(self.distance):
+            raise ValueError(f"ExplorationViews: {len(self.cells)} cells, {len(self.gain)} gains, {len(self.distance)} distances")
+        self.total = self.gain.astype(np.int64).sum(axis=1)
+        self.heading = best_heading(self.gain, 2)[0]
+        self.window, self.radius, self.field = tuple(int(v) for v in window), int(radius), field
+
+    def __len__(self) -> int:
+        return len(self.cells)
+
+    def select(self, min_fraction: float = 0.5) -> np.ndarray:
+        """indices (in raster order) of the cells with total >= max(1, ceil(min_fraction * max(total))), Viewpoints.select's rule;
+        none when no cell gains anything"""
+        f = float(min_fraction)
+        if not 0.0 <= f <= 1.0:
+            raise ValueError(f"select: min_fraction {min_fraction} outside [0, 1]")
+        if len(self.total) == 0 or int(self.total.max()) <= 0:
+            return np.zeros((0,), np.int64)
+        need = max(1, int(np.ceil(f * int(self.total.max()))))
+        return np.flatnonzero(self.total >= need)
+
+    def best(self):
+        """the index of the cell with the largest total, the first in raster order among equals; None when no cell gains anything"""
+        if len(self.total) == 0 or int(self.total.max()) <= 0:
+            return None
+        return int(np.argmax(self.total))
+
+    def nearest(self, min_fraction: float = 0.5):
+        """the index of the selected cell (select) with the shortest travel distance -- a1 + b1 sqrt(2) < a2 + b2 sqrt(2) decided in
+        integers, as the field does -- the first in raster order among equals; None when no cell gains anything.  Without
+        distances it is the first selected cell."""
+        best = None
+        for i in self.select(min_fraction):
+            pair = (int(self.distance[i, 0]), int(self.distance[i, 1]))
+            if best is None or _pair_less(pair, best[1]):
+                best = (int(i), pair)
+        return None if best is None else best[0]
+
+
+def _pair_less(p, q) -> bool:
+    """a1 + b1 sqrt(2) < a2 + b2 sqrt(2) for integer pairs, without rounding (Python's integers are unbounded)"""
+    da, db = p[0] - q[0], p[1] - q[1]
+    if da <= 0 and db <= 0:
+        return (da, db) != (0, 0)
+    if da >= 0 and db >= 0:
+        return False
+    return da * da > 2 * db * db if da < 0 else da * da < 2 * db * db
+
+
 class Registration:
     """Map.register_frames' result.  corrections (V, 4, 4) float64, V = 1 (joint) or one per frame: to be left-multiplied onto the
     recording's transforms (audit_visibility(corrections=[..., reg.correction])).  transforms (n, 4, 4): the corrected camera -> map
@@ -336,9 +397,13 @@ class Map:
         unknown 4-neighbour (ops.frontier_mask) -- grouped into 8-connected islands (ops.label_islands) of at least min_cells cells,
         largest first (equal sizes in raster order of their first cell).  A centre is the island's own cell nearest to its centroid
         (the first in raster order among equals), in full-map (row, col): a frontier cell, so a planner can end on it."""
-        from .. import ops
         explored = self._explored_crop()
         free = np.asarray(self.get_obstacle_cropped()) != 0
+        return self._frontiers_of(free, explored, min_cells)
+
+    def _frontiers_of(self, free, explored, min_cells: int = 5):
+        """get_frontiers on a free map and an explored map of the obstacle crop's shape (host or device masks)"""
+        from .. import ops
         mask = ops.frontier_mask(free, explored, device=True)
         with ops.label_islands(mask) as isl:
             labels, areas = np.asarray(isl.labels), isl.table[:, 0].astype(np.int64)
@@ -349,6 +414,134 @@ class Map:
             d2 = np.sum((cells - cells.mean(axis=0)) ** 2, axis=1)
             centres[i] = cells[int(np.argmin(d2))] + (int(self.rmin), int(self.cmin))
         return centres, (areas[keep] if keep else np.zeros((0,), np.int64))
+
+    # ------------------------------------------------------------------------ next-best-view goals (csrc/avl_viewshed.hip)
+    # get_frontiers ranks the edge of the explored area by size and plan_to_nearest_frontier walks to its closest cell; neither
+    # knows how much unknown space the robot would SEE from a cell.  The viewshed does: per candidate cell the unknown cells of
+    # the obstacle crop with a free 2-D sight line within sensor range.  One height band (the explored map's own), cell centres,
+    # no field of view other than sums of 45-degree sectors; optimistic by default (unknown cells do not block).  Upstream has
+    # no counterpart.  DESIGN.md 4.28.
+    def _view_radius(self, max_range: float) -> int:
+        from .. import ops
+        max_range = float(max_range)
+        if not (np.isfinite(max_range) and max_range > 0.0):
+            raise ValueError(f"max_range {max_range} (metres; finite and > 0)")
+        radius = int(max_range / float(self.cs))
+        if radius < 1:
+            raise ValueError(f"max_range {max_range} m is less than one cell of {self.cs} m")
+        if radius > ops.VIEWSHED_MAX_RADIUS:
+            raise ValueError(f"max_range {max_range} m is {radius} cells: the viewshed reaches {ops.VIEWSHED_MAX_RADIUS} cells, "
+                             f"{ops.VIEWSHED_MAX_RADIUS * float(self.cs):g} m on this map")
+        return radius
+
+    def _view_free(self, customized: bool = False) -> np.ndarray:
+        if self.obstacles_cropped is None:
+            self.generate_obstacle_map()
+        base = self.get_customized_obstacle_cropped() if customized else self.get_obstacle_cropped()
+        if base is None:
+            raise ValueError("get_exploration_views: no customised obstacle map (call customize_obstacle_map first)")
+        return np.asarray(base) != 0
+
+    def _exploration_views(self, free, explored, curr_pos, radius: int, stride: int, opaque_unknown: bool) -> "ExplorationViews":
+        """get_exploration_views on a free map and an explored map (host bool arrays over the obstacle crop)"""
+        from .. import ops
+        stride = int(stride)
+        if stride < 1:
+            raise ValueError(f"get_exploration_views: stride {stride} < 1")
+        rmin, cmin = int(self.rmin), int(self.cmin)
+        window = (rmin, cmin, free.shape[0], free.shape[1])
+        known = free & explored
+        cand = np.zeros(free.shape, dtype=bool)
+        cand[::stride, ::stride] = known[::stride, ::stride]
+        centres = self._frontiers_of(free, explored)[0]
+        cand[centres[:, 0] - rmin, centres[:, 1] - cmin] = True
+        field, planes = None, None
+        if curr_pos is not None:
+            cell = np.asarray(curr_pos, dtype=np.float64).reshape(2).astype(np.int64) - (rmin, cmin)
+            if not (0 <= cell[0] < free.shape[0] and 0 <= cell[1] < free.shape[1]):
+                raise ValueError(f"get_exploration_views: {list(curr_pos)} lies outside the obstacle crop [{self.rmin}:{self.rmax + 1}, "
+                                 f"{self.cmin}:{self.cmax + 1}]")
+            field = ops.travel_field(known, cell.reshape(1, 2))
+            planes = field.planes()
+            cand &= planes[0] >= 0
+        local = np.argwhere(cand)                                           # raster order
+        if planes is None:
+            distance = np.full((len(local), 2), -1, np.int32)
+        else:
+            distance = np.stack([planes[0][local[:, 0], local[:, 1]], planes[1][local[:, 0], local[:, 1]]], axis=1)
+        gain = ops.viewshed_gain(free, explored, local.astype(np.int32), radius, opaque_unknown)
+        return ExplorationViews(local + (rmin, cmin), gain, distance, window, radius, field)
+
+    def get_exploration_views(self, curr_pos=None, max_range: float = 3.0, stride: int = 4, customized: bool = False,
+                              opaque_unknown: bool = False) -> "ExplorationViews":
+        """Which cells are worth going to?  The candidates are the known-free cells of the obstacle crop (get_known_free_cropped;
+        customized: of the customised crop) whose crop row and column are multiples of `stride`, plus the centres of
+        get_frontiers(), in raster order; with curr_pos (full-map (row, col), inside the crop) only those the robot can reach --
+        one travel field from its cell over the known-free map (get_travel_field([curr_pos], known_free=True)), whose pairs are
+        kept as the travel distance.  One ops.viewshed_gain call over the crop tells for each how many unknown cells within
+        radius = int(max_range / cs) cells it would see; a max_range of less than one cell or of more than
+        ops.VIEWSHED_MAX_RADIUS cells raises ValueError.  opaque_unknown: unknown cells block the view (the conservative
+        variant).  -> ExplorationViews."""
+        radius = self._view_radius(max_range)
+        free = self._view_free(customized)
+        return self._exploration_views(free, self._explored_crop(), curr_pos, radius, stride, bool(opaque_unknown))
+
+    def _view_path(self, views: "ExplorationViews", k: int, curr_pos, navigator):
+        """the path from curr_pos to candidate k: the navigator's, or the travel field's own walk in full-map cells"""
+        pos = [int(views.cells[k, 0]), int(views.cells[k, 1])]
+        if navigator is not None:
+            return pos, navigator.plan_to_next_best_view(curr_pos, views, among=[k])[1]
+        if views.field is None:
+            return pos, [curr_pos, pos]
+        r0, c0 = views.window[:2]
+        walk = views.field.descend((pos[0] - r0, pos[1] - c0))
+        return pos, [[r + r0, c + c0] for r, c in reversed(walk)]
+
+    def get_next_best_view(self, curr_pos: List[float], navigator=None, min_fraction: float = 0.5, **kw):
+        """-> (pos, heading_octant, gain, path): among the candidates of get_exploration_views(curr_pos, **kw) that gain at least
+        max(1, ceil(min_fraction * the best cell's gain)) unknown cells (ExplorationViews.select) the one with the shortest travel
+        distance from curr_pos (the field's exact comparison of pairs, the first in raster order among equals), the first of its
+        best two neighbouring sectors, its gain, and the path to it: Navigator.plan_to_next_best_view's with a navigator, else the
+        cells of the travel field's shortest walk.  (curr_pos, None, 0, [curr_pos]) when no reachable candidate gains anything:
+        the map is fully explored."""
+        views = self.get_exploration_views(curr_pos, **kw)
+        k = views.nearest(min_fraction)
+        if k is None:
+            return curr_pos, None, 0, [curr_pos]
+        pos, path = self._view_path(views, k, curr_pos, navigator)
+        return pos, int(views.heading[k]), int(views.total[k]), path
+
+    def plan_exploration(self, curr_pos: List[float], k: int = 5, navigator=None, min_fraction: float = 0.5, max_range: float = 3.0,
+                         stride: int = 4, customized: bool = False, opaque_unknown: bool = False):
+        """A greedy tour of at most k views -> [(pos, heading_octant, gain, path), ...]: take the next best view
+        (get_next_best_view's choice), OR what it sees (ops.viewshed_seen) into a device copy of the explored crop, and choose
+        again from there -- candidates, frontier centres, travel field and gains all on the map as it would then be known -- until
+        k views are chosen or no candidate gains anything.  Every gain is the one at the time of choice.  A navigator plans the
+        first leg only (its graph is of the map as it is known now); the later legs are the travel field's walks over the map as it
+        would be known by then.  self.first_seen and the file on disk are not modified."""
+        from .. import ops
+        from ..device import DeviceArray
+        if int(k) < 0:
+            raise ValueError(f"plan_exploration: k {k} < 0")
+        radius = self._view_radius(max_range)
+        free = self._view_free(customized)
+        explored = DeviceArray.from_numpy(np.ascontiguousarray(self._explored_crop()).view(np.uint8))
+        rmin, cmin = int(self.rmin), int(self.cmin)
+        tour, pos = [], curr_pos
+        try:
+            for _ in range(int(k)):
+                views = self._exploration_views(free, explored.numpy() != 0, pos, radius, stride, bool(opaque_unknown))
+                i = views.nearest(min_fraction)
+                if i is None:
+                    break
+                cell, path = self._view_path(views, i, pos, navigator if not tour else None)
+                tour.append((cell, int(views.heading[i]), int(views.total[i]), path))
+                eye = np.array([[cell[0] - rmin, cell[1] - cmin]], np.int32)
+                ops.viewshed_seen(free, explored, eye, radius, bool(opaque_unknown), out=explored, device=True)
+                pos = cell
+        finally:
+            explored.free()
+        return tour
 
     # ------------------------------------------------------------------------ stale voxels (csrc/avl_audit.hip)
     # The builder only adds voxels: what a later visit saw through stays in the map.  The audit walks the sight rays of the frames

@@ -75,6 +75,17 @@ class Navigator:
         k, path = self.plan_to_nearest(start_full_map, np.asarray(viewpoints.cells, dtype=np.float64)[keep])
         return int(keep[k]), path
 
+    def plan_to_next_best_view(self, start_full_map: Tuple[float, float], views, min_fraction: float = 0.5, among=None):
+        """-> (index, path): plan_to_nearest over the cells of a Map.get_exploration_views result that gain at least
+        max(1, ceil(min_fraction * the best cell's gain)) unknown cells (ExplorationViews.select), or over the rows `among` of its
+        cells; index is the chosen cell's row in views.cells.  ValueError when no cell gains anything, NoPathError when none can
+        be reached."""
+        keep = views.select(min_fraction) if among is None else np.asarray(among, dtype=np.int64).reshape(-1)
+        if len(keep) == 0:
+            raise ValueError("plan_to_next_best_view: no candidate cell gains anything")
+        k, path = self.plan_to_nearest(start_full_map, np.asarray(views.cells, dtype=np.float64)[keep])
+        return int(keep[k]), path
+
     def _goals_to_cropped(self, goals_full_map) -> np.ndarray:
         goals = np.asarray(goals_full_map, dtype=np.float64).reshape(-1, 2)
         return goals - np.array([self.rowmin, self.colmin], np.float64)

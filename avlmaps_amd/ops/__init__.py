@@ -85,6 +85,9 @@ from .rooms import (  # noqa: F401
     DOOR_TABLE_COLS, grow_labels, LabelGrowth, lift_labels_2d, ROOM_TABLE_COLS, room_seeds, room_tables, ROOMS_MAX,
     RoomSegmentation, _seed_image, segment_rooms,
 )
+from .viewshed import (  # noqa: F401
+    best_heading, octant_of, viewshed_gain, VIEWSHED_MAX_RADIUS, viewshed_seen,
+)
 # the shared marshalling layer; its one device predicate keeps both of the names it had here
 from ._args import (  # noqa: F401
     _dev_u8, _image_any, _image_shape, _image_u8, _is_dev, _is_dev as _on_device, _result,

@@ -1418,6 +1418,28 @@ AVL_API int avl_room_door_table(const void* ws, size_t ws_bytes, int32_t K, int 
 AVL_API int avl_lift_labels_2d(const int32_t* d_labels, int H, int W, const int32_t* d_grid_pos, int64_t N, int rmin, int cmin,
                                int32_t* d_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * (27) 2-D viewsheds on the explored map: the unknown cells a candidate cell would see, per 45-degree sector, and the cells a set
+ *     of eyes sees (csrc/avl_viewshed.hip).  d_free_u8, d_explored_u8: (H, W) uint8 masks as in avl_frontier_mask;
+ *     a cell is opaque when free == 0 and unknown when free != 0 and explored == 0; opaque cells block, with opaque_unknown != 0
+ *     unknown cells block as well.  d_eyes: (E, 2) int32 (row, col).  Target t is visible from eye e when both lie inside the
+ *     image, t != e, dr^2 + dc^2 <= radius^2 (equality counts) and no cell strictly between them on the sight line e -> t -- the
+ *     walk of (21) without the height axis, rows before columns, not symmetric -- is blocking.  The eye's own cell never blocks,
+ *     the target cell is never tested, and an eye may stand on any cell.  Sides 1 .. 16384, 1 <= radius <= 127 cells,
+ *     0 <= E < 2^31.  Both calls are asynchronous on `stream`, check their arguments before any device work and allocate nothing;
+ *     every result is an integer and does not depend on the launch geometry.  Upstream has no counterpart.
+ * ------------------------------------------------------------------------------------------------ */
+/* d_gain (E, 8) int32: per eye and sector k = [k * 45, (k + 1) * 45) degrees of atan2(dr, dc) the number of visible targets that
+ * are unknown; a row of -1 for an eye outside the image.  The sector in integers: if dc > 0 and dr >= 0 it is 0 when dr < dc, else
+ * 1; otherwise replace (dr, dc) by (-dc, dr), add 2 and repeat.  E = 0 does nothing and touches no pointer. */
+AVL_API int avl_viewshed_gain(const uint8_t* d_free_u8, const uint8_t* d_explored_u8, int H, int W, const int32_t* d_eyes, int64_t E,
+                              int radius, int opaque_unknown, int32_t* d_gain, void* stream);
+/* d_seen (H, W) uint8: 1 on every cell, of any class, that is visible from at least one of the M eyes and on the eyes' own cells;
+ * eyes outside the image contribute nothing.  accumulate == 0: the mask is zeroed first (also with M = 0); accumulate != 0: the
+ * ones are OR-ed into what d_seen holds. */
+AVL_API int avl_viewshed_seen(const uint8_t* d_free_u8, const uint8_t* d_explored_u8, int H, int W, const int32_t* d_eyes, int64_t M,
+                              int radius, int opaque_unknown, int accumulate, uint8_t* d_seen, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
