@@ -164,12 +164,15 @@ constexpr int kTileRows = (kSplitThreads / 64) * 32;  // voxels per workgroup it
 // image layout: [nkc][2 (hi, lo)][Qtot][KC + pad] fp16, Qtot = Q rounded up to 32
 __global__ __launch_bounds__(256) void sim_prep_queries_kernel(const float* __restrict__ q, int Q, int D, int64_t ldq,
                                                                float* __restrict__ inv_scale, _Float16* __restrict__ img,
-                                                               int Qtot, int KC, int nkc, int interleaved) {
+                                                               int Qtot, int KC, int nkc, int interleaved,
+                                                               const int32_t* __restrict__ qmap) {
+    // qmap (column-block launches, nullable): image row r is the caller's query row qmap[r]; q already points at the window's
+    // first column
     __shared__ float red[4];
     __shared__ float scale_s;
     const int qg = blockIdx.x;
     const bool live = qg < Q;
-    const float* row = q + (int64_t)qg * ldq;
+    const float* row = q + (int64_t)(live && qmap ? qmap[qg] : qg) * ldq;
     float m = 0.f;
     if (live)
         for (int d = threadIdx.x; d < D; d += blockDim.x) m = fmaxf(m, fabsf(row[d]));
@@ -252,9 +255,11 @@ __device__ __forceinline__ void split8(const f32x4 v0, const f32x4 v1, half8& hi
 // would need the row maximum before the first product), so a row is only as accurate as float32 when its largest |element|
 // lies in [kGuardLo, kGuardHi): below, the elements sink into the fp16 subnormal range (a voxel touched once from 4 m away
 // stores feat * exp(-r^2/1.2) ~ 1e-6, vlmap_builder.py:166-168) and above fp16 saturates.  Every lane tracks the maximum of
-// the 32 floats it loads per k step (v_max3_f32 with |.| modifiers: 16 VALU ops per step); the epilogue publishes one 32-bit
-// word per (wave, tile) with a bit per out-of-range / non-finite row, and sim_fixup_rows_kernel recomputes exactly those rows
-// in float32 (np.argmax semantics for NaN).  Prepared maps carry a per-row power-of-two scale instead (avl_sim_prepare_map).
+// the 32 floats it loads per k step (v_max3_f32 with |.| modifiers: 16 VALU ops per step); the epilogue forms one 32-bit
+// word per (wave, tile) with a bit per out-of-range / non-finite row, and exactly those rows are recomputed in float32
+// (fixup_row, np.argmax semantics for NaN): by the same wave, right there, when the launch is the whole call; by
+// sim_fixup_rows_kernel from the published words when the call has several launches, whose words are OR-ed together.
+// Prepared maps carry a per-row power-of-two scale instead (avl_sim_prepare_map).
 constexpr float kGuardLo = 0x1p-7f, kGuardHi = 0x1p15f;
 
 __device__ __forceinline__ void guard_max8(float& m, const f32x4 v0, const f32x4 v1) {
@@ -271,17 +276,56 @@ __device__ __forceinline__ void guard_max8(float& m, const f32x4 v0, const f32x4
 #endif
 }
 
+// One row the range guard flagged, recomputed in float32 on the vector ALU by one whole wave (all 64 lanes call it with the same
+// `row`): every score, and the row argmax with np.argmax semantics (first NaN wins, else first maximum).  Shared by
+// sim_fixup_rows_kernel and by the split kernels' epilogue (one-launch calls), so that a flagged row gets the same bits from either.
+__device__ __forceinline__ void fixup_row(const float* __restrict__ feat, int D, int64_t ld, const float* __restrict__ q, int Q,
+                                          int64_t ldq, int64_t row, int lane, float* __restrict__ scores,
+                                          int32_t* __restrict__ argmax, float* __restrict__ best) {
+    const float* a = feat + row * ld;
+    float bv = -INFINITY;
+    int bi = 0;
+    bool have = false, nan_seen = false;
+    for (int qi = 0; qi < Q; ++qi) {
+        const float* qr = q + (int64_t)qi * ldq;
+        float sum = 0.f;
+        for (int d = lane; d < D; d += 64) sum = fmaf(a[d], qr[d], sum);
+        for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
+        if (lane == 0 && scores) scores[row * (int64_t)Q + qi] = sum;
+        if (!nan_seen) {
+            if (sum != sum) { nan_seen = true; bv = sum; bi = qi; }
+            else if (!have || sum > bv) { bv = sum; bi = qi; have = true; }
+        }
+    }
+    if (lane == 0) {
+        if (argmax) argmax[row] = bi;
+        if (best) best[row] = bv;
+    }
+}
+
+// what a one-launch call's epilogue needs to recompute its flagged rows itself (the arguments of sim_fixup_rows_kernel)
+struct FixupArgs {
+    const float* feat;
+    int D;
+    int64_t ld;
+    const float* q;
+    int64_t ldq;
+};
+
 // epilogue shared by the split-fp16 kernels: this lane holds voxel `row`, queries q_base + t*32 + 8g + 4kg + e (g<4, e<4) in
 // acc[t][a][4g+e]; the NA partial accumulators are summed, scaled back by the per-query 2^-S, optionally stored, and reduced
 // to the row's first maximum (one cross-half shuffle); later query chunks chain through `best`
 // XR: the chunk's last 1..4 query rows (local rows 32 QT ..) were contracted by v_mfma_f32_4x4x4_16b_f16 instead of a mostly
 // padded 32-row tile: xacc[r] = this lane's HALF (its 32 of the step's 64 columns) of voxel `row` . extra query r
-template <int QT, int NA, bool XR = false>
+// INL (raw map, image built in the kernel, no column blocks): with flags == nullptr the launch is the whole call, and the wave
+// recomputes the rows its guard flags itself (fixup_row) instead of publishing guard words for sim_fixup_rows_kernel
+template <int QT, int NA, bool XR = false, bool INL = false>
 __device__ __forceinline__ void split_epilogue(const f32x16 (&acc)[QT][NA], const float* isc, int q_base, int rows, int Q,
                                                float* __restrict__ scores, int32_t* __restrict__ argmax,
                                                float* __restrict__ best, int64_t row, int64_t N, int kg, int first_chunk,
                                                float rscale = 1.f, uint32_t* __restrict__ flags = nullptr, float rmax = 1.f,
-                                               const int32_t* qml = nullptr, f32x4 xacc = f32x4{0.f, 0.f, 0.f, 0.f}) {
+                                               const int32_t* qml = nullptr, f32x4 xacc = f32x4{0.f, 0.f, 0.f, 0.f},
+                                               const FixupArgs& fx = FixupArgs{}) {
     // qml (column-block launches, avl_sim_scores_blocks): this launch's query rows are a gathered subset of the caller's;
     // qml[row of this chunk] = the caller's query index, ascending, so "first maximum" inside the launch is unchanged and only
     // the published index / score column and the tie-break against earlier launches use the caller's numbering.  The table
@@ -349,7 +393,7 @@ __device__ __forceinline__ void split_epilogue(const f32x16 (&acc)[QT][NA], cons
                 if (32 * QT + r < rows) sr[qml ? qml[32 * QT + r] : q_base + 32 * QT + r] = xv[r];
         }
     }
-    if (argmax || best || flags) {
+    if (argmax || best || flags || INL) {
         if (qml && bi != INT_MAX) bi = qml[bi - q_base];
         const float ov = __shfl_xor(bv, 32, 64);
         const int oi = __shfl_xor(bi, 32, 64);
@@ -365,16 +409,20 @@ __device__ __forceinline__ void split_epilogue(const f32x16 (&acc)[QT][NA], cons
                     bi = qml ? qml[32 * QT + r] : q_base + 32 * QT + r;
                 }
         }
-        if (flags) {
+        unsigned long long mask = 0ull;
+        if (flags || INL) {
             // one word per 32-row unit: bit j = row j of the unit must be recomputed in float32 (largest |element| outside
             // the range the unscaled fp16 split resolves, non-finite, or no score compared greater than -inf: NaN)
             const float m = fmaxf(rmax, __shfl_xor(rmax, 32, 64));
             const bool bad = row < N && (!(m == 0.f || (m >= kGuardLo && m < kGuardHi)) || bi == INT_MAX);
-            const unsigned long long mask = __ballot(bad);
-            const int64_t row0 = __shfl(row, 0, 64);
-            if ((threadIdx.x & 63) == 0 && row0 < N) {   // later launches of one call (other query chunks / column blocks) OR in
-                const uint32_t w = (uint32_t)(mask | (mask >> 32));
-                flags[row0 >> 5] = first_chunk ? w : (flags[row0 >> 5] | w);
+            mask = __ballot(bad);
+            if (flags) {
+                const int64_t row0 = __shfl(row, 0, 64);
+                if ((threadIdx.x & 63) == 0 && row0 < N) {   // later launches of one call (other query chunks / column blocks) OR in
+                    const uint32_t w = (uint32_t)(mask | (mask >> 32));
+                    flags[row0 >> 5] = first_chunk ? w : (flags[row0 >> 5] | w);
+                }
+                mask = 0ull;
             }
         }
         if ((argmax || best) && kg == 0 && row < N) {
@@ -389,6 +437,21 @@ __device__ __forceinline__ void split_epilogue(const f32x16 (&acc)[QT][NA], cons
             }
             if (argmax) argmax[row] = bi;
             if (best) best[row] = bv;
+        }
+        if constexpr (INL) {
+            // cold and wave-uniform (no bit is ever set on LSeg-scale rows): lanes b and b + 32 hold row b of the wave's unit.  The
+            // fence orders this wave's stores above before the recomputed ones, which are what must land in memory.
+            uint32_t word = (uint32_t)(mask | (mask >> 32));
+            if (word) {
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
+                int lane = threadIdx.x & 63;
+                asm volatile("" : "+v"(lane));   // opaque: per-lane addresses of the cold path are not hoisted out of the tile loop
+                while (word) {
+                    const int b = __ffs((int)word) - 1;
+                    word &= word - 1;
+                    fixup_row(fx.feat, fx.D, fx.ld, fx.q, Q, fx.ldq, __shfl(row, b, 64), lane, scores, argmax, best);
+                }
+            }
         }
     }
 }
@@ -490,10 +553,10 @@ __global__ __launch_bounds__(256) void sim_prepare_map24_kernel(const float* __r
     }
 }
 
-// Recompute the rows the range guard flagged (one bit per row, one word per 32 rows) in float32 on the vector ALU, wave per
-// row: every score, and the row argmax with np.argmax semantics (first NaN wins, else first maximum).  Flagged rows are rare
-// on in-range maps (none at all on LSeg-scale rows), so this is a ~3 us scan of N/32 words; on a map full of tiny rows it is
-// the slow-but-correct path and the prepared map (per-row scale) is the fast one.
+// Calls of several launches (query chunks, K chunks, K-swap, streamed, column blocks): recompute the rows the range guard
+// flagged (one bit per row, one word per 32 rows) in float32 on the vector ALU, wave per row (fixup_row).  Flagged rows are rare
+// on in-range maps (none at all on LSeg-scale rows), so this is a 4-5 us scan of N/32 words; on a map full of tiny rows it is
+// the slow-but-correct path and the prepared map (per-row scale) is the fast one.  One-launch calls do not come here.
 __global__ __launch_bounds__(256) void sim_fixup_rows_kernel(const float* __restrict__ feat, int64_t N, int D, int64_t ld,
                                                              const float* __restrict__ q, int Q, int64_t ldq,
                                                              const uint32_t* __restrict__ flags, float* __restrict__ scores,
@@ -514,39 +577,10 @@ __global__ __launch_bounds__(256) void sim_fixup_rows_kernel(const float* __rest
                 word &= word - 1;
                 const int64_t row = (base + l) * 32 + b;
                 if (row >= N) continue;
-                const float* a = feat + row * ld;
-                float bv = -INFINITY;
-                int bi = 0;
-                bool have = false, nan_seen = false;
-                for (int qi = 0; qi < Q; ++qi) {
-                    const float* qr = q + (int64_t)qi * ldq;
-                    float sum = 0.f;
-                    for (int d = lane; d < D; d += 64) sum = fmaf(a[d], qr[d], sum);
-                    for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
-                    if (lane == 0 && scores) scores[row * (int64_t)Q + qi] = sum;
-                    if (!nan_seen) {
-                        if (sum != sum) { nan_seen = true; bv = sum; bi = qi; }
-                        else if (!have || sum > bv) { bv = sum; bi = qi; have = true; }
-                    }
-                }
-                if (lane == 0) {
-                    if (argmax) argmax[row] = bi;
-                    if (best) best[row] = bv;
-                }
+                fixup_row(feat, D, ld, q, Q, ldq, row, lane, scores, argmax, best);
             }
         }
     }
-}
-
-// column-block launches: out[r, 0:cols] = q[rows[r], col0 : col0 + cols]  (the gathered query rows of one support group)
-__global__ __launch_bounds__(256) void sim_gather_queries_kernel(const float* __restrict__ q, int64_t ldq, const int32_t* __restrict__ rows,
-                                                                 int nrows, int col0, int cols, float* __restrict__ out) {
-    const int r = blockIdx.x;
-    if (r >= nrows) return;
-    const int32_t sr = rows[r];                 // -1: a zero row
-    const float* src = q + (int64_t)(sr < 0 ? 0 : sr) * ldq + col0;
-    float* dst = out + (int64_t)r * cols;
-    for (int c = threadIdx.x; c < cols; c += blockDim.x) dst[c] = sr < 0 ? 0.f : src[c];
 }
 
 // QT = number of 32-query MFMA tiles of this chunk (1..3); `rows` = valid query rows of the chunk (<= 32*QT):
@@ -676,7 +710,9 @@ __global__ __launch_bounds__(kSplitThreads) void sim_split_f16_kernel(
 #pragma unroll
             for (int b = 0; b < RB; ++b) {
                 const int r = r0 + NW * b;
-                const float* qr = q_raw + (int64_t)(q_base + (r < rows ? r : rows - 1)) * ldq;
+                // QM: the caller's own matrix through the query map (q_raw points at the window's first column): no gathered copy
+                const int qrow = q_base + (r < rows ? r : rows - 1);
+                const float* qr = q_raw + (int64_t)(QM ? qmap[qrow] : qrow) * ldq;
 #pragma unroll
                 for (int t = 0; t < 8; ++t) v[b][t] = (lane + 64 * t < D) ? qr[lane + 64 * t] : 0.f;
             }
@@ -927,8 +963,11 @@ __global__ __launch_bounds__(kSplitThreads) void sim_split_f16_kernel(
             if (row_scale) rscale = row_scale[rowc];
         }
         // QM (column-block launches) is a template parameter so that the dense kernels keep their register budget
-        split_epilogue<QT, NA, XR>(acc, isc, q_base, rows, Q, scores, argmax, best, row, N, kg, first_chunk, rscale, PRE ? nullptr : flags, rmax,
-                                   QM ? qml : nullptr, xacc0 + xacc1);
+        // one-launch calls (raw map, the whole query set resident, no column blocks) pass flags == nullptr: the epilogue recomputes
+        // the rows its guard flags from the caller's own map and queries (q_base == 0, rows == Q, feat = the map's first column)
+        constexpr bool INL = !PRE && FQ && !QM;
+        split_epilogue<QT, NA, XR, INL>(acc, isc, q_base, rows, Q, scores, argmax, best, row, N, kg, first_chunk, rscale, PRE ? nullptr : flags,
+                                        rmax, QM ? qml : nullptr, xacc0 + xacc1, FixupArgs{feat, D, ld, q_raw, ldq});
     }
 }
 
@@ -1957,9 +1996,11 @@ static int run_fixup(const float* d_feat, int64_t N, int D, int64_t ld, const fl
     return AVL_OK;
 }
 
-// One column block of a similarity call: Qg gathered query rows x the map columns [feat, feat + D) (the whole call when
+// One column block of a similarity call: Qg query rows (picked by qmap) x the map columns [feat, feat + D) (the whole call when
 // qmap == nullptr).  PRE: d_row_scale = per-row 2^-s of the prepared map (nullable).  !PRE: d_flags = (N + 31) / 32 range-guard
 // words, written by the first launch of the call and OR-ed into by the others; the caller runs sim_fixup_rows_kernel at the end.
+// d_flags == nullptr (one resident launch, the whole call): the launch recomputes its flagged rows itself.
+// Column blocks: d_q = the caller's matrix at the window's first column, ldq its row stride; the kernels go through d_qmap.
 // Qs = row stride of d_scores (the caller's Q); qmap[local row] = the caller's query index (ascending), nullptr = identity.
 template <bool PRE>
 static int run_split(const float* d_feat, int64_t N, int D, int64_t ld, const float* d_q, int Qg, int64_t ldq, int Qs,
@@ -1972,7 +2013,7 @@ static int run_split(const float* d_feat, int64_t N, int D, int64_t ld, const fl
     const bool fq = split_plan_is_fused(p, D);   // resident image built inside the kernel: no prep launch, no workspace
     if (!fq)
         hipLaunchKernelGGL(sim_prep_queries_kernel, dim3(p.Qtot), dim3(256), 0, st, d_q, Qg, D, ldq, inv_scale, img, p.Qtot, p.KC,
-                           p.nkc, p.stream ? 1 : 0);
+                           p.nkc, p.stream ? 1 : 0, d_qmap);
     const int64_t ntiles = (N + kTileRows - 1) / kTileRows;
     int64_t blocks = ntiles < num_cus() ? ntiles : num_cus();
     if (blocks < 1) blocks = 1;
@@ -2097,8 +2138,9 @@ int avl_sim_workspace_bytes_n(int64_t N, int D, int Q, size_t* h_bytes) {
 }
 
 // Workspace layout of the matrix-core paths (every part aligned to kHdrAlign):
-//   [query image of the widest plan][range-guard words (raw split path)][gathered queries Q x D f32][query map Q x i32]
-// the last two only for column-block calls.
+//   [query image of the widest plan][range-guard words (raw calls of several launches)][query map Q x i32 (column-block calls)]
+// avl_sim_workspace_bytes_n still reports the figure of the earlier layout (guard words for every raw call, a gathered Q x D copy
+// of the queries for column-block calls): an upper bound, so that a caller's buffer serves every call.
 static size_t blocks_bytes(int D, int Q) { return align_up((size_t)Q * D * sizeof(float), kHdrAlign) + align_up((size_t)Q * sizeof(int32_t), kHdrAlign); }
 
 struct ColGroup {
@@ -2210,8 +2252,12 @@ static int sim_scores_impl(const float* d_feat, const float* d_row_scale, int64_
             img_bytes = p.ws_bytes;
         }
         img_bytes = img_bytes ? align_up(img_bytes, kHdrAlign) : 0;
-        const size_t flag_bytes = (use_split && !prepared) ? guard_bytes(N) : 0;
-        const size_t blk_bytes = blocks ? blocks_bytes(D, Q) : 0;
+        // a raw-map call that is ONE resident launch recomputes the rows its range guard flags in that launch's epilogue: no guard
+        // words, no sim_fixup_rows_kernel.  Calls of several launches (query chunks, K chunks, K-swap, streamed, column blocks)
+        // OR their guard words together and end in the fix-up kernel.
+        const bool one_launch = use_split && !prepared && !blocks && split_plan_is_fused(p, D) && p.nchunks == 1;
+        const size_t flag_bytes = (use_split && !prepared && !one_launch) ? guard_bytes(N) : 0;
+        const size_t blk_bytes = blocks ? align_up((size_t)Q * sizeof(int32_t), kHdrAlign) : 0;   // the query map
         const size_t need = img_bytes + flag_bytes + blk_bytes;
         char* ws = static_cast<char*>(d_workspace);
         void* tmp_ws = nullptr;
@@ -2228,32 +2274,29 @@ static int sim_scores_impl(const float* d_feat, const float* d_row_scale, int64_
                           : run_split<false>(d_feat, N, D, ld_feat, d_queries, Q, ld_q, Q, d_scores, amax, best, p, ws, nullptr, flags,
                                              nullptr, true, st);
         } else {
-            float* qg = reinterpret_cast<float*>(ws + img_bytes + flag_bytes);
-            int32_t* qmap = reinterpret_cast<int32_t*>(ws + img_bytes + flag_bytes + align_up((size_t)Q * D * sizeof(float), kHdrAlign));
+            int32_t* qmap = reinterpret_cast<int32_t*>(ws + img_bytes + flag_bytes);
             std::vector<int32_t> h_map;
             h_map.reserve((size_t)Q);
             for (const ColGroup& g : groups) h_map.insert(h_map.end(), g.rows.begin(), g.rows.end());
             AVL_HIP_CHECK(hipMemcpyAsync(qmap, h_map.data(), (size_t)Q * sizeof(int32_t), hipMemcpyHostToDevice, st));   // pageable: staged
-            size_t row_off = 0, qg_off = 0;
+            size_t row_off = 0;
             for (size_t g = 0; g < groups.size() && rc == AVL_OK; ++g) {
                 const ColGroup& cg = groups[g];
                 const int Qg = (int)cg.rows.size();
-                float* qg_g = qg + qg_off;
                 const int32_t* qmap_g = qmap + row_off;
-                hipLaunchKernelGGL(sim_gather_queries_kernel, dim3((unsigned)Qg), dim3(256), 0, st, d_queries, ld_q, qmap_g, Qg, cg.col0,
-                                   cg.cols, qg_g);
                 // the column window of every row: a pointer offset of 4 B per column; a compact map has two planes per row and its window
-                // travels as col0 (windows are 128-aligned: whole residual lines)
+                // travels as col0 (windows are 128-aligned: whole residual lines).  The queries are read in place, through the query map
+                // and the same window of the caller's matrix (no gathered copy)
                 const float* feat_g = p24 ? d_feat : d_feat + cg.col0;
-                rc = prepared ? run_split<true>(feat_g, N, cg.cols, ld_feat, qg_g, Qg, cg.cols, Q, d_scores, amax, best, gplans[g], ws,
+                const float* q_g = d_queries + cg.col0;
+                rc = prepared ? run_split<true>(feat_g, N, cg.cols, ld_feat, q_g, Qg, ld_q, Q, d_scores, amax, best, gplans[g], ws,
                                                 d_row_scale, nullptr, qmap_g, g == 0, st, p24, p24 ? cg.col0 : 0)
-                              : run_split<false>(feat_g, N, cg.cols, ld_feat, qg_g, Qg, cg.cols, Q, d_scores, amax, best, gplans[g], ws, nullptr,
+                              : run_split<false>(feat_g, N, cg.cols, ld_feat, q_g, Qg, ld_q, Q, d_scores, amax, best, gplans[g], ws, nullptr,
                                                  flags, qmap_g, g == 0, st);
                 row_off += (size_t)Qg;
-                qg_off += (size_t)Qg * cg.cols;
             }
         }
-        if (rc == AVL_OK && use_split && !prepared)
+        if (rc == AVL_OK && use_split && !prepared && !one_launch)
             rc = run_fixup(d_feat, N, D, ld_feat, d_queries, Q, ld_q, flags, d_scores, d_argmax, d_best, st);
         if (tmp_ws) (void)hipFreeAsync(tmp_ws, st);
     } else {
