@@ -2092,7 +2092,14 @@ static int run_split(const float* d_feat, int64_t N, int D, int64_t ld, const fl
 
 static int run_mfma_f32(const float* d_feat, int64_t N, int D, int64_t ld, const float* d_q, int Q, int64_t ldq,
                         float* d_scores, int32_t* d_argmax, float* d_best, const SplitPlan& p, void* d_ws, hipStream_t st) {
-    float* img = reinterpret_cast<float*>(d_ws);   // needs nkc*Qtot*(KC+4)*4 bytes <= the split image of the same plan
+    float* img = reinterpret_cast<float*>(d_ws);
+    // the query image sim_prep_queries_f32_kernel writes: the caller sized d_ws by the split image of the same plan (p.ws_bytes)
+    const size_t img_bytes = (size_t)p.nkc * p.Qtot * (p.KC + kRowPadF32) * sizeof(float);
+    if (img_bytes > p.ws_bytes) {
+        set_error("avl_sim_scores: the fp32 query image of %zu bytes (nkc=%d Qtot=%d KC=%d) does not fit the plan's %zu", img_bytes, p.nkc,
+                  p.Qtot, p.KC, p.ws_bytes);
+        return AVL_ERR_STATE;
+    }
     hipLaunchKernelGGL(sim_prep_queries_f32_kernel, dim3(p.Qtot), dim3(256), 0, st, d_q, Q, D, ldq, img, p.Qtot, p.KC, p.nkc);
     const int64_t ntiles = (N + kTileRows - 1) / kTileRows;
     int64_t blocks = ntiles < num_cus() ? ntiles : num_cus();
