@@ -256,6 +256,10 @@ _SIGS = {
     # 2-D viewsheds and information gain on the explored map (csrc/avl_viewshed.hip): upstream has no counterpart
     "avl_viewshed_gain": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _i64, C.c_int, C.c_int, _vp, _vp]),
     "avl_viewshed_seen": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _i64, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    # cost-weighted travel fields and the layered costmap (csrc/avl_costfield.hip): upstream has no counterpart; the field's
+    # workspace is avl_travel2d's, so there is no size query of its own
+    "avl_costfield2d": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "avl_costmap2d": (C.c_int, [_vp, _i64, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

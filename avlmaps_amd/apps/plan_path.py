@@ -10,6 +10,8 @@ setup_scene + move_to (robot/habitat_lang_robot.py:88-104, 432-461) without the 
                                         [--goal nbv [--view-range METRES] [--nbv-count K] [--nbv-conservative]]
                                         [--view [--view-range METRES] [--view-fraction F]]
                                         [--room NAME|ID [--door-width M] [--room-names a,b,c]]
+                                        [--planner visgraph|cost [--robot-radius M] [--inflation-radius M] [--cost-scaling K]
+                                         [--avoid NAME[:RADIUS[:PENALTY]]]...]
 
 Loads <scene>/vlmap/vlmaps.h5df (with --text-model hash a missing map is first created with the model-free feature stand-in, as
 apps.create_map --features hash does), builds the obstacle map (Map.generate_obstacle_map), takes the goal from
@@ -81,9 +83,21 @@ the highest mean frame score.  --door-width (default 0.9 m) is the widest openin
 needed; the JSON line has "goal_kind": "room", "room", "rooms" and "route", the rooms from --start's to the goal's through the
 fewest doors (null when --start lies in no room or the two are not connected).
 
+With --planner cost the path to the goal is not the Navigator's visibility-graph path, which is shortest and so touches every
+corner it turns around, but the cheapest 8-connected walk on a costmap of the obstacle crop (Map.get_costmap, Map.plan_cost_path;
+DESIGN.md 4.29, csrc/avl_costfield.hip): cells closer to an obstacle than --robot-radius (default 0.15 m) are impassable, the price
+then decays with the clearance at --cost-scaling per metre (default 5) out to --inflation-radius (default 0.5 m), and every
+--avoid NAME[:RADIUS[:PENALTY]] (repeatable; defaults 0.3 m and 200) adds a penalty on and around the cells of that category, which
+joins the category list.  The goal is chosen as without the flag; goals that the Navigator itself chooses among several (--goal
+frontier or nbv, --view, --nearest path) are not offered.  The path lists the start's cell, the cells where the direction changes
+and the goal's cell; the JSON line gains "planner", "path_cost" (the summed price of the cells entered, diagonal steps times
+sqrt(2), counted from the goal) and "min_clearance_m" (the smallest distance from a cell of the walk to an obstacle cell; null on a
+map without obstacles).  The default, --planner visgraph, is the behaviour described above, unchanged.
+
 With --render the plan is also drawn: the top-down colour map of the obstacle crop (Map.generate_rgb_topdown_map) with the
 obstacle cells the planner used darkened, the path as a polyline, the start in green and the goal in red, as a PNG.  The JSON line
-then has "render", the file."""
+then has "render", the file.  With --planner cost the costmap lies under the path: the dearer a cell the redder, free cells that
+the costmap makes impassable dark red."""
 from __future__ import annotations
 
 import argparse
@@ -140,7 +154,31 @@ def parse_args(argv=None):
     ap.add_argument("--room", default=None, metavar="NAME|ID", help="go to the centre of a room (Map.get_rooms): its id, or a name for AVLMap.name_rooms")
     ap.add_argument("--door-width", type=float, default=None, metavar="M", help="--room: openings up to M metres separate rooms (default 0.9)")
     ap.add_argument("--room-names", default=None, help="--room NAME: the comma separated names the rooms are named from (default: NAME alone)")
+    ap.add_argument("--planner", choices=["visgraph", "cost"], default="visgraph",
+                    help="visgraph = the Navigator's shortest visibility-graph path (default); cost = the cheapest walk on a costmap (Map.plan_cost_path)")
+    ap.add_argument("--robot-radius", type=float, default=None, metavar="M", help="--planner cost: cells closer to an obstacle are impassable (default 0.15)")
+    ap.add_argument("--inflation-radius", type=float, default=None, metavar="M", help="--planner cost: how far from an obstacle cells cost extra (default 0.5)")
+    ap.add_argument("--cost-scaling", type=float, default=None, metavar="K", help="--planner cost: the decay of the inflation per metre (default 5.0)")
+    ap.add_argument("--avoid", action="append", default=[], metavar="NAME[:RADIUS[:PENALTY]]",
+                    help="--planner cost: keep off a category's cells: PENALTY (default 200) on them, falling to 0 at RADIUS metres (default 0.3); repeatable")
     args = ap.parse_args(argv)
+    if args.planner != "cost":
+        if args.avoid or any(v is not None for v in (args.robot_radius, args.inflation_radius, args.cost_scaling)):
+            ap.error("--avoid, --robot-radius, --inflation-radius and --cost-scaling belong to --planner cost")
+    else:
+        if args.goal != "object" or args.view or args.nearest == "path" or args.relation == "face":
+            ap.error("--planner cost plans to one given goal: no --goal frontier or nbv, --view, --nearest path or --relation face")
+        if args.avoid and args.room is not None:
+            ap.error("--avoid names categories of an object goal's list: not with --room")
+        args.robot_radius = 0.15 if args.robot_radius is None else args.robot_radius
+        args.inflation_radius = 0.5 if args.inflation_radius is None else args.inflation_radius
+        args.cost_scaling = 5.0 if args.cost_scaling is None else args.cost_scaling
+        if not (0.0 <= args.robot_radius < float("inf") and 0.0 <= args.inflation_radius < float("inf") and 0.0 <= args.cost_scaling < float("inf")):
+            ap.error("--robot-radius, --inflation-radius and --cost-scaling are finite numbers >= 0")
+        try:
+            args.avoid = [parse_avoid(v) for v in args.avoid]
+        except ValueError as e:
+            ap.error(str(e))
     if args.room is not None:
         if (args.query is not None or args.goal != "object" or args.relation is not None or args.area or args.sound or args.image
                 or args.goal_2d or args.view or args.nearest == "path"):
@@ -202,6 +240,21 @@ def parse_args(argv=None):
     return args
 
 
+def parse_avoid(text):
+    """--avoid NAME[:RADIUS[:PENALTY]] -> (name, radius in metres, penalty); ValueError with the message for the command line"""
+    parts = text.split(":")
+    if not 1 <= len(parts) <= 3 or not parts[0].strip():
+        raise ValueError(f"--avoid {text!r}: expected NAME[:RADIUS[:PENALTY]]")
+    try:
+        radius = float(parts[1]) if len(parts) > 1 else 0.3
+        penalty = int(parts[2]) if len(parts) > 2 else 200
+    except ValueError:
+        raise ValueError(f"--avoid {text!r}: RADIUS is a number of metres and PENALTY an integer") from None
+    if not (0.0 <= radius < float("inf")) or not 0 <= penalty <= 254:
+        raise ValueError(f"--avoid {text!r}: RADIUS is a number of metres >= 0, PENALTY lies in 0 .. 254")
+    return parts[0].strip(), radius, penalty
+
+
 def relation_goal(vm, args, start):
     """the goal point of --relation (left, right, between and the compass four), SystemExit when nothing is in front"""
     if args.relation == "between":
@@ -260,13 +313,33 @@ def room_goal(vm, avlmap, args, start):
     return rooms.centre(k), {"goal_kind": "room", "room": k, "rooms": rooms.n, "route": route}
 
 
+def cost_plan(vm, args, obstacles, start, goal):
+    """--planner cost: (the path, the JSON extras, the costmap); SystemExit when the start cannot reach the goal"""
+    import numpy as np
+    from avlmaps_amd import ops
+    from avlmaps_amd.utils.navigation_utils import NoPathError
+    which = dict(customized=args.customize_obstacles, known_free=args.known_free)
+    costmap = vm.get_costmap(args.robot_radius, args.inflation_radius, args.cost_scaling, avoid=args.avoid, **which)
+    try:
+        walk, price = vm.plan_cost_path(start, goal, costmap=costmap, waypoints=False, with_cost=True, **which)
+    except NoPathError as e:
+        raise SystemExit(f"--planner cost: {e}") from None
+    try:
+        clearance = ops.distance_transform_edt(np.asarray(obstacles) != 0)
+        least = min(float(clearance[int(p[0]) - int(vm.rmin), int(p[1]) - int(vm.cmin)]) for p in walk) * float(vm.cs)
+    except ValueError:                                # a map without obstacles has no clearance
+        least = None
+    path = [list(p) for p in ops.drop_collinear([tuple(p) for p in walk])]
+    return path, {"planner": "cost", "path_cost": price, "min_clearance_m": least}, costmap
+
+
 def clamp_cell(cell, rmin, cmin, shape):
     """the full-map cell moved into the (H, W) crop that starts at (rmin, cmin)"""
     return [min(max(int(cell[0]), int(rmin)), int(rmin) + int(shape[0]) - 1),
             min(max(int(cell[1]), int(cmin)), int(cmin) + int(shape[1]) - 1)]
 
 
-def render_plan(vm, obstacles, start, goal, path, view=None, marks=()):
+def render_plan(vm, obstacles, start, goal, path, view=None, marks=(), costmap=None):
     """(H, W, 3) uint8: the crop of the top-down colour map, obstacle cells (obstacles == 0) at a third of their brightness, the
     cells of `view` (a crop-shaped bool: Viewpoints.mask(), where the object can be seen from, or the cells a next best view would
     see) half-way to cyan, the path in yellow, the start green, the goal red, the full-map cells of `marks` (the later views of a
@@ -278,6 +351,13 @@ def render_plan(vm, obstacles, start, goal, path, view=None, marks=()):
     img = np.ascontiguousarray(vm.generate_rgb_topdown_map()[r0:r0 + H, c0:c0 + W])
     blocked = np.asarray(obstacles) == 0
     img[blocked] = img[blocked] // 3
+    if costmap is not None:
+        price = np.asarray(costmap)
+        alpha = (price.astype(np.float32) / 254.0 * 0.6)[..., None]
+        red = np.array([255, 0, 0], np.float32)
+        tinted = (img.astype(np.float32) * (1.0 - alpha) + red * alpha).astype(np.uint8)
+        img = np.where((~blocked & (price > 1))[..., None], tinted, img)
+        img[~blocked & (price == 0)] = (96, 0, 0)
     if view is not None:
         seen = np.asarray(view, dtype=bool)
         img[seen] = ((img[seen].astype(np.uint16) + np.array([0, 255, 255], np.uint16)) // 2).astype(np.uint8)
@@ -323,6 +403,7 @@ def main(argv=None):
     if args.goal == "object" and args.room is None:
         cats = ([c.strip() for c in args.categories.split(",")] if args.categories
                 else [args.query] + ([args.query_b] if args.query_b else []) + ["other"])
+        cats += [a[0] for a in args.avoid if a[0] not in cats]
         vm.init_categories(cats)
     vm.generate_obstacle_map(args.h_min, args.h_max)
     obstacles = vm.get_obstacle_cropped()
@@ -387,10 +468,14 @@ def main(argv=None):
         g = avlmap.index_goal(obj=args.query, area=args.area or None, sound=args.sound or None, img=img, want_heat=False)
         goal = clamp_cell(g.cell, vm.rmin, vm.cmin, vm.obstacles_cropped.shape)
         extra = {"goal_voxel": g.voxel, "goal_value": g.value, "goal_cell": [float(g.cell[0]), float(g.cell[1])]}
-    nav = Navigator()
+    nav, costmap = Navigator(), None
     try:
-        nav.build_visgraph(obstacles, vm.rmin, vm.cmin)
-        if args.goal == "frontier":
+        if args.planner != "cost":
+            nav.build_visgraph(obstacles, vm.rmin, vm.cmin)
+        if args.planner == "cost":
+            path, more, costmap = cost_plan(vm, args, obstacles, start, goal)
+            extra = dict(extra, **more)
+        elif args.goal == "frontier":
             k, path = nav.plan_to_nearest_frontier(start, frontiers)
             goal = [int(frontiers[0][k, 0]), int(frontiers[0][k, 1])]
             extra = {"goal_kind": "frontier", "frontiers": int(len(frontiers[0])), "frontier_cells": int(frontiers[1][k])}
@@ -431,7 +516,7 @@ def main(argv=None):
             eye = np.array([[int(goal[0]) - int(vm.rmin), int(goal[1]) - int(vm.cmin)]], np.int32)
             view = ops.viewshed_seen(free, vm.get_explored_cropped(), eye, int(args.view_range / float(vm.cs)), args.nbv_conservative) != 0
             marks = [v[0] for v in tour[1:]]
-        Image.fromarray(render_plan(vm, obstacles, start, goal, path, view, marks)).save(args.render)
+        Image.fromarray(render_plan(vm, obstacles, start, goal, path, view, marks, costmap)).save(args.render)
         out["render"] = args.render
     print(json.dumps(out))
     return out

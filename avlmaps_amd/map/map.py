@@ -842,6 +842,108 @@ class Map:
         included -- even when that cell is an obstacle, from which it may step onto a free neighbour"""
         return self.get_travel_field([curr_pos], customized, known_free).reachable()
 
+    # ------------------------------------------------------------------------ costmaps and cost-aware paths (csrc/avl_costfield.hip)
+    # A price per cell of the obstacle crop -- lethal within the robot's radius of an obstacle, decaying with the clearance out to
+    # the inflation radius, plus a penalty around anything to keep off -- and the cheapest 8-connected walk under those prices.
+    # Narrow doors get expensive instead of closed (upstream's Map._dilate_map closes them).  DESIGN.md 4.29.
+    def _avoid_distance(self, what):
+        """the distance plane of one `avoid` entry: per cell of the crop the distance to the nearest cell of the mask, on the
+        device; None for an empty mask.  A plain Map knows no names (VLMap resolves them)."""
+        from .. import ops
+        if isinstance(what, str):
+            raise ValueError(f"get_costmap: avoiding {what!r} by name needs a VLMap with categories; pass a mask of the crop's shape")
+        shape = tuple(np.asarray(self.obstacles_cropped).shape)
+        if ops._image_shape(what) != shape:
+            raise ValueError(f"get_costmap: an avoid mask is {ops._image_shape(what)}, the obstacle crop {shape}")
+        return ops.distance_to_mask(what)
+
+    def get_costmap(self, robot_radius: float = 0.15, inflation_radius: float = 0.5, cost_scaling: float = 5.0, avoid=(),
+                    customized: bool = False, known_free: bool = False, device: bool = False, peak: int = 100):
+        """The (h, w) uint8 costmap of the obstacle crop (customized / known_free as get_travel_field), the price of entering each
+        cell (ops.build_costmap): 0 = impassable, else 1 .. 254.  The inflation layer prices the clearance d, the distance to the
+        nearest obstacle cell of the crop (ops.distance_transform_edt of the free map): lethal where d < robot_radius, else
+        floor(peak * exp(-cost_scaling * (d - robot_radius))) out to inflation_radius, 0 beyond; radii in metres, cost_scaling
+        per metre, all converted with cs.  avoid: a list of (mask_or_name, radius_m, penalty[, lethal]) -- a crop-shaped mask
+        (host or device) or, on a VLMap, a category name; each adds floor(penalty * (1 - distance / radius_m)) within radius_m of
+        the mask's cells, the penalty itself on them, and lethal=True makes those cells impassable.  An empty mask adds nothing.
+        A map without any obstacle cell has no inflation layer."""
+        from .. import ops
+        free = self._travel_free(customized, known_free)
+        cs = float(self.cs)
+        layers = []
+        try:
+            clearance = ops.distance_transform_edt(free, device=True)
+        except ValueError:                              # no obstacle cell to measure to: nothing to inflate
+            clearance = None
+        if clearance is not None:
+            layers.append((clearance, ops.inflation_table(robot_radius / cs, inflation_radius / cs, cost_scaling * cs, peak)))
+        for entry in avoid:
+            if not 3 <= len(entry) <= 4:
+                raise ValueError(f"get_costmap: an avoid entry is (mask_or_name, radius_m, penalty[, lethal]), got {entry!r}")
+            table = ops.penalty_table(float(entry[1]) / cs, entry[2], bool(entry[3]) if len(entry) == 4 else False)
+            plane = self._avoid_distance(entry[0])
+            if plane is not None:
+                layers.append((plane, table))
+        return ops.build_costmap(free, layers, device=device)
+
+    def _cost_inputs(self, costmap, costmap_kw, device):
+        """(the free map, the costmap) of get_cost_field and plan_cost_path: a costmap that is passed in is taken as it is, and then
+        only customized / known_free, which choose the free map, may accompany it"""
+        free = self._travel_free(bool(costmap_kw.get("customized", False)), bool(costmap_kw.get("known_free", False)))
+        if costmap is None:
+            return free, self.get_costmap(**dict(costmap_kw, device=device))
+        extra = sorted(set(costmap_kw) - {"customized", "known_free"})
+        if extra:
+            raise ValueError(f"a costmap was passed: {', '.join(extra)} would be ignored")
+        return free, costmap
+
+    def get_cost_field(self, sources, costmap=None, **costmap_kw):
+        """ops.cost_field over the obstacle crop under `costmap` (default: get_costmap(**costmap_kw)): the cheapest walk from the
+        nearest source to every cell.  sources as get_travel_field: (M, 2) full-map (row, col) points or a crop-shaped mask.
+        customized / known_free in costmap_kw choose the free map also when a costmap is passed.  -> ops.CostField over the crop."""
+        from .. import ops
+        free, costmap = self._cost_inputs(costmap, costmap_kw, device=True)
+        src = sources if ops._is_dev(sources) else np.asarray(sources)
+        if not ops._is_dev(src) and src.shape != free.shape:
+            pts = np.asarray(src, dtype=np.float64).reshape(-1, 2)
+            cells = pts.astype(np.int64) - np.array([int(self.rmin), int(self.cmin)])
+            if len(cells) and (cells.min() < 0 or cells[:, 0].max() >= free.shape[0] or cells[:, 1].max() >= free.shape[1]):
+                raise ValueError(f"get_cost_field: a source lies outside the obstacle crop [{self.rmin}:{self.rmax + 1}, "
+                                 f"{self.cmin}:{self.cmax + 1}]")
+            src = cells
+        return ops.cost_field(free, costmap, src)
+
+    def plan_cost_path(self, start, goal, costmap=None, waypoints: bool = True, with_cost: bool = False, **costmap_kw):
+        """The cheapest 8-connected path from start to goal under `costmap` (default: get_costmap(**costmap_kw)), full-map
+        (row, col) in and out like Navigator.plan_to: [[row, col], ...] cell centres from the start's cell to the goal's.  The
+        field is grown from the GOAL and descended from the start (CostField.descend), so one field serves many starts; the path
+        driven forwards enters the same cells but for the two ends, so its price differs from the field's by
+        cost[start] - cost[goal], the same for every path between the two.  waypoints=True keeps the ends and the cells where the
+        direction changes.  A start or goal on an impassable cell snaps to the nearest passable one, by the rule the Navigator snaps
+        to the nearest free cell.  with_cost=True: -> (path, the field's price A + B sqrt(2) at the start).  NoPathError when the
+        start is not reached; ValueError for a point outside the crop."""
+        from .. import ops
+        from ..utils.navigation_utils import NoPathError, _inside, _nearest_free
+        free, costmap = self._cost_inputs(costmap, costmap_kw, device=False)
+        cost = costmap if isinstance(costmap, np.ndarray) else costmap.numpy()
+        passable = free & (cost != 0)
+        r0, c0 = int(self.rmin), int(self.cmin)
+        cells = []
+        for point in (start, goal):
+            r, c = _inside(passable, (float(point[0]) - r0, float(point[1]) - c0))
+            if not passable[int(r), int(c)]:
+                r, c = _nearest_free(passable, (r, c))
+            cells.append((int(r), int(c)))
+        field = ops.cost_field(free, cost, np.array([cells[1]], dtype=np.int64))
+        a, b = field.planes()
+        if a[cells[0]] < 0:
+            raise NoPathError(f"no passable way from cell {cells[0]} to cell {cells[1]} of the obstacle crop")
+        walk = field.descend(cells[0], waypoints=waypoints)
+        path = [[float(r + r0), float(c + c0)] for r, c in walk]
+        if with_cost:
+            return path, float(a[cells[0]]) + float(b[cells[0]]) * float(np.sqrt(2.0))
+        return path
+
     def get_rooms(self, door_width: float = 0.9, min_core_area: float = 0.25, customized: bool = False, known_free: bool = False):
         """The rooms of this map: a Rooms (map/rooms.py) of ops.segment_rooms over the obstacle crop (customized: the customised
         crop; known_free: get_known_free_cropped), DESIGN.md 4.27.  The free space is eroded by half a door width -- radius =

@@ -399,6 +399,14 @@ class VLMap(Map):
         mask = ops.mask_from_argmax(self._argmax_device(), cat_id)
         return ops.pool_label_2d(mask, self._device_pos(), int(self.gs), device=True)
 
+    def _avoid_distance(self, what):
+        """Map._avoid_distance that also takes a category name: the predicted mask (_predict_mask_device) is measured to inside the
+        crop window in place, so it never leaves the device"""
+        from .. import ops
+        if isinstance(what, str):
+            return ops.distance_to_mask(self._predict_mask_device(what), window=self._crop_window())
+        return super()._avoid_distance(what)
+
     def get_predict_mask(self, name: str) -> np.ndarray:
         """The top-down mask of a category over the obstacle crop: 1 where a voxel whose argmax over scores_mat is the category
         lies in the column, in obstacles_cropped's shape and dtype.  Reference: vlmap_3d.py:75-81.  The comparison and the pooling

@@ -1440,6 +1440,37 @@ AVL_API int avl_viewshed_gain(const uint8_t* d_free_u8, const uint8_t* d_explore
 AVL_API int avl_viewshed_seen(const uint8_t* d_free_u8, const uint8_t* d_explored_u8, int H, int W, const int32_t* d_eyes, int64_t M,
                               int radius, int opaque_unknown, int accumulate, uint8_t* d_seen, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * (28) cost-weighted travel fields and the layered costmap that prices their cells (csrc/avl_costfield.hip).
+ *     Upstream has no counterpart: it dilates the obstacle map by a fixed number of cells (Map._dilate_map).
+ *     d_free, d_sources as in (25); d_cost (H, W) uint8 with rows of ld_cost cells, the price of entering a cell.  A cell is passable
+ *     when free != 0 and cost != 0 (price 0 on a free cell is lethal); the legal-step rule is that of (25) with "passable" in place
+ *     of "free", and a source may lie on an impassable cell.  A step u -> v adds (cost[v], 0) when straight and (0, cost[v]) when
+ *     diagonal; the field of a cell is the pair (A, B) of the cheapest legal walk (price A + B sqrt(2)) from any source: (0, 0) on a
+ *     source, (-1, -1) where no walk ends.  Pairs are compared exactly in integers, so the planes are the same on every run; with
+ *     cost == 1 everywhere they are avl_travel2d's.  1 <= H, W <= 16384 and H * W <= 2^22, which keeps A, B < 2^30; every argument
+ *     is checked before any device work.
+ * ------------------------------------------------------------------------------------------------ */
+/* d_straight, d_diagonal, d_stats and the synchronisation are avl_travel2d's: rounds in batches of 8, the stream SYNCHRONISED after
+ * each batch, the last launch asynchronous, AVL_ERR_STATE ("did not converge") after H * W + 1 rounds.  The workspace is
+ * avl_travel2d's as well: ws_bytes >= avl_travel2d_workspace_bytes(H, W) serves (the same layout; the prices are read from d_cost). */
+AVL_API int avl_costfield2d(const uint8_t* d_free, int64_t ld_free, const uint8_t* d_cost, int64_t ld_cost, const uint8_t* d_sources,
+                            int64_t ld_src, int H, int W, int32_t* d_straight, int32_t* d_diagonal, int64_t* d_stats, void* ws,
+                            size_t ws_bytes, void* stream);
+/* One layer of avl_costmap2d: d_distance (H, W) float64, contiguous -- an avl_edt2d plane: the EDT of the free map (clearance) or
+ * of an inverted mask (nearness to things to avoid); d_table: n_table >= 1 uint8 prices on the device, indexed by the SQUARED
+ * distance in cells, the last entry serving every larger one. */
+typedef struct avl_cost_layer {
+    const double* d_distance;
+    const uint8_t* d_table;
+    int32_t n_table;
+} avl_cost_layer;
+/* d_cost_out (H, W) uint8, contiguous: 0 where d_free == 0; else with t_l = d_table_l[min(d2_l, n_table_l - 1)],
+ * d2_l = (int64) rint(d_l * d_l) (exact for avl_edt2d planes): 0 when any t_l == 255 (lethal), else min(254, 1 + sum t_l).
+ * h_layers: n_layers (0 .. 8) layers in HOST memory, read before the call returns.  No workspace.  Asynchronous. */
+AVL_API int avl_costmap2d(const uint8_t* d_free, int64_t ld_free, int H, int W, const avl_cost_layer* h_layers, int n_layers,
+                          uint8_t* d_cost_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
