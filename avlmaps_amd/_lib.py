@@ -260,6 +260,12 @@ _SIGS = {
     # workspace is avl_travel2d's, so there is no size query of its own
     "avl_costfield2d": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _sz, _vp]),
     "avl_costmap2d": (C.c_int, [_vp, _i64, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp]),
+    # K travel fields in one batch, their set-to-set arrivals and the sound field around walls (csrc/avl_travel_many.hip): upstream
+    # has no counterpart; the batch's workspace is K of avl_travel2d's, so there is no size query of its own
+    "avl_travel2d_many": (C.c_int, [_vp, _i64, C.c_int, C.c_int, _vp, _vp, C.c_int, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "avl_travel_arrive": (C.c_int, [_vp, _i64, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "avl_travel_sound2d": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _f64, C.c_int, _vp, _vp, _vp]),
+    "avl_travel_sound_normalize": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

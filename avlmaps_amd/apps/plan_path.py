@@ -2,7 +2,8 @@
 setup_scene + move_to (robot/habitat_lang_robot.py:88-104, 432-461) without the simulator.
 
     python -m avlmaps_amd.apps.plan_path --data-dir <scene> --query sofa --start ROW COL [--text-model clip|hash]
-                                        [--area NAME]... [--sound NAME]... [--image PNG] [--goal-2d [--travel [--travel-from-start]]]
+                                        [--area NAME]... [--sound NAME]... [--image PNG] [--goal-2d [--travel [--travel-from-start] [--sound-travel]]]
+                                        [--tour NAME,NAME,... [--tour-closed]]
                                         [--customize-obstacles [--potential-obstacles a,b,c --obstacles a,b]
                                          [--dilate-iter N] [--gaussian-sigma S]]
                                         [--relation left|right|between|north|south|east|west|face --heading DEG [--query-b NAME]]
@@ -31,7 +32,14 @@ sound=..), the first maximum of the product of the 2-D distribution maps over th
 2-D map and is rejected.  With --goal-2d --travel the object factor decays with the travel distance on the obstacle crop instead
 of the straight line (AVLMap.index_goal_2d_travel, csrc/avl_travel.hip): the goal cell is near the object by the way the robot has
 to walk, not through a wall; --travel-from-start multiplies in the travel decay from --start, which prefers the nearest of
-several objects by that way.  Area and sound factors stay Euclidean.
+several objects by that way.  Area and sound factors stay Euclidean, unless --sound-travel asks for the sound factors around walls
+as well (AVLMap.index_sound_2d_travel, csrc/avl_travel_many.hip: one travel field per sound segment, in batches).
+
+With --tour NAME,NAME,... (1 to 10 objects, no --query) the robot visits all of them in the best order (VLMap.plan_object_tour: one
+batch of travel fields over the start and the objects' cells, the set-to-set distances, an exact Held-Karp on them); --tour-closed
+comes back to --start.  The JSON line has "tour" (the names in visiting order), "skipped" (the names no walk from --start reaches),
+"matrix_length" and "driven_length" in cells, and "legs", the cells of every leg's walk.  It plans no single path: the flags that
+choose another goal or planner, --known-free and --render are rejected.
 
 With --customize-obstacles the path is planned on Map.get_customized_obstacle_cropped() as upstream's robot does
 (habitat_lang_robot.py:89-104): VLMap.customize_obstacle_map keeps only the obstacles whose class is one of --obstacles among
@@ -128,6 +136,11 @@ def parse_args(argv=None):
                     help="with --goal-2d: object factors decay with the travel distance around walls (AVLMap.index_goal_2d_travel)")
     ap.add_argument("--travel-from-start", action="store_true",
                     help="with --goal-2d --travel: one more factor, the travel decay from --start")
+    ap.add_argument("--sound-travel", action="store_true",
+                    help="with --goal-2d --travel and --sound: the sound factors decay around walls too (AVLMap.index_sound_2d_travel)")
+    ap.add_argument("--tour", default=None, metavar="NAME,NAME,...",
+                    help="visit these objects in the best order (VLMap.plan_object_tour): prints the order, the skipped goals and the legs")
+    ap.add_argument("--tour-closed", action="store_true", help="with --tour: come back to --start at the end")
     ap.add_argument("--customize-obstacles", action="store_true",
                     help="plan on the customised obstacle map (VLMap.customize_obstacle_map) instead of the raw one")
     ap.add_argument("--potential-obstacles", default=None, help="comma separated class list the voxels are scored against")
@@ -162,6 +175,17 @@ def parse_args(argv=None):
     ap.add_argument("--avoid", action="append", default=[], metavar="NAME[:RADIUS[:PENALTY]]",
                     help="--planner cost: keep off a category's cells: PENALTY (default 200) on them, falling to 0 at RADIUS metres (default 0.3); repeatable")
     args = ap.parse_args(argv)
+    if args.tour is not None:
+        args.tour = [c.strip() for c in args.tour.split(",") if c.strip()]
+        if not 1 <= len(args.tour) <= 10:
+            ap.error("--tour takes 1 to 10 comma separated object names")
+        if (args.query is not None or args.goal != "object" or args.relation is not None or args.area or args.sound or args.image
+                or args.goal_2d or args.view or args.nearest == "path" or args.room is not None or args.planner == "cost" or args.render
+                or args.known_free):
+            ap.error("--tour orders its own goals: no --query, --goal frontier or nbv, --relation, --area, --sound, --image, --goal-2d, "
+                     "--view, --nearest path, --room, --planner cost, --known-free or --render")
+    elif args.tour_closed:
+        ap.error("--tour-closed belongs to --tour")
     if args.planner != "cost":
         if args.avoid or any(v is not None for v in (args.robot_radius, args.inflation_radius, args.cost_scaling)):
             ap.error("--avoid, --robot-radius, --inflation-radius and --cost-scaling belong to --planner cost")
@@ -195,8 +219,8 @@ def parse_args(argv=None):
         if args.query is not None or args.relation is not None or args.area or args.sound or args.image or args.goal_2d or args.nearest == "path":
             ap.error(f"--goal {args.goal} takes its goal from the explored map: no --query, --relation, --area, --sound, --image, --goal-2d or --nearest path")
         args.known_free = True
-    elif args.query is None and args.room is None:
-        ap.error("--query is required (or --goal frontier, or --room)")
+    elif args.query is None and args.room is None and args.tour is None:
+        ap.error("--query is required (or --goal frontier, --room or --tour)")
     if args.goal == "nbv":
         if args.view or args.view_fraction is not None:
             ap.error("--goal nbv looks for unknown space, not at an object: no --view or --view-fraction")
@@ -237,6 +261,8 @@ def parse_args(argv=None):
         ap.error("--travel belongs to --goal-2d")
     if args.travel_from_start and not args.travel:
         ap.error("--travel-from-start belongs to --goal-2d --travel")
+    if args.sound_travel and not (args.travel and args.sound):
+        ap.error("--sound-travel belongs to --goal-2d --travel with a --sound")
     return args
 
 
@@ -402,7 +428,7 @@ def main(argv=None):
         vm._init_clip()
     if args.goal == "object" and args.room is None:
         cats = ([c.strip() for c in args.categories.split(",")] if args.categories
-                else [args.query] + ([args.query_b] if args.query_b else []) + ["other"])
+                else (args.tour or [args.query]) + ([args.query_b] if args.query_b else []) + ["other"])
         cats += [a[0] for a in args.avoid if a[0] not in cats]
         vm.init_categories(cats)
     vm.generate_obstacle_map(args.h_min, args.h_max)
@@ -416,6 +442,16 @@ def main(argv=None):
         obstacles = vm.get_known_free_cropped(customized=args.customize_obstacles)
     start = [float(args.start[0]), float(args.start[1])]
     extra = {}
+    if args.tour is not None:
+        try:
+            tour = vm.plan_object_tour(start, args.tour, closed=args.tour_closed, customized=args.customize_obstacles)
+        except ValueError as e:
+            raise SystemExit(f"--tour: {e}") from None
+        out = {"start": start, "tour": tour.names, "skipped": tour.skipped_names, "closed": tour.closed,
+               "matrix_length": tour.matrix_length, "driven_length": tour.driven_length,
+               "legs": [[[float(r), float(c)] for r, c in leg] for leg in tour.legs]}
+        print(json.dumps(out))
+        return out
     if args.relation == "face":
         try:
             turn = float(vm.get_delta_angle_to(start, args.heading, args.query))
@@ -450,8 +486,9 @@ def main(argv=None):
         goal = None if args.nearest == "path" else vm.get_nearest_pos(start, args.query)
     elif args.goal_2d:
         if args.travel:
-            g = avlmap.index_goal_2d_travel(obj=args.query, area=args.area or None, sound=args.sound or None, want_heat=False,
-                                            start=start if args.travel_from_start else None)
+            query = avlmap.index_goal_2d_sound_travel if args.sound_travel else avlmap.index_goal_2d_travel
+            g = query(obj=args.query, area=args.area or None, sound=args.sound or None, want_heat=False,
+                      start=start if args.travel_from_start else None)
         else:
             g = avlmap.index_goal_2d(obj=args.query, area=args.area or None, sound=args.sound or None, want_heat=False)
         goal = [int(g.cell[0]), int(g.cell[1])]

@@ -57,17 +57,8 @@ constexpr int kTravelThreads = 256;
 constexpr int kTravelCells = kTravelTile * kTravelTile / kTravelThreads;   // cells per thread: 4, rows ty, ty + 8, ty + 16, ty + 24
 constexpr int kTravelSweeps = 64;                // in-tile sweep cap: an open tile converges in ~33, a corridor maze continues next round
 constexpr int kTravelHalo = kTravelTile + 2;
-// (the state word, the passability bits, the header words, the marks and the legal-step rule: avl_travel_tile.h, shared with avl_rooms.hip)
-
-// a1 + b1 sqrt(2) < a2 + b2 sqrt(2) for two reached words, exactly
-__device__ __forceinline__ bool travel_less(unsigned long long p, unsigned long long q) {
-    const int da = (int)(unsigned)(p >> 32) - (int)(unsigned)(q >> 32);
-    const int db = (int)(unsigned)p - (int)(unsigned)q;
-    if (da <= 0 && db <= 0) return (da | db) != 0;
-    if (da >= 0 && db >= 0) return false;
-    const long long a2 = (long long)da * da, b2 = 2ll * ((long long)db * db);
-    return da < 0 ? a2 > b2 : a2 < b2;               // da < 0 < db: |da| > db sqrt(2);  db < 0 < da: da < |db| sqrt(2)
-}
+// (the state word, the pair order travel_less, the passability bits, the header words, the marks and the legal-step rule:
+// avl_travel_tile.h, shared with avl_rooms.hip and avl_travel_many.hip)
 
 // pass = free | source << 1 per cell, state = (0, 0) on sources and unreached elsewhere; the tile of every source and its eight
 // neighbours (a source on a tile border is their halo) start active

@@ -1,6 +1,7 @@
-// What the travel-distance field (avl_travel.hip) and the label growth on it (avl_rooms.hip) share: the packed state word, the
-// single-word loads and stores, the passability bits, the active marks, the legal-step rule and the host loop that launches rounds
-// in batches until one activates no tile.  One definition of each, so that the two kernel families cannot drift apart.  The tile
+// What the travel-distance field (avl_travel.hip), the label growth on it (avl_rooms.hip) and the batch of K fields
+// (avl_travel_many.hip) share: the packed state word and the exact order of two of them, the single-word loads and stores, the
+// passability bits, the active marks, the legal-step rule and the host loop that launches rounds in batches until one activates no
+// tile.  One definition of each, so that the kernel families cannot drift apart.  The tile
 // geometry (side, threads, sweep cap) belongs to each family's source; the helpers here take the side as a template argument.
 #pragma once
 #include <algorithm>
@@ -25,6 +26,16 @@ __device__ __forceinline__ unsigned long long travel_load(const unsigned long lo
 }
 __device__ __forceinline__ void travel_store(unsigned long long* p, unsigned long long v) {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// a1 + b1 sqrt(2) < a2 + b2 sqrt(2) for two reached words, exactly
+__device__ __forceinline__ bool travel_less(unsigned long long p, unsigned long long q) {
+    const int da = (int)(unsigned)(p >> 32) - (int)(unsigned)(q >> 32);
+    const int db = (int)(unsigned)p - (int)(unsigned)q;
+    if (da <= 0 && db <= 0) return (da | db) != 0;
+    if (da >= 0 && db >= 0) return false;
+    const long long a2 = (long long)da * da, b2 = 2ll * ((long long)db * db);
+    return da < 0 ? a2 > b2 : a2 < b2;               // da < 0 < db: |da| > db sqrt(2);  db < 0 < da: da < |db| sqrt(2)
 }
 
 // marks tile t active for the coming round; *count counts the tiles that were not marked yet

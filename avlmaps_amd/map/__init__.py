@@ -7,3 +7,4 @@ from .vlmap_builder_multi_floor import VLMapBuilderMultiFloor  # noqa: F401
 from .vlmap_multi_floor import VLMapMultiFloor  # noqa: F401
 from .gtmap import GTMap  # noqa: F401
 from .rooms import Rooms  # noqa: F401
+from .tour import Tour, TOUR_MAX_GOALS  # noqa: F401

@@ -312,8 +312,8 @@ class AVLMap:
             raise MissingSubMap("AVLMap.index_sound needs an audio-text model: AVLMap(..., audio_text_model=...) or "
                                 "sound_map.aclp = ...")
 
-    def _sound_field(self, sound_name: str, decay_rate: float):
-        from .. import ops
+    def _sound_segments(self, sound_name: str):
+        """(probabilities (S,), CSR offsets (S + 1,), cells (L, 2) int32 full-map (row, col)) of the sound segments"""
         self._require_sound()
         probabilities, locations = self.sound_map.get_distribution_and_locations(sound_name)
         if self._sound_cells is None:
@@ -327,6 +327,11 @@ class AVLMap:
                 raise ValueError(f"a sound location lies outside the {gs} x {gs} map")
             self._sound_cells = (np.concatenate([[0], np.cumsum(counts)]), cells.astype(np.int32))
         offsets, cells = self._sound_cells
+        return probabilities, offsets, cells
+
+    def _sound_field(self, sound_name: str, decay_rate: float):
+        from .. import ops
+        probabilities, offsets, cells = self._sound_segments(sound_name)
         return ops.sound_field(offsets, cells, probabilities, self.vlmap.gs, decay_rate)
 
     def index_sound_2d(self, sound_name: str, decay_rate: float = 0.01) -> np.ndarray:
@@ -335,6 +340,37 @@ class AVLMap:
         gf = self._sound_field(sound_name, decay_rate)
         self._check_bounds(gf, f"sound {sound_name!r}")
         return ops.field_normalize(gf).numpy()
+
+    def _sound_travel_device(self, sound_name: str, decay_rate: float = 0.01):
+        """index_sound_2d_travel's map as an (h, w) float32 DeviceArray"""
+        from .. import ops
+        probabilities, offsets, cells = self._sound_segments(sound_name)
+        vm = self.vlmap
+        r0, r1, c0, c1 = vm._crop_window()
+        free = vm._travel_free()
+        inside = (cells[:, 0] >= r0) & (cells[:, 0] < r1) & (cells[:, 1] >= c0) & (cells[:, 1] < c1)
+        sets, peaks = [], []
+        for s, p in enumerate(np.asarray(probabilities, dtype=np.float32)):
+            own = cells[offsets[s]:offsets[s + 1]][inside[offsets[s]:offsets[s + 1]]]
+            if len(own):                                 # a segment with no location left adds nothing
+                sets.append(own - np.array([r0, c0], dtype=cells.dtype))
+                peaks.append(p)
+        if not sets:
+            raise ValueError(f"sound {sound_name!r}: no sound location lies inside the obstacle crop")
+        counts = np.array([len(s) for s in sets], dtype=np.int64)
+        gf = ops.sound_travel_field(free, np.concatenate([[0], np.cumsum(counts)]), np.concatenate(sets), np.array(peaks, np.float32),
+                                    decay_rate)
+        self._check_bounds(gf, f"sound {sound_name!r}")
+        return ops.sound_travel_normalize(gf)
+
+    def index_sound_2d_travel(self, sound_name: str, decay_rate: float = 0.01) -> np.ndarray:
+        """index_sound_2d around walls: (h, w) float32 over the obstacle crop.  index_sound_2d's sum -- per segment in order the
+        float64 term max(p - (p * d) * decay_rate, 0) added into a float32 field -- with d the TRAVEL distance on the obstacle
+        crop from the nearest of the segment's locations (ops.sound_travel_field, csrc/avl_travel_many.hip): a ringing phone is
+        colder behind the wall than in front of it, and silent where no walk ends.  Locations outside the crop are dropped, a
+        segment with no location left adds nothing; the map is min-max normalised over the crop (index_sound_2d: over the full
+        map).  ValueError when no location lies inside the crop or the map is constant."""
+        return self._sound_travel_device(sound_name, decay_rate).numpy()
 
     def index_sound(self, sound_name: str, decay_rate: float = 0.01) -> np.ndarray:
         """(N,) float32.  Reference: avlmap.py:135-144."""
@@ -473,13 +509,25 @@ class AVLMap:
         """index_goal_2d whose object factors decay around walls: an object factor is vlmap.get_travel_distribution_map(name, rate)
         (csrc/avl_travel.hip), so the goal cell is near the object by the way the robot has to walk, not through the wall behind it.
         Area and sound factors are exactly those of index_goal_2d and stay Euclidean: their fields are maxima over weighted peaks,
-        which one distance transform cannot give.
+        which one distance transform cannot give (index_goal_2d_sound_travel takes the sound factors around walls as well).
 
         start: the robot's full-map (row, col); it adds one more factor after the others, the UN-normalised travel decay
         ops.travel_decay_2d(get_travel_field([start]), start_decay_rate) from the robot's cell ("the nearest sofa by the way I have
         to walk"); start_decay_rate defaults to 0.01 and is required to be finite and >= 0.  The product and its first maximum go
         through ops.product_argmax_2d like index_goal_2d's: the definition is the NumPy product of the stand-alone public calls, bit
         for bit.  Raises what those calls raise; ValueError without obj, area and sound."""
+        return self._goal_2d_travel(obj, area, sound, decay_rates, want_heat, start, start_decay_rate, False)
+
+    def index_goal_2d_sound_travel(self, obj=None, area=None, sound=None, decay_rates=None, want_heat: bool = True, start=None,
+                                   start_decay_rate=None) -> "Goal2D":
+        """index_goal_2d_travel whose sound factors decay around walls too: every sound factor is index_sound_2d_travel(name, rate)
+        -- one travel field per sound segment, in batches (csrc/avl_travel_many.hip), normalised over the crop -- in the place
+        index_goal_2d_travel gives the Euclidean one.  Everything else is index_goal_2d_travel's: the arguments, the factor order,
+        the object and start factors, the area factor (one cone per frame pose, it stays Euclidean), and the definition as the
+        NumPy product of the stand-alone public calls, bit for bit.  Without a sound it is index_goal_2d_travel."""
+        return self._goal_2d_travel(obj, area, sound, decay_rates, want_heat, start, start_decay_rate, True)
+
+    def _goal_2d_travel(self, obj, area, sound, decay_rates, want_heat, start, start_decay_rate, sound_travel) -> "Goal2D":
         from .. import ops
         specs = self._goal_specs(obj, area, sound, None, (), decay_rates)
         if not specs:
@@ -494,6 +542,8 @@ class AVLMap:
         for kind, what, rate in specs:
             if kind == "obj":
                 terms.append(vm._travel_distribution_map_device(what, rate))
+            elif kind == "sound" and sound_travel:
+                terms.append(self._sound_travel_device(what, rate))
             else:
                 gf = self._area_field(what, rate) if kind == "area" else self._sound_field(what, rate)
                 self._check_bounds(gf, f"{kind} {what!r}")

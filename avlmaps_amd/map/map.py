@@ -842,6 +842,86 @@ class Map:
         included -- even when that cell is an obstacle, from which it may step onto a free neighbour"""
         return self.get_travel_field([curr_pos], customized, known_free).reachable()
 
+    # ------------------------------------------------------------------------ many travel fields in one batch (csrc/avl_travel_many.hip)
+    # K fields on one free map in one call, the distances between sets of cells read from them, and the order in which to visit a
+    # handful of goals.  Upstream has no counterpart.  DESIGN.md 4.30.
+    def _travel_sets(self, sets, shape, what: str):
+        """[set, ...] -> [[(row, col), ...], ...] in crop cells: a set is a list of full-map (row, col) points -- their int() cells,
+        which must lie inside the crop -- or a mask of the crop's shape (its nonzero cells in raster order)"""
+        out = []
+        for k, s in enumerate(sets):
+            s = np.asarray(s)
+            if s.shape == tuple(shape):
+                cells = np.argwhere(s != 0)
+            else:
+                cells = np.asarray(s, dtype=np.float64).reshape(-1, 2).astype(np.int64) - np.array([int(self.rmin), int(self.cmin)])
+                if len(cells) and (cells.min() < 0 or cells[:, 0].max() >= shape[0] or cells[:, 1].max() >= shape[1]):
+                    raise ValueError(f"{what}: a cell of set {k} lies outside the obstacle crop [{self.rmin}:{self.rmax + 1}, "
+                                     f"{self.cmin}:{self.cmax + 1}]")
+            if len(cells) == 0:
+                raise ValueError(f"{what}: set {k} is empty")
+            out.append([(int(r), int(c)) for r, c in cells])
+        if not out:
+            raise ValueError(f"{what}: no set")
+        return out
+
+    @staticmethod
+    def _sets_csr(sets):
+        offsets = np.concatenate([[0], np.cumsum([len(s) for s in sets])]).astype(np.int64)
+        return offsets, np.array([c for s in sets for c in s], dtype=np.int32).reshape(-1, 2)
+
+    def get_travel_fields(self, sets, customized: bool = False, known_free: bool = False, device: bool = False):
+        """ops.travel_fields over the obstacle crop, one field per set, in one batch (customized / known_free / device as
+        get_travel_field).  A set is a list of full-map (row, col) points -- their int() cells, which must lie inside the crop -- or
+        a mask of the crop's shape; its cells may be obstacle cells.  -> ops.TravelFields over the crop: field k's planes are
+        get_travel_field(sets[k])'s, byte for byte."""
+        from .. import ops
+        free = self._travel_free(customized, known_free)
+        offsets, cells = self._sets_csr(self._travel_sets(sets, free.shape, "get_travel_fields"))
+        return ops.travel_fields(free, offsets, cells, device=device)
+
+    def get_travel_matrix(self, sets, customized: bool = False, known_free: bool = False):
+        """-> ops.TravelArrivals, (K, K): how far it is to walk from every set to every other one (get_travel_fields over the sets,
+        then ops.travel_arrivals at the same sets).  Entry [k, j] is the pair (a, b) of the shortest walk that leaves set k and
+        arrives at set j, a + b sqrt(2) cells; sets on obstacle cells are left and arrived at by one step off / onto them, so the
+        matrix is symmetric; (0, 0) where two sets share a cell, -1 where no walk connects them.  cell[k, j] indexes the
+        concatenated cells of the sets."""
+        from .. import ops
+        free = self._travel_free(customized, known_free)
+        offsets, cells = self._sets_csr(self._travel_sets(sets, free.shape, "get_travel_matrix"))
+        return ops.travel_arrivals(ops.travel_fields(free, offsets, cells, device=True), offsets, cells)
+
+    def plan_tour(self, start, goals, closed: bool = False, customized: bool = False, known_free: bool = False):
+        """The order in which to visit `goals` from `start`, and the walks.  start: a full-map (row, col); goals: 1 to
+        tour.TOUR_MAX_GOALS sets as get_travel_fields takes them.  One ops.travel_fields call over [start] + goals and one
+        ops.travel_arrivals give the matrix of set-to-set distances; the order is an exact Held-Karp on its integer pairs
+        (tour.held_karp: sums compared like the kernel compares pairs, ties to the lexicographically smallest order); closed=True
+        also returns to the start.  Goals no walk from the start reaches are left out and listed in Tour.skipped.
+
+        The order is optimal for the set-to-set matrix.  The legs are then driven: leg i is fields.field(goal).descend(cell) from
+        the cell the last leg ended on, trimmed to its last free cell.  The driven length can exceed the matrix length, because a
+        set is entered at one cell and left from there, while the matrix lets every leg leave from the set's best cell.
+        -> tour.Tour with full-map cells."""
+        from .. import ops
+        from . import tour as T
+        goals = list(goals)
+        if not 1 <= len(goals) <= T.TOUR_MAX_GOALS:
+            raise ValueError(f"plan_tour: 1 to {T.TOUR_MAX_GOALS} goals, got {len(goals)}")
+        free = self._travel_free(customized, known_free)
+        sets = self._travel_sets([[start]] + goals, free.shape, "plan_tour")
+        offsets, cells = self._sets_csr(sets)
+        fields = ops.travel_fields(free, offsets, cells, device=True)
+        arr = ops.travel_arrivals(fields, offsets, cells)
+        order, pair, skipped = T.held_karp(arr.a, arr.b, closed)
+        fields.planes()                                  # one copy for all legs
+        at, legs, driven = sets[0][0], [], []
+        for g in order + ([0] if closed and order else []):
+            walk = T.drive_leg(fields.field(g), free, at, ops.TRAVEL_NEIGHBOURS)
+            at = walk[-1]
+            driven.append(T.step_counts(walk))
+            legs.append([(r + int(self.rmin), c + int(self.cmin)) for r, c in walk])
+        return T.Tour([g - 1 for g in order], [g - 1 for g in skipped], pair, legs, driven, closed)
+
     # ------------------------------------------------------------------------ costmaps and cost-aware paths (csrc/avl_costfield.hip)
     # A price per cell of the obstacle crop -- lethal within the robot's radius of an obstacle, decaying with the clearance out to
     # the inflation radius, plus a penalty around anything to keep off -- and the cheapest 8-connected walk under those prices.

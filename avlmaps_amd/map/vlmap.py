@@ -626,6 +626,26 @@ class VLMap(Map):
         smoothing or the map is constant, as get_distribution_map."""
         return self._travel_distribution_map_device(name, decay_rate, customized).numpy()
 
+    def plan_object_tour(self, start, names, closed: bool = False, customized: bool = False):
+        """Map.plan_tour over categories: "go to the sofa, the table and the lamp, in the best order".  The goal of a name is the
+        set of crop cells of its pooled 2-D mask after get_travel_distribution_map's smoothing (predicted mask ->
+        gaussian_filter(float32, sigma=1) > 0.5, on the device; only the (h, w) byte mask comes to the host, where the sets are
+        listed).  start: a full-map (row, col).  -> tour.Tour; Tour.names / Tour.skipped_names are the names in visiting order and
+        the ones no walk from the start reaches.  ValueError for a name without a target cell after the smoothing."""
+        from .. import ops
+        names = list(names)
+        window = self._crop_window()
+        goals = []
+        for name in names:
+            mask = ops.mask_smooth_2d(self._predict_mask_device(name), 1, window=window)
+            if not mask.any():
+                raise ValueError(f"plan_object_tour: the mask of {name!r} has no target cell after the smoothing")
+            goals.append(mask)
+        tour = self.plan_tour(start, goals, closed=closed, customized=customized)
+        tour.names = [names[k] for k in tour.order]
+        tour.skipped_names = [names[k] for k in tour.skipped]
+        return tour
+
     def get_voxel_rooms(self, rooms, device: bool = False):
         """(N,) int32: the room of every voxel, rooms.labels[row - rmin, col - cmin] of its cell and 0 outside the crop
         (ops.lift_labels_2d on the resident positions).  rooms: Map.get_rooms' result.  A voxel above an obstacle cell -- the top

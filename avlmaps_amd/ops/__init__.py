@@ -92,6 +92,10 @@ from .costmap import (  # noqa: F401
     build_costmap, cost_field, COST_LETHAL, COST_MAX, COST_MAX_CELLS, COST_MAX_LAYERS, CostField, distance_to_mask, drop_collinear,
     inflation_table, penalty_table,
 )
+from .travelmany import (  # noqa: F401
+    sound_travel_field, sound_travel_normalize, travel_arrivals, travel_fields, TRAVEL_MANY_MAX_FIELDS, TRAVEL_MANY_MAX_PAIRS,
+    TravelArrivals, TravelFields,
+)
 # the shared marshalling layer; its one device predicate keeps both of the names it had here
 from ._args import (  # noqa: F401
     _dev_u8, _image_any, _image_shape, _image_u8, _is_dev, _is_dev as _on_device, _result,

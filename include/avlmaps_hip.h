@@ -1471,6 +1471,44 @@ typedef struct avl_cost_layer {
 AVL_API int avl_costmap2d(const uint8_t* d_free, int64_t ld_free, int H, int W, const avl_cost_layer* h_layers, int n_layers,
                           uint8_t* d_cost_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * (29) K travel-distance fields of (25) on one free map in one batch, the set-to-set arrivals read from their planes, and the sound
+ *     field that decays around walls (csrc/avl_travel_many.hip).  Upstream has no counterpart.
+ *     Sets are CSR: d_offsets (K + 1) int64 from 0 to L, d_cells (L, 2) int32 (row, col), both on the device; set k is
+ *     cells[offsets[k] .. offsets[k + 1]).  A set may repeat a cell and its cells may lie on obstacles; a cell outside the map is
+ *     passed over.  1 <= K <= 1024, sides as in (25), K * ceil(H / 32) * ceil(W / 32) <= 2^28; int64 indexing throughout; every
+ *     argument is checked before any device work.
+ * ------------------------------------------------------------------------------------------------ */
+/* Field k is avl_travel2d's field whose sources are the cells of set k: the same step rule, pair order and planes, byte for byte.
+ * d_straight, d_diagonal: (K, H, W) int32, contiguous.  d_stats: 2 + K int64 on the device = [rounds that had an active (field,
+ * tile) pair, pair runs, reached cells of field 0 .. K - 1].  The batch runs as many rounds as its slowest field; rounds in batches
+ * of 8, the stream SYNCHRONISED after each batch, the last launch asynchronous, AVL_ERR_STATE ("did not converge") after H * W + 1
+ * rounds.  Workspace: ws_bytes >= K * avl_travel2d_workspace_bytes(H, W); there is no size query of its own.  The layout is
+ *   256 + align256(256) + align256(8 K T) + align256(H W) + align256(8 K H W) bytes, T = ceil(H / 32) * ceil(W / 32)
+ * (a header, two mark words per (field, tile) pair, ONE free plane for all fields, a 64-bit state word per field and cell), which
+ * is at most K times the single field's figure because align256(K x) <= K align256(x). */
+AVL_API int avl_travel2d_many(const uint8_t* d_free, int64_t ld_free, int H, int W, const int64_t* d_offsets, const int32_t* d_cells, int K,
+                              int64_t L, int32_t* d_straight, int32_t* d_diagonal, int64_t* d_stats, void* ws, size_t ws_bytes, void* stream);
+/* Arrivals of K fields (the planes of avl_travel2d_many on d_free) at M target sets (CSR as above, 1 <= M <= 1024, L < 2^31).  For a
+ * target cell t, arrive_k(t) is (0, 0) when t's pair in field k is (0, 0); otherwise the exact minimum over the eight neighbours u
+ * of t of pair_k(u) + step(u -> t), over the u whose pair is reached and, for a diagonal step, with both cells that share an edge
+ * with u and t free; t itself need not be free (the mirror image of "a source may lie on an obstacle").  For a free t this is
+ * pair_k(t).  Outputs (K, M) int32: d_a, d_b the minimum over the set's cells; d_cell the index into d_cells of the first cell in
+ * CSR order that attains it; d_from the index of the winning neighbour in the order E, NE, N, NW, W, SW, S, SE, the first among
+ * ties, -1 when the target is a source.  -1 in all four where no cell of the set is arrived at.  No workspace.  Asynchronous. */
+AVL_API int avl_travel_arrive(const uint8_t* d_free, int64_t ld_free, int H, int W, const int32_t* d_straight, const int32_t* d_diagonal,
+                              int K, const int64_t* d_offsets, const int32_t* d_cells, int M, int64_t L, int32_t* d_a, int32_t* d_b,
+                              int32_t* d_cell, int32_t* d_from, void* stream);
+/* avl_field_sound of (9) with the travel distance.  d_straight, d_diagonal (K, H, W): the field of segment s = 0 .. K - 1;
+ * d_peaks (K) float32 >= 0.  For every cell, segments in order:  d = double(a) + double(b) * 1.4142135623730951 (unfused);
+ * t = p - (p * d) * decay_rate in float64, < 0 -> 0, unreached -> 0;  acc = float(double(acc) + t).  first != 0: acc starts from 0;
+ * first == 0: from what d_field (H, W) float32 holds, so that many segments go through in chunks.  A segment with p == 0 adds
+ * exactly +0.  d_minmax (2) float32: [min, max] of the field after this call.  Asynchronous. */
+AVL_API int avl_travel_sound2d(const int32_t* d_straight, const int32_t* d_diagonal, int K, int H, int W, const float* d_peaks,
+                               double decay_rate, int first, float* d_field, float* d_minmax, void* stream);
+/* d_out = (d_field - min) / (max - min) in float32, avl_field_normalize's expression on an (H, W) field.  Asynchronous. */
+AVL_API int avl_travel_sound_normalize(const float* d_field, const float* d_minmax, int H, int W, float* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
