@@ -2,8 +2,8 @@
 //
 // Upstream has no counterpart: its only answer to "keep away from walls" is to dilate the obstacle map by a fixed number of cells
 // (avlmaps/map/map.py, Map._dilate_map), which closes narrow doors instead of making them expensive.  This file is the weighted
-// sibling of avl_travel.hip: the same tiles, state word, marks, legal-step rule and host loop (avl_travel_tile.h), with one more
-// operand, the price of the cell a step enters.
+// sibling of avl_travel.hip: the same tile scheme, workspace and host loop (avl_travel_tile.h), with one more operand, the price
+// of the cell a step enters.
 //
 // Definition.  free, sources, cost (H, W) uint8, each with its own row length.  A cell is passable when
 // free != 0 && cost != 0: price 0 on a free cell means lethal.  The legal-step rule is 4.26's with "passable" in place of "free",
@@ -17,12 +17,12 @@
 // Bounds.  H * W <= 2^22 (kCostMaxCells), on top of the side limit of avl_travel.hip.  Every stored word is the price of a walk
 // without repeated cells: a candidate that returned to a cell would be dearer than the word that cell already holds (prices are
 // positive), and words only decrease.  Such a walk has fewer than H * W steps of price <= 255 each, so A, B < 2^22 * 2^8 = 2^30:
-// the low half of the packed word never carries into the high half, the differences da, db of cost_less fit an int, and
-// da^2 < 2^60, 2 db^2 < 2^61 stay inside int64.
+// the low half of the packed word never carries into the high half, and travel_less stays inside its bounds.
 //
-// State, work, the in-place 64-bit accesses and the marks: the head of avl_travel.hip, word for word.  The only new operand of a
-// round is the thread's own four cell prices, held in registers: candidate = neighbour + cost[v] * (diagonal ? 1 : 2^32).  No price
-// plane in LDS.  The initialisation folds cost == 0 into the passability byte, so the legal-step rule never looks at a price.
+// State and work: avl_travel.hip's word and the shared tile body, here the priced variant travel_tile_relax<true, false>.  The only
+// new operand of a round is the thread's own four cell prices, held in registers: candidate = neighbour + cost[v] * (diagonal ? 1 :
+// 2^32).  No price plane in LDS.  The initialisation folds cost == 0 into the passability byte, so the legal-step rule
+// (travel_legal_in<kTravelHalo>) never looks at a price.
 //
 // Convergence.  avl_travel.hip's argument holds verbatim for positive prices: every stored word is (0, 0) on a source or "a stored
 // neighbour + a legal step", so the price of a real legal walk and never below the minimum; words only decrease; a cell whose word
@@ -30,9 +30,8 @@
 // the Bellman fixed point, which with strictly positive step prices is the cheapest-walk field.  The optimal pair of a cell whose
 // cheapest walk has k steps is in place after at most k rounds, k < H * W: the host gives up after H * W + 1 rounds.
 //
-// The workspace is avl_travel2d's: the same header, marks, passability bytes and state words; the prices are read from the
-// caller's plane.  cost_layout() below repeats travel_layout() piece by piece and the entry point refuses to run if its total is
-// not what avl_travel2d_workspace_bytes reports.
+// The workspace is avl_travel2d's, travel_layout() itself: the same header, marks, passability bytes and state words; the prices
+// are read from the caller's plane.
 //
 // The costmap (avl_costmap2d) is element-wise: per cell the layers' tables are looked up at the squared distance and summed.
 #include <algorithm>
@@ -40,28 +39,11 @@
 
 #include "avl_common.h"
 #include "avl_travel_tile.h"
-#include "avl_wave.h"
 
 namespace avl {
 
-constexpr int kCostMaxSide = 16384;              // kTravelMaxSide
 constexpr int64_t kCostMaxCells = 1ll << 22;     // H * W: keeps A, B < 2^30, see the head of the file
-constexpr int kCostTile = 32;                    // avl_travel.hip's geometry: the workspace and the marks are shared
-constexpr int kCostThreads = 256;
-constexpr int kCostCells = kCostTile * kCostTile / kCostThreads;   // cells per thread: 4, rows ty, ty + 8, ty + 16, ty + 24
-constexpr int kCostSweeps = 64;
-constexpr int kCostHalo = kCostTile + 2;
 constexpr int kCostMaxLayers = 8;
-
-// A1 + B1 sqrt(2) < A2 + B2 sqrt(2) for two reached words, exactly (A, B < 2^30)
-__device__ __forceinline__ bool cost_less(unsigned long long p, unsigned long long q) {
-    const int da = (int)(unsigned)(p >> 32) - (int)(unsigned)(q >> 32);
-    const int db = (int)(unsigned)p - (int)(unsigned)q;
-    if (da <= 0 && db <= 0) return (da | db) != 0;
-    if (da >= 0 && db >= 0) return false;
-    const long long a2 = (long long)da * da, b2 = 2ll * ((long long)db * db);
-    return da < 0 ? a2 > b2 : a2 < b2;
-}
 
 // pass = (free && cost != 0) | source << 1 per cell, state = (0, 0) on sources and unreached elsewhere; the tile of every source
 // and its eight neighbours start active
@@ -70,131 +52,24 @@ __global__ __launch_bounds__(256) void cost_init_kernel(const uint8_t* __restric
                                                         const uint8_t* __restrict__ src_u8, int64_t ld_src, int H, int W,
                                                         uint8_t* __restrict__ pass, unsigned long long* __restrict__ state,
                                                         unsigned* __restrict__ flags, unsigned* __restrict__ hdr) {
-    const int tw = (W + kCostTile - 1) / kCostTile, th = (H + kCostTile - 1) / kCostTile;
+    const int tw = travel_tiles(W), th = travel_tiles(H);
     const int64_t n = (int64_t)H * W;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const int r = (int)(i / W), c = (int)(i - (int64_t)r * W);
-        const bool fr = free_u8[(int64_t)r * ld_free + c] != 0 && cost_u8[(int64_t)r * ld_cost + c] != 0;
-        const bool sr = src_u8[(int64_t)r * ld_src + c] != 0;
-        pass[i] = (uint8_t)((fr ? kTravelFree : 0) | (sr ? kTravelSource : 0));
-        state[i] = sr ? 0ull : kTravelUnreached;
-        if (sr) {
-            if (hdr[kTravelHdrAny] == 0u) atomicExch(&hdr[kTravelHdrAny], 1u);
-            travel_mark_around<kCostTile>(flags, r, c, th, tw, &hdr[kTravelHdrInit]);
-        }
+        const bool passable = free_u8[(int64_t)r * ld_free + c] != 0 && cost_u8[(int64_t)r * ld_cost + c] != 0;
+        travel_init_cell(i, r, c, passable, src_u8[(int64_t)r * ld_src + c] != 0, th, tw, pass, state, flags, hdr);
     }
 }
 
-// One round: travel_round_kernel with the entered cell's price in the candidate.
-__global__ __launch_bounds__(kCostThreads) void cost_round_kernel(const uint8_t* __restrict__ pass, const uint8_t* __restrict__ cost_u8,
-                                                                  int64_t ld_cost, unsigned long long* state, int H, int W,
-                                                                  unsigned* __restrict__ cur, unsigned* __restrict__ next,
-                                                                  unsigned* __restrict__ activated) {
-    __shared__ unsigned long long s_state[kCostHalo * kCostHalo];
-    __shared__ uint8_t s_pass[kCostHalo * kCostHalo];
-    __shared__ unsigned s_active, s_dirty;
-    const int tw = (W + kCostTile - 1) / kCostTile, th = (H + kCostTile - 1) / kCostTile;
-    const int tile_r = blockIdx.x / tw, tile_c = blockIdx.x - tile_r * tw;
-    if (threadIdx.x == 0) {
-        s_active = cur[blockIdx.x];
-        s_dirty = 0u;
-        if (s_active) cur[blockIdx.x] = 0u;           // this buffer takes the marks of the round after the next
-    }
-    __syncthreads();
-    if (s_active == 0u) return;
-    const int r0 = tile_r * kCostTile - 1, c0 = tile_c * kCostTile - 1;        // the halo's origin
-#pragma unroll
-    for (int k = 0; k < (kCostHalo * kCostHalo + kCostThreads - 1) / kCostThreads; ++k) {
-        const int i = k * kCostThreads + threadIdx.x;
-        if (i < kCostHalo * kCostHalo) {
-            const int r = r0 + i / kCostHalo, c = c0 + i % kCostHalo;
-            const bool in = r >= 0 && r < H && c >= 0 && c < W;
-            s_state[i] = in ? travel_load(&state[(int64_t)r * W + c]) : kTravelUnreached;
-            s_pass[i] = in ? pass[(int64_t)r * W + c] : (uint8_t)0;
-        }
-    }
-    __syncthreads();
-    const int tx = threadIdx.x % kCostTile, ty = threadIdx.x / kCostTile;
-    unsigned long long first[kCostCells], mine[kCostCells];
-    unsigned long long price[kCostCells];             // the price of entering this cell
-    unsigned legal[kCostCells];                       // bit k: the step from the neighbour in direction k to this cell is legal
-#pragma unroll
-    for (int j = 0; j < kCostCells; ++j) {
-        const int at = (ty + 8 * j + 1) * kCostHalo + tx + 1;
-        const int r = r0 + 1 + ty + 8 * j, c = c0 + 1 + tx;
-        first[j] = mine[j] = s_state[at];
-        legal[j] = travel_legal_in<kCostHalo>(s_pass, at);
-        // a cell with a legal incoming step is passable, so it lies inside the map and its price is 1 .. 255
-        price[j] = legal[j] ? (unsigned long long)cost_u8[(int64_t)r * ld_cost + c] : 0ull;
-    }
-    bool more = true;
-    for (int sweep = 0; sweep < kCostSweeps && more; ++sweep) {
-        unsigned long long best[kCostCells];
-#pragma unroll
-        for (int j = 0; j < kCostCells; ++j) {
-            const int at = (ty + 8 * j + 1) * kCostHalo + tx + 1;
-            unsigned long long b = mine[j];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                if (!(legal[j] >> k & 1u)) continue;
-                const unsigned long long s = s_state[at + travel_dr(k) * kCostHalo + travel_dc(k)];
-                if (s == kTravelUnreached) continue;
-                const unsigned long long cand = s + price[j] * ((k & 1) ? kTravelDiagonal : kTravelStraight);
-                if (b == kTravelUnreached || cost_less(cand, b)) b = cand;
-            }
-            best[j] = b;
-        }
-        __syncthreads();                               // every read of this sweep is done
-        int changed = 0;
-#pragma unroll
-        for (int j = 0; j < kCostCells; ++j) {
-            if (best[j] != mine[j]) {
-                mine[j] = best[j];
-                s_state[(ty + 8 * j + 1) * kCostHalo + tx + 1] = best[j];
-                changed = 1;
-            }
-        }
-        more = __syncthreads_or(changed) != 0;
-    }
-    // write back; bit k of dirty: the neighbour tile in direction k reads a changed cell as halo
-    unsigned dirty = 0;
-#pragma unroll
-    for (int j = 0; j < kCostCells; ++j) {
-        if (mine[j] == first[j]) continue;
-        const int lr = ty + 8 * j, lc = tx;
-        travel_store(&state[(int64_t)(r0 + 1 + lr) * W + (c0 + 1 + lc)], mine[j]);     // changed cells lie inside the map
-        dirty |= travel_halo_readers<kCostTile>(lr, lc);
-    }
-    if (dirty) atomicOr(&s_dirty, dirty);
-    __syncthreads();
-    if (threadIdx.x < 8) {
-        const int k = threadIdx.x;
-        const int ur = tile_r + travel_dr(k), uc = tile_c + travel_dc(k);
-        if ((s_dirty >> k & 1u) && ur >= 0 && ur < th && uc >= 0 && uc < tw) travel_mark(next, ur * tw + uc, activated);
-    } else if (threadIdx.x == 8 && more) {
-        travel_mark(next, blockIdx.x, activated);      // the sweep cap: go on in the next round
-    }
-}
-
-// the two int32 planes, the number of reached cells, and the host's counters into d_stats = [rounds, tile runs, reached, any source]
-__global__ __launch_bounds__(256) void cost_unpack_kernel(const unsigned long long* __restrict__ state, int64_t n,
-                                                          int32_t* __restrict__ straight, int32_t* __restrict__ diagonal,
-                                                          long long rounds, long long tile_runs, int any_source,
-                                                          unsigned long long* __restrict__ stats) {
-    unsigned long long reached = 0;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const unsigned long long s = state[i];
-        straight[i] = (int32_t)(unsigned)(s >> 32);
-        diagonal[i] = (int32_t)(unsigned)s;
-        reached += s != kTravelUnreached;
-    }
-    reached = wave_sum(reached);
-    if ((threadIdx.x & (kWave - 1)) == 0 && reached) atomicAdd(&stats[2], reached);
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        stats[0] = (unsigned long long)rounds;
-        stats[1] = (unsigned long long)tile_runs;
-        stats[3] = (unsigned long long)any_source;
-    }
+// One round: the shared body with the entered cell's price in the candidate.
+__global__ __launch_bounds__(kTravelThreads) void cost_round_kernel(const uint8_t* __restrict__ pass, const uint8_t* __restrict__ cost_u8,
+                                                                    int64_t ld_cost, unsigned long long* state, int H, int W,
+                                                                    unsigned* __restrict__ cur, unsigned* __restrict__ next,
+                                                                    unsigned* __restrict__ activated) {
+    __shared__ TravelTileLds lds;
+    if (!travel_take_mark(cur, &lds.active, &lds.dirty)) return;
+    const int tile_r = blockIdx.x / travel_tiles(W), tile_c = blockIdx.x - tile_r * travel_tiles(W);
+    travel_tile_relax<true, false>(lds, pass, cost_u8, ld_cost, state, H, W, tile_r, tile_c, 0, next, activated);
 }
 
 struct CostLayers {
@@ -230,29 +105,6 @@ __global__ __launch_bounds__(256) void costmap_kernel(const uint8_t* __restrict_
     }
 }
 
-static int cost_check_shape(const char* what, int H, int W) {
-    AVL_REQUIRE(H > 0 && W > 0 && H <= kCostMaxSide && W <= kCostMaxSide, "%s: bad shape %d x %d (sides 1 .. %d)", what, H, W,
-                kCostMaxSide);
-    return AVL_OK;
-}
-
-struct CostLayout {
-    size_t hdr, flags, pass, state, total;
-};
-
-// travel_layout() of avl_travel.hip, piece by piece (avl_costfield2d checks the total against avl_travel2d_workspace_bytes)
-static CostLayout cost_layout(int H, int W) {
-    const size_t tiles = (size_t)((H + kCostTile - 1) / kCostTile) * (size_t)((W + kCostTile - 1) / kCostTile);
-    Carver c;
-    CostLayout l;
-    l.hdr = c.take(kTravelHdrWords * sizeof(unsigned));
-    l.flags = c.take(2 * tiles * sizeof(unsigned));
-    l.pass = c.take((size_t)H * W);
-    l.state = c.take((size_t)H * W * sizeof(unsigned long long));
-    l.total = c.total() + 256;                        // the entry point aligns the base itself
-    return l;
-}
-
 }  // namespace avl
 
 using namespace avl;
@@ -262,7 +114,7 @@ extern "C" {
 int avl_costfield2d(const uint8_t* d_free, int64_t ld_free, const uint8_t* d_cost, int64_t ld_cost, const uint8_t* d_sources,
                     int64_t ld_src, int H, int W, int32_t* d_straight, int32_t* d_diagonal, int64_t* d_stats, void* ws, size_t ws_bytes,
                     void* stream) {
-    int rc = cost_check_shape("avl_costfield2d", H, W);
+    int rc = travel_check_shape("avl_costfield2d", H, W);
     if (rc != AVL_OK) return rc;
     const int64_t n = (int64_t)H * W;
     AVL_REQUIRE(n <= kCostMaxCells, "avl_costfield2d: %d x %d = %lld cells, at most 2^22 (the sums of prices must stay below 2^30)", H, W,
@@ -272,14 +124,7 @@ int avl_costfield2d(const uint8_t* d_free, int64_t ld_free, const uint8_t* d_cos
     AVL_REQUIRE(ld_free >= W, "avl_costfield2d: free rows of %lld cells cannot hold %d columns", (long long)ld_free, W);
     AVL_REQUIRE(ld_cost >= W, "avl_costfield2d: cost rows of %lld cells cannot hold %d columns", (long long)ld_cost, W);
     AVL_REQUIRE(ld_src >= W, "avl_costfield2d: source rows of %lld cells cannot hold %d columns", (long long)ld_src, W);
-    const CostLayout l = cost_layout(H, W);
-    size_t travel_bytes = 0;
-    rc = avl_travel2d_workspace_bytes(H, W, &travel_bytes);
-    if (rc != AVL_OK) return rc;
-    if (travel_bytes != l.total) {
-        set_error("avl_costfield2d: the layout needs %zu bytes, avl_travel2d_workspace_bytes reports %zu", l.total, travel_bytes);
-        return AVL_ERR_STATE;
-    }
+    const TravelLayout l = travel_layout(H, W);
     AVL_REQUIRE(ws && ws_bytes >= l.total, "avl_costfield2d: workspace of %zu bytes, need %zu", ws_bytes, l.total);
     hipStream_t st = as_stream(stream);
     char* base = (char*)align256_ptr(ws);
@@ -287,8 +132,7 @@ int avl_costfield2d(const uint8_t* d_free, int64_t ld_free, const uint8_t* d_cos
     unsigned* flags = (unsigned*)(base + l.flags);
     uint8_t* pass = (uint8_t*)(base + l.pass);
     unsigned long long* state = (unsigned long long*)(base + l.state);
-    const int tw = (W + kCostTile - 1) / kCostTile, th = (H + kCostTile - 1) / kCostTile;
-    const unsigned tiles = (unsigned)(tw * th);
+    const unsigned tiles = (unsigned)(travel_tiles(W) * travel_tiles(H));
 
     AVL_HIP_CHECK(hipMemsetAsync(hdr, 0, l.pass - l.hdr, st));              // the header and both mark buffers
     AVL_HIP_CHECK(hipMemsetAsync(d_stats, 0, 4 * sizeof(int64_t), st));
@@ -303,21 +147,17 @@ int avl_costfield2d(const uint8_t* d_free, int64_t ld_free, const uint8_t* d_cos
     rc = travel_run_rounds(
         "avl_costfield2d", max_rounds, hdr, flags, tiles, st,
         [&](int64_t, unsigned* cur, unsigned* next, unsigned* activated) {
-            hipLaunchKernelGGL(cost_round_kernel, dim3(tiles), dim3(kCostThreads), 0, st, (const uint8_t*)pass, d_cost, ld_cost, state, H, W,
+            hipLaunchKernelGGL(cost_round_kernel, dim3(tiles), dim3(kTravelThreads), 0, st, (const uint8_t*)pass, d_cost, ld_cost, state, H, W,
                                cur, next, activated);
         },
         &rounds, &tile_runs, host);
     if (rc != AVL_OK) return rc;
-    hipLaunchKernelGGL(cost_unpack_kernel, dim3(stride_blocks(n)), dim3(256), 0, st, (const unsigned long long*)state, n, d_straight,
-                       d_diagonal, (long long)rounds, (long long)tile_runs, (int)(host[kTravelHdrAny] != 0),
-                       reinterpret_cast<unsigned long long*>(d_stats));
-    AVL_HIP_CHECK(hipGetLastError());
-    return AVL_OK;
+    return travel_unpack(state, n, d_straight, d_diagonal, rounds, tile_runs, host[kTravelHdrAny] != 0, d_stats, st);
 }
 
 int avl_costmap2d(const uint8_t* d_free, int64_t ld_free, int H, int W, const avl_cost_layer* h_layers, int n_layers, uint8_t* d_cost_out,
                   void* stream) {
-    int rc = cost_check_shape("avl_costmap2d", H, W);
+    int rc = travel_check_shape("avl_costmap2d", H, W);
     if (rc != AVL_OK) return rc;
     AVL_REQUIRE(d_free && d_cost_out, "avl_costmap2d: null free image or output");
     AVL_REQUIRE(ld_free >= W, "avl_costmap2d: free rows of %lld cells cannot hold %d columns", (long long)ld_free, W);

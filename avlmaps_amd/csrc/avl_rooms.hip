@@ -26,7 +26,8 @@
 // or none, both upper bounds of the true owner, and its reader has been marked active for the next round, whose launch boundary
 // makes the new word visible.
 //
-// Work, on the tile scheme of travel_round_kernel: 32 x 32 tiles, 256 threads, 4 cells per thread.  An active tile loads a one-cell
+// Work, on the tile scheme of avl_travel_tile.h with a sweep of its own between the shared prologue (travel_take_mark) and epilogue
+// (travel_wake): 32 x 32 tiles, 256 threads, 4 cells per thread.  An active tile loads a one-cell
 // halo of the converged 64-bit state, the pass byte and the owner word into LDS, computes ONCE per tile run the mask of tight legal
 // predecessors of each of its cells (registers), and sweeps: a minimum over at most 8 LDS words, a barrier, the writes of what got
 // smaller, a barrier that ORs "something changed".  It writes back only the cells that changed, wakes the neighbours that see a
@@ -51,12 +52,6 @@
 
 namespace avl {
 
-constexpr int kGrowMaxSide = 16384;              // avl_travel.hip's kTravelMaxSide
-constexpr int kGrowTile = 32;                    // avl_travel.hip's kTravelTile: the same tiles
-constexpr int kGrowThreads = 256;
-constexpr int kGrowCells = kGrowTile * kGrowTile / kGrowThreads;
-constexpr int kGrowSweeps = 64;                  // in-tile sweep cap, avl_travel.hip's kTravelSweeps
-constexpr int kGrowHalo = kGrowTile + 2;
 constexpr unsigned kGrowNone = ~0u;              // no label yet
 constexpr int kGrowHdrNegative = 2;              // header word: a negative seed was seen
 
@@ -89,7 +84,7 @@ __global__ __launch_bounds__(256) void grow_init_kernel(const uint8_t* __restric
                                                         const int32_t* __restrict__ diagonal, int H, int W, uint8_t* __restrict__ pass,
                                                         unsigned long long* __restrict__ state, unsigned* __restrict__ owner,
                                                         unsigned* __restrict__ flags, unsigned* __restrict__ hdr) {
-    const int tw = (W + kGrowTile - 1) / kGrowTile, th = (H + kGrowTile - 1) / kGrowTile;
+    const int tw = travel_tiles(W), th = travel_tiles(H);
     const int64_t n = (int64_t)H * W;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const int r = (int)(i / W), c = (int)(i - (int64_t)r * W);
@@ -99,33 +94,27 @@ __global__ __launch_bounds__(256) void grow_init_kernel(const uint8_t* __restric
         pass[i] = (uint8_t)((fr ? kTravelFree : 0) | (sr ? kTravelSource : 0));
         state[i] = a < 0 ? kTravelUnreached : ((unsigned long long)(unsigned)a << 32 | (unsigned)b);
         owner[i] = sr ? (unsigned)s : kGrowNone;
-        if (sr) travel_mark_around<kGrowTile>(flags, r, c, th, tw, &hdr[kTravelHdrInit]);
+        if (sr) travel_mark_around<kTravelTile>(flags, r, c, th, tw, &hdr[kTravelHdrInit]);
     }
 }
 
 // One label round: see the head of the file.  cur / next: the active marks of this round and of the coming one.
-__global__ __launch_bounds__(kGrowThreads) void grow_round_kernel(const uint8_t* __restrict__ pass, const unsigned long long* __restrict__ state,
+__global__ __launch_bounds__(kTravelThreads) void grow_round_kernel(const uint8_t* __restrict__ pass, const unsigned long long* __restrict__ state,
                                                                   unsigned* owner, int H, int W, unsigned* __restrict__ cur,
                                                                   unsigned* __restrict__ next, unsigned* __restrict__ activated) {
-    __shared__ unsigned long long s_state[kGrowHalo * kGrowHalo];
-    __shared__ unsigned s_owner[kGrowHalo * kGrowHalo];
-    __shared__ uint8_t s_pass[kGrowHalo * kGrowHalo];
+    __shared__ unsigned long long s_state[kTravelHalo * kTravelHalo];
+    __shared__ unsigned s_owner[kTravelHalo * kTravelHalo];
+    __shared__ uint8_t s_pass[kTravelHalo * kTravelHalo];
     __shared__ unsigned s_active, s_dirty;
-    const int tw = (W + kGrowTile - 1) / kGrowTile, th = (H + kGrowTile - 1) / kGrowTile;
+    if (!travel_take_mark(cur, &s_active, &s_dirty)) return;
+    const int tw = travel_tiles(W), th = travel_tiles(H);
     const int tile_r = blockIdx.x / tw, tile_c = blockIdx.x - tile_r * tw;
-    if (threadIdx.x == 0) {
-        s_active = cur[blockIdx.x];
-        s_dirty = 0u;
-        if (s_active) cur[blockIdx.x] = 0u;           // this buffer takes the marks of the round after the next
-    }
-    __syncthreads();
-    if (s_active == 0u) return;
-    const int r0 = tile_r * kGrowTile - 1, c0 = tile_c * kGrowTile - 1;        // the halo's origin
+    const int r0 = tile_r * kTravelTile - 1, c0 = tile_c * kTravelTile - 1;    // the halo's origin
 #pragma unroll
-    for (int k = 0; k < (kGrowHalo * kGrowHalo + kGrowThreads - 1) / kGrowThreads; ++k) {
-        const int i = k * kGrowThreads + threadIdx.x;
-        if (i < kGrowHalo * kGrowHalo) {
-            const int r = r0 + i / kGrowHalo, c = c0 + i % kGrowHalo;
+    for (int k = 0; k < (kTravelHalo * kTravelHalo + kTravelThreads - 1) / kTravelThreads; ++k) {
+        const int i = k * kTravelThreads + threadIdx.x;
+        if (i < kTravelHalo * kTravelHalo) {
+            const int r = r0 + i / kTravelHalo, c = c0 + i % kTravelHalo;
             const bool in = r >= 0 && r < H && c >= 0 && c < W;
             s_state[i] = in ? state[(int64_t)r * W + c] : kTravelUnreached;
             s_owner[i] = in ? grow_load(&owner[(int64_t)r * W + c]) : kGrowNone;
@@ -133,20 +122,20 @@ __global__ __launch_bounds__(kGrowThreads) void grow_round_kernel(const uint8_t*
         }
     }
     __syncthreads();
-    const int tx = threadIdx.x % kGrowTile, ty = threadIdx.x / kGrowTile;
-    unsigned first[kGrowCells], mine[kGrowCells];
-    unsigned tight[kGrowCells];                       // bit k: the neighbour in direction k is a tight legal predecessor
+    const int tx = threadIdx.x % kTravelTile, ty = threadIdx.x / kTravelTile;
+    unsigned first[kTravelCells], mine[kTravelCells];
+    unsigned tight[kTravelCells];                     // bit k: the neighbour in direction k is a tight legal predecessor
 #pragma unroll
-    for (int j = 0; j < kGrowCells; ++j) {
-        const int at = (ty + 8 * j + 1) * kGrowHalo + tx + 1;
+    for (int j = 0; j < kTravelCells; ++j) {
+        const int at = (ty + 8 * j + 1) * kTravelHalo + tx + 1;
         first[j] = mine[j] = s_owner[at];
-        const unsigned legal = travel_legal_in<kGrowHalo>(s_pass, at);
+        const unsigned legal = travel_legal_in<kTravelHalo>(s_pass, at);
         const unsigned long long here = s_state[at];
         unsigned m = 0;
         if (here != kTravelUnreached) {
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
-                const unsigned long long s = s_state[at + travel_dr(k) * kGrowHalo + travel_dc(k)];
+                const unsigned long long s = s_state[at + travel_dr(k) * kTravelHalo + travel_dc(k)];
                 const bool ok = (legal >> k & 1u) && s != kTravelUnreached && s + ((k & 1) ? kTravelDiagonal : kTravelStraight) == here;
                 m |= ok ? 1u << k : 0u;
             }
@@ -154,24 +143,24 @@ __global__ __launch_bounds__(kGrowThreads) void grow_round_kernel(const uint8_t*
         tight[j] = m;
     }
     bool more = true;
-    for (int sweep = 0; sweep < kGrowSweeps && more; ++sweep) {
-        unsigned best[kGrowCells];
+    for (int sweep = 0; sweep < kTravelSweeps && more; ++sweep) {
+        unsigned best[kTravelCells];
 #pragma unroll
-        for (int j = 0; j < kGrowCells; ++j) {
-            const int at = (ty + 8 * j + 1) * kGrowHalo + tx + 1;
+        for (int j = 0; j < kTravelCells; ++j) {
+            const int at = (ty + 8 * j + 1) * kTravelHalo + tx + 1;
             unsigned b = mine[j];
 #pragma unroll
             for (int k = 0; k < 8; ++k)
-                if (tight[j] >> k & 1u) b = min(b, s_owner[at + travel_dr(k) * kGrowHalo + travel_dc(k)]);
+                if (tight[j] >> k & 1u) b = min(b, s_owner[at + travel_dr(k) * kTravelHalo + travel_dc(k)]);
             best[j] = b;
         }
         __syncthreads();                               // every read of this sweep is done
         int changed = 0;
 #pragma unroll
-        for (int j = 0; j < kGrowCells; ++j) {
+        for (int j = 0; j < kTravelCells; ++j) {
             if (best[j] != mine[j]) {
                 mine[j] = best[j];
-                s_owner[(ty + 8 * j + 1) * kGrowHalo + tx + 1] = best[j];
+                s_owner[(ty + 8 * j + 1) * kTravelHalo + tx + 1] = best[j];
                 changed = 1;
             }
         }
@@ -179,21 +168,13 @@ __global__ __launch_bounds__(kGrowThreads) void grow_round_kernel(const uint8_t*
     }
     unsigned dirty = 0;
 #pragma unroll
-    for (int j = 0; j < kGrowCells; ++j) {
+    for (int j = 0; j < kTravelCells; ++j) {
         if (mine[j] == first[j]) continue;
         const int lr = ty + 8 * j, lc = tx;
         grow_store(&owner[(int64_t)(r0 + 1 + lr) * W + (c0 + 1 + lc)], mine[j]);       // changed cells lie inside the map
-        dirty |= travel_halo_readers<kGrowTile>(lr, lc);
+        dirty |= travel_halo_readers<kTravelTile>(lr, lc);
     }
-    if (dirty) atomicOr(&s_dirty, dirty);
-    __syncthreads();
-    if (threadIdx.x < 8) {
-        const int k = threadIdx.x;
-        const int ur = tile_r + travel_dr(k), uc = tile_c + travel_dc(k);
-        if ((s_dirty >> k & 1u) && ur >= 0 && ur < th && uc >= 0 && uc < tw) travel_mark(next, ur * tw + uc, activated);
-    } else if (threadIdx.x == 8 && more) {
-        travel_mark(next, blockIdx.x, activated);      // the sweep cap: go on in the next round
-    }
+    travel_wake(dirty, more, &s_dirty, tile_r, tile_c, th, tw, 0, next, activated);
 }
 
 // the int32 owner plane (no label -> 0) and the label phase's counters into stats[4 .. 7]
@@ -211,29 +192,24 @@ __global__ __launch_bounds__(256) void grow_finish_kernel(const unsigned* __rest
     }
 }
 
-static int grow_check_shape(const char* what, int H, int W) {
-    AVL_REQUIRE(H > 0 && W > 0 && H <= kGrowMaxSide && W <= kGrowMaxSide, "%s: bad shape %d x %d (sides 1 .. %d)", what, H, W, kGrowMaxSide);
-    return AVL_OK;
-}
-
 struct GrowLayout {
     size_t hdr, flags, pass, state, owner, mask, travel, travel_bytes, total;
 };
 
-static int grow_layout(int H, int W, GrowLayout* l) {
-    const size_t tiles = (size_t)((H + kGrowTile - 1) / kGrowTile) * (size_t)((W + kGrowTile - 1) / kGrowTile);
-    int rc = avl_travel2d_workspace_bytes(H, W, &l->travel_bytes);
-    if (rc != AVL_OK) return rc;
+static GrowLayout grow_layout(int H, int W) {
+    const size_t tiles = (size_t)travel_tiles(H) * (size_t)travel_tiles(W);
     Carver c;
-    l->hdr = c.take(kTravelHdrWords * sizeof(unsigned));
-    l->flags = c.take(2 * tiles * sizeof(unsigned));
-    l->pass = c.take((size_t)H * W);
-    l->state = c.take((size_t)H * W * sizeof(unsigned long long));
-    l->owner = c.take((size_t)H * W * sizeof(unsigned));
-    l->mask = c.take((size_t)H * W);
-    l->travel = c.take(l->travel_bytes);
-    l->total = c.total() + 256;                       // the entry point aligns the base itself
-    return AVL_OK;
+    GrowLayout l;
+    l.hdr = c.take(kTravelHdrWords * sizeof(unsigned));
+    l.flags = c.take(2 * tiles * sizeof(unsigned));
+    l.pass = c.take((size_t)H * W);
+    l.state = c.take((size_t)H * W * sizeof(unsigned long long));
+    l.owner = c.take((size_t)H * W * sizeof(unsigned));
+    l.mask = c.take((size_t)H * W);
+    l.travel_bytes = travel_layout(H, W).total;       // phase 1 runs avl_travel2d on a workspace of its own
+    l.travel = c.take(l.travel_bytes);
+    l.total = c.total() + 256;                        // the entry point aligns the base itself
+    return l;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -538,26 +514,21 @@ extern "C" {
 
 int avl_grow_labels_workspace_bytes(int H, int W, size_t* bytes) {
     AVL_REQUIRE(bytes, "avl_grow_labels_workspace_bytes: null output");
-    int rc = grow_check_shape("avl_grow_labels_workspace_bytes", H, W);
+    int rc = travel_check_shape("avl_grow_labels_workspace_bytes", H, W);
     if (rc != AVL_OK) return rc;
-    GrowLayout l;
-    rc = grow_layout(H, W, &l);
-    if (rc != AVL_OK) return rc;
-    *bytes = l.total;
+    *bytes = grow_layout(H, W).total;
     return AVL_OK;
 }
 
 int avl_grow_labels(const uint8_t* d_free, int64_t ld_free, const int32_t* d_seeds, int64_t ld_seeds, int H, int W, int32_t* d_straight,
                     int32_t* d_diagonal, int32_t* d_owner, int64_t* d_stats, void* ws, size_t ws_bytes, void* stream) {
-    int rc = grow_check_shape("avl_grow_labels", H, W);
+    int rc = travel_check_shape("avl_grow_labels", H, W);
     if (rc != AVL_OK) return rc;
     AVL_REQUIRE(d_free && d_seeds, "avl_grow_labels: null free or seed image");
     AVL_REQUIRE(d_straight && d_diagonal && d_owner && d_stats, "avl_grow_labels: null output plane or stats pointer");
     AVL_REQUIRE(ld_free >= W, "avl_grow_labels: free rows of %lld cells cannot hold %d columns", (long long)ld_free, W);
     AVL_REQUIRE(ld_seeds >= W, "avl_grow_labels: seed rows of %lld cells cannot hold %d columns", (long long)ld_seeds, W);
-    GrowLayout l;
-    rc = grow_layout(H, W, &l);
-    if (rc != AVL_OK) return rc;
+    const GrowLayout l = grow_layout(H, W);
     AVL_REQUIRE(ws && ws_bytes >= l.total, "avl_grow_labels: workspace of %zu bytes, need %zu", ws_bytes, l.total);
     hipStream_t st = as_stream(stream);
     char* base = (char*)align256_ptr(ws);
@@ -567,8 +538,7 @@ int avl_grow_labels(const uint8_t* d_free, int64_t ld_free, const int32_t* d_see
     unsigned long long* state = (unsigned long long*)(base + l.state);
     unsigned* owner = (unsigned*)(base + l.owner);
     uint8_t* mask = (uint8_t*)(base + l.mask);
-    const int tw = (W + kGrowTile - 1) / kGrowTile, th = (H + kGrowTile - 1) / kGrowTile;
-    const unsigned tiles = (unsigned)(tw * th);
+    const unsigned tiles = (unsigned)(travel_tiles(W) * travel_tiles(H));
     const int64_t n = (int64_t)H * W;
 
     AVL_HIP_CHECK(hipMemsetAsync(hdr, 0, l.pass - l.hdr, st));              // the header and both mark buffers
@@ -586,7 +556,7 @@ int avl_grow_labels(const uint8_t* d_free, int64_t ld_free, const int32_t* d_see
     rc = travel_run_rounds(
         "avl_grow_labels", n + 1, hdr, flags, tiles, st,
         [&](int64_t, unsigned* cur, unsigned* next, unsigned* activated) {
-            hipLaunchKernelGGL(grow_round_kernel, dim3(tiles), dim3(kGrowThreads), 0, st, (const uint8_t*)pass, (const unsigned long long*)state, owner,
+            hipLaunchKernelGGL(grow_round_kernel, dim3(tiles), dim3(kTravelThreads), 0, st, (const uint8_t*)pass, (const unsigned long long*)state, owner,
                                H, W, cur, next, activated);
         },
         &rounds, &tile_runs, host);
@@ -599,7 +569,7 @@ int avl_grow_labels(const uint8_t* d_free, int64_t ld_free, const int32_t* d_see
 
 int avl_room_seeds_workspace_bytes(int H, int W, size_t* bytes) {
     AVL_REQUIRE(bytes, "avl_room_seeds_workspace_bytes: null output");
-    int rc = grow_check_shape("avl_room_seeds_workspace_bytes", H, W);
+    int rc = travel_check_shape("avl_room_seeds_workspace_bytes", H, W);
     if (rc != AVL_OK) return rc;
     SeedWork w;
     rc = seed_work(H, W, nullptr, &w);
@@ -610,7 +580,7 @@ int avl_room_seeds_workspace_bytes(int H, int W, size_t* bytes) {
 
 int avl_room_seeds(const double* d_clearance, int H, int W, double radius, int64_t min_seed_cells, int32_t* d_seeds, int32_t* d_k, void* ws,
                    size_t ws_bytes, void* stream) {
-    int rc = grow_check_shape("avl_room_seeds", H, W);
+    int rc = travel_check_shape("avl_room_seeds", H, W);
     if (rc != AVL_OK) return rc;
     AVL_REQUIRE(d_clearance && d_seeds && d_k, "avl_room_seeds: null clearance, seed or count pointer");
     AVL_REQUIRE(std::isfinite(radius) && radius >= 0.0, "avl_room_seeds: radius must be finite and >= 0");
@@ -654,7 +624,7 @@ int avl_room_seeds(const double* d_clearance, int H, int W, double radius, int64
 
 int avl_room_table(const int32_t* d_labels, const int32_t* d_seeds, const double* d_clearance, int H, int W, int32_t K, int64_t* d_table,
                    void* stream) {
-    int rc = grow_check_shape("avl_room_table", H, W);
+    int rc = travel_check_shape("avl_room_table", H, W);
     if (rc != AVL_OK) return rc;
     AVL_REQUIRE(K >= 0 && K <= kRoomMaxRooms, "avl_room_table: %d rooms (0 .. %d)", K, kRoomMaxRooms);
     if (K == 0) return AVL_OK;
@@ -680,7 +650,7 @@ int avl_room_doors_workspace_bytes(int32_t K, size_t* bytes) {
 
 int avl_room_doors(const int32_t* d_labels, const double* d_clearance, int H, int W, int32_t K, int64_t* d_count, void* ws, size_t ws_bytes,
                    void* stream) {
-    int rc = grow_check_shape("avl_room_doors", H, W);
+    int rc = travel_check_shape("avl_room_doors", H, W);
     if (rc != AVL_OK) return rc;
     AVL_REQUIRE(K >= 0 && K <= kRoomMaxRooms, "avl_room_doors: %d rooms (0 .. %d)", K, kRoomMaxRooms);
     AVL_REQUIRE(d_labels && d_clearance && d_count, "avl_room_doors: null label, clearance or count pointer");
@@ -703,7 +673,7 @@ int avl_room_doors(const int32_t* d_labels, const double* d_clearance, int H, in
 
 int avl_room_door_table(const void* ws, size_t ws_bytes, int32_t K, int W, int64_t D, int64_t* d_table, void* stream) {
     AVL_REQUIRE(K >= 0 && K <= kRoomMaxRooms, "avl_room_door_table: %d rooms (0 .. %d)", K, kRoomMaxRooms);
-    AVL_REQUIRE(W > 0 && W <= kGrowMaxSide, "avl_room_door_table: bad width %d", W);
+    AVL_REQUIRE(W > 0 && W <= kTravelMaxSide, "avl_room_door_table: bad width %d", W);
     const DoorWork w = door_work(K, ws ? align256_ptr(const_cast<void*>(ws)) : nullptr);
     AVL_REQUIRE(D >= 0 && D <= w.cap, "avl_room_door_table: %lld pairs, the table of %d rooms holds %lld", (long long)D, K, (long long)w.cap);
     if (D == 0) return AVL_OK;
@@ -718,7 +688,7 @@ int avl_room_door_table(const void* ws, size_t ws_bytes, int32_t K, int W, int64
 
 int avl_lift_labels_2d(const int32_t* d_labels, int H, int W, const int32_t* d_grid_pos, int64_t N, int rmin, int cmin, int32_t* d_out,
                        void* stream) {
-    int rc = grow_check_shape("avl_lift_labels_2d", H, W);
+    int rc = travel_check_shape("avl_lift_labels_2d", H, W);
     if (rc != AVL_OK) return rc;
     AVL_REQUIRE(N >= 0, "avl_lift_labels_2d: negative voxel count %lld", (long long)N);
     if (N == 0) return AVL_OK;

@@ -10,26 +10,14 @@
 // length a + b * sqrt(2); the field of a cell is the pair (a, b) of the shortest legal walk from any source to it, (0, 0) on a
 // source, (-1, -1) where no walk ends.  sqrt(2) is irrational, so different pairs differ in length: the minimum is unique.
 //
-// Order.  Pairs are compared exactly in integers (travel_less): the sign cases of da against db, then da^2 against 2 db^2 in
-// int64.  With a, b <= H * W <= 2^28 both squares stay below 2^57.  No floating-point key is involved.
+// Order.  Pairs are compared exactly in integers (travel_less in avl_travel_tile.h, with its bounds).
 //
 // State.  One 64-bit word per cell, a in the high half and b in the low half; all ones = unreached, which unpacks to (-1, -1).
 // A candidate is "neighbour + step", a plain 64-bit addition: b never carries into a.
 //
-// Work.  The grid is cut into 32 x 32 tiles, one 256-thread workgroup each, four cells per thread.  A round is one plain launch
-// over all tiles; a tile that is not marked active returns at once.  An active tile loads its cells and a one-cell halo of state
-// and passability into LDS, turns passability into one byte per cell of legal incoming directions (registers), and sweeps
-// pull-relaxations over its cells: every thread reads the neighbours of its cells, a barrier, every thread writes what got
-// smaller, a barrier that also ORs "something changed".  The sweeps end when one changes nothing or after kTravelSweeps of them.
-// The tile writes the cells that changed back, marks each of its eight neighbours active for the next round when a cell they
-// see as halo changed, and marks itself when it ran into the sweep cap.  The host launches kTravelRoundBatch rounds, reads how
-// many tiles each round activated, and stops when the last round of a batch activated none (rounds after an empty round find
-// no active tile and return at once).
-//
-// One state buffer, read and written in place with single aligned 64-bit accesses (relaxed atomics of device scope, so the
-// compiler can neither split nor duplicate them).  Only the workgroup that owns a cell writes it.  A neighbour that reads the
-// cell as halo in the same round sees the old or the new word, never a mixture; both are lengths of real walks.  If it saw the
-// old one, the owner has marked it active for the next round, whose launch boundary makes the new word visible.
+// Work.  The tile scheme of avl_travel_tile.h, described there at travel_tile_relax: rounds of 32 x 32 tiles that relax in LDS,
+// write back what changed and wake the tiles that read it.  This family is the plain variant, travel_tile_relax<false, false>:
+// every step costs 1 and the passability byte holds the source bit.
 //
 // Convergence.  Every stored word is (0, 0) on a source or was produced as "a stored neighbour + a legal step": by induction the
 // length of a real legal walk from a source, so never below the definition's minimum.  Words only decrease.  A cell whose word
@@ -38,9 +26,6 @@
 // with strictly positive step lengths is the shortest-walk field itself, whatever order the tiles ran in.  The optimal pair of
 // a cell whose shortest walk has k steps is in place after at most k rounds, and a walk without repeated cells has fewer than
 // H * W steps: the host gives up with an error after H * W + 1 rounds, which cannot happen unless the device misbehaves.
-//
-// No grid-wide barrier, no wait on another workgroup; every device loop has a compile-time bound or is a grid-stride loop over
-// the cells.
 #include <algorithm>
 #include <cmath>
 
@@ -51,119 +36,29 @@
 
 namespace avl {
 
-constexpr int kTravelMaxSide = 16384;            // avl_edt2d.hip's kEdtMaxSide: the decay maps of both families cover the same crops
-constexpr int kTravelTile = 32;                  // cells per tile side
-constexpr int kTravelThreads = 256;
-constexpr int kTravelCells = kTravelTile * kTravelTile / kTravelThreads;   // cells per thread: 4, rows ty, ty + 8, ty + 16, ty + 24
-constexpr int kTravelSweeps = 64;                // in-tile sweep cap: an open tile converges in ~33, a corridor maze continues next round
-constexpr int kTravelHalo = kTravelTile + 2;
-// (the state word, the pair order travel_less, the passability bits, the header words, the marks and the legal-step rule:
-// avl_travel_tile.h, shared with avl_rooms.hip and avl_travel_many.hip)
-
 // pass = free | source << 1 per cell, state = (0, 0) on sources and unreached elsewhere; the tile of every source and its eight
 // neighbours (a source on a tile border is their halo) start active
 __global__ __launch_bounds__(256) void travel_init_kernel(const uint8_t* __restrict__ free_u8, int64_t ld_free,
                                                           const uint8_t* __restrict__ src_u8, int64_t ld_src, int H, int W,
                                                           uint8_t* __restrict__ pass, unsigned long long* __restrict__ state,
                                                           unsigned* __restrict__ flags, unsigned* __restrict__ hdr) {
-    const int tw = (W + kTravelTile - 1) / kTravelTile, th = (H + kTravelTile - 1) / kTravelTile;
+    const int tw = travel_tiles(W), th = travel_tiles(H);
     const int64_t n = (int64_t)H * W;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const int r = (int)(i / W), c = (int)(i - (int64_t)r * W);
-        const bool fr = free_u8[(int64_t)r * ld_free + c] != 0, sr = src_u8[(int64_t)r * ld_src + c] != 0;
-        pass[i] = (uint8_t)((fr ? kTravelFree : 0) | (sr ? kTravelSource : 0));
-        state[i] = sr ? 0ull : kTravelUnreached;
-        if (sr) {
-            if (hdr[kTravelHdrAny] == 0u) atomicExch(&hdr[kTravelHdrAny], 1u);
-            travel_mark_around<kTravelTile>(flags, r, c, th, tw, &hdr[kTravelHdrInit]);
-        }
+        travel_init_cell(i, r, c, free_u8[(int64_t)r * ld_free + c] != 0, src_u8[(int64_t)r * ld_src + c] != 0, th, tw, pass, state, flags, hdr);
     }
 }
 
-// One round: see the head of the file.  cur / next: the active marks of this round and of the coming one.
+// One round: the shared body with unit steps (its legal-step rule is travel_legal_in<kTravelHalo> on the loaded pass bytes).
+// cur / next: the active marks of this round and of the coming one.
 __global__ __launch_bounds__(kTravelThreads) void travel_round_kernel(const uint8_t* __restrict__ pass, unsigned long long* state, int H,
                                                                       int W, unsigned* __restrict__ cur, unsigned* __restrict__ next,
                                                                       unsigned* __restrict__ activated) {
-    __shared__ unsigned long long s_state[kTravelHalo * kTravelHalo];
-    __shared__ uint8_t s_pass[kTravelHalo * kTravelHalo];
-    __shared__ unsigned s_active, s_dirty;
-    const int tw = (W + kTravelTile - 1) / kTravelTile, th = (H + kTravelTile - 1) / kTravelTile;
-    const int tile_r = blockIdx.x / tw, tile_c = blockIdx.x - tile_r * tw;
-    if (threadIdx.x == 0) {
-        s_active = cur[blockIdx.x];
-        s_dirty = 0u;
-        if (s_active) cur[blockIdx.x] = 0u;           // this buffer takes the marks of the round after the next
-    }
-    __syncthreads();
-    if (s_active == 0u) return;
-    const int r0 = tile_r * kTravelTile - 1, c0 = tile_c * kTravelTile - 1;    // the halo's origin
-#pragma unroll
-    for (int k = 0; k < (kTravelHalo * kTravelHalo + kTravelThreads - 1) / kTravelThreads; ++k) {
-        const int i = k * kTravelThreads + threadIdx.x;
-        if (i < kTravelHalo * kTravelHalo) {
-            const int r = r0 + i / kTravelHalo, c = c0 + i % kTravelHalo;
-            const bool in = r >= 0 && r < H && c >= 0 && c < W;
-            s_state[i] = in ? travel_load(&state[(int64_t)r * W + c]) : kTravelUnreached;
-            s_pass[i] = in ? pass[(int64_t)r * W + c] : (uint8_t)0;
-        }
-    }
-    __syncthreads();
-    const int tx = threadIdx.x % kTravelTile, ty = threadIdx.x / kTravelTile;
-    unsigned long long first[kTravelCells], mine[kTravelCells];
-    unsigned legal[kTravelCells];                     // bit k: the step from the neighbour in direction k to this cell is legal
-#pragma unroll
-    for (int j = 0; j < kTravelCells; ++j) {
-        const int at = (ty + 8 * j + 1) * kTravelHalo + tx + 1;
-        first[j] = mine[j] = s_state[at];
-        legal[j] = travel_legal_in<kTravelHalo>(s_pass, at);
-    }
-    bool more = true;
-    for (int sweep = 0; sweep < kTravelSweeps && more; ++sweep) {
-        unsigned long long best[kTravelCells];
-#pragma unroll
-        for (int j = 0; j < kTravelCells; ++j) {
-            const int at = (ty + 8 * j + 1) * kTravelHalo + tx + 1;
-            unsigned long long b = mine[j];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                if (!(legal[j] >> k & 1u)) continue;
-                const unsigned long long s = s_state[at + travel_dr(k) * kTravelHalo + travel_dc(k)];
-                if (s == kTravelUnreached) continue;
-                const unsigned long long cand = s + ((k & 1) ? kTravelDiagonal : kTravelStraight);
-                if (b == kTravelUnreached || travel_less(cand, b)) b = cand;
-            }
-            best[j] = b;
-        }
-        __syncthreads();                               // every read of this sweep is done
-        int changed = 0;
-#pragma unroll
-        for (int j = 0; j < kTravelCells; ++j) {
-            if (best[j] != mine[j]) {
-                mine[j] = best[j];
-                s_state[(ty + 8 * j + 1) * kTravelHalo + tx + 1] = best[j];
-                changed = 1;
-            }
-        }
-        more = __syncthreads_or(changed) != 0;
-    }
-    // write back; bit k of dirty: the neighbour tile in direction k reads a changed cell as halo
-    unsigned dirty = 0;
-#pragma unroll
-    for (int j = 0; j < kTravelCells; ++j) {
-        if (mine[j] == first[j]) continue;
-        const int lr = ty + 8 * j, lc = tx;
-        travel_store(&state[(int64_t)(r0 + 1 + lr) * W + (c0 + 1 + lc)], mine[j]);     // changed cells lie inside the map
-        dirty |= travel_halo_readers<kTravelTile>(lr, lc);
-    }
-    if (dirty) atomicOr(&s_dirty, dirty);
-    __syncthreads();
-    if (threadIdx.x < 8) {
-        const int k = threadIdx.x;
-        const int ur = tile_r + travel_dr(k), uc = tile_c + travel_dc(k);
-        if ((s_dirty >> k & 1u) && ur >= 0 && ur < th && uc >= 0 && uc < tw) travel_mark(next, ur * tw + uc, activated);
-    } else if (threadIdx.x == 8 && more) {
-        travel_mark(next, blockIdx.x, activated);      // the sweep cap: go on in the next round
-    }
+    __shared__ TravelTileLds lds;
+    if (!travel_take_mark(cur, &lds.active, &lds.dirty)) return;
+    const int tile_r = blockIdx.x / travel_tiles(W), tile_c = blockIdx.x - tile_r * travel_tiles(W);
+    travel_tile_relax<false, false>(lds, pass, nullptr, 0, state, H, W, tile_r, tile_c, 0, next, activated);
 }
 
 // the two int32 planes, the number of reached cells, and the host's counters into d_stats = [rounds, tile runs, reached, any source]
@@ -204,18 +99,14 @@ __global__ __launch_bounds__(256) void travel_decay_kernel(const int32_t* __rest
     block_minmax_atomic<256>(mn, mx, minmax, s_red);
 }
 
-static int travel_check_shape(const char* what, int H, int W) {
+int travel_check_shape(const char* what, int H, int W) {
     AVL_REQUIRE(H > 0 && W > 0 && H <= kTravelMaxSide && W <= kTravelMaxSide, "%s: bad shape %d x %d (sides 1 .. %d)", what, H, W,
                 kTravelMaxSide);
     return AVL_OK;
 }
 
-struct TravelLayout {
-    size_t hdr, flags, pass, state, total;
-};
-
-static TravelLayout travel_layout(int H, int W) {
-    const size_t tiles = (size_t)((H + kTravelTile - 1) / kTravelTile) * (size_t)((W + kTravelTile - 1) / kTravelTile);
+TravelLayout travel_layout(int H, int W) {
+    const size_t tiles = (size_t)travel_tiles(H) * (size_t)travel_tiles(W);
     Carver c;
     TravelLayout l;
     l.hdr = c.take(kTravelHdrWords * sizeof(unsigned));
@@ -224,6 +115,14 @@ static TravelLayout travel_layout(int H, int W) {
     l.state = c.take((size_t)H * W * sizeof(unsigned long long));
     l.total = c.total() + 256;                        // the entry point aligns the base itself
     return l;
+}
+
+int travel_unpack(const unsigned long long* state, int64_t n, int32_t* d_straight, int32_t* d_diagonal, int64_t rounds, int64_t tile_runs,
+                  bool any_source, int64_t* d_stats, hipStream_t st) {
+    hipLaunchKernelGGL(travel_unpack_kernel, dim3(stride_blocks(n)), dim3(256), 0, st, state, n, d_straight, d_diagonal, (long long)rounds,
+                       (long long)tile_runs, (int)any_source, reinterpret_cast<unsigned long long*>(d_stats));
+    AVL_HIP_CHECK(hipGetLastError());
+    return AVL_OK;
 }
 
 }  // namespace avl
@@ -256,8 +155,7 @@ int avl_travel2d(const uint8_t* d_free, int64_t ld_free, const uint8_t* d_source
     unsigned* flags = (unsigned*)(base + l.flags);
     uint8_t* pass = (uint8_t*)(base + l.pass);
     unsigned long long* state = (unsigned long long*)(base + l.state);
-    const int tw = (W + kTravelTile - 1) / kTravelTile, th = (H + kTravelTile - 1) / kTravelTile;
-    const unsigned tiles = (unsigned)(tw * th);        // at most 512 * 512
+    const unsigned tiles = (unsigned)(travel_tiles(W) * travel_tiles(H));      // at most 512 * 512
     const int64_t n = (int64_t)H * W;
 
     AVL_HIP_CHECK(hipMemsetAsync(hdr, 0, l.pass - l.hdr, st));              // the header and both mark buffers
@@ -277,11 +175,7 @@ int avl_travel2d(const uint8_t* d_free, int64_t ld_free, const uint8_t* d_source
         },
         &rounds, &tile_runs, host);
     if (rc != AVL_OK) return rc;
-    hipLaunchKernelGGL(travel_unpack_kernel, dim3(stride_blocks(n)), dim3(256), 0, st, (const unsigned long long*)state, n, d_straight,
-                       d_diagonal, (long long)rounds, (long long)tile_runs, (int)(host[kTravelHdrAny] != 0),
-                       reinterpret_cast<unsigned long long*>(d_stats));
-    AVL_HIP_CHECK(hipGetLastError());
-    return AVL_OK;
+    return travel_unpack(state, n, d_straight, d_diagonal, rounds, tile_runs, host[kTravelHdrAny] != 0, d_stats, st);
 }
 
 int avl_travel_decay_2d(const int32_t* d_straight, const int32_t* d_diagonal, int H, int W, double cell_size, double decay_rate,

@@ -6,17 +6,18 @@
 // and its cells may lie on obstacles.
 //
 // Work.  One work item is a (field, tile) pair: a flat grid of K * tiles workgroups, workgroup k * tiles + t runs tile t of field k
-// when mark [k * tiles + t] of the round is set and returns at once otherwise.  The tile's body is travel_round_kernel's on the
-// helpers of avl_travel_tile.h.  Two mark buffers of K * tiles words, one `activated` counter per round for the whole batch, and
-// the host loop travel_run_rounds with tiles := K * tiles: the batch has converged when a round wakes no pair, so it runs as many
-// rounds as its slowest field and shares every launch and every synchronisation.
+// when mark [k * tiles + t] of the round is set and returns at once otherwise.  The tile's body is the shared one of
+// avl_travel_tile.h, here travel_tile_relax<false, true>: unit steps, the source bit read off the state word.  Two mark buffers
+// of K * tiles words, one `activated` counter per round for the whole batch, and the host loop travel_run_rounds with
+// tiles := K * tiles: the batch has converged when a round wakes no pair, so it runs as many rounds as its slowest field and
+// shares every launch and every synchronisation.
 //
 // What differs from the single field:
 //   * The free bits are ONE plane of H * W bytes for all K fields (copied out of the caller's strided image once).
 //   * A field's source bit is not stored.  A cell is a source of field k exactly when its state word is (0, 0): the initialisation
 //     writes (0, 0) on the sources alone, every other stored word is "a stored neighbour + a legal step" and so has a + b >= 1, and
-//     a source is never relaxed.  The LDS passability byte is therefore free | (state == 0) << 1 at load time and travel_legal_in
-//     applies unchanged.  A (0, 0) word never changes, so a halo read that races with a neighbour's write-back sees the same bit.
+//     a source is never relaxed.  The LDS passability byte is therefore free | (state == 0) << 1 at load time and the legal-step
+//     rule applies unchanged.  A (0, 0) word never changes, so a halo read that races with a neighbour's write-back sees the same bit.
 //   * A mark made by field k stays inside field k: the neighbour tile (ur, uc) is bounds-checked against (th, tw) first and then
 //     offset by k * tiles, so no index of field k can fall into the marks of field k - 1 or k + 1.
 //
@@ -34,14 +35,8 @@
 
 namespace avl {
 
-constexpr int kManyMaxSide = 16384;              // kTravelMaxSide
 constexpr int kManyMaxFields = 1024;
 constexpr int64_t kManyMaxPairs = 1ll << 28;     // K * tiles: the flat grid
-constexpr int kManyTile = 32;                    // avl_travel.hip's geometry: the planes must be its planes byte for byte
-constexpr int kManyThreads = 256;
-constexpr int kManyCells = kManyTile * kManyTile / kManyThreads;   // cells per thread: 4, rows ty, ty + 8, ty + 16, ty + 24
-constexpr int kManySweeps = 64;
-constexpr int kManyHalo = kManyTile + 2;
 
 // the shared free plane, every state word unreached, and zeros in the header, both mark buffers (`words` uint32 from hdr on) and the
 // stats: one launch instead of a kernel and two memsets.  `span` = the largest of the four counts.
@@ -66,7 +61,7 @@ __global__ __launch_bounds__(256) void many_init_kernel(const uint8_t* __restric
 __global__ __launch_bounds__(256) void many_sources_kernel(const int64_t* __restrict__ offsets, const int32_t* __restrict__ cells, int K,
                                                            int64_t L, int H, int W, unsigned long long* __restrict__ state,
                                                            unsigned* __restrict__ flags, unsigned* __restrict__ hdr) {
-    const int tw = (W + kManyTile - 1) / kManyTile, th = (H + kManyTile - 1) / kManyTile;
+    const int tw = travel_tiles(W), th = travel_tiles(H);
     const int64_t n = (int64_t)H * W, tiles = (int64_t)tw * th;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < L; i += (int64_t)gridDim.x * blockDim.x) {
         int lo = 0, hi = K;                           // offsets[lo] <= i < offsets[hi] when the offsets are CSR offsets
@@ -79,98 +74,21 @@ __global__ __launch_bounds__(256) void many_sources_kernel(const int64_t* __rest
         if (r < 0 || r >= H || c < 0 || c >= W) continue;
         travel_store(&state[(int64_t)lo * n + (int64_t)r * W + c], 0ull);
         if (hdr[kTravelHdrAny] == 0u) atomicExch(&hdr[kTravelHdrAny], 1u);
-        travel_mark_around<kManyTile>(flags + (int64_t)lo * tiles, r, c, th, tw, &hdr[kTravelHdrInit]);
+        travel_mark_around<kTravelTile>(flags + (int64_t)lo * tiles, r, c, th, tw, &hdr[kTravelHdrInit]);
     }
 }
 
 // One round of every (field, tile) pair: see the head of the file.  cur / next: the active marks of this round and of the coming one.
-__global__ __launch_bounds__(kManyThreads) void many_round_kernel(const uint8_t* __restrict__ freep, unsigned long long* state_all, int H, int W,
-                                                                  unsigned tiles, unsigned* __restrict__ cur, unsigned* __restrict__ next,
-                                                                  unsigned* __restrict__ activated) {
-    __shared__ unsigned long long s_state[kManyHalo * kManyHalo];
-    __shared__ uint8_t s_pass[kManyHalo * kManyHalo];
-    __shared__ unsigned s_active, s_dirty;
-    if (threadIdx.x == 0) {
-        s_active = cur[blockIdx.x];
-        s_dirty = 0u;
-        if (s_active) cur[blockIdx.x] = 0u;           // this buffer takes the marks of the round after the next
-    }
-    __syncthreads();
-    if (s_active == 0u) return;
-    const int tw = (W + kManyTile - 1) / kManyTile, th = (H + kManyTile - 1) / kManyTile;
+__global__ __launch_bounds__(kTravelThreads) void many_round_kernel(const uint8_t* __restrict__ freep, unsigned long long* state_all, int H, int W,
+                                                                    unsigned tiles, unsigned* __restrict__ cur, unsigned* __restrict__ next,
+                                                                    unsigned* __restrict__ activated) {
+    __shared__ TravelTileLds lds;
+    if (!travel_take_mark(cur, &lds.active, &lds.dirty)) return;
     const unsigned field = blockIdx.x / tiles, tile = blockIdx.x - field * tiles;
-    const int tile_r = (int)tile / tw, tile_c = (int)tile - tile_r * tw;
-    unsigned long long* state = state_all + (int64_t)field * ((int64_t)H * W);
-    const int r0 = tile_r * kManyTile - 1, c0 = tile_c * kManyTile - 1;        // the halo's origin
-#pragma unroll
-    for (int k = 0; k < (kManyHalo * kManyHalo + kManyThreads - 1) / kManyThreads; ++k) {
-        const int i = k * kManyThreads + threadIdx.x;
-        if (i < kManyHalo * kManyHalo) {
-            const int r = r0 + i / kManyHalo, c = c0 + i % kManyHalo;
-            const bool in = r >= 0 && r < H && c >= 0 && c < W;
-            const unsigned long long s = in ? travel_load(&state[(int64_t)r * W + c]) : kTravelUnreached;
-            s_state[i] = s;
-            s_pass[i] = in ? (uint8_t)(freep[(int64_t)r * W + c] | (s == 0ull ? kTravelSource : 0)) : (uint8_t)0;
-        }
-    }
-    __syncthreads();
-    const int tx = threadIdx.x % kManyTile, ty = threadIdx.x / kManyTile;
-    unsigned long long first[kManyCells], mine[kManyCells];
-    unsigned legal[kManyCells];                       // bit k: the step from the neighbour in direction k to this cell is legal
-#pragma unroll
-    for (int j = 0; j < kManyCells; ++j) {
-        const int at = (ty + 8 * j + 1) * kManyHalo + tx + 1;
-        first[j] = mine[j] = s_state[at];
-        legal[j] = travel_legal_in<kManyHalo>(s_pass, at);
-    }
-    bool more = true;
-    for (int sweep = 0; sweep < kManySweeps && more; ++sweep) {
-        unsigned long long best[kManyCells];
-#pragma unroll
-        for (int j = 0; j < kManyCells; ++j) {
-            const int at = (ty + 8 * j + 1) * kManyHalo + tx + 1;
-            unsigned long long b = mine[j];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                if (!(legal[j] >> k & 1u)) continue;
-                const unsigned long long s = s_state[at + travel_dr(k) * kManyHalo + travel_dc(k)];
-                if (s == kTravelUnreached) continue;
-                const unsigned long long cand = s + ((k & 1) ? kTravelDiagonal : kTravelStraight);
-                if (b == kTravelUnreached || travel_less(cand, b)) b = cand;
-            }
-            best[j] = b;
-        }
-        __syncthreads();                               // every read of this sweep is done
-        int changed = 0;
-#pragma unroll
-        for (int j = 0; j < kManyCells; ++j) {
-            if (best[j] != mine[j]) {
-                mine[j] = best[j];
-                s_state[(ty + 8 * j + 1) * kManyHalo + tx + 1] = best[j];
-                changed = 1;
-            }
-        }
-        more = __syncthreads_or(changed) != 0;
-    }
-    // write back; bit k of dirty: the neighbour tile in direction k reads a changed cell as halo
-    unsigned dirty = 0;
-#pragma unroll
-    for (int j = 0; j < kManyCells; ++j) {
-        if (mine[j] == first[j]) continue;
-        const int lr = ty + 8 * j, lc = tx;
-        travel_store(&state[(int64_t)(r0 + 1 + lr) * W + (c0 + 1 + lc)], mine[j]);     // changed cells lie inside the map
-        dirty |= travel_halo_readers<kManyTile>(lr, lc);
-    }
-    if (dirty) atomicOr(&s_dirty, dirty);
-    __syncthreads();
-    const int base = (int)(field * tiles);            // the field's own marks: K * tiles <= 2^28
-    if (threadIdx.x < 8) {
-        const int k = threadIdx.x;
-        const int ur = tile_r + travel_dr(k), uc = tile_c + travel_dc(k);
-        if ((s_dirty >> k & 1u) && ur >= 0 && ur < th && uc >= 0 && uc < tw) travel_mark(next, base + ur * tw + uc, activated);
-    } else if (threadIdx.x == 8 && more) {
-        travel_mark(next, (int)blockIdx.x, activated);  // the sweep cap: go on in the next round
-    }
+    const int tile_r = (int)tile / travel_tiles(W), tile_c = (int)tile - tile_r * travel_tiles(W);
+    // the field's own words and marks: K * tiles <= 2^28
+    travel_tile_relax<false, true>(lds, freep, nullptr, 0, state_all + (int64_t)field * ((int64_t)H * W), H, W, tile_r, tile_c,
+                                   (int)(field * tiles), next, activated);
 }
 
 // the two int32 planes of field blockIdx.y, its number of reached cells, and the host's counters into
@@ -302,7 +220,8 @@ __global__ __launch_bounds__(256) void many_sound_normalize_kernel(const float* 
 }
 
 static int many_check_shape(const char* what, int H, int W, int K) {
-    AVL_REQUIRE(H > 0 && W > 0 && H <= kManyMaxSide && W <= kManyMaxSide, "%s: bad shape %d x %d (sides 1 .. %d)", what, H, W, kManyMaxSide);
+    int rc = travel_check_shape(what, H, W);
+    if (rc != AVL_OK) return rc;
     AVL_REQUIRE(K >= 1 && K <= kManyMaxFields, "%s: %d fields (1 .. %d)", what, K, kManyMaxFields);
     return AVL_OK;
 }
@@ -312,7 +231,7 @@ struct ManyLayout {
 };
 
 static ManyLayout many_layout(int H, int W, int K) {
-    const size_t tiles = (size_t)((H + kManyTile - 1) / kManyTile) * (size_t)((W + kManyTile - 1) / kManyTile);
+    const size_t tiles = (size_t)travel_tiles(H) * (size_t)travel_tiles(W);
     Carver c;
     ManyLayout l;
     l.hdr = c.take(kTravelHdrWords * sizeof(unsigned));
@@ -337,14 +256,10 @@ int avl_travel2d_many(const uint8_t* d_free, int64_t ld_free, int H, int W, cons
     AVL_REQUIRE(d_straight && d_diagonal && d_stats, "avl_travel2d_many: null output plane or stats pointer");
     AVL_REQUIRE(ld_free >= W, "avl_travel2d_many: free rows of %lld cells cannot hold %d columns", (long long)ld_free, W);
     AVL_REQUIRE(L >= K && L <= (1ll << 40), "avl_travel2d_many: %lld cells for %d sets (every set holds one or more)", (long long)L, K);
-    const int tw = (W + kManyTile - 1) / kManyTile, th = (H + kManyTile - 1) / kManyTile;
-    const int64_t tiles1 = (int64_t)tw * th;
+    const int64_t tiles1 = (int64_t)travel_tiles(W) * travel_tiles(H);
     AVL_REQUIRE((int64_t)K * tiles1 <= kManyMaxPairs, "avl_travel2d_many: %d fields of %lld tiles exceed 2^28 (field, tile) pairs", K,
                 (long long)tiles1);
-    size_t one = 0;
-    rc = avl_travel2d_workspace_bytes(H, W, &one);
-    if (rc != AVL_OK) return rc;
-    const size_t need = (size_t)K * one;
+    const size_t need = (size_t)K * travel_layout(H, W).total;
     const ManyLayout l = many_layout(H, W, K);
     AVL_REQUIRE(ws && ws_bytes >= need, "avl_travel2d_many: workspace of %zu bytes, need %zu (%d x avl_travel2d_workspace_bytes)", ws_bytes,
                 need, K);
@@ -372,7 +287,7 @@ int avl_travel2d_many(const uint8_t* d_free, int64_t ld_free, int H, int W, cons
     rc = travel_run_rounds(
         "avl_travel2d_many", max_rounds, hdr, flags, pairs, st,
         [&](int64_t, unsigned* cur, unsigned* next, unsigned* activated) {
-            hipLaunchKernelGGL(many_round_kernel, dim3(pairs), dim3(kManyThreads), 0, st, (const uint8_t*)freep, state, H, W, tiles, cur, next,
+            hipLaunchKernelGGL(many_round_kernel, dim3(pairs), dim3(kTravelThreads), 0, st, (const uint8_t*)freep, state, H, W, tiles, cur, next,
                                activated);
         },
         &rounds, &tile_runs, host);

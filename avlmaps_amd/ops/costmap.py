@@ -10,7 +10,7 @@ import numpy as np
 from .. import _lib
 from ..device import DeviceArray, as_device
 from ._args import _image_shape, _image_u8, _is_dev, _result, _workspace
-from .travel import _source_mask, TRAVEL_NEIGHBOURS
+from .travel import _field_front, _host_window, _PairField
 
 COST_MAX_CELLS = 1 << 22     # kCostMaxCells: H * W of a cost field, which keeps both sums of prices below 2^30
 COST_MAX_LAYERS = 8          # kCostMaxLayers
@@ -146,43 +146,20 @@ def drop_collinear(walk):
     return keep
 
 
-class CostField:
+class CostField(_PairField):
     """cost_field's result.  straight, diagonal: (H, W) int32 host arrays or DeviceArrays, the summed prices A of the straight and
     B of the diagonal steps of the cheapest legal walk from the nearest source (price A + B * sqrt(2)); (0, 0) on a source, -1 in
     both where no walk ends.  reached: the number of reached cells.  rounds, tile_runs: how many rounds had an active tile and how
     many tiles ran in all -- information about the schedule, not part of the result."""
+    _what = "cost"
 
     def __init__(self, straight, diagonal, shape, reached, rounds, tile_runs, passable, prices, stream=None):
-        self.straight, self.diagonal, self.shape = straight, diagonal, tuple(shape)
-        self.reached, self.rounds, self.tile_runs = int(reached), int(rounds), int(tile_runs)
-        self._passable, self._prices, self._stream, self._host = passable, prices, stream, None
-
-    def planes(self):
-        """(straight, diagonal) as host arrays (a device field is copied once and kept)"""
-        if self._host is None:
-            if isinstance(self.straight, np.ndarray):
-                self._host = (self.straight, self.diagonal)
-            else:
-                self._host = (self.straight.numpy(self._stream), self.diagonal.numpy(self._stream))
-        return self._host
+        super().__init__(straight, diagonal, shape, reached, rounds, tile_runs, stream)
+        self._passable, self._prices = passable, prices
 
     def cost(self) -> np.ndarray:
         """(H, W) float64: float64(A) + float64(B) * sqrt(2), inf where unreached"""
-        a, b = self.planes()
-        d = a.astype(np.float64) + b.astype(np.float64) * np.sqrt(2.0)
-        d[a < 0] = np.inf
-        return d
-
-    def reachable(self) -> np.ndarray:
-        """(H, W) bool: the cells a walk from a source ends on, the sources included"""
-        return self.planes()[0] >= 0
-
-    def _maps_host(self):
-        if callable(self._passable):
-            self._passable = self._passable()
-        if callable(self._prices):
-            self._prices = self._prices()
-        return self._passable, self._prices
+        return self._length()
 
     def descend(self, cell, waypoints=False):
         """The cells of a cheapest walk from `cell` back to a source, [(row, col), ...] from `cell` to the source, on the host:
@@ -190,34 +167,8 @@ class CostField:
         the order TRAVEL_NEIGHBOURS (E, NE, N, NW, W, SW, S, SE) whose pair plus price[v] -- on the straight sum for a straight step,
         on the diagonal sum for a diagonal one -- equals v's pair and from which the step is legal.  waypoints=True keeps the two
         ends and the cells where the direction changes.  ValueError from an unreached cell or one outside the map."""
-        a, b = self.planes()
-        passable, price = self._maps_host()
-        H, W = self.shape
-        r, c = int(cell[0]), int(cell[1])
-        if not (0 <= r < H and 0 <= c < W):
-            raise ValueError(f"descend: cell {(r, c)} lies outside the {H} x {W} map")
-        if a[r, c] < 0:
-            raise ValueError(f"descend: cell {(r, c)} is not reached from any source")
-        walk = [(r, c)]
-        while a[r, c] or b[r, c]:
-            p = int(price[r, c])
-            for dr, dc in TRAVEL_NEIGHBOURS:
-                ur, uc = r + dr, c + dc
-                if not (0 <= ur < H and 0 <= uc < W) or a[ur, uc] < 0:
-                    continue
-                diag = dr != 0 and dc != 0
-                if a[ur, uc] + (0 if diag else p) != a[r, c] or b[ur, uc] + (p if diag else 0) != b[r, c]:
-                    continue
-                if diag and not (passable[ur, c] and passable[r, uc]):
-                    continue
-                r, c = ur, uc
-                break
-            else:
-                raise RuntimeError(f"descend: no predecessor at {(r, c)}: the planes are not a cost field of this map")
-            walk.append((r, c))
-        if waypoints:
-            return drop_collinear(walk)
-        return walk
+        walk = self._descend(cell, self._host_map("_passable"), self._host_map("_prices"))
+        return drop_collinear(walk) if waypoints else walk
 
 
 def _cost_u8(cost, shape):
@@ -246,31 +197,16 @@ def cost_field(free, cost, sources, device=False, stream=None, window=None) -> C
     mismatch and for cells outside the map; more than COST_MAX_CELLS cells or a side above TRAVEL_MAX_SIDE raises AvlError before
     any device work.  The call synchronises the stream."""
     lib = _lib.load()
-    shape = _image_shape(free)
-    if len(shape) != 2 or shape[0] < 1 or shape[1] < 1:
-        raise ValueError(f"expected a non-empty 2-D free map, got shape {shape}")
-    r0, r1, c0, c1 = (0, shape[0], 0, shape[1]) if window is None else (int(v) for v in window)
-    if not (0 <= r0 < r1 <= shape[0] and 0 <= c0 < c1 <= shape[1]):
-        raise ValueError(f"window [{r0}:{r1}, {c0}:{c1}] is not inside the {shape} map")
-    H, W = r1 - r0, c1 - c0
+    free, shape, win, (smask, s_ld, s_off) = _field_front("cost_field", free, window, sources)
+    H, W = win[1] - win[0], win[3] - win[2]
+    off = win[0] * shape[1] + win[2]
     cost = _cost_u8(cost, shape)
-    s = np.asarray(sources) if not _is_dev(sources) else sources
-    cells = not _is_dev(s) and s.shape != shape and s.ndim == 2 and s.shape[1] == 2
-    if cells:
-        smask, s_ld, s_off = _source_mask(s, H, W), W, 0
-    else:
-        smask, s_ld, s_off = _source_mask(s, shape[0], shape[1]), shape[1], r0 * shape[1] + c0
-        if isinstance(smask, np.ndarray) and window is not None and not smask[r0:r1, c0:c1].any():
-            raise ValueError("cost_field: there is no source")
     if H * W > COST_MAX_CELLS:                       # the library's own refusal: it looks at the shape before any pointer
         _lib.check(lib.avl_costfield2d(None, W, None, W, None, W, H, W, None, None, None, None, 0, stream), "avl_costfield2d")
     ws, nws = _workspace(lib.avl_travel2d_workspace_bytes, "avl_costfield2d", H, W)      # the travel field's workspace serves
-    if isinstance(free, np.ndarray) and free.dtype not in (np.dtype(bool), np.dtype(np.uint8)):
-        free = free != 0
     fp, _, fkeep = _image_u8(free, stream)
     cp, _, ckeep = _image_u8(cost, stream)
     sp, _, skeep = _image_u8(smask, stream)
-    off = r0 * shape[1] + c0
     straight, diagonal = DeviceArray((H, W), np.int32), DeviceArray((H, W), np.int32)
     stats = DeviceArray((4,), np.int64)
     _lib.check(lib.avl_costfield2d(fp + off, shape[1], cp + off, shape[1], sp + s_off, s_ld, H, W, straight.ptr, diagonal.ptr, stats.ptr,
@@ -279,16 +215,12 @@ def cost_field(free, cost, sources, device=False, stream=None, window=None) -> C
     if not any_source:
         raise ValueError("cost_field: there is no source")
 
-    def host(x, keep):
-        h = x if isinstance(x, np.ndarray) else (keep.numpy(stream) if isinstance(keep, DeviceArray) else keep.cpu().numpy())
-        return np.asarray(h)[r0:r1, c0:c1]
-
     def prices_host():
-        return host(cost, ckeep).astype(np.uint8)
+        return _host_window(cost, ckeep, stream, win).astype(np.uint8)
 
     def passable_host():
-        return (host(free, fkeep) != 0) & (prices_host() != 0)
+        return (_host_window(free, fkeep, stream, win) != 0) & (prices_host() != 0)
 
-    if device:                                       # the stream is drained: nothing queued still reads the inputs or the workspace
-        return CostField(straight, diagonal, (H, W), reached, rounds, tile_runs, passable_host, prices_host, stream)
-    return CostField(straight.numpy(stream), diagonal.numpy(stream), (H, W), reached, rounds, tile_runs, passable_host, prices_host, stream)
+    if not device:                                   # (device: the stream is drained, nothing queued still reads the inputs or the workspace)
+        straight, diagonal = straight.numpy(stream), diagonal.numpy(stream)
+    return CostField(straight, diagonal, (H, W), reached, rounds, tile_runs, passable_host, prices_host, stream)

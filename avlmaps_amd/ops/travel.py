@@ -18,16 +18,15 @@ UNREACHED = -1
 TRAVEL_NEIGHBOURS = ((0, 1), (-1, 1), (-1, 0), (-1, -1), (0, -1), (1, -1), (1, 0), (1, 1))
 
 
-class TravelField:
-    """travel_field's result.  straight, diagonal: (H, W) int32 host arrays or DeviceArrays, the numbers a and b of straight and
-    diagonal steps of the shortest legal walk from the nearest source (length a + b * sqrt(2)); (0, 0) on a source, UNREACHED in
-    both where no walk ends.  reached: the number of reached cells.  rounds, tile_runs: how many rounds had an active tile and how
-    many tiles ran in all -- information about the schedule, not part of the result."""
+class _PairField:
+    """What TravelField and CostField share: the two int32 planes of a field of pairs, host or device, the length a + b * sqrt(2)
+    and the walk back to a source.  _what names the field in the messages."""
+    _what = "travel"
 
-    def __init__(self, straight, diagonal, shape, reached, rounds, tile_runs, free, stream=None):
+    def __init__(self, straight, diagonal, shape, reached, rounds, tile_runs, stream):
         self.straight, self.diagonal, self.shape = straight, diagonal, tuple(shape)
         self.reached, self.rounds, self.tile_runs = int(reached), int(rounds), int(tile_runs)
-        self._free, self._stream, self._host = free, stream, None
+        self._stream, self._host = stream, None
 
     def planes(self):
         """(straight, diagonal) as host arrays (a device field is copied once and kept)"""
@@ -38,8 +37,7 @@ class TravelField:
                 self._host = (self.straight.numpy(self._stream), self.diagonal.numpy(self._stream))
         return self._host
 
-    def distance(self) -> np.ndarray:
-        """(H, W) float64: float64(a) + float64(b) * sqrt(2), inf where unreached"""
+    def _length(self) -> np.ndarray:
         a, b = self.planes()
         d = a.astype(np.float64) + b.astype(np.float64) * np.sqrt(2.0)
         d[a < 0] = np.inf
@@ -49,17 +47,18 @@ class TravelField:
         """(H, W) bool: the cells a walk from a source ends on, the sources included"""
         return self.planes()[0] >= 0
 
-    def _free_host(self):
-        f = self._free() if callable(self._free) else self._free
-        self._free = f
-        return f
+    def _host_map(self, name):
+        """the host plane kept under `name`, fetched once when it was given as a function"""
+        v = getattr(self, name)
+        if callable(v):
+            v = v()
+            setattr(self, name, v)
+        return v
 
-    def descend(self, cell):
-        """The cells of a shortest walk from `cell` back to a source, [(row, col), ...] from `cell` to the source, on the host.  At
-        each cell it takes the first neighbour in the order TRAVEL_NEIGHBOURS (E, NE, N, NW, W, SW, S, SE) whose pair plus the
-        step equals the cell's pair and from which the step is legal.  ValueError from an unreached cell or one outside the map."""
+    def _descend(self, cell, passable, price=None):
+        """the walk of descend(): a step into v adds price[v] (1 without a price plane) to the straight or to the diagonal sum, and a
+        diagonal step needs both edge-sharing cells passable"""
         a, b = self.planes()
-        free = self._free_host()
         H, W = self.shape
         r, c = int(cell[0]), int(cell[1])
         if not (0 <= r < H and 0 <= c < W):
@@ -68,21 +67,43 @@ class TravelField:
             raise ValueError(f"descend: cell {(r, c)} is not reached from any source")
         walk = [(r, c)]
         while a[r, c] or b[r, c]:
+            p = 1 if price is None else int(price[r, c])
             for dr, dc in TRAVEL_NEIGHBOURS:
                 ur, uc = r + dr, c + dc
                 if not (0 <= ur < H and 0 <= uc < W) or a[ur, uc] < 0:
                     continue
                 diag = dr != 0 and dc != 0
-                if a[ur, uc] + (not diag) != a[r, c] or b[ur, uc] + diag != b[r, c]:
+                if a[ur, uc] + (0 if diag else p) != a[r, c] or b[ur, uc] + (p if diag else 0) != b[r, c]:
                     continue
-                if diag and not (free[ur, c] and free[r, uc]):
+                if diag and not (passable[ur, c] and passable[r, uc]):
                     continue
                 r, c = ur, uc
                 break
             else:
-                raise RuntimeError(f"descend: no predecessor at {(r, c)}: the planes are not a travel field of this map")
+                raise RuntimeError(f"descend: no predecessor at {(r, c)}: the planes are not a {self._what} field of this map")
             walk.append((r, c))
         return walk
+
+
+class TravelField(_PairField):
+    """travel_field's result.  straight, diagonal: (H, W) int32 host arrays or DeviceArrays, the numbers a and b of straight and
+    diagonal steps of the shortest legal walk from the nearest source (length a + b * sqrt(2)); (0, 0) on a source, UNREACHED in
+    both where no walk ends.  reached: the number of reached cells.  rounds, tile_runs: how many rounds had an active tile and how
+    many tiles ran in all -- information about the schedule, not part of the result."""
+
+    def __init__(self, straight, diagonal, shape, reached, rounds, tile_runs, free, stream=None):
+        super().__init__(straight, diagonal, shape, reached, rounds, tile_runs, stream)
+        self._free = free
+
+    def distance(self) -> np.ndarray:
+        """(H, W) float64: float64(a) + float64(b) * sqrt(2), inf where unreached"""
+        return self._length()
+
+    def descend(self, cell):
+        """The cells of a shortest walk from `cell` back to a source, [(row, col), ...] from `cell` to the source, on the host.  At
+        each cell it takes the first neighbour in the order TRAVEL_NEIGHBOURS (E, NE, N, NW, W, SW, S, SE) whose pair plus the
+        step equals the cell's pair and from which the step is legal.  ValueError from an unreached cell or one outside the map."""
+        return self._descend(cell, self._host_map("_free"))
 
 
 def _source_mask(sources, H, W):
@@ -106,6 +127,37 @@ def _source_mask(sources, H, W):
     return mask
 
 
+def _field_front(who, free, window, sources=None):
+    """The front end of travel_field, cost_field and travel_fields: the shape check, the window, and the source mask or cells.
+    -> (free, shape, (r0, r1, c0, c1), source): free with a numeric host image turned into a bool one; source = (mask, its row
+    length, the window's offset in it), None without `sources`.  `who` names the caller in the messages."""
+    shape = _image_shape(free)
+    if len(shape) != 2 or shape[0] < 1 or shape[1] < 1:
+        raise ValueError(f"expected a non-empty 2-D free map, got shape {shape}")
+    r0, r1, c0, c1 = (0, shape[0], 0, shape[1]) if window is None else (int(v) for v in window)
+    if not (0 <= r0 < r1 <= shape[0] and 0 <= c0 < c1 <= shape[1]):
+        raise ValueError(f"window [{r0}:{r1}, {c0}:{c1}] is not inside the {shape} map")
+    if isinstance(free, np.ndarray) and free.dtype not in (np.dtype(bool), np.dtype(np.uint8)):
+        free = free != 0
+    source = None
+    if sources is not None:
+        H, W = r1 - r0, c1 - c0
+        s = np.asarray(sources) if not _is_dev(sources) else sources
+        if not _is_dev(s) and s.shape != shape and s.ndim == 2 and s.shape[1] == 2:      # cells, relative to the window
+            source = (_source_mask(s, H, W), W, 0)
+        else:
+            source = (_source_mask(s, shape[0], shape[1]), shape[1], r0 * shape[1] + c0)
+            if isinstance(source[0], np.ndarray) and window is not None and not source[0][r0:r1, c0:c1].any():
+                raise ValueError(f"{who}: there is no source")
+    return free, shape, (r0, r1, c0, c1), source
+
+
+def _host_window(image, keep, stream, win):
+    """the window of a plane on the host: `image` as the caller gave it, `keep` what _image_u8 kept of a device image"""
+    h = image if isinstance(image, np.ndarray) else (keep.numpy(stream) if isinstance(keep, DeviceArray) else keep.cpu().numpy())
+    return np.asarray(h)[win[0]:win[1], win[2]:win[3]]
+
+
 def travel_field(free, sources, device=False, stream=None, window=None) -> TravelField:
     """The multi-source travel-distance field of DESIGN.md 4.26.  free: 2-D bool / uint8 / numeric image, nonzero = free (the
     convention of Map.obstacles_cropped), host or device.  sources: a mask of the same shape, nonzero = source (a source may lie on
@@ -116,41 +168,26 @@ def travel_field(free, sources, device=False, stream=None, window=None) -> Trave
     ValueError without a source, for a shape mismatch and for cells outside the map; a side above TRAVEL_MAX_SIDE raises AvlError
     before any device work.  The call synchronises the stream."""
     lib = _lib.load()
-    shape = _image_shape(free)
-    if len(shape) != 2 or shape[0] < 1 or shape[1] < 1:
-        raise ValueError(f"expected a non-empty 2-D free map, got shape {shape}")
-    r0, r1, c0, c1 = (0, shape[0], 0, shape[1]) if window is None else (int(v) for v in window)
-    if not (0 <= r0 < r1 <= shape[0] and 0 <= c0 < c1 <= shape[1]):
-        raise ValueError(f"window [{r0}:{r1}, {c0}:{c1}] is not inside the {shape} map")
-    H, W = r1 - r0, c1 - c0
-    s = np.asarray(sources) if not _is_dev(sources) else sources
-    cells = not _is_dev(s) and s.shape != shape and s.ndim == 2 and s.shape[1] == 2
-    if cells:
-        smask, s_ld, s_off = _source_mask(s, H, W), W, 0
-    else:
-        smask, s_ld, s_off = _source_mask(s, shape[0], shape[1]), shape[1], r0 * shape[1] + c0
-        if isinstance(smask, np.ndarray) and window is not None and not smask[r0:r1, c0:c1].any():
-            raise ValueError("travel_field: there is no source")
+    free, shape, win, (smask, s_ld, s_off) = _field_front("travel_field", free, window, sources)
+    H, W = win[1] - win[0], win[3] - win[2]
+    off = win[0] * shape[1] + win[2]
     ws, nws = _workspace(lib.avl_travel2d_workspace_bytes, "avl_travel2d", H, W)
-    if isinstance(free, np.ndarray) and free.dtype not in (np.dtype(bool), np.dtype(np.uint8)):
-        free = free != 0
     fp, _, fkeep = _image_u8(free, stream)
     sp, _, skeep = _image_u8(smask, stream)
     straight, diagonal = DeviceArray((H, W), np.int32), DeviceArray((H, W), np.int32)
     stats = DeviceArray((4,), np.int64)
-    _lib.check(lib.avl_travel2d(fp + r0 * shape[1] + c0, shape[1], sp + s_off, s_ld, H, W, straight.ptr, diagonal.ptr, stats.ptr, ws.ptr,
-                                nws, stream), "avl_travel2d")
+    _lib.check(lib.avl_travel2d(fp + off, shape[1], sp + s_off, s_ld, H, W, straight.ptr, diagonal.ptr, stats.ptr, ws.ptr, nws, stream),
+               "avl_travel2d")
     rounds, tile_runs, reached, any_source = (int(v) for v in stats.numpy(stream))
     if not any_source:
         raise ValueError("travel_field: there is no source")
 
     def free_host():
-        f = free if isinstance(free, np.ndarray) else (fkeep.numpy(stream) if isinstance(fkeep, DeviceArray) else fkeep.cpu().numpy())
-        return np.asarray(f)[r0:r1, c0:c1] != 0
+        return _host_window(free, fkeep, stream, win) != 0
 
-    if device:                                       # the stream is drained: nothing queued still reads the inputs or the workspace
-        return TravelField(straight, diagonal, (H, W), reached, rounds, tile_runs, free_host, stream)
-    return TravelField(straight.numpy(stream), diagonal.numpy(stream), (H, W), reached, rounds, tile_runs, free_host, stream)
+    if not device:                                   # (device: the stream is drained, nothing queued still reads the inputs or the workspace)
+        straight, diagonal = straight.numpy(stream), diagonal.numpy(stream)
+    return TravelField(straight, diagonal, (H, W), reached, rounds, tile_runs, free_host, stream)
 
 
 def travel_decay_2d(field: TravelField, decay_rate, cell_size=1.0, normalize=False, device=False, stream=None):

@@ -8,9 +8,9 @@ import numpy as np
 
 from .. import _lib
 from ..device import DeviceArray, DeviceView, as_device
-from ._args import _image_shape, _image_u8
+from ._args import _image_u8
 from .fields import _check_decay, GoalField
-from .travel import TravelField
+from .travel import _field_front, _host_window, TravelField
 
 TRAVEL_MANY_MAX_FIELDS = 1024    # kManyMaxFields
 TRAVEL_MANY_MAX_PAIRS = 1 << 28  # kManyMaxPairs: (field, tile) pairs of one batch
@@ -52,16 +52,6 @@ def _sets_to_device(offsets, cells, stream):
     packed[len(offsets):].view(np.int32)[:] = cells.ravel()
     d = DeviceArray.from_numpy(packed, stream)
     return d.ptr, d.ptr + 8 * len(offsets), d
-
-
-def _window(free, window):
-    shape = _image_shape(free)
-    if len(shape) != 2 or shape[0] < 1 or shape[1] < 1:
-        raise ValueError(f"expected a non-empty 2-D free map, got shape {shape}")
-    r0, r1, c0, c1 = (0, shape[0], 0, shape[1]) if window is None else (int(v) for v in window)
-    if not (0 <= r0 < r1 <= shape[0] and 0 <= c0 < c1 <= shape[1]):
-        raise ValueError(f"window [{r0}:{r1}, {c0}:{c1}] is not inside the {shape} map")
-    return shape, r0, r1, c0, c1
 
 
 class TravelFields:
@@ -113,8 +103,9 @@ def travel_fields(free, offsets, cells, device=False, stream=None, window=None) 
     offsets, an empty set, and a cell outside the map or the window; more than TRAVEL_MANY_MAX_FIELDS sets or a side above
     TRAVEL_MAX_SIDE raise AvlError before any device work.  The call synchronises the stream."""
     lib = _lib.load()
-    shape, r0, r1, c0, c1 = _window(free, window)
-    H, W = r1 - r0, c1 - c0
+    free, shape, win, _ = _field_front("travel_fields", free, window)
+    H, W = win[1] - win[0], win[3] - win[2]
+    off = win[0] * shape[1] + win[2]
     offsets, cells = _csr_sets("travel_fields", offsets, cells, H, W)
     K, L = len(offsets) - 1, len(cells)
     if K > TRAVEL_MANY_MAX_FIELDS:
@@ -124,24 +115,20 @@ def travel_fields(free, offsets, cells, device=False, stream=None, window=None) 
     _lib.require_gpu()
     nws = K * one.value
     ws = DeviceArray((nws,), np.uint8)
-    if isinstance(free, np.ndarray) and free.dtype not in (np.dtype(bool), np.dtype(np.uint8)):
-        free = free != 0
     fp, _, fkeep = _image_u8(free, stream)
     op, cp, k1 = _sets_to_device(offsets, cells, stream)
     straight, diagonal = DeviceArray((K, H, W), np.int32), DeviceArray((K, H, W), np.int32)
     stats = DeviceArray((2 + K,), np.int64)
-    _lib.check(lib.avl_travel2d_many(fp + r0 * shape[1] + c0, shape[1], H, W, op, cp, K, L, straight.ptr, diagonal.ptr, stats.ptr, ws.ptr,
+    _lib.check(lib.avl_travel2d_many(fp + off, shape[1], H, W, op, cp, K, L, straight.ptr, diagonal.ptr, stats.ptr, ws.ptr,
                                      nws, stream), "avl_travel2d_many")
     st = stats.numpy(stream)
 
     def free_host():
-        f = free if isinstance(free, np.ndarray) else (fkeep.numpy(stream) if isinstance(fkeep, DeviceArray) else fkeep.cpu().numpy())
-        return np.asarray(f)[r0:r1, c0:c1] != 0
+        return _host_window(free, fkeep, stream, win) != 0
 
-    free_dev = (fkeep, fp + r0 * shape[1] + c0, shape[1])
-    if device:                                       # the stream is drained: nothing queued still reads the inputs or the workspace
-        return TravelFields(straight, diagonal, (H, W), st[2:], st[0], st[1], free_host, free_dev, stream)
-    return TravelFields(straight.numpy(stream), diagonal.numpy(stream), (H, W), st[2:], st[0], st[1], free_host, free_dev, stream)
+    if not device:                                   # (device: the stream is drained, nothing queued still reads the inputs or the workspace)
+        straight, diagonal = straight.numpy(stream), diagonal.numpy(stream)
+    return TravelFields(straight, diagonal, (H, W), st[2:], st[0], st[1], free_host, (fkeep, fp + off, shape[1]), stream)
 
 
 class TravelArrivals:
@@ -199,8 +186,8 @@ def sound_travel_field(free, offsets, cells, peaks, decay_rate, chunk=64, window
     `chunk`.  Segments with peak 0 add exactly +0 and are skipped.  -> GoalField, field (H, W) float32 and its [min, max]."""
     lib = _lib.load()
     decay = _check_decay(decay_rate)
-    shape, r0, r1, c0, c1 = _window(free, window)
-    H, W = r1 - r0, c1 - c0
+    _, _, win, _ = _field_front("sound_travel_field", free, window)
+    H, W = win[1] - win[0], win[3] - win[2]
     peaks = np.ascontiguousarray(peaks, dtype=np.float32).reshape(-1)
     offsets, cells = _csr_sets("sound_travel_field", offsets, cells, H, W)
     if len(offsets) - 1 != len(peaks):
@@ -224,7 +211,7 @@ def sound_travel_field(free, offsets, cells, peaks, decay_rate, chunk=64, window
         sizes = offsets[seg + 1] - offsets[seg]
         offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
         cs = np.concatenate([cells[offsets[s]:offsets[s + 1]] for s in seg])
-        tf = travel_fields(fdev, offs, cs, device=True, stream=stream, window=(r0, r1, c0, c1))
+        tf = travel_fields(fdev, offs, cs, device=True, stream=stream, window=win)
         pp, _, keep = as_device(peaks[seg], np.float32, stream)
         _lib.check(lib.avl_travel_sound2d(tf.straight.ptr, tf.diagonal.ptr, len(seg), H, W, pp, decay, int(at == 0), field.ptr, mm.ptr,
                                           stream), "avl_travel_sound2d")

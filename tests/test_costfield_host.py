@@ -132,8 +132,13 @@ def test_new_names_exist_with_their_signatures():
     m.obstacles_cropped = np.ones((4, 5), np.uint8)
     with pytest.raises(ValueError, match="by name needs a VLMap"):
         m._avoid_distance("carpet")
-    src = (ROOT / "avlmaps_amd" / "csrc" / "avl_costfield.hip").read_text()
-    assert f"kCostTile = {ops.TRAVEL_TILE};" in src and f"kCostSweeps = {ops.TRAVEL_SWEEPS};" in src
+    # the tile geometry, the order and the round's body are the travel field's by one definition, not by an equal copy
+    csrc = ROOT / "avlmaps_amd" / "csrc"
+    head, src = (csrc / "avl_travel_tile.h").read_text(), (csrc / "avl_costfield.hip").read_text()
+    assert f"constexpr int kTravelTile = {ops.TRAVEL_TILE};" in head and f"constexpr int kTravelSweeps = {ops.TRAVEL_SWEEPS};" in head
+    assert not re.search(r"constexpr int k(Travel|Cost|Many|Grow)(Tile|Threads|Cells|Sweeps|Halo|MaxSide)\b", src)
+    assert '#include "avl_travel_tile.h"' in src and "travel_tile_relax<" in src and "__syncthreads_or" not in src
+    assert all("cost_less" not in p.read_text() for p in csrc.iterdir() if p.is_file())
 
 
 def test_python_checks_come_before_the_device(lib):

@@ -84,8 +84,10 @@ def test_the_tile_scheme_is_shared_not_copied():
         assert '#include "avl_travel_tile.h"' in src and "travel_legal_in<" in src and "travel_run_rounds(" in src, name
         assert "int travel_dr(" not in src and "void travel_mark(" not in src, name
     src = (csrc / "avl_rooms.hip").read_text()
-    assert f"kGrowTile = {ops.TRAVEL_TILE};" in src and f"kGrowSweeps = {ops.TRAVEL_SWEEPS};" in src
-    assert "avl_travel2d(" in src                                                    # phase 1 is the existing entry point
+    assert f"constexpr int kTravelTile = {ops.TRAVEL_TILE};" in head and f"constexpr int kTravelSweeps = {ops.TRAVEL_SWEEPS};" in head
+    assert not re.search(r"constexpr int k(Travel|Cost|Many|Grow)(Tile|Threads|Cells|Sweeps|Halo|MaxSide)\b", src)
+    assert "travel_take_mark(" in src and "travel_wake(" in src                      # the round's prologue and epilogue are the header's
+    assert "avl_travel2d(" in src                                                   # phase 1 is the existing entry point
 
 
 def test_arguments_are_refused_before_any_device_work(lib):

@@ -121,8 +121,14 @@ def test_new_names_exist_with_their_signatures():
     assert _params(AVLMap.index_goal_2d_travel) == [("self", E), ("obj", None), ("area", None), ("sound", None), ("decay_rates", None),
                                                     ("want_heat", True), ("start", None), ("start_decay_rate", None)]
     # the kernel's tile and sweep cap, as the tests state them
-    src = (ROOT / "avlmaps_amd" / "csrc" / "avl_travel.hip").read_text()
-    assert f"kTravelTile = {ops.TRAVEL_TILE};" in src and f"kTravelSweeps = {ops.TRAVEL_SWEEPS};" in src
+    # ... which the shared header alone defines; the source holds the kernel as a call of the shared body, not a sweep loop
+    csrc = ROOT / "avlmaps_amd" / "csrc"
+    head, src = (csrc / "avl_travel_tile.h").read_text(), (csrc / "avl_travel.hip").read_text()
+    for name, value in (("Tile", ops.TRAVEL_TILE), ("Sweeps", ops.TRAVEL_SWEEPS), ("Threads", 256), ("MaxSide", ops.TRAVEL_MAX_SIDE)):
+        assert f"constexpr int kTravel{name} = {value};" in head, name
+    assert not re.search(r"constexpr int k(Travel|Cost|Many|Grow)(Tile|Threads|Cells|Sweeps|Halo|MaxSide)\b", src)
+    assert '#include "avl_travel_tile.h"' in src and "travel_tile_relax<" in src and "__syncthreads_or" not in src
+    assert head.count("bool travel_less") == 1 and "bool travel_less" not in src
 
 
 def test_python_checks_come_before_the_device(lib):

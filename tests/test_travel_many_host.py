@@ -143,17 +143,24 @@ def test_entry_points_refuse_bad_arguments_before_any_device_work():
 
 def test_the_batch_kernel_has_the_single_fields_geometry():
     from avlmaps_amd import ops
-    single = (ROOT / "avlmaps_amd" / "csrc" / "avl_travel.hip").read_text()
-    many = (ROOT / "avlmaps_amd" / "csrc" / "avl_travel_many.hip").read_text()
+    """... because there is one geometry and one body: the header's, which the sources of all four families use and none repeats"""
+    csrc = ROOT / "avlmaps_amd" / "csrc"
+    head = (csrc / "avl_travel_tile.h").read_text()
+    many = (csrc / "avl_travel_many.hip").read_text()
 
     def const(text, name):
         return int(re.search(rf"constexpr int {name} = (\d+);", text).group(1))
-    assert const(many, "kManyTile") == const(single, "kTravelTile") == ops.TRAVEL_TILE
-    assert const(many, "kManySweeps") == const(single, "kTravelSweeps") == ops.TRAVEL_SWEEPS
-    assert const(many, "kManyThreads") == const(single, "kTravelThreads")
-    assert const(many, "kManyMaxSide") == const(single, "kTravelMaxSide") == ops.TRAVEL_MAX_SIDE
+    assert const(head, "kTravelTile") == ops.TRAVEL_TILE and const(head, "kTravelSweeps") == ops.TRAVEL_SWEEPS
+    assert const(head, "kTravelThreads") == 256 and const(head, "kTravelMaxSide") == ops.TRAVEL_MAX_SIDE
     assert const(many, "kManyMaxFields") == ops.TRAVEL_MANY_MAX_FIELDS
-    assert "travel_less" in many and "bool travel_less" not in many and "bool travel_less" not in single      # one definition, in the header
+    for name in ("avl_travel.hip", "avl_costfield.hip", "avl_travel_many.hip", "avl_rooms.hip"):
+        src = (csrc / name).read_text()
+        assert not re.search(r"constexpr int k(Travel|Cost|Many|Grow)(Tile|Threads|Cells|Sweeps|Halo|MaxSide)\b", src), name
+        assert "bool travel_less" not in src and "cost_less" not in src, name
+        if name != "avl_rooms.hip":                                               # the three field families: no sweep loop of their own
+            assert '#include "avl_travel_tile.h"' in src and "travel_tile_relax<" in src and "__syncthreads_or" not in src, name
+    assert head.count("bool travel_less") == 1 and "cost_less" not in head          # one definition, in the header
+    assert "travel_less" in many                                                    # (the arrivals compare with it)
 
 
 # ------------------------------------------------------------------ the app's flags
