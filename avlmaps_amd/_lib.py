@@ -266,6 +266,11 @@ _SIGS = {
     "avl_travel_arrive": (C.c_int, [_vp, _i64, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _i64, _vp, _vp, _vp, _vp, _vp]),
     "avl_travel_sound2d": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _f64, C.c_int, _vp, _vp, _vp]),
     "avl_travel_sound_normalize": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp]),
+    # comparing two voxel maps on the cell index (csrc/avl_mapdiff.hip): upstream has no counterpart; every buffer is an output sized
+    # by the voxel count and the workspace is the index, so there is no size query
+    "avl_map_match_cells": (C.c_int, [_vp, _sz, _i64, C.c_int, C.c_int, _vp, _i64, _vp, C.c_int, _vp, _vp, _vp]),
+    "avl_row_dots_f32": (C.c_int, [_vp, _i64, _vp, _i64, C.c_int, _vp, _vp, _vp]),
+    "avl_map_diff_status": (C.c_int, [_vp, _vp, _i64, _f64, _vp, C.c_int, _vp, _vp, _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -4,6 +4,8 @@
                                          [--prune --out <dir>] [--render PNG] [--config YAML]
                                          [--register [--register-angle DEG] [--register-step DEG] [--register-radius M]
                                                      [--register-min-fraction F]]
+                                         [--compare OTHER_SCENE_DIR [--compare-radius R] [--compare-threshold T]
+                                                    [--compare-shift DR DC DH] [--compare-json PATH]]
 
 Loads <scene>/vlmap/vlmaps.h5df and walks the depth rays of the scene's frames, then of every --revisit directory (the same
 dataset layout, poses.txt in the scene's world frame), through the map's voxels (Map.audit_visibility): per voxel
@@ -16,7 +18,15 @@ itself).  --render writes a top-down PNG of the map's columns: grey = kept voxel
 of up to --register-angle degrees in steps of --register-step and whole-cell shifts of up to --register-radius metres) and audits
 it under the correction found, for a recording whose poses.txt is NOT in the scene's world frame.  The JSON line then carries
 "registration": one {dir, angle_deg, shift_cells, score, valid, fraction} per revisit.  A revisit of which fewer than
---register-min-fraction of the points land on occupied cells is not audited under a bad pose: the app stops with a message."""
+--register-min-fraction of the points land on occupied cells is not audited under a bad pose: the app stops with a message.
+
+--compare loads the map under OTHER_SCENE_DIR -- a later map of the same place on the same grid -- and says what changed between
+the two (VLMap.compare): the JSON line then carries "compare": the summary (voxels that vanished, appeared, changed,
+the changed volume in m^3) and the object-sized changes, which are also printed one per line.  A voxel's partner is the nearest
+occupied cell of the other map within --compare-radius cells (0 .. 2, default 1); a pair whose feature rows have a cosine below
+--compare-threshold (default 0.8) counts as changed; --compare-shift moves this map's cells by whole cells first.  The audit of
+this map under the --revisit frames tells vanished from never looked at.  --compare-json also writes the summary and the list to
+PATH.  Whole-cell shifts only: a revisit from another odometry origin has to be built with corrected poses first."""
 from __future__ import annotations
 
 import argparse
@@ -41,7 +51,24 @@ def parse_args(argv=None):
     ap.add_argument("--register-radius", type=float, default=None, help="largest shift searched, metres (default 0.5)")
     ap.add_argument("--register-min-fraction", type=float, default=None,
                     help="stop when fewer than this share of a revisit's points land on occupied cells (default 0.5)")
+    ap.add_argument("--compare", default=None, metavar="OTHER_SCENE_DIR", help="a later map of the same place: list what changed")
+    ap.add_argument("--compare-radius", type=int, default=None, help="cells within which a voxel finds its partner, 0 .. 2 (default 1)")
+    ap.add_argument("--compare-threshold", type=float, default=None, help="cosine below which a matched pair has changed (default 0.8)")
+    ap.add_argument("--compare-shift", type=int, nargs=3, default=None, metavar=("DR", "DC", "DH"),
+                    help="this map's cell c is the other map's cell c + shift (default 0 0 0)")
+    ap.add_argument("--compare-json", default=None, metavar="PATH", help="also write the summary and the change list to PATH")
+    ap.add_argument("--compare-min-voxels", type=int, default=None, help="smallest component listed as a change (default 20)")
     args = ap.parse_args(argv)
+    compare = ("compare_radius", "compare_threshold", "compare_shift", "compare_json", "compare_min_voxels")
+    if args.compare is None and any(getattr(args, k) is not None for k in compare):
+        ap.error("--compare-radius, --compare-threshold, --compare-shift, --compare-json and --compare-min-voxels need --compare")
+    for k, default in zip(compare, (1, 0.8, [0, 0, 0], None, 20)):
+        if getattr(args, k) is None:
+            setattr(args, k, default)
+    if not 0 <= args.compare_radius <= 2:
+        ap.error("--compare-radius is 0, 1 or 2 cells")
+    if not 0.0 < args.compare_threshold <= 1.0:
+        ap.error("--compare-threshold is a cosine, 0 < T <= 1")
     if args.prune and not args.out:
         ap.error("--prune needs --out (pass the scene itself to overwrite its map)")
     tuning = ("register_angle", "register_step", "register_radius", "register_min_fraction")
@@ -94,6 +121,21 @@ def main(argv=None):
         from PIL import Image
         Image.fromarray(image).save(str(args.render))
         out["files"].append(str(args.render))
+    if args.compare:
+        other = VLMap(cfg.map_config, data_dir=args.compare)
+        other.prefetch_device = False
+        if not other.load_map(args.compare):
+            raise SystemExit(f"no map under {args.compare}: run apps.create_map first")
+        # the audit above saw this map through the --revisit frames: with a revisit, an unmatched voxel they never looked at is unseen
+        changes = vm.compare(other, radius=args.compare_radius, threshold=args.compare_threshold, shift=tuple(args.compare_shift),
+                             audit=audit if args.revisit else None, min_rays=args.min_rays)
+        found = [c.to_json() for c in changes.objects(min_voxels=args.compare_min_voxels)]
+        out["compare"] = {"other": str(args.compare), "summary": changes.summary(), "changes": found}
+        for c in found:
+            print(f"{c['kind']:9s} {c['count']:7d} voxels  box {c['bbox']}  {c.get('name', '')}")
+        if args.compare_json:
+            Path(args.compare_json).write_text(json.dumps(out["compare"]))
+            out["files"].append(str(args.compare_json))
     if args.prune:
         out["removed"] = vm.prune_voxels(stale)
         save_dir = Path(args.out) / "vlmap"

@@ -163,6 +163,22 @@ class AVLMap:
             raise IndexError(f"object {label} has {int(vo.table[int(label) - 1, 0])} voxels, fewer than min_voxels = {min_voxels}")
         return vm.heatmap_from_mask(vo.mask_of(int(label)), cs, decay_rate).numpy()
 
+    def index_changes(self, changes, kinds=("appeared", "changed"), decay_rate: float = 0.1) -> np.ndarray:
+        """(N,) float32 heat that decays from the voxels of a MapChanges (VLMap.compare) named in `kinds`: 1 on them.  This map is
+        the one whose voxels the kinds lie over: "appeared", "changed" and "unseen_b" the later map B's (`other` of compare),
+        "vanished", "unseen" and "changed_a" the earlier map A's; ValueError when the kinds mix the two or the voxel count is
+        another map's, or when no voxel is marked.  Upstream has no counterpart.  The heat can go into index_goal(extra=[...]) as
+        it stands: go and look at what changed."""
+        cs = cfg_get(cfg_get(self.config, "params"), "cs")
+        vm = self.vlmap
+        kinds = (kinds,) if isinstance(kinds, str) else tuple(kinds)
+        mask = changes.mask(kinds)
+        if mask.shape != (len(vm.grid_pos),):
+            raise ValueError(f"index_changes: {tuple(kinds)} mark {mask.shape[0]} voxels, this map has {len(vm.grid_pos)}")
+        if not mask.any():
+            raise ValueError(f"index_changes: no voxel is {' or '.join(kinds)}")
+        return vm.heatmap_from_mask(mask.astype(np.uint8), cs, decay_rate).numpy()
+
     def index_related_object(self, subject: str, relation: str, anchor: str, decay_rate: float = 0.1, radius: float = 0.25,
                              **kwargs) -> np.ndarray:
         """(N,) float32 heat of "the mug on the table": index_scene_object's heat of the subject of the FIRST hit of

@@ -164,6 +164,23 @@ class VLMap(Map):
             self.visibility = None
         return removed
 
+    def compare(self, other, radius: int = 1, threshold: float = 0.8, shift=(0, 0, 0), audit=None, other_audit=None, min_rays: int = 3):
+        """What changed between this map (A, the earlier one) and `other` (B, a later map of the same place): a MapChanges
+        (map/changes.py) with the voxels of A that vanished, the voxels of B that appeared and the voxels whose feature row was
+        replaced by something else (ops.map_diff).  A's cell c corresponds to B's cell c + shift; a voxel's partner is
+        the nearest occupied cell of the other map within `radius` cells (0 .. 2), each direction with its own; a pair whose
+        rows have a cosine below `threshold` (0 < threshold <= 1) is changed.  The rows are the raw float32 grid_feat of both maps,
+        not the compact resident copies.  audit: a VisibilityAudit of THIS map made from the other session's frames
+        (self.audit_visibility([other's data_dir])), other_audit: one of `other` made from this session's frames; with one, an
+        unmatched voxel that fewer than min_rays of the other session's sight rays passed through is unseen, not vanished /
+        appeared.  ValueError unless gs, cs, the number of height cells and the feature width agree.  Whole-cell shifts only: a
+        revisit recorded from another odometry origin has to be built with corrected poses first (Map.register_frames gives the
+        correction); resampling one map under a rotation or a sub-cell shift is out of scope.  Upstream has no counterpart: its
+        maps are static."""
+        from .changes import compare_maps
+        return compare_maps(self, other, radius=radius, threshold=threshold, shift=shift, audit=audit, other_audit=other_audit,
+                            min_rays=min_rays)
+
     def _init_clip(self, clip_version="ViT-B/32"):
         """Reference: vlmap.py:67-90."""
         if hasattr(self, "clip_model"):

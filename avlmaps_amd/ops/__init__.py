@@ -96,6 +96,10 @@ from .travelmany import (  # noqa: F401
     sound_travel_field, sound_travel_normalize, travel_arrivals, travel_fields, TRAVEL_MANY_MAX_FIELDS, TRAVEL_MANY_MAX_PAIRS,
     TravelArrivals, TravelFields,
 )
+from .mapdiff import (  # noqa: F401
+    cosine_of, DIFF_CHANGED, DIFF_MAX_DIM, DIFF_MAX_RADIUS, DIFF_NO_MATCH, DIFF_SAME, DIFF_STREAM_ROWS, DIFF_UNSEEN, diff_status,
+    DiffSide, map_diff, MapDiff, match_cells, row_dots,
+)
 # the shared marshalling layer; its one device predicate keeps both of the names it had here
 from ._args import (  # noqa: F401
     _dev_u8, _image_any, _image_shape, _image_u8, _is_dev, _is_dev as _on_device, _result,

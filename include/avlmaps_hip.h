@@ -1509,6 +1509,39 @@ AVL_API int avl_travel_sound2d(const int32_t* d_straight, const int32_t* d_diago
 /* d_out = (d_field - min) / (max - min) in float32, avl_field_normalize's expression on an (H, W) field.  Asynchronous. */
 AVL_API int avl_travel_sound_normalize(const float* d_field, const float* d_minmax, int H, int W, float* d_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * (30) comparing two voxel maps of one place: the join of two voxel lists by cell, the dot products of every joined pair of feature
+ *     rows and the status of every voxel (csrc/avl_mapdiff.hip), on the cell index of (20).  Upstream has no
+ *     counterpart: its maps are static.  Every output is sized by the number of voxels and allocated by the caller; the only
+ *     workspace is the index that avl_cell_index_build made, so there is no size query.  Every result has one value: the join is
+ *     integer, the sums are added in a fixed order, the status is a float64 predicate in a fixed grouping.  All calls are asynchronous
+ *     on `stream`, check their arguments before any device work and allocate nothing.
+ * ------------------------------------------------------------------------------------------------ */
+/* For each of the n_a cells (row, col, h) of d_cells (n_a, 3) int32, moved by h_shift (3 int32 in HOST memory, NULL = no shift): the
+ * nearest occupied cell of the index of the OTHER map (d_index of N_b voxels on gs x gs x vh, as avl_cell_index_build made it)
+ * within Chebyshev radius 0 <= radius <= 2.  The winner minimises the pair (squared cell distance, linear cell (row * gs + col) * vh
+ * + h of the hit), compared in that order.  d_match (n_a) int32: the row of the other map that owns the winning cell (the largest
+ * row of the cell, as everywhere on this index), -1 where no cell within the radius is occupied or the moved cell lies outside the
+ * grid; d_d2 (n_a) int32: the squared cell distance 0 .. 12, -1 with it.  Cells outside the grid count as empty.  0 <= n_a <
+ * 2^31 - 1; n_a = 0 does nothing, N_b = 0 gives -1 everywhere. */
+AVL_API int avl_map_match_cells(const void* d_index, size_t index_bytes, int64_t N_b, int gs, int vh, const int32_t* d_cells, int64_t n_a,
+                                const int32_t* h_shift, int radius, int32_t* d_match, int32_t* d_d2, void* stream);
+/* d_sums (n_a, 3) float64: for every i with m = d_match[i] in 0 .. N_b - 1 the sums (a.b, a.a, b.b) of a = d_feat_a[i, :] and b =
+ * d_feat_b[m, :], float32 rows of D contiguous elements, 1 <= D <= 8192; three zeros for every other i.  The order of the additions is
+ * part of the contract: lane l = 0 .. 63 owns the elements d with (d / 4) % 64 == l and adds their products, each formed exactly in
+ * float64, in ascending d into one float64 accumulator per sum that starts at +0.0, each addition rounded once and none fused with
+ * its product; the 64 lane values are then combined by the xor butterfly with offsets 32, 16, 8, 4, 2, 1 (v = v + partner).  The
+ * bytes do not depend on the run, on n_a, on the alignment of the matrices or on which load path served them. */
+AVL_API int avl_row_dots_f32(const float* d_feat_a, int64_t n_a, const float* d_feat_b, int64_t N_b, int D, const int32_t* d_match,
+                             double* d_sums, void* stream);
+/* d_status (n) uint8 from d_match (n) and d_sums (n, 3) = (ab, aa, bb):  2 (no match) where d_match[i] < 0;  0 (same) where
+ * aa > 0 && bb > 0 && ab > 0 && ab * ab >= t2 * (aa * bb) in float64 with the products in exactly that grouping;  1 (changed)
+ * otherwise.  t2 is the square of the cosine threshold, 0 < t2 <= 1.  With d_through (n) int32 (may be NULL) a voxel without a match
+ * whose d_through[i] < min_rays gets 3 (unseen) instead of 2.  d_counts (4) int32 receives the number of voxels of each status (it is
+ * set, not added to).  n = 0 writes four zeros. */
+AVL_API int avl_map_diff_status(const int32_t* d_match, const double* d_sums, int64_t n, double t2, const int32_t* d_through, int min_rays,
+                                uint8_t* d_status, int32_t* d_counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
