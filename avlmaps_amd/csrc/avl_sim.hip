@@ -25,6 +25,7 @@
 #include <algorithm>
 #include <climits>
 #include <cstdlib>
+#include <type_traits>
 #include <vector>
 
 #include "avl_common.h"
@@ -666,6 +667,8 @@ __device__ __forceinline__ void map_operands(const f32x4 (&b)[8], int m, half8& 
     }
 }
 
+#include "avl_sim_f16.h"   // what the fp16 kernels below share: per-query tables, MFMA step, step drivers
+
 // P24 (with PRE): the map is the COMPACT prepared form of sim_prepare_map24_kernel -- per 32 columns 64 B of fp16 hi[32] followed by
 // 32 B of int8 residuals in units of ulp(hi) / 256, 3 bytes per element instead of 4: a quarter less HBM traffic per pass, the
 // residuals are rebuilt as fp16 in registers (residual_pair) and the three MFMAs stay fp16.
@@ -695,11 +698,9 @@ __global__ __launch_bounds__(kSplitThreads) void sim_split_f16_kernel(
     const int img_b = (rows + zrow) * row_b;     // bytes of the hi (or lo) image resident in LDS
     float* isc = reinterpret_cast<float*>(smem + 2 * img_b);  // per-query 2^-S of this chunk
     int32_t* qml = reinterpret_cast<int32_t*>(isc + TQ);  // QM: the caller's query index of every row of this chunk
-    if constexpr (QM) {
-        if (threadIdx.x < TQ) qml[threadIdx.x] = threadIdx.x < rows ? qmap[q_base + threadIdx.x] : INT_MAX;
-    }
+    fill_query_map<QM>(qml, TQ, rows, qmap, q_base);
     if constexpr (!FQ) {
-        if (threadIdx.x < TQ) isc[threadIdx.x] = threadIdx.x < rows ? inv_scale[q_base + threadIdx.x] : 0.f;
+        fill_inv_scale(isc, TQ, rows, inv_scale, q_base);
     } else {
         if (threadIdx.x >= rows && threadIdx.x < TQ) isc[threadIdx.x] = 0.f;
         // wave w converts query rows w, w+8, ...: the loads of four rows are issued together (lane owns k = lane + 64 t),
@@ -775,19 +776,18 @@ __global__ __launch_bounds__(kSplitThreads) void sim_split_f16_kernel(
     }
     __syncthreads();
 
-    const int64_t ntiles = (N + kTileRows - 1) / kTileRows;
     const char* a_base[QT];
 #pragma unroll
     for (int t = 0; t < QT; ++t) a_base[t] = smem + min(t * 32 + j, rows - 1 + zrow) * row_b + kg * 64;
     // XR: lane (block lane / 4, i = lane % 4) supplies extra query row i (the zero row beyond the last one) as the A operand
     const char* xa_base = smem + min(32 * QT + (lane & 3), rows - 1 + zrow) * row_b + kg * 64;
-    (void)xa_base;
 
     // work split: full rounds of interleaved 256-row tiles (all workgroups sweep one compact window of the map: measured
     // 1.2 % faster at 2 M voxels than one contiguous range per workgroup), then ONE tail round in which what is left
     // (< gridDim.x tiles) is dealt out in 32-row units, balanced over all workgroups -- every CU stays busy with a partial
     // load instead of a third of the chip idling (300 k voxels = 4.58 rounds: -4 %; 200 k: -14 %)
-    (void)ntiles;
+    // (the same six values as a struct built once changes all 84 instantiations of this and the K-swap kernel, which therefore
+    // repeats them: profiles/sim_blocks_isa.txt)
     const int64_t G = gridDim.x;
     const int64_t R = N / (G * kTileRows);                       // complete interleaved rounds
     const int64_t tail_row0 = R * G * kTileRows;
@@ -816,9 +816,7 @@ __global__ __launch_bounds__(kSplitThreads) void sim_split_f16_kernel(
         const float* rp = feat + rowc * ld + 32 * kg;
         const char* rp24 = reinterpret_cast<const char*>(feat) + rowc * (ld * 3);   // P24: first byte of the row, ld = columns of a full row
 
-        // NA independent accumulator sets per query tile (hi*hi | cross terms) so that back-to-back MFMAs never wait on
-        // each other's result: a dependent 32x32x16 MFMA cannot issue until its predecessor retires
-        f32x16 acc[QT][NA];
+        f32x16 acc[QT][NA];   // NA independent accumulator sets per query tile: see mfma_step
 #pragma unroll
         for (int t = 0; t < QT; ++t)
 #pragma unroll
@@ -839,8 +837,7 @@ __global__ __launch_bounds__(kSplitThreads) void sim_split_f16_kernel(
             const float* p = rp + kc * KC;
             const int sa0 = (col0 + kc * KC) >> 6;          // P24: index of this chunk's first step in the row
 
-            f32x4 buf0[8], buf1[8];
-            auto load = [&](f32x4(&b)[8], int s) {
+            auto load = [&](f32x4(&b)[8], int s) {   // own copy of voxel_load_step (avl_sim_f16.h): it changes 24 instantiations' metadata here
                 if constexpr (P24) {
                     compact_load_step(b, rp24, ld, kg, sa0 + s);
                 } else {
@@ -851,37 +848,28 @@ __global__ __launch_bounds__(kSplitThreads) void sim_split_f16_kernel(
             };
             // operands(m, bh, bl): the voxel-side fragments of the m-th 8-column group of step s
             auto compute_with = [&](auto&& operands, int s) {
+                if constexpr (!XR) {
+                    mfma_step<QT, NA>(acc, s, img_b, operands, [&](int t, int off) { return a_base[t] + off; });
+                } else {
+                    // own copy of mfma_step (avl_sim_f16.h) for the six extra-row instantiations, with their 4x4x4 products behind
+                    // every group: as a hook of the shared step these change the schedule.  No ablation switch reaches this copy.
 #pragma unroll
-                for (int m = 0; m < 4; ++m) {
-                    half8 bh, bl;
-                    operands(m, bh, bl);
-                    const int off = (s * 64 + 8 * m) * 2;
-                    half8 ah[QT], al[QT];
+                    for (int m = 0; m < 4; ++m) {
+                        half8 bh, bl;
+                        operands(m, bh, bl);
+                        const int off = (s * 64 + 8 * m) * 2;
+                        half8 ah[QT], al[QT];
 #pragma unroll
-                    for (int t = 0; t < QT; ++t) {
-#ifdef AVL_ABL_NOLDS
-                        for (int e = 0; e < 8; ++e) { ah[t][e] = (_Float16)1; al[t][e] = (_Float16)2; }
-                        asm volatile("" : "+v"(ah[t]), "+v"(al[t]));
-#else
-                        ah[t] = *reinterpret_cast<const half8*>(a_base[t] + off);
-                        al[t] = *reinterpret_cast<const half8*>(a_base[t] + off + img_b);
-#endif
-                    }
-#ifdef AVL_ABL_NOMFMA
+                        for (int t = 0; t < QT; ++t) {
+                            ah[t] = *reinterpret_cast<const half8*>(a_base[t] + off);
+                            al[t] = *reinterpret_cast<const half8*>(a_base[t] + off + img_b);
+                        }
 #pragma unroll
-                    for (int t = 0; t < QT; ++t) asm volatile("" ::"v"(ah[t]), "v"(al[t]), "v"(bh), "v"(bl));
-#else
-                    // term-major, tile-minor issue order: consecutive MFMAs target different accumulators
+                        for (int t = 0; t < QT; ++t) acc[t][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[t], bh, acc[t][0], 0, 0, 0);
 #pragma unroll
-                    for (int t = 0; t < QT; ++t) acc[t][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[t], bh, acc[t][0], 0, 0, 0);
-#ifndef AVL_ABL_HIONLY   // ablation for the argmax-only question: what ONE product per pair would cost
+                        for (int t = 0; t < QT; ++t) acc[t][X1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[t], bh, acc[t][X1], 0, 0, 0);
 #pragma unroll
-                    for (int t = 0; t < QT; ++t) acc[t][X1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[t], bh, acc[t][X1], 0, 0, 0);
-#pragma unroll
-                    for (int t = 0; t < QT; ++t) acc[t][X2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[t], bl, acc[t][X2], 0, 0, 0);
-#endif
-#endif
-                    if constexpr (XR) {
+                        for (int t = 0; t < QT; ++t) acc[t][X2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[t], bl, acc[t][X2], 0, 0, 0);
                         using half4 = __attribute__((ext_vector_type(4))) _Float16;
                         const half8 xh = *reinterpret_cast<const half8*>(xa_base + off);
                         const half8 xl = *reinterpret_cast<const half8*>(xa_base + off + img_b);
@@ -902,50 +890,12 @@ __global__ __launch_bounds__(kSplitThreads) void sim_split_f16_kernel(
                 compute_with([&](int m, half8& bh, half8& bl) { map_operands<PRE, P24>(b, m, bh, bl, rmax); }, s);
             };
             if constexpr (P24 && NSTEPS > 0) {
-                // Compact map, compile-time trip count, window starting on a 128-column block (the launcher checks): the residual line
-                // of a block serves its two steps and is requested ONCE, with the even step -- 64 B per lane half into a buffer of its
-                // own (two, by block parity: the odd step still reads one while the next block's is in flight); hi: two buffers by
-                // step parity.  One step ahead, like the ring below.
-                static_assert(NSTEPS % 2 == 0, "whole 128-column blocks");
-                f32x4 hb[2][4], lb[2][4];
-                auto load_hi = [&](int st) {
-                    const f32x4* g = reinterpret_cast<const f32x4*>(rp24 + 128 * (sa0 + st) + 64 * kg);
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) hb[st & 1][t] = g[t];
-                };
-                auto load_lo = [&](int blk) {
-                    const f32x4* g = reinterpret_cast<const f32x4*>(rp24 + 2 * ld + 128 * ((sa0 >> 1) + blk) + 64 * kg);
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) lb[blk & 1][t] = g[t];
-                };
-                load_hi(0);
-                load_lo(0);
-#pragma unroll
-                for (int st = 0; st < NSTEPS; ++st) {
-                    if (st + 1 < NSTEPS) {
-                        load_hi(st + 1);
-                        if (((st + 1) & 1) == 0) load_lo((st + 1) >> 1);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                    compute_with([&](int m, half8& bh, half8& bl) {
-                        compact_operands(hb[st & 1][m], lb[(st >> 1) & 1][2 * (st & 1) + (m >> 1)], m & 1, bh, bl);
-                    }, st);
-                }
+                drive_compact_blocks<NSTEPS>(rp24, ld, kg, sa0, compute_with);
             } else if constexpr (NSTEPS > 0) {
-                // compile-time trip count, ring of kRing register buffers: the loads of the next kRing - 1 steps are in flight
-                // while step s is computed, all waits are counted vmcnt (depth per variant: RingDepth)
-                constexpr int kRing = RingDepth<PRE, XR, QM>::value;
-                f32x4 ring[kRing][8];
-#pragma unroll
-                for (int r = 0; r + 1 < kRing; ++r)
-                    if (r < NSTEPS) load(ring[r], r);
-#pragma unroll
-                for (int s = 0; s < NSTEPS; ++s) {
-                    if (s + kRing - 1 < NSTEPS) load(ring[(s + kRing - 1) % kRing], s + kRing - 1);
-                    __builtin_amdgcn_sched_barrier(0);   // keep the prefetch block ahead of the compute block
-                    compute(ring[s % kRing], s);
-                }
+                drive_ring<NSTEPS, RingDepth<PRE, XR, QM>::value>(load, compute);   // depth per variant: RingDepth
             } else {
+                // own copy of the run-time two-buffer loop: as a shared block it changes every instantiation that has it
+                f32x4 buf0[8], buf1[8];
                 load(buf0, 0);
                 for (int s = 0; s < nsteps; s += 2) {
                     if (s + 1 < nsteps) load(buf1, s + 1);
@@ -994,10 +944,8 @@ __global__ __launch_bounds__(kSplitThreads) void sim_kswap_f16_kernel(
     const int img_b = (rows + zrow) * row_b;
     float* isc = reinterpret_cast<float*>(smem + 2 * img_b);
     int32_t* qml = reinterpret_cast<int32_t*>(isc + QT * 32);
-    if constexpr (QM) {
-        if (threadIdx.x < QT * 32) qml[threadIdx.x] = threadIdx.x < rows ? qmap[q_base + threadIdx.x] : INT_MAX;
-    }
-    if (threadIdx.x < QT * 32) isc[threadIdx.x] = threadIdx.x < rows ? inv_scale[q_base + threadIdx.x] : 0.f;
+    fill_query_map<QM>(qml, QT * 32, rows, qmap, q_base);
+    fill_inv_scale(isc, QT * 32, rows, inv_scale, q_base);
     // the image of chunk kc -> LDS with direct global-to-LDS loads (global_load_lds_dwordx4: a wave instruction lands 64 x 16 B
     // at a wave-uniform LDS address; no staging registers -- the T tiles' accumulators are live across a swap -- and all of a
     // wave's pieces are in flight at once instead of a chain of load/store round trips)
@@ -1015,7 +963,7 @@ __global__ __launch_bounds__(kSplitThreads) void sim_kswap_f16_kernel(
         }
     };
     auto fill_wait = [&]() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };
-    if (zrow)
+    if (zrow)   // (the zero row as a shared function changes every instantiation of this kernel: profiles/sim_blocks_isa.txt)
         for (int i = threadIdx.x; i < row_b / 4; i += kSplitThreads) {
             reinterpret_cast<uint32_t*>(smem + rows * row_b)[i] = 0u;
             reinterpret_cast<uint32_t*>(smem + img_b + rows * row_b)[i] = 0u;
@@ -1035,7 +983,7 @@ __global__ __launch_bounds__(kSplitThreads) void sim_kswap_f16_kernel(
     const int64_t tail_units = (N - tail_row0 + 31) / 32;
     const int64_t tu0 = tail_units * blockIdx.x / G, tu1 = tail_units * (blockIdx.x + 1) / G;
     const int64_t n_it = R + (tu0 < tu1 ? 1 : 0);                  // iterations of this workgroup (workgroup-uniform)
-    constexpr int kElB = P24 ? 3 : 4, kLaneB = P24 ? 96 : 128, kStepB = 2 * kLaneB, kLoads = P24 ? 6 : 8;
+    constexpr int kElB = VoxelBytes<P24>::kElB, kLaneB = VoxelBytes<P24>::kLaneB;
 
     for (int64_t it0 = 0; it0 < n_it; it0 += T) {
         // slot b of this group = iteration it0 + b of the workgroup; its row / activity are recomputed where they are needed (three
@@ -1087,79 +1035,19 @@ __global__ __launch_bounds__(kSplitThreads) void sim_kswap_f16_kernel(
                 const char* p = reinterpret_cast<const char*>(feat) + (row < N ? row : N - 1) * (ld * kElB) +
                                 (P24 ? 0 : kLaneB * kg + (int64_t)pass * KC * kElB);
                 const int sa0 = (col0 + pass * KC) >> 6;
-                auto load = [&](f32x4(&buf)[8], int s) {
-                    if constexpr (P24) {
-                        compact_load_step(buf, p, ld, kg, sa0 + s);
-                    } else {
-                        const f32x4* g = reinterpret_cast<const f32x4*>(p + kStepB * s);
-#pragma unroll
-                        for (int t = 0; t < kLoads; ++t) buf[t] = g[t];
-                    }
-                };
+                auto load = [&](f32x4(&buf)[8], int s) { voxel_load_step<P24>(buf, p, ld, kg, sa0, s); };
                 auto compute_with = [&](auto&& operands, int s) {
-#pragma unroll
-                    for (int m = 0; m < 4; ++m) {
-                        half8 bh, bl;
-                        operands(m, bh, bl);
-                        const int off = (s * 64 + 8 * m) * 2;
-                        half8 ah[QT], al[QT];
-#pragma unroll
-                        for (int t = 0; t < QT; ++t) {
-                            ah[t] = *reinterpret_cast<const half8*>(a_base[t] + off);
-                            al[t] = *reinterpret_cast<const half8*>(a_base[t] + off + img_b);
-                        }
-#pragma unroll
-                        for (int t = 0; t < QT; ++t) acc[b][t][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[t], bh, acc[b][t][0], 0, 0, 0);
-#pragma unroll
-                        for (int t = 0; t < QT; ++t) acc[b][t][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[t], bh, acc[b][t][0], 0, 0, 0);
-#pragma unroll
-                        for (int t = 0; t < QT; ++t) acc[b][t][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[t], bl, acc[b][t][0], 0, 0, 0);
-                    }
+                    mfma_step<QT, 1>(acc[b], s, img_b, operands, [&](int t, int off) { return a_base[t] + off; });
                 };
                 auto compute = [&](const f32x4(&buf)[8], int s) {
                     compute_with([&](int m, half8& bh, half8& bl) { map_operands<PRE, P24>(buf, m, bh, bl, rmax[b]); }, s);
                 };
                 if constexpr (NS > 0 && P24) {
-                    // compact map, window on a 128-column block: the residual line of a block is requested once, with its even step
-                    // (see the resident kernel)
-                    static_assert(NS % 2 == 0, "whole 128-column blocks");
-                    f32x4 hb[2][4], lb[2][4];
-                    auto load_hi = [&](int st) {
-                        const f32x4* g = reinterpret_cast<const f32x4*>(p + 128 * (sa0 + st) + 64 * kg);
-#pragma unroll
-                        for (int t = 0; t < 4; ++t) hb[st & 1][t] = g[t];
-                    };
-                    auto load_lo = [&](int blk) {
-                        const f32x4* g = reinterpret_cast<const f32x4*>(p + 2 * ld + 128 * ((sa0 >> 1) + blk) + 64 * kg);
-#pragma unroll
-                        for (int t = 0; t < 4; ++t) lb[blk & 1][t] = g[t];
-                    };
-                    load_hi(0);
-                    load_lo(0);
-#pragma unroll
-                    for (int st = 0; st < NS; ++st) {
-                        if (st + 1 < NS) {
-                            load_hi(st + 1);
-                            if (((st + 1) & 1) == 0) load_lo((st + 1) >> 1);
-                        }
-                        __builtin_amdgcn_sched_barrier(0);
-                        compute_with([&](int m, half8& bh, half8& bl) {
-                            compact_operands(hb[st & 1][m], lb[(st >> 1) & 1][2 * (st & 1) + (m >> 1)], m & 1, bh, bl);
-                        }, st);
-                    }
+                    drive_compact_blocks<NS>(p, ld, kg, sa0, compute_with);
                 } else if constexpr (NS > 0) {
-                    // (carrying the register buffer of a slot's first step over from the previous slot's last step, and across the
-                    // image swap, was measured: no gain on prepared / compact maps -- 1.635 vs 1.621 ms, 1.258 vs 1.239 ms at
-                    // 2 M x 1024 x 64 -- and 25-29 spills on raw ones; every slot restarts its two-buffer ring)
-                    f32x4 ring[2][8];
-                    load(ring[0], 0);
-#pragma unroll
-                    for (int s = 0; s < NS; ++s) {
-                        if (s + 1 < NS) load(ring[(s + 1) & 1], s + 1);
-                        __builtin_amdgcn_sched_barrier(0);
-                        compute(ring[s & 1], s);
-                    }
+                    drive_ring<NS, 2>(load, compute);
                 } else {
+                    // own copy of the run-time two-buffer loop: see the resident kernel
                     f32x4 buf0[8], buf1[8];
                     load(buf0, 0);
                     for (int s = 0; s < nsteps; s += 2) {
@@ -1209,7 +1097,6 @@ __global__ __launch_bounds__(kSplitThreads) void sim_kswap_f16_kernel(
 // image layout: [nch][Qtot][hi KS | lo KS | pad 8] fp16 (sim_prep_queries_kernel, interleaved) -- a chunk's rows are one
 // contiguous block, copied linearly; the 16-byte pad keeps ds_read_b128 of 32 consecutive rows conflict-free
 // ------------------------------------------------------------------------------------------------
-constexpr int kStreamFill = 9;   // 16-byte staging registers per thread: one LDS buffer <= 9 * 512 * 16 B = 72 KB
 
 template <int QT, int SPC, bool PRE, bool QM = false, bool P24 = false>
 __global__ __launch_bounds__(kSplitThreads) void sim_stream_f16_kernel(
@@ -1219,9 +1106,7 @@ __global__ __launch_bounds__(kSplitThreads) void sim_stream_f16_kernel(
     uint32_t* __restrict__ flags, const int32_t* __restrict__ qmap, int col0) {
     static_assert(SPC % 2 == 0, "the register buffer of a chunk's first step must not move between chunks");
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int KS = 64 * SPC;
-    constexpr int row_b = (2 * KS + kRowPadHalves) * 2;   // bytes per query row of one chunk: hi[KS] | lo[KS] | pad
-    constexpr int lo_b = 2 * KS;                          // byte offset of the lo half inside a row
+    constexpr int row_b = StreamLayout<SPC>::row_b, lo_b = StreamLayout<SPC>::lo_b, NSTG = StreamLayout<SPC>::NSTG;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int j = lane & 31, kg = lane >> 5;
     // a partial last MFMA tile reads one extra all-zero row per buffer instead of re-reading a valid row: zeros toggle far
@@ -1229,56 +1114,26 @@ __global__ __launch_bounds__(kSplitThreads) void sim_stream_f16_kernel(
     const int zrow = rows < 32 * QT ? 1 : 0;
     const int buf_b = (rows + zrow) * row_b;              // one LDS buffer = the chunk's rows, a linear copy of the image
     float* isc = reinterpret_cast<float*>(smem + 2 * buf_b);
-    if (threadIdx.x < QT * 32) isc[threadIdx.x] = threadIdx.x < rows ? inv_scale[q_base + threadIdx.x] : 0.f;
+    fill_inv_scale(isc, QT * 32, rows, inv_scale, q_base);
     int32_t* qml = reinterpret_cast<int32_t*>(isc + QT * 32);   // QM: the caller's query index of every row of this chunk
-    if constexpr (QM) {
-        if (threadIdx.x < QT * 32) qml[threadIdx.x] = threadIdx.x < rows ? qmap[q_base + threadIdx.x] : INT_MAX;
-    }
+    fill_query_map<QM>(qml, QT * 32, rows, qmap, q_base);
     const int units = (rows * row_b) >> 4;
-    if (zrow)
+    if (zrow)   // (the zero row as a shared function changes every instantiation of this kernel: profiles/sim_blocks_isa.txt)
         for (int i = threadIdx.x; i < row_b / 4; i += kSplitThreads) {
             reinterpret_cast<uint32_t*>(smem + rows * row_b)[i] = 0u;
             reinterpret_cast<uint32_t*>(smem + buf_b + rows * row_b)[i] = 0u;
         }
 
-    // the next chunk is staged in SPC slices, one per k step (registers: 5 x 16 B at SPC = 2, 3 x 16 B at SPC = 4)
-    constexpr int NSTG = kStreamFill - ((SPC - 1) * kStreamFill) / SPC;
+    // the next chunk is staged in SPC slices, one per k step
     f32x4 stg[NSTG];
-    auto stage_load = [&](int c, int i0, int i1) {
-        const f32x4* src = reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(img) + ((int64_t)c * Qtot + q_base) * row_b);
-#pragma unroll
-        for (int i = i0; i < i1; ++i) {
-            const int u = threadIdx.x + i * kSplitThreads;
-            if (u < units) stg[i - i0] = src[u];
-        }
-    };
-    auto stage_store = [&](int b, int i0, int i1) {
-        f32x4* dst = reinterpret_cast<f32x4*>(smem + b * buf_b);
-#pragma unroll
-        for (int i = i0; i < i1; ++i) {
-            const int u = threadIdx.x + i * kSplitThreads;
-            if (u < units) dst[u] = stg[i - i0];
-        }
-    };
+    auto stage_load = [&](int c, int i0, int i1) { stage_load_slice<kSplitThreads>(stg, img, c, Qtot, q_base, row_b, units, i0, i1); };
+    auto stage_store = [&](int b, int i0, int i1) { stage_store_slice<kSplitThreads>(stg, smem + b * buf_b, units, i0, i1); };
 
     const int64_t ntiles = (N + kTileRows - 1) / kTileRows;
-    // byte geometry of a lane's walk: float32 / prepared rows are 4 B per column and a lane owns 128 B of every 64-column step;
-    // the compact form (P24) is 3 B per column, 96 B per lane and step (hi[32] | residual bytes[32])
-    constexpr int kElB = P24 ? 3 : 4, kLaneB = P24 ? 96 : 128, kStepB = 2 * kLaneB, kLoads = P24 ? 6 : 8;
-    auto tile_ptr = [&](int64_t tile) {
-        const int64_t r = tile * kTileRows + wave * 32 + j;
-        return reinterpret_cast<const char*>(feat) + (r < N ? r : N - 1) * (ld * kElB) + (P24 ? 0 : kLaneB * kg);   // P24: first byte of the row
-    };
+    auto tile_ptr = [&](int64_t tile) { return stream_tile_ptr<P24>(feat, tile, kTileRows, wave, j, kg, N, ld); };
     f32x4 ring[2][8];
-    auto load = [&](f32x4(&b)[8], const char* src, int step) {     // step `step` of the window whose row (lane line) starts at src
-        if constexpr (P24) {
-            compact_load_step(b, src, ld, kg, (col0 >> 6) + step);
-        } else {
-            const f32x4* g = reinterpret_cast<const f32x4*>(src + kStepB * step);
-#pragma unroll
-            for (int t = 0; t < kLoads; ++t) b[t] = g[t];
-        }
-    };
+    // step `step` of the window whose row (lane line) starts at src
+    auto load = [&](f32x4(&b)[8], const char* src, int step) { voxel_load_step<P24>(b, src, ld, kg, col0 >> 6, step); };
     load(ring[0], tile_ptr(blockIdx.x), 0);   // first tile, step 0: in flight while chunk 0 is brought in
 #pragma unroll
     for (int s = 0; s < SPC; ++s) {
@@ -1290,7 +1145,7 @@ __global__ __launch_bounds__(kSplitThreads) void sim_stream_f16_kernel(
 
     int a_off[QT];
 #pragma unroll
-    for (int t = 0; t < QT; ++t) a_off[t] = min(t * 32 + j, rows - 1 + zrow) * row_b + kg * 64;
+    for (int t = 0; t < QT; ++t) a_off[t] = query_row_offset(t, j, kg, rows - 1 + zrow, row_b);
 
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int64_t row = tile * kTileRows + wave * 32 + j;
@@ -1328,6 +1183,7 @@ __global__ __launch_bounds__(kSplitThreads) void sim_stream_f16_kernel(
                     half8 bh, bl;
                     map_operands<PRE, P24>(b, m, bh, bl, rmax);
                     const int off = (s * 64 + 8 * m) * 2;
+                    // own copy of mfma_step (avl_sim_f16.h): a shared product function changes 36 of this kernel's 48 instantiations
                     if constexpr (QT == 4) {
                         // four tiles: the hi fragments serve both of their products before the lo fragments are fetched, so only
                         // four operand fragments are live at a time (the term-major order below spilled 5 VGPRs here)
@@ -1361,12 +1217,7 @@ __global__ __launch_bounds__(kSplitThreads) void sim_stream_f16_kernel(
                 stage_store(cur ^ 1, i0, i1);
 #endif
             }
-            // publish the next chunk / retire this one: LDS traffic only, the voxel prefetch stays in flight
-#ifndef AVL_ABL_NOBARRIER
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-#endif
+            stream_publish();   // publish the next chunk / retire this one; the voxel prefetch stays in flight
             cur ^= 1;
         }
         float rscale = 1.f;
@@ -1394,7 +1245,8 @@ __global__ __launch_bounds__(kSplitThreads) void sim_stream_f16_kernel(
 // (prepared and compact maps need no split / guard registers: three tiles per chunk pass fit without a spill, 245-255 VGPRs)
 template <int QT, bool P24, bool PRE = false>
 struct StreamTB {
-    static constexpr int value = QT == 1 ? 4 : (QT == 2 ? ((P24 || PRE) ? AVL_TB2_P24 : AVL_TB2) : 1);
+    static_assert(QT == 2, "only instantiated for two query tiles (pick_stream_kernel): from three on blocking costs 1-4 %");
+    static constexpr int value = (P24 || PRE) ? AVL_TB2_P24 : AVL_TB2;
 };
 
 // (Tried and dropped, round 2: ONE pass over several column windows -- the chunk loop switching query rows / running the
@@ -1413,9 +1265,7 @@ __global__ __launch_bounds__(NT) void sim_stream_tb_f16_kernel(
     static_assert(SPC % 2 == 0, "the register buffer of a chunk's first step must not move between chunks");
     constexpr int TB = StreamTB<QT, P24, PRE>::value;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int KS = 64 * SPC;
-    constexpr int row_b = (2 * KS + kRowPadHalves) * 2;   // bytes per query row of one chunk: hi[KS] | lo[KS] | pad
-    constexpr int lo_b = 2 * KS;                          // byte offset of the lo half inside a row
+    constexpr int row_b = StreamLayout<SPC>::row_b, lo_b = StreamLayout<SPC>::lo_b, NSTG = StreamLayout<SPC>::NSTG;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int j = lane & 31, kg = lane >> 5;
     // a partial last MFMA tile reads one extra all-zero row per buffer instead of re-reading a valid row: zeros toggle far
@@ -1423,38 +1273,20 @@ __global__ __launch_bounds__(NT) void sim_stream_tb_f16_kernel(
     const int zrow = rows < 32 * QT ? 1 : 0;
     const int buf_b = (rows + zrow) * row_b;              // one LDS buffer = the chunk's rows, a linear copy of the image
     float* isc = reinterpret_cast<float*>(smem + 2 * buf_b);
-    if (threadIdx.x < QT * 32) isc[threadIdx.x] = threadIdx.x < rows ? inv_scale[q_base + threadIdx.x] : 0.f;
+    fill_inv_scale(isc, QT * 32, rows, inv_scale, q_base);
     int32_t* qml = reinterpret_cast<int32_t*>(isc + QT * 32);   // QM: the caller's query index of every row of this chunk
-    if constexpr (QM) {
-        if (threadIdx.x < QT * 32) qml[threadIdx.x] = threadIdx.x < rows ? qmap[q_base + threadIdx.x] : INT_MAX;
-    }
+    fill_query_map<QM>(qml, QT * 32, rows, qmap, q_base);
     const int units = (rows * row_b) >> 4;
-    if (zrow)
+    if (zrow)   // (the zero row as a shared function changes every instantiation of this kernel: profiles/sim_blocks_isa.txt)
         for (int i = threadIdx.x; i < row_b / 4; i += NT) {
             reinterpret_cast<uint32_t*>(smem + rows * row_b)[i] = 0u;
             reinterpret_cast<uint32_t*>(smem + buf_b + rows * row_b)[i] = 0u;
         }
 
-    // the next chunk is staged in SPC slices, one per k step of the block's FIRST tile (registers: 5 x 16 B at SPC = 2,
-    // 3 x 16 B at SPC = 4); the other tiles of the block only compute
-    constexpr int NSTG = kStreamFill - ((SPC - 1) * kStreamFill) / SPC;
+    // the next chunk is staged in SPC slices, one per k step of the block's FIRST tile; the other tiles of the block only compute
     f32x4 stg[NSTG];
-    auto stage_load = [&](int c, int i0, int i1) {
-        const f32x4* src = reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(img) + ((int64_t)c * Qtot + q_base) * row_b);
-#pragma unroll
-        for (int i = i0; i < i1; ++i) {
-            const int u = threadIdx.x + i * NT;
-            if (u < units) stg[i - i0] = src[u];
-        }
-    };
-    auto stage_store = [&](int b, int i0, int i1) {
-        f32x4* dst = reinterpret_cast<f32x4*>(smem + b * buf_b);
-#pragma unroll
-        for (int i = i0; i < i1; ++i) {
-            const int u = threadIdx.x + i * NT;
-            if (u < units) dst[u] = stg[i - i0];
-        }
-    };
+    auto stage_load = [&](int c, int i0, int i1) { stage_load_slice<NT>(stg, img, c, Qtot, q_base, row_b, units, i0, i1); };
+    auto stage_store = [&](int b, int i0, int i1) { stage_store_slice<NT>(stg, smem + b * buf_b, units, i0, i1); };
 
     // work split: full rounds of interleaved TB-tile blocks (all workgroups sweep one compact window of the map), then what
     // is left (< gridDim.x * TB tiles) dealt out evenly, at most TB tiles per workgroup
@@ -1472,21 +1304,10 @@ __global__ __launch_bounds__(NT) void sim_stream_tb_f16_kernel(
             cnt = it == R ? (int)(rb - ra) : 0;
         }
     };
-    constexpr int kElB = P24 ? 3 : 4, kLaneB = P24 ? 96 : 128, kStepB = 2 * kLaneB, kLoads = P24 ? 6 : 8;   // see sim_stream_f16_kernel
-    auto tile_ptr = [&](int64_t tile) {
-        const int64_t r = tile * (NT / 64 * 32) + wave * 32 + j;
-        return reinterpret_cast<const char*>(feat) + (r < N ? r : N - 1) * (ld * kElB) + (P24 ? 0 : kLaneB * kg);   // P24: first byte of the row
-    };
+    auto tile_ptr = [&](int64_t tile) { return stream_tile_ptr<P24>(feat, tile, NT / 64 * 32, wave, j, kg, N, ld); };
     f32x4 ring[2][8];
-    auto load = [&](f32x4(&b)[8], const char* src, int step) {     // step `step` of the window whose row (lane line) starts at src
-        if constexpr (P24) {
-            compact_load_step(b, src, ld, kg, (col0 >> 6) + step);
-        } else {
-            const f32x4* g = reinterpret_cast<const f32x4*>(src + kStepB * step);
-#pragma unroll
-            for (int t = 0; t < kLoads; ++t) b[t] = g[t];
-        }
-    };
+    // step `step` of the window whose row (lane line) starts at src
+    auto load = [&](f32x4(&b)[8], const char* src, int step) { voxel_load_step<P24>(b, src, ld, kg, col0 >> 6, step); };
     int64_t tile0;
     int cnt;
     block_of(0, tile0, cnt);
@@ -1502,7 +1323,7 @@ __global__ __launch_bounds__(NT) void sim_stream_tb_f16_kernel(
 
     int a_off[QT];
 #pragma unroll
-    for (int t = 0; t < QT; ++t) a_off[t] = min(t * 32 + j, rows - 1 + zrow) * row_b + kg * 64;
+    for (int t = 0; t < QT; ++t) a_off[t] = query_row_offset(t, j, kg, rows - 1 + zrow, row_b);
 
     for (int64_t it = 0; cnt > 0; ++it) {
         int64_t tile0_next;
@@ -1529,7 +1350,7 @@ __global__ __launch_bounds__(NT) void sim_stream_tb_f16_kernel(
             const char* ab = smem + cur * buf_b;
 #pragma unroll
             for (int b = 0; b < TB; ++b) {
-                if (TB == 1 || b < cnt) {   // workgroup-uniform
+                if (b < cnt) {   // workgroup-uniform
 #pragma unroll
                     for (int s = 0; s < SPC; ++s) {
                         const int i0 = (s * kStreamFill) / SPC, i1 = ((s + 1) * kStreamFill) / SPC;
@@ -1556,7 +1377,7 @@ __global__ __launch_bounds__(NT) void sim_stream_tb_f16_kernel(
                             half8 bh, bl;
                             map_operands<PRE, P24>(v, m, bh, bl, rmax[b]);
                             const int off = (s * 64 + 8 * m) * 2;
-                            half8 ah[QT], al[QT];
+                            half8 ah[QT], al[QT];   // own copy of mfma_step (avl_sim_f16.h), as in sim_stream_f16_kernel
 #pragma unroll
                             for (int t = 0; t < QT; ++t) {
                                 ah[t] = *reinterpret_cast<const half8*>(ab + a_off[t] + off);
@@ -1575,17 +1396,12 @@ __global__ __launch_bounds__(NT) void sim_stream_tb_f16_kernel(
                     }
                 }
             }
-            // publish the next chunk / retire this one: LDS traffic only, the voxel prefetch stays in flight
-#ifndef AVL_ABL_NOBARRIER
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-#endif
+            stream_publish();   // publish the next chunk / retire this one; the voxel prefetch stays in flight
             cur ^= 1;
         }
 #pragma unroll
         for (int b = 0; b < TB; ++b) {
-            if (TB == 1 || b < cnt) {
+            if (b < cnt) {
                 const int64_t row = (tile0 + b) * (NT / 64 * 32) + wave * 32 + j;
                 float rscale = 1.f;
                 if constexpr (PRE) {
@@ -1943,6 +1759,15 @@ static const void* pick_stream_kernel_spc(int SPC, int QT, bool tile_block) {
     return SPC == 4 ? pick_stream_kernel<4, PRE, QM, P24>(QT, tile_block) : pick_stream_kernel<2, PRE, QM, P24>(QT, tile_block);
 }
 
+// the run-time map form as template arguments: pick(QM, P24) gets two std::bool_constant values (P24: prepared maps only)
+template <bool PRE, class Pick>
+static const void* with_map_form(bool qm, bool p24, Pick&& pick) {
+    if constexpr (PRE) {
+        if (p24) return qm ? pick(std::true_type{}, std::true_type{}) : pick(std::false_type{}, std::true_type{});
+    }
+    return qm ? pick(std::true_type{}, std::false_type{}) : pick(std::false_type{}, std::false_type{});
+}
+
 #ifndef AVL_KSWAP_T
 #define AVL_KSWAP_T 3
 #endif
@@ -1961,26 +1786,29 @@ static const void* pick_kswap_kernel(int QT, int ns) {
 
 static bool split_plan_is_fused(const SplitPlan& p, int D) { return !p.stream && p.nkc == 1 && D <= 512; }
 
-template <int QT, bool QM>
-static const void* pick_split24_kernel(bool s8, bool fq) {   // compact prepared map (P24)
-    if (fq) return s8 ? reinterpret_cast<const void*>(sim_split_f16_kernel<QT, 8, true, true, QM, true>)
-                      : reinterpret_cast<const void*>(sim_split_f16_kernel<QT, 0, true, true, QM, true>);
-    return reinterpret_cast<const void*>(sim_split_f16_kernel<QT, 0, true, false, QM, true>);
+// the resident kernel: s8 = fully unrolled k loop (D = 512), fq = query image built in the kernel, xr = extra-row variant
+// (Q = 32 QT + 1..4 on the fused D = 512 path, never through a query map: QT then counts the FULL tiles, 1 or 2)
+template <int QT, bool PRE, bool QM, bool P24>
+static const void* pick_split_kernel_qt(bool s8, bool fq, bool xr) {
+    if constexpr (QT <= 2 && !QM) {
+        if (xr) return reinterpret_cast<const void*>(sim_split_f16_kernel<QT, 8, PRE, true, false, P24, true>);
+    }
+    if (fq) return s8 ? reinterpret_cast<const void*>(sim_split_f16_kernel<QT, 8, PRE, true, QM, P24>)
+                      : reinterpret_cast<const void*>(sim_split_f16_kernel<QT, 0, PRE, true, QM, P24>);
+    return reinterpret_cast<const void*>(sim_split_f16_kernel<QT, 0, PRE, false, QM, P24>);
+}
+template <bool PRE, bool QM, bool P24>
+static const void* pick_split_kernel(int QT, bool s8, bool fq, bool xr) {
+    return QT == 3 ? pick_split_kernel_qt<3, PRE, QM, P24>(s8, fq, xr)
+                   : (QT == 2 ? pick_split_kernel_qt<2, PRE, QM, P24>(s8, fq, xr) : pick_split_kernel_qt<1, PRE, QM, P24>(s8, fq, xr));
 }
 
-// extra-row variants (Q = 32 QT + 1..4 on the fused D = 512 path): raw / prepared / compact map
-template <int QT>
-static const void* pick_split_xr_kernel(bool prepared, bool p24) {
-    if (p24) return reinterpret_cast<const void*>(sim_split_f16_kernel<QT, 8, true, true, false, true, true>);
-    if (prepared) return reinterpret_cast<const void*>(sim_split_f16_kernel<QT, 8, true, true, false, false, true>);
-    return reinterpret_cast<const void*>(sim_split_f16_kernel<QT, 8, false, true, false, false, true>);
-}
-
-template <int QT, bool PRE, bool QM>
-static const void* pick_split_kernel(bool s8, bool fq) {
-    if (fq) return s8 ? reinterpret_cast<const void*>(sim_split_f16_kernel<QT, 8, PRE, true, QM>)
-                      : reinterpret_cast<const void*>(sim_split_f16_kernel<QT, 0, PRE, true, QM>);
-    return reinterpret_cast<const void*>(sim_split_f16_kernel<QT, 0, PRE, false, QM>);
+// one launch of any of the four fp16 families (all run kSplitThreads threads; the tile-blocked kernel's NT is left at that)
+static int launch_chunk(const void* kern, size_t lds, int64_t blocks, void** args, hipStream_t st) {
+    int rc = ensure_dynamic_lds(kern, lds);
+    if (rc != AVL_OK) return rc;
+    AVL_HIP_CHECK(hipLaunchKernel(kern, dim3((unsigned)blocks), dim3(kSplitThreads), args, lds, st));
+    return AVL_OK;
 }
 
 static int run_fixup(const float* d_feat, int64_t N, int D, int64_t ld, const float* d_q, int Q, int64_t ldq, const uint32_t* d_flags,
@@ -2021,20 +1849,14 @@ static int run_split(const float* d_feat, int64_t N, int D, int64_t ld, const fl
         for (int ci = 0; ci < p.nchunks; ++ci) {
             const SplitChunk& c = p.chunks[ci];
             const bool tb = ((ld * (p24 ? 3 : 4)) % 4096) != 0;   // tile blocking (QT = 2 only) loses on 4 KiB-multiple row strides, see the kernel
-            const void* kern = nullptr;
-            if constexpr (PRE) {
-                if (p24) kern = d_qmap ? pick_stream_kernel_spc<true, true, true>(p.SPC, c.QT, tb) : pick_stream_kernel_spc<true, false, true>(p.SPC, c.QT, tb);
-            }
-            if (!kern) kern = d_qmap ? pick_stream_kernel_spc<PRE, true, false>(p.SPC, c.QT, tb) : pick_stream_kernel_spc<PRE, false, false>(p.SPC, c.QT, tb);
-            const size_t lds = p.lds_bytes(c);
-            int rc = ensure_dynamic_lds(kern, lds);
-            if (rc != AVL_OK) return rc;
-            const _Float16* img_c = img;
-            const float* isc_c = inv_scale;
+            const void* kern = with_map_form<PRE>(d_qmap != nullptr, p24, [&](auto qm, auto c24) {
+                return pick_stream_kernel_spc<PRE, decltype(qm)::value, decltype(c24)::value>(p.SPC, c.QT, tb);
+            });
             int Qtot = p.Qtot, nch = p.nkc, q_base = c.q_base, rows = c.rows, first = (ci == 0 && first_launch) ? 1 : 0;
-            void* args[] = {&d_feat, &N, &D, &ld, &img_c, &isc_c, &Qtot, &nch, &q_base, &rows, &Qs, &d_scores, &d_argmax, &d_best, &first,
+            void* args[] = {&d_feat, &N, &D, &ld, &img, &inv_scale, &Qtot, &nch, &q_base, &rows, &Qs, &d_scores, &d_argmax, &d_best, &first,
                             &d_row_scale, &d_flags, &d_qmap, &col0};
-            AVL_HIP_CHECK(hipLaunchKernel(kern, dim3((unsigned)blocks), dim3(kSplitThreads), args, lds, st));
+            int rc = launch_chunk(kern, p.lds_bytes(c), blocks, args, st);
+            if (rc != AVL_OK) return rc;
         }
         AVL_HIP_CHECK(hipGetLastError());
         return AVL_OK;
@@ -2042,20 +1864,14 @@ static int run_split(const float* d_feat, int64_t N, int D, int64_t ld, const fl
     if (p.kswap) {
         const SplitChunk& c = p.chunks[0];
         const int s8 = (p24 && col0 % 128 != 0) ? 0 : ((p.KC == 512 && D == 1024) ? 8 : ((p.KC == 384 && D == 768) ? 6 : 0));
-        const void* kern = nullptr;
-        if constexpr (PRE) {
-            if (p24) kern = d_qmap ? pick_kswap_kernel<true, true, true>(c.QT, s8) : pick_kswap_kernel<true, false, true>(c.QT, s8);
-        }
-        if (!kern) kern = d_qmap ? pick_kswap_kernel<PRE, true, false>(c.QT, s8) : pick_kswap_kernel<PRE, false, false>(c.QT, s8);
-        const size_t lds = p.lds_bytes(c);
-        int rc = ensure_dynamic_lds(kern, lds);
-        if (rc != AVL_OK) return rc;
-        const _Float16* img_c = img;
-        const float* isc_c = inv_scale;
+        const void* kern = with_map_form<PRE>(d_qmap != nullptr, p24, [&](auto qm, auto c24) {
+            return pick_kswap_kernel<PRE, decltype(qm)::value, decltype(c24)::value>(c.QT, s8);
+        });
         int Qtot = p.Qtot, KC = p.KC, q_base = c.q_base, rows = c.rows, first = first_launch ? 1 : 0;
-        void* args[] = {&d_feat, &N, &D, &ld, &img_c, &isc_c, &Qtot, &KC, &q_base, &rows, &Qs, &d_scores, &d_argmax, &d_best, &first,
+        void* args[] = {&d_feat, &N, &D, &ld, &img, &inv_scale, &Qtot, &KC, &q_base, &rows, &Qs, &d_scores, &d_argmax, &d_best, &first,
                         &d_row_scale, &d_flags, &d_qmap, &col0};
-        AVL_HIP_CHECK(hipLaunchKernel(kern, dim3((unsigned)blocks), dim3(kSplitThreads), args, lds, st));
+        int rc = launch_chunk(kern, p.lds_bytes(c), blocks, args, st);
+        if (rc != AVL_OK) return rc;
         AVL_HIP_CHECK(hipGetLastError());
         return AVL_OK;
     }
@@ -2069,22 +1885,14 @@ static int run_split(const float* d_feat, int64_t N, int D, int64_t ld, const fl
         // split is at its register limit -- so raw maps take the path from two full tiles on)
         const bool use_xr = kSimExtraRows && s8 && fq && !d_qmap && xr >= 1 && xr <= 4 && c.rows > 32 && c.rows / 32 <= 2 &&
                             (PRE || c.rows / 32 == 2);
-        const void* kern = use_xr ? (c.rows / 32 == 2 ? pick_split_xr_kernel<2>(PRE, p24) : pick_split_xr_kernel<1>(PRE, p24))
-                           : (p24 && d_qmap) ? (c.QT == 3 ? pick_split24_kernel<3, true>(s8, fq) : (c.QT == 2 ? pick_split24_kernel<2, true>(s8, fq) : pick_split24_kernel<1, true>(s8, fq)))
-                           : p24  ? (c.QT == 3 ? pick_split24_kernel<3, false>(s8, fq) : (c.QT == 2 ? pick_split24_kernel<2, false>(s8, fq) : pick_split24_kernel<1, false>(s8, fq)))
-                           : d_qmap ? (c.QT == 3 ? pick_split_kernel<3, PRE, true>(s8, fq)
-                                               : (c.QT == 2 ? pick_split_kernel<2, PRE, true>(s8, fq) : pick_split_kernel<1, PRE, true>(s8, fq)))
-                                  : (c.QT == 3 ? pick_split_kernel<3, PRE, false>(s8, fq)
-                                               : (c.QT == 2 ? pick_split_kernel<2, PRE, false>(s8, fq) : pick_split_kernel<1, PRE, false>(s8, fq)));
-        const size_t lds = p.lds_bytes(c);
-        int rc = ensure_dynamic_lds(kern, lds);
-        if (rc != AVL_OK) return rc;
-        const _Float16* img_c = img;
-        const float* isc_c = inv_scale;
+        const void* kern = with_map_form<PRE>(d_qmap != nullptr, p24, [&](auto qm, auto c24) {
+            return pick_split_kernel<PRE, decltype(qm)::value, decltype(c24)::value>(use_xr ? c.rows / 32 : c.QT, s8, fq, use_xr);
+        });
         int Qtot = p.Qtot, KC = p.KC, nkc = p.nkc, q_base = c.q_base, rows = c.rows, first = (ci == 0 && first_launch) ? 1 : 0;
-        void* args[] = {&d_feat, &N, &D, &ld, &img_c, &isc_c, &d_q, &ldq, &Qtot, &KC, &nkc, &q_base, &rows, &Qs,
+        void* args[] = {&d_feat, &N, &D, &ld, &img, &inv_scale, &d_q, &ldq, &Qtot, &KC, &nkc, &q_base, &rows, &Qs,
                         &d_scores, &d_argmax, &d_best, &first, &d_row_scale, &d_flags, &d_qmap, &col0};
-        AVL_HIP_CHECK(hipLaunchKernel(kern, dim3((unsigned)blocks), dim3(kSplitThreads), args, lds, st));
+        int rc = launch_chunk(kern, p.lds_bytes(c), blocks, args, st);
+        if (rc != AVL_OK) return rc;
     }
     AVL_HIP_CHECK(hipGetLastError());
     return AVL_OK;
