@@ -271,6 +271,13 @@ _SIGS = {
     "avl_map_match_cells": (C.c_int, [_vp, _sz, _i64, C.c_int, C.c_int, _vp, _i64, _vp, C.c_int, _vp, _vp, _vp]),
     "avl_row_dots_f32": (C.c_int, [_vp, _i64, _vp, _i64, C.c_int, _vp, _vp, _vp]),
     "avl_map_diff_status": (C.c_int, [_vp, _vp, _i64, _f64, _vp, C.c_int, _vp, _vp, _vp]),
+    # fusing a revisit into the map (csrc/avl_mapfuse.hip): upstream has no counterpart; outputs are sized by n_a, n_b and D, the
+    # scratch is the cell index, avl_argsort_bits' workspace and one int32 array, so there is no size query
+    "avl_map_move_cells": (C.c_int, [_vp, _i64, _vp, _vp, C.c_int, _f64, C.c_int, _vp, _vp, _vp]),
+    "avl_map_fuse_plan": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, C.c_int, C.c_int, _vp, _sz, _vp, _sz, _vp, _i64,
+                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "avl_map_fuse_rows": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, C.c_int, _f64, _f64,
+                                    C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -6,6 +6,8 @@
                                                      [--register-min-fraction F]]
                                          [--compare OTHER_SCENE_DIR [--compare-radius R] [--compare-threshold T]
                                                     [--compare-shift DR DC DH] [--compare-json PATH]]
+                                         [--fuse OTHER_SCENE_DIR --fuse-out DIR [--fuse-keep-vanished] [--fuse-keep-changed]
+                                                 [--fuse-gain G] [--fuse-json PATH]]
 
 Loads <scene>/vlmap/vlmaps.h5df and walks the depth rays of the scene's frames, then of every --revisit directory (the same
 dataset layout, poses.txt in the scene's world frame), through the map's voxels (Map.audit_visibility): per voxel
@@ -26,7 +28,16 @@ the changed volume in m^3) and the object-sized changes, which are also printed 
 occupied cell of the other map within --compare-radius cells (0 .. 2, default 1); a pair whose feature rows have a cosine below
 --compare-threshold (default 0.8) counts as changed; --compare-shift moves this map's cells by whole cells first.  The audit of
 this map under the --revisit frames tells vanished from never looked at.  --compare-json also writes the summary and the list to
-PATH.  Whole-cell shifts only: a revisit from another odometry origin has to be built with corrected poses first."""
+PATH.  Whole-cell shifts only: for a revisit from another odometry origin use --fuse, which resamples it onto this grid first.
+
+--fuse loads the map under OTHER_SCENE_DIR -- a later map of the same place, built on its own -- and folds it into this one
+(VLMap.fuse): the transform between the two recordings' frames (Map.transform_from; with --register corrected by
+the registration of OTHER_SCENE_DIR's frames to this map), the other map resampled onto this grid (VLMap.resample), the comparison
+of the two (VLMap.compare with the --compare-* settings), then the fusion: vanished voxels of this map leave (unless
+--fuse-keep-vanished), replaced ones give way to the other map's (unless --fuse-keep-changed), shared cells get the weighted mean,
+with the other map's weights times --fuse-gain (default 1).  The fused map is saved under --fuse-out/vlmap, which may be neither
+input scene: no input map is written over.  The JSON line then carries "fuse": the transform, the comparison's summary and the
+counts; --fuse-json also writes that to PATH."""
 from __future__ import annotations
 
 import argparse
@@ -58,9 +69,26 @@ def parse_args(argv=None):
                     help="this map's cell c is the other map's cell c + shift (default 0 0 0)")
     ap.add_argument("--compare-json", default=None, metavar="PATH", help="also write the summary and the change list to PATH")
     ap.add_argument("--compare-min-voxels", type=int, default=None, help="smallest component listed as a change (default 20)")
+    ap.add_argument("--fuse", default=None, metavar="OTHER_SCENE_DIR", help="a later map of the same place, built on its own: fold it into this one")
+    ap.add_argument("--fuse-out", default=None, metavar="DIR", help="scene directory the fused map is written to (needed with --fuse)")
+    ap.add_argument("--fuse-keep-vanished", action="store_true", help="keep this map's voxels that the other map no longer holds")
+    ap.add_argument("--fuse-keep-changed", action="store_true", help="average replaced voxels with the other map's instead of giving way")
+    ap.add_argument("--fuse-gain", type=float, default=None, help="factor on the other map's weights, > 0 (default 1)")
+    ap.add_argument("--fuse-json", default=None, metavar="PATH", help="also write the transform, the summary and the counts to PATH")
     args = ap.parse_args(argv)
+    if args.fuse is None and (args.fuse_out or args.fuse_keep_vanished or args.fuse_keep_changed or args.fuse_gain is not None or args.fuse_json):
+        ap.error("--fuse-out, --fuse-keep-vanished, --fuse-keep-changed, --fuse-gain and --fuse-json need --fuse")
+    if args.fuse is not None:
+        if not args.fuse_out:
+            ap.error("--fuse needs --fuse-out")
+        if Path(args.fuse_out).resolve() in (Path(args.data_dir).resolve(), Path(args.fuse).resolve()):
+            ap.error("--fuse-out may be neither input scene: no input map is written over")
+    if args.fuse_gain is None:
+        args.fuse_gain = 1.0
+    if not (args.fuse_gain > 0.0 and args.fuse_gain < float("inf")):
+        ap.error("--fuse-gain is a finite factor greater than 0")
     compare = ("compare_radius", "compare_threshold", "compare_shift", "compare_json", "compare_min_voxels")
-    if args.compare is None and any(getattr(args, k) is not None for k in compare):
+    if args.compare is None and args.fuse is None and any(getattr(args, k) is not None for k in compare):
         ap.error("--compare-radius, --compare-threshold, --compare-shift, --compare-json and --compare-min-voxels need --compare")
     for k, default in zip(compare, (1, 0.8, [0, 0, 0], None, 20)):
         if getattr(args, k) is None:
@@ -142,6 +170,32 @@ def main(argv=None):
         save_dir.mkdir(parents=True, exist_ok=True)
         save_3d_map(save_dir / "vlmaps.h5df", vm.grid_feat, vm.grid_pos, vm.weight, vm.occupied_ids, vm.mapped_iter_list, vm.grid_rgb)
         out["files"].append(str(save_dir / "vlmaps.h5df"))
+    if args.fuse:
+        other = VLMap(cfg.map_config, data_dir=args.fuse)
+        other.prefetch_device = False
+        if not other.load_map(args.fuse):
+            raise SystemExit(f"no map under {args.fuse}: run apps.create_map first")
+        reg = None
+        if args.register:
+            reg = vm.register_frames(args.fuse, max_angle_deg=args.register_angle, angle_step_deg=args.register_step,
+                                     radius_m=args.register_radius, stride=args.stride)
+            if reg.fraction[0] < args.register_min_fraction:
+                raise SystemExit(f"{args.fuse}: only {reg.fraction[0]:.2f} of {int(reg.valid[0])} depth points land on the map at the best pose "
+                                 f"found (--register-min-fraction {args.register_min_fraction}): not fusing under a pose this poor")
+        T = vm.transform_from(args.fuse, registration=reg)
+        moved = other.resample(T)
+        changes = vm.compare(moved, radius=args.compare_radius, threshold=args.compare_threshold)
+        counts = vm.fuse(moved, changes=changes, drop_vanished=not args.fuse_keep_vanished, replace_changed=not args.fuse_keep_changed,
+                         gain=args.fuse_gain)
+        save_dir = Path(args.fuse_out) / "vlmap"
+        save_dir.mkdir(parents=True, exist_ok=True)
+        save_3d_map(save_dir / "vlmaps.h5df", vm.grid_feat, vm.grid_pos, vm.weight, vm.occupied_ids, vm.mapped_iter_list, vm.grid_rgb)
+        out["files"].append(str(save_dir / "vlmaps.h5df"))
+        out["fuse"] = {"other": str(args.fuse), "transform": [[float(v) for v in row] for row in T], "resampled": moved.resample_counts,
+                       "summary": changes.summary(), "counts": counts}
+        if args.fuse_json:
+            Path(args.fuse_json).write_text(json.dumps(out["fuse"]))
+            out["files"].append(str(args.fuse_json))
     print(json.dumps(out))
     return out
 

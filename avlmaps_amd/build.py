@@ -53,6 +53,7 @@ SOURCES = {
     "avl_costfield.hip": ["-ffp-contract=off"],    # the field is integer; the costmap's d * d is one float64 product that rint() takes alone
     "avl_travel_many.hip": ["-ffp-contract=off"],  # the fields are integer; the sound sum's a + b * sqrt(2) and p - (p * d) * decay round like NumPy, unfused
     "avl_mapdiff.hip": ["-ffp-contract=off"],      # a row's sums are float64 products and additions in a pinned order, none fused; the status predicate rounds each product once
+    "avl_mapfuse.hip": ["-ffp-contract=off"],      # the moved point and a fused element are float64 products and sums in a pinned order, each rounded once
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fvisibility=hidden", "-Wall",
           "-Wno-unused-function", "-munsafe-fp-atomics"]

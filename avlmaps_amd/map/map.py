@@ -577,6 +577,23 @@ class Map:
         n = min(len(depth_paths), len(poses))
         return depth_paths[:n], transforms[:n], float(builder.min_depth), float(builder.max_depth), own_first
 
+    def transform_from(self, other_data_dir, registration=None) -> np.ndarray:
+        """(4, 4) float64: the transform from the base frame of a map built from `other_data_dir` on its own into this map's base
+        frame, for VLMap.resample and VLMap.fuse.  Host only.  Both frames are defined by _audit_frames: with own = the directory's
+        camera -> map transforms in its own frame (its first pose) and here = the same frames in this map's frame (this map's
+        first pose), S = here[0] @ inv(own[0]) satisfies S @ own[i] == here[i] for every frame.  registration: a joint
+        Registration of that directory against this map (register_frames); its correction is left-multiplied.  A map without a
+        scene of its own shares the directory's frame: the identity."""
+        own = self._audit_frames(other_data_dir)[1]
+        here = self._audit_frames(other_data_dir, self._own_first_pose())[1]
+        if len(own) == 0:
+            raise ValueError(f"transform_from: {other_data_dir} holds no posed frame")
+        S = np.asarray(here[0], dtype=np.float64) @ np.linalg.inv(np.asarray(own[0], dtype=np.float64))
+        if registration is not None:
+            S = np.asarray(registration.correction, dtype=np.float64) @ S
+        S[3] = (0.0, 0.0, 0.0, 1.0)
+        return S
+
     def audit_visibility(self, data_dirs=None, stride: int = 4, end_margin: int = 2, batch: int = 16, corrections=None) -> "VisibilityAudit":
         """Audit the map's voxels against the depth frames of `data_dirs` (default: the map's own scene; a revisit is a second
         directory; frame ids run on consecutively across directories).  Pass A folds every frame's hits into last_hit (N,) int32,

@@ -141,28 +141,60 @@ class VLMap(Map):
                 self.occupied_ids = out
             if self.scores_mat is not None:
                 self.scores_mat = np.ascontiguousarray(np.asarray(self.scores_mat)[keep])
-            # everything that mirrors the old arrays on the device, or was computed from them
-            self._dev_feat = self._dev_feat_src = None
-            self._dev_pos = self._dev_pos_src = None
-            self._dev_rgb = self._dev_rgb_src = None
-            plan = getattr(self, "_heat_plan_obj", None)
-            if plan is not None:
-                plan.close()
-            self._heat_plan_obj = self._heat_plan_src = None
-            self._dev_scores = self._dev_scores_src = None
-            self._quantile_cache = {}
-            self._argmax = self._argmax_src = None
-            self._dev_argmax = self._dev_argmax_src = None
-            cached = getattr(self, "_instances_cache", None)
-            if cached is not None:
-                cached[1].close()
-            self._instances_cache = None
-            cached = getattr(self, "_objects_cache", None)
-            if cached is not None:
-                cached[1].close()
-            self._objects_cache = None
-            self.visibility = None
+            self._drop_derived()
         return removed
+
+    def _drop_derived(self) -> None:
+        """Forget everything that mirrors the voxel arrays on the device, or was computed from them: prune_voxels and fuse call it
+        under _dev_lock after they replaced the arrays."""
+        self._dev_feat = self._dev_feat_src = None
+        self._dev_pos = self._dev_pos_src = None
+        self._dev_rgb = self._dev_rgb_src = None
+        plan = getattr(self, "_heat_plan_obj", None)
+        if plan is not None:
+            plan.close()
+        self._heat_plan_obj = self._heat_plan_src = None
+        self._dev_scores = self._dev_scores_src = None
+        self._quantile_cache = {}
+        self._argmax = self._argmax_src = None
+        self._dev_argmax = self._dev_argmax_src = None
+        cached = getattr(self, "_instances_cache", None)
+        if cached is not None:
+            cached[1].close()
+        self._instances_cache = None
+        cached = getattr(self, "_objects_cache", None)
+        if cached is not None:
+            cached[1].close()
+        self._objects_cache = None
+        self.visibility = None
+
+    def resample(self, transform=None, shift=(0, 0, 0)) -> "VLMap":
+        """A new VLMap on this map's grid and config whose voxels are this map's moved by the (4, 4) float64 `transform` of base
+        coordinates (None = identity; Map.transform_from gives the one between two recordings' frames) and then by `shift` whole
+        cells (row, col, h), which is ADDED to the moved cells (map/fuse.py, ops.fuse_maps with an empty first map).
+        Forward and nearest-cell: a voxel's cell centre is moved and lands in one cell; rows that land in one cell are averaged by
+        weight, rows that leave the grid or the height band are dropped.  Under a rotation some cells receive two or three voxels and
+        neighbouring cells none, so surfaces come out with pinholes; features are not interpolated.  scores_mat is not carried over
+        (index the new map); categories and mapped_iter_list are.  With no arguments the result equals this map."""
+        from .fuse import resample_map
+        return resample_map(self, transform, shift)
+
+    def fuse(self, other, transform=None, shift=(0, 0, 0), changes=None, drop_vanished: bool = True, replace_changed: bool = True,
+             gain: float = 1.0) -> dict:
+        """Fold `other` (B, a later map of the same place) into this map (A) in place, like prune_voxels: a cell that both maps hold
+        gets the mean of its rows weighted by the maps' weights -- the builder's running mean in closed form --, a cell that only B
+        holds is appended (map/fuse.py, ops.fuse_maps).  transform: B's base frame -> A's (None = identity); shift
+        has VLMap.compare's meaning: A's cell c corresponds to B's cell c + shift.  gain (> 0) scales B's weights: above 1 the
+        revisit counts for more.  changes: the MapChanges of self.compare(other, shift=shift); with it the vanished voxels of A are
+        dropped (drop_vanished) and the voxels of A whose content was replaced give way to B's (replace_changed), while B's voxels
+        that this session never looked at (unseen_b) stay out.  It is accepted only with transform=None and its own shift: resample
+        `other` first otherwise.  Returns the counts (ops.FUSE_COUNTS, voxels_a, voxels_b, voxels).  ValueError unless gs, cs, the
+        height cells and the feature width agree.  Afterwards scores_mat is None (the rows changed: index again), every derived
+        device copy is dropped, and mapped_iter_list stays this map's: the frames of B's recording are not recorded in it.  The
+        raw float32 rows are fused, not the compact resident copies; not for rows sharded over ranks.  The result is not what a
+        joint build of both recordings gives: the builder's float32 running mean rounds differently."""
+        from .fuse import fuse_into
+        return fuse_into(self, other, transform, shift, changes, drop_vanished, replace_changed, gain)
 
     def compare(self, other, radius: int = 1, threshold: float = 0.8, shift=(0, 0, 0), audit=None, other_audit=None, min_rays: int = 3):
         """What changed between this map (A, the earlier one) and `other` (B, a later map of the same place): a MapChanges
@@ -174,9 +206,9 @@ class VLMap(Map):
         (self.audit_visibility([other's data_dir])), other_audit: one of `other` made from this session's frames; with one, an
         unmatched voxel that fewer than min_rays of the other session's sight rays passed through is unseen, not vanished /
         appeared.  ValueError unless gs, cs, the number of height cells and the feature width agree.  Whole-cell shifts only: a
-        revisit recorded from another odometry origin has to be built with corrected poses first (Map.register_frames gives the
-        correction); resampling one map under a rotation or a sub-cell shift is out of scope.  Upstream has no counterpart: its
-        maps are static."""
+        revisit recorded from another odometry origin -- a rotation or a sub-cell shift away -- is resampled onto this map's grid
+        first, a.compare(b.resample(T)) with T from Map.transform_from (Map.register_frames gives the correction).  Upstream has
+        no counterpart: its maps are static."""
         from .changes import compare_maps
         return compare_maps(self, other, radius=radius, threshold=threshold, shift=shift, audit=audit, other_audit=other_audit,
                             min_rays=min_rays)

@@ -100,6 +100,10 @@ from .mapdiff import (  # noqa: F401
     cosine_of, DIFF_CHANGED, DIFF_MAX_DIM, DIFF_MAX_RADIUS, DIFF_NO_MATCH, DIFF_SAME, DIFF_STREAM_ROWS, DIFF_UNSEEN, diff_status,
     DiffSide, map_diff, MapDiff, match_cells, row_dots,
 )
+from .mapfuse import (  # noqa: F401
+    check_gain, check_transform, FUSE_COUNTS, FUSE_ERR_OUTSIDE, FUSE_ERR_SHARED, FUSE_MAX_DIM, fuse_maps, fuse_plan, fuse_rows, FusedMap,
+    FusePlan, move_cells,
+)
 # the shared marshalling layer; its one device predicate keeps both of the names it had here
 from ._args import (  # noqa: F401
     _dev_u8, _image_any, _image_shape, _image_u8, _is_dev, _is_dev as _on_device, _result,

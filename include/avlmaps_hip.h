@@ -1542,6 +1542,66 @@ AVL_API int avl_row_dots_f32(const float* d_feat_a, int64_t n_a, const float* d_
 AVL_API int avl_map_diff_status(const int32_t* d_match, const double* d_sums, int64_t n, double t2, const int32_t* d_through, int min_rays,
                                 uint8_t* d_status, int32_t* d_counts, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * (31) fusing a revisit into the map: the cells of map B moved into map A's grid under a 4 x 4 transform, the join of both voxel
+ *     lists by cell, and the weighted mean of the joined rows (csrc/avl_mapfuse.hip).  The arithmetic is the
+ *     builder's running mean in closed form (vlmap_builder.py:172-178: feat = (feat * w + new * a) / (w + a)) applied to finished
+ *     maps: sum(w_i f_i) / sum(w_i).  Every output is allocated by the caller and sized by n_a, n_b and D as stated below; the
+ *     scratch is the cell index of (20), the workspace of avl_argsort_bits and one int32 array, so there is no size query.  Every
+ *     result has one value: the move is float64 with every product and sum rounded once, the plan is integer, a fused element is a
+ *     float64 sum in member order.  All calls are asynchronous on `stream`, check their arguments before any device work and
+ *     allocate nothing.
+ * ------------------------------------------------------------------------------------------------ */
+/* Moves the n cells (row, col, h) of d_cells (n, 3) int32 on the gs x gs x vh grid of cell size cs.  A cell stands for the centre of
+ * the interval of base coordinates that base_pos2grid_id_3d (mapping_utils.py:345-349) maps to it: with k = gs / 2 - index (integer
+ * division) for row and col, x = (k + 0.5 * sign(k)) * cs -- the cell k = 0 is two cells wide upstream (truncation toward zero) and
+ * its centre is 0 --, and z = (h + 0.5) * cs.  h_T (16 float64 in HOST memory, row-major 4 x 4, finite, bottom row 0 0 0 1; NULL =
+ * identity): x' = ((T00 * x + T01 * y) + T02 * z) + T03 and likewise y' and z', every product and sum rounded once in float64, none
+ * fused.  The moved cell is upstream's (int)(gs / 2.0 - (int)(x' / cs)), (int)(gs / 2.0 - (int)(y' / cs)), (int)(z' / cs): float64
+ * divides, truncation toward zero.  h_shift (3 int32 in HOST memory, NULL = none) is then added in index space.  d_inside (n) uint8:
+ * 0 where a moved coordinate is not finite, a quotient is not below 2^31 in magnitude or a final index leaves the grid; d_out (n, 3)
+ * int32 holds the final cell where d_inside is 1 and (-1, -1, -1) elsewhere.  With h_T = NULL the call is integer only: the cell
+ * plus the shift.  1 <= gs <= 16384, vh >= 1, gs * gs * vh < 2^31, cs > 0 and finite, 0 <= n < 2^31 - 1; n = 0 does nothing. */
+AVL_API int avl_map_move_cells(const int32_t* d_cells, int64_t n, const double* h_T, const int32_t* h_shift, int gs, double cs, int vh,
+                               int32_t* d_out, uint8_t* d_inside, void* stream);
+/* Joins map A's cells d_cells_a (n_a, 3) and map B's moved cells d_cells_b (n_b, 3) by cell.  A row of B is SELECTED when d_use_b
+ * (n_b uint8, NULL = all ones) is non-zero, its weight d_w_b (float32) is finite and > 0, d_inside_b (n_b uint8, NULL = all ones) is
+ * non-zero and its cell lies inside the grid.  A row of A is selected when d_use_a is non-zero and its weight is finite and > 0; a
+ * selected row of A outside the grid sets bit 0 of the error word and is dropped, two selected rows of A in one cell set bit 1.
+ * The output voxels: first every selected row of A in row order, then every cell that only selected rows of B reach, ordered by the
+ * smallest such row.
+ *   d_head (4) int32: n_out, the selected rows of A, the selected rows of B, the error word;
+ *   d_a_row (n_a + n_b) int32: the first n_out hold the A row of an output voxel or -1;
+ *   d_b_start (n_a + n_b + 1) int32 and d_b_rows (n_b) int32: the CSR of the selected rows of B of every output voxel, ascending
+ *     (entries of d_b_start past n_out hold the number of selected rows, entries of d_b_rows past that number -1);
+ *   d_out_of_a (n_a), d_out_of_b (n_b) int32: the output voxel of every input row, -1 for a row that is not selected;
+ *   d_counts (6) int32: rows of A not selected; rows of B whose use or weight unselects them; further rows of B outside; rows of B
+ *     in a cell of a selected row of A; new cells; rows of B in a new cell beyond its first.  [1] .. [5] add up to n_b.
+ * Scratch: d_index, index_bytes >= avl_cell_index_work_bytes(max(n_a, n_b), gs, vh), built twice here; d_sort_work, sort_work_bytes
+ * >= avl_argsort_bits_work_bytes(n_b, 4, bits) with bits = the bit length of n_a + n_b; d_scratch: 9 * max(n_a, n_b) + 1024 int32 at
+ * an 8-byte aligned address (scratch_i32 = its length).  0 <= n_a, n_b and n_a + n_b < 2^31 - 1; the grid as in (20). */
+AVL_API int avl_map_fuse_plan(const int32_t* d_cells_a, const uint8_t* d_use_a, const float* d_w_a, int64_t n_a, const int32_t* d_cells_b,
+                              const uint8_t* d_inside_b, const uint8_t* d_use_b, const float* d_w_b, int64_t n_b, int gs, int vh, void* d_index,
+                              size_t index_bytes, void* d_sort_work, size_t sort_work_bytes, int32_t* d_scratch, int64_t scratch_i32,
+                              int32_t* d_head, int32_t* d_a_row, int32_t* d_b_start, int32_t* d_b_rows, int32_t* d_out_of_a,
+                              int32_t* d_out_of_b, int32_t* d_counts, void* stream);
+/* The n_out fused voxels of a plan.  The members of voxel v: row d_a_row[v] of A when >= 0, then the rows d_b_rows[d_b_start[v] ..
+ * d_b_start[v + 1]) of B in that order; a member index outside its map is skipped.  In float64, with g = g_a or g_b (> 0, finite)
+ * by side: w_i = (double)weight_i * g; W = w_0 + w_1 + .. in member order; per element d, acc = w_0 * (double)f_0[d] + w_1 *
+ * (double)f_1[d] + .. in member order, every product and every addition rounded once, none fused, the first product taken as it
+ * is (a sole -0.0 stays -0.0).  d_feat_out[v, d] = (float)(acc / W), d_weight_out[v] = (float)W, d_rgb_out[v, c] = (uint8)(int)(acc_c
+ * / W) with acc_c the same sum over (double)rgb_i[c]: truncated, as upstream's uint8 store truncates.  A voxel with one member and
+ * g = 1 comes back bit for bit.  The elements are independent: rows are read and written 16 bytes at a time where D % 4 == 0 and
+ * the matrix is 16-byte aligned and by scalars otherwise, chosen per matrix, same bytes.  d_grid_pos_out (n_out, 3): the cell of
+ * the first member (d_cells_b are the MOVED cells).  d_occupied (gs, gs, vh) int32, NULL = not wanted: set to -1 and then to v at
+ * the cell of voxel v.  A voxel without a member gets zeros and no cell.  Matrices are (rows, D) float32 contiguous, 1 <= D <= 8192;
+ * 0 <= n_out <= n_a + n_b < 2^31 - 1; n_out = 0 only clears d_occupied. */
+AVL_API int avl_map_fuse_rows(int64_t n_out, const int32_t* d_a_row, const int32_t* d_b_start, const int32_t* d_b_rows, const float* d_feat_a,
+                              const float* d_w_a, const uint8_t* d_rgb_a, const int32_t* d_cells_a, int64_t n_a, const float* d_feat_b,
+                              const float* d_w_b, const uint8_t* d_rgb_b, const int32_t* d_cells_b, int64_t n_b, int D, double g_a, double g_b,
+                              int gs, int vh, float* d_feat_out, float* d_weight_out, uint8_t* d_rgb_out, int32_t* d_grid_pos_out,
+                              int32_t* d_occupied, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
