@@ -278,6 +278,12 @@ _SIGS = {
                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "avl_map_fuse_rows": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, C.c_int, _f64, _f64,
                                     C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # resampling a finished map backward (csrc/avl_mappull.hip): upstream has no counterpart; two plan calls around the read-back of
+    # n_out, the scratch is the cell index and one int32 array of a stated length, so there is no size query
+    "avl_map_pull_plan": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, C.c_int, _f64, C.c_int, C.c_int, _f64, _vp, _sz, _vp, _i64, _vp, _vp]),
+    "avl_map_pull_fill": (C.c_int, [_i64, _vp, _vp, C.c_int, _f64, C.c_int, C.c_int, _f64, _vp, _sz, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp,
+                                    _vp, _vp]),
+    "avl_map_pull_rows": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _i64, C.c_int, _vp, _vp, _vp, _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

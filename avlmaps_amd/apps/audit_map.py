@@ -7,7 +7,8 @@
                                          [--compare OTHER_SCENE_DIR [--compare-radius R] [--compare-threshold T]
                                                     [--compare-shift DR DC DH] [--compare-json PATH]]
                                          [--fuse OTHER_SCENE_DIR --fuse-out DIR [--fuse-keep-vanished] [--fuse-keep-changed]
-                                                 [--fuse-gain G] [--fuse-json PATH]]
+                                                 [--fuse-gain G] [--fuse-json PATH]
+                                                 [--fuse-resample forward|nearest|linear] [--fuse-min-support S]]
 
 Loads <scene>/vlmap/vlmaps.h5df and walks the depth rays of the scene's frames, then of every --revisit directory (the same
 dataset layout, poses.txt in the scene's world frame), through the map's voxels (Map.audit_visibility): per voxel
@@ -37,7 +38,11 @@ of the two (VLMap.compare with the --compare-* settings), then the fusion: vanis
 --fuse-keep-vanished), replaced ones give way to the other map's (unless --fuse-keep-changed), shared cells get the weighted mean,
 with the other map's weights times --fuse-gain (default 1).  The fused map is saved under --fuse-out/vlmap, which may be neither
 input scene: no input map is written over.  The JSON line then carries "fuse": the transform, the comparison's summary and the
-counts; --fuse-json also writes that to PATH."""
+counts; --fuse-json also writes that to PATH.  --fuse-resample chooses how the other map is resampled (VLMap.resample's method,
+DESIGN.md 4.34): forward (the default) moves every voxel to its nearest cell and leaves pinholes under a rotation, which the
+comparison reads as vanished voxels; linear and nearest ask backward from every cell of this grid and leave none -- use linear for
+a turned revisit, nearest where features must not be blended across object borders.  --fuse-min-support (0 < S <= 1, default 0.5)
+is linear's threshold on a cell's support.  The "fuse" JSON echoes both."""
 from __future__ import annotations
 
 import argparse
@@ -75,9 +80,23 @@ def parse_args(argv=None):
     ap.add_argument("--fuse-keep-changed", action="store_true", help="average replaced voxels with the other map's instead of giving way")
     ap.add_argument("--fuse-gain", type=float, default=None, help="factor on the other map's weights, > 0 (default 1)")
     ap.add_argument("--fuse-json", default=None, metavar="PATH", help="also write the transform, the summary and the counts to PATH")
+    ap.add_argument("--fuse-resample", default=None, choices=("forward", "nearest", "linear"),
+                    help="how the other map is resampled onto this grid (default forward; linear for a turned revisit)")
+    ap.add_argument("--fuse-min-support", type=float, default=None, metavar="S",
+                    help="the support a cell needs under --fuse-resample linear, 0 < S <= 1 (default 0.5)")
     args = ap.parse_args(argv)
     if args.fuse is None and (args.fuse_out or args.fuse_keep_vanished or args.fuse_keep_changed or args.fuse_gain is not None or args.fuse_json):
         ap.error("--fuse-out, --fuse-keep-vanished, --fuse-keep-changed, --fuse-gain and --fuse-json need --fuse")
+    if args.fuse is None and (args.fuse_resample is not None or args.fuse_min_support is not None):
+        ap.error("--fuse-resample and --fuse-min-support need --fuse")
+    if args.fuse_min_support is not None and args.fuse_resample != "linear":
+        ap.error("--fuse-min-support needs --fuse-resample linear")
+    if args.fuse_resample is None:
+        args.fuse_resample = "forward"
+    if args.fuse_min_support is None:
+        args.fuse_min_support = 0.5
+    if not 0.0 < args.fuse_min_support <= 1.0:
+        ap.error("--fuse-min-support is greater than 0 and at most 1")
     if args.fuse is not None:
         if not args.fuse_out:
             ap.error("--fuse needs --fuse-out")
@@ -183,7 +202,7 @@ def main(argv=None):
                 raise SystemExit(f"{args.fuse}: only {reg.fraction[0]:.2f} of {int(reg.valid[0])} depth points land on the map at the best pose "
                                  f"found (--register-min-fraction {args.register_min_fraction}): not fusing under a pose this poor")
         T = vm.transform_from(args.fuse, registration=reg)
-        moved = other.resample(T)
+        moved = other.resample(T, method=args.fuse_resample, min_support=args.fuse_min_support)
         changes = vm.compare(moved, radius=args.compare_radius, threshold=args.compare_threshold)
         counts = vm.fuse(moved, changes=changes, drop_vanished=not args.fuse_keep_vanished, replace_changed=not args.fuse_keep_changed,
                          gain=args.fuse_gain)
@@ -192,6 +211,7 @@ def main(argv=None):
         save_3d_map(save_dir / "vlmaps.h5df", vm.grid_feat, vm.grid_pos, vm.weight, vm.occupied_ids, vm.mapped_iter_list, vm.grid_rgb)
         out["files"].append(str(save_dir / "vlmaps.h5df"))
         out["fuse"] = {"other": str(args.fuse), "transform": [[float(v) for v in row] for row in T], "resampled": moved.resample_counts,
+                       "resample": args.fuse_resample, "min_support": args.fuse_min_support,
                        "summary": changes.summary(), "counts": counts}
         if args.fuse_json:
             Path(args.fuse_json).write_text(json.dumps(out["fuse"]))

@@ -54,6 +54,7 @@ SOURCES = {
     "avl_travel_many.hip": ["-ffp-contract=off"],  # the fields are integer; the sound sum's a + b * sqrt(2) and p - (p * d) * decay round like NumPy, unfused
     "avl_mapdiff.hip": ["-ffp-contract=off"],      # a row's sums are float64 products and additions in a pinned order, none fused; the status predicate rounds each product once
     "avl_mapfuse.hip": ["-ffp-contract=off"],      # the moved point and a fused element are float64 products and sums in a pinned order, each rounded once
+    "avl_mappull.hip": ["-ffp-contract=off"],      # the pulled-back point, the corner weights and a gathered element are float64 products and sums in a pinned order
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fvisibility=hidden", "-Wall",
           "-Wno-unused-function", "-munsafe-fp-atomics"]

@@ -23,21 +23,13 @@
 // depend on each other, so both paths give the same bytes.  Member indices and weights are the same addresses for all lanes of a
 // group and are read again per chunk from cache (two chunks at D = 512).  Four float64 accumulators per lane, no LDS, no cross-lane
 // step.  Rows of B are gathered as whole contiguous rows; the grid keeps every CU at 16 workgroups.
-#include "avl_cellindex.h"
+#include "avl_mapfuse.h"
 #include "avl_scan.h"
 
 namespace avl {
 
-constexpr int kMfMaxDim = 8192;
 constexpr int kMfScanThreads = 256, kMfScanPer = 4;
 constexpr int kMfErrOutside = 1, kMfErrShared = 2;
-
-struct MfTransform {
-    double t[12];
-};
-
-// upstream's int(gs / 2 - int(q)) for q = x / cs with |q| < 2^31
-__device__ __forceinline__ int64_t mf_index(double q, int gs) { return (int64_t)((double)gs / 2.0 - (double)(int64_t)q); }
 
 __global__ __launch_bounds__(256) void mf_move_kernel(const int32_t* __restrict__ cells, int64_t n, MfTransform T, bool moving, int sr, int sc, int sh,
                                                       int gs, double cs, int vh, int32_t* __restrict__ out, uint8_t* __restrict__ inside) {
@@ -63,12 +55,6 @@ __global__ __launch_bounds__(256) void mf_move_kernel(const int32_t* __restrict_
         out[3 * i + 2] = ok ? (int32_t)h : -1;
         inside[i] = ok ? 1 : 0;
     }
-}
-
-__device__ __forceinline__ bool mf_weight_ok(float w) { return w > 0.0f && w < __builtin_inff(); }     // false for a NaN
-
-__device__ __forceinline__ int mf_lin(const int32_t* __restrict__ cells, int64_t i, int gs, int vh) {
-    return (int)ci_linear(cells[3 * i], cells[3 * i + 1], cells[3 * i + 2], gs, vh);                    // -1 outside; inside < 2^31
 }
 
 // flag[i] = row i of A is selected and inside; masked = its cell, (-1, -1, -1) for every other row
@@ -110,12 +96,6 @@ __global__ __launch_bounds__(256) void mf_finish_a_kernel(const int32_t* __restr
 }
 
 constexpr int kMfPending = -2;                          // out_of_b of a selected row of B that no row of A meets, until it is numbered
-
-// every lane of the wave calls it
-__device__ __forceinline__ void mf_count(bool p, int32_t* counter) {
-    const int c = __popcll(__ballot(p));
-    if ((threadIdx.x & (kWave - 1)) == 0 && c) atomicAdd(counter, c);
-}
 
 __global__ __launch_bounds__(256) void mf_select_b_kernel(const int32_t* __restrict__ cells, const uint8_t* __restrict__ inside,
                                                           const uint8_t* __restrict__ use, const float* __restrict__ w, int64_t n, int gs, int vh,
@@ -214,27 +194,6 @@ __global__ __launch_bounds__(256) void mf_csr_kernel(const int64_t* __restrict__
         }
     }
 }
-
-// the four elements d .. d + 3 of a row (d < D), zeros past D; `vec`: D % 4 == 0 and the row is 16-byte aligned
-__device__ __forceinline__ float4 mf_load4(const float* __restrict__ row, int d, int D, bool vec) {
-    if (vec) return *reinterpret_cast<const float4*>(row + d);
-    float4 v;
-    v.x = row[d];
-    v.y = d + 1 < D ? row[d + 1] : 0.0f;
-    v.z = d + 2 < D ? row[d + 2] : 0.0f;
-    v.w = d + 3 < D ? row[d + 3] : 0.0f;
-    return v;
-}
-
-struct MfAcc {
-    double x, y, z, w;
-    bool any;
-    __device__ __forceinline__ void add(double wi, float4 f) {
-        const double px = wi * (double)f.x, py = wi * (double)f.y, pz = wi * (double)f.z, pw = wi * (double)f.w;
-        if (any) x = x + px, y = y + py, z = z + pz, w = w + pw;
-        else x = px, y = py, z = pz, w = pw, any = true;
-    }
-};
 
 template <int L>
 __global__ __launch_bounds__(256) void mf_rows_kernel(int64_t n_out, const int32_t* __restrict__ a_row, const int32_t* __restrict__ b_start,

@@ -1,5 +1,6 @@
-"""One map out of two sessions: VLMap.resample and VLMap.fuse (ops/mapfuse.py, csrc/avl_mapfuse.hip).  Upstream has
-no counterpart: a revisit can only be folded in there by building one map from both recordings."""
+"""One map out of two sessions: VLMap.resample and VLMap.fuse (ops/mapfuse.py, csrc/avl_mapfuse.hip; the backward
+resampling: ops/mappull.py, csrc/avl_mappull.hip).  Upstream has no counterpart: a revisit can only be folded in there by building one map from both
+recordings."""
 from __future__ import annotations
 
 import numpy as np
@@ -37,14 +38,24 @@ def _shift_tuple(shift):
     return tuple(int(s) for s in np.asarray(shift).reshape(-1))
 
 
-def resample_map(vm, transform=None, shift=(0, 0, 0)):
+RESAMPLE_METHODS = ("forward", "nearest", "linear")
+
+
+def resample_map(vm, transform=None, shift=(0, 0, 0), method="forward", min_support=0.5):
     """VLMap.resample: see there"""
     from .. import ops
+    if method not in RESAMPLE_METHODS:
+        raise ValueError(f"resample: method {method!r} (one of {', '.join(RESAMPLE_METHODS)})")
+    ops.check_min_support(min_support, "resample")
     dims = _map_dims(vm, "this map")
     pos, feat, weight, rgb, has_rgb = _arrays(vm, "resample")
     D = dims["D"]
-    res = ops.fuse_maps(np.zeros((0, 3), np.int32), np.zeros((0, D), np.float32), np.zeros((0,), np.float32), np.zeros((0, 3), np.uint8),
-                        pos, feat, weight, rgb, dims["gs"], dims["cs"], dims["vh"], transform=transform, shift=shift)
+    if method == "forward":
+        res = ops.fuse_maps(np.zeros((0, 3), np.int32), np.zeros((0, D), np.float32), np.zeros((0,), np.float32), np.zeros((0, 3), np.uint8),
+                            pos, feat, weight, rgb, dims["gs"], dims["cs"], dims["vh"], transform=transform, shift=shift)
+    else:
+        res = ops.pull_map(pos, feat, weight, rgb, dims["gs"], dims["cs"], dims["vh"], transform=transform, shift=shift, interp=method,
+                           min_support=min_support)
     out = type(vm)(vm.map_config, data_dir=str(getattr(vm, "data_dir", "") or ""))
     out.prefetch_device, out.compact_map = vm.prefetch_device, vm.compact_map
     out.grid_pos, out.grid_feat, out.weight, out.occupied_ids = res.grid_pos, res.grid_feat, res.weight, res.occupied_ids

@@ -168,16 +168,26 @@ class VLMap(Map):
         self._objects_cache = None
         self.visibility = None
 
-    def resample(self, transform=None, shift=(0, 0, 0)) -> "VLMap":
+    def resample(self, transform=None, shift=(0, 0, 0), method: str = "forward", min_support: float = 0.5) -> "VLMap":
         """A new VLMap on this map's grid and config whose voxels are this map's moved by the (4, 4) float64 `transform` of base
         coordinates (None = identity; Map.transform_from gives the one between two recordings' frames) and then by `shift` whole
-        cells (row, col, h), which is ADDED to the moved cells (map/fuse.py, ops.fuse_maps with an empty first map).
-        Forward and nearest-cell: a voxel's cell centre is moved and lands in one cell; rows that land in one cell are averaged by
-        weight, rows that leave the grid or the height band are dropped.  Under a rotation some cells receive two or three voxels and
-        neighbouring cells none, so surfaces come out with pinholes; features are not interpolated.  scores_mat is not carried over
-        (index the new map); categories and mapped_iter_list are.  With no arguments the result equals this map."""
+        cells (row, col, h), which is ADDED to the moved cells (map/fuse.py).  scores_mat is not carried over (index the new map);
+        categories and mapped_iter_list are.  With no arguments the result equals this map.
+        method="forward" (the default; ops.fuse_maps with an empty first map): a voxel's cell centre is moved and
+        lands in one cell; rows that land in one cell are averaged by weight, rows that leave the grid or the height band are
+        dropped.  Under a rotation some cells receive two or three voxels and neighbouring cells none, so surfaces come out with
+        pinholes, which compare() reads as vanished voxels; features are not interpolated.  The voxels keep this map's row order.
+        method="linear" or "nearest" (ops.pull_map) work backward: every cell of the grid asks where its centre came
+        from under the inverse transform, so a turned surface comes out without pinholes.  For a revisit turned against this map use
+        b.resample(T, method="linear"): a voxel is the mean of up to eight neighbouring voxels, by trilinear weight times the
+        voxels' weights, and exists when the weights of the neighbours that hold a voxel add up to `min_support` (0 < .. <= 1) or
+        more, which keeps a wall one cell thick and shaves the rim of a surface.  "linear" blends rows across the border of two
+        objects; choose "nearest", which copies the one voxel that the centre falls into, bit for bit, where features must stay
+        what the builder wrote (category maps, compare() with a high threshold).  The backward methods order the voxels by linear
+        cell ((row * gs + col) * vh + h), not by this map's rows, and need one voxel per cell.  resample_counts holds the
+        method's counts.  The raw float32 rows are resampled, not the compact resident copies; not for rows sharded over ranks."""
         from .fuse import resample_map
-        return resample_map(self, transform, shift)
+        return resample_map(self, transform, shift, method, min_support)
 
     def fuse(self, other, transform=None, shift=(0, 0, 0), changes=None, drop_vanished: bool = True, replace_changed: bool = True,
              gain: float = 1.0) -> dict:
@@ -188,7 +198,8 @@ class VLMap(Map):
         revisit counts for more.  changes: the MapChanges of self.compare(other, shift=shift); with it the vanished voxels of A are
         dropped (drop_vanished) and the voxels of A whose content was replaced give way to B's (replace_changed), while B's voxels
         that this session never looked at (unseen_b) stay out.  It is accepted only with transform=None and its own shift: resample
-        `other` first otherwise.  Returns the counts (ops.FUSE_COUNTS, voxels_a, voxels_b, voxels).  ValueError unless gs, cs, the
+        `other` first otherwise -- for a turned revisit other.resample(T, method="linear"), which leaves no pinholes for compare()
+        to read as vanished ("nearest" where features must not be blended across object borders).  Returns the counts (ops.FUSE_COUNTS, voxels_a, voxels_b, voxels).  ValueError unless gs, cs, the
         height cells and the feature width agree.  Afterwards scores_mat is None (the rows changed: index again), every derived
         device copy is dropped, and mapped_iter_list stays this map's: the frames of B's recording are not recorded in it.  The
         raw float32 rows are fused, not the compact resident copies; not for rows sharded over ranks.  The result is not what a
@@ -207,7 +218,9 @@ class VLMap(Map):
         unmatched voxel that fewer than min_rays of the other session's sight rays passed through is unseen, not vanished /
         appeared.  ValueError unless gs, cs, the number of height cells and the feature width agree.  Whole-cell shifts only: a
         revisit recorded from another odometry origin -- a rotation or a sub-cell shift away -- is resampled onto this map's grid
-        first, a.compare(b.resample(T)) with T from Map.transform_from (Map.register_frames gives the correction).  Upstream has
+        first, with T from Map.transform_from (Map.register_frames gives the correction): a.compare(b.resample(T, method="linear")) for a
+        turned revisit -- the default forward resampling leaves pinholes that read as vanished voxels here; method="nearest" where
+        features must not be blended across object borders.  Upstream has
         no counterpart: its maps are static."""
         from .changes import compare_maps
         return compare_maps(self, other, radius=radius, threshold=threshold, shift=shift, audit=audit, other_audit=other_audit,

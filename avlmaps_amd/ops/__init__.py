@@ -104,6 +104,10 @@ from .mapfuse import (  # noqa: F401
     check_gain, check_transform, FUSE_COUNTS, FUSE_ERR_OUTSIDE, FUSE_ERR_SHARED, FUSE_MAX_DIM, fuse_maps, fuse_plan, fuse_rows, FusedMap,
     FusePlan, move_cells,
 )
+from .mappull import (  # noqa: F401
+    check_interp, check_min_support, inverse_transform, PULL_COUNTS, PULL_INTERP, PULL_MAX_DIM, pull_map, pull_plan, pull_rows, PulledMap,
+    PullPlan,
+)
 # the shared marshalling layer; its one device predicate keeps both of the names it had here
 from ._args import (  # noqa: F401
     _dev_u8, _image_any, _image_shape, _image_u8, _is_dev, _is_dev as _on_device, _result,

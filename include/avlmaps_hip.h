@@ -1602,6 +1602,69 @@ AVL_API int avl_map_fuse_rows(int64_t n_out, const int32_t* d_a_row, const int32
                               int gs, int vh, float* d_feat_out, float* d_weight_out, uint8_t* d_rgb_out, int32_t* d_grid_pos_out,
                               int32_t* d_occupied, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * (32) resampling a finished voxel map backward: for every cell of the target grid the rows of map B that its centre came from,
+ *     and the voxel gathered from them (csrc/avl_mappull.hip).  (31)'s move is a forward, nearest-cell scatter that
+ *     leaves pinholes under a rotation; this is the inverse mapping.  Upstream has no counterpart: its maps are static and it never
+ *     resamples one.  The plan is two calls around one read-back of n_out, which has no bound from n_b.  The scratch is the cell
+ *     index of (20) and one int32 array whose length is stated below, so there is no size query.  Every result has one value: the
+ *     pulled-back point is float64 with every product and sum rounded once, the members and their order are fixed, an element is a
+ *     float64 sum in corner order.  All calls are asynchronous on `stream`, check their arguments before any device work and
+ *     allocate nothing.
+ * ------------------------------------------------------------------------------------------------ */
+/* Passes 1 and 2 of the plan.  Map B has n_b cells d_cells_b (n_b, 3) int32 on the gs x gs x vh grid of cell size cs.  A row is
+ * SELECTED when d_use_b (n_b uint8, NULL = all ones) is non-zero, its weight d_w_b (float32) is finite and > 0 and its cell lies
+ * inside the grid; two selected rows in one cell set bit 1 of the error word.
+ * THE MEMBERS of target cell c = (row, col, h):  c' = c - h_shift (3 int32 in HOST memory, NULL = none).  With h_P = NULL the sole
+ * member is the selected row of B in cell c', lambda = 1: integers only, whatever the mode.  Otherwise p is the centre of c' by
+ * avl_map_move_cells' rule (k = gs / 2 - index, x = (k + 0.5 * sign(k)) * cs, z = (h + 0.5) * cs) and q = P p with h_P (16 float64
+ * in HOST memory, row-major 4 x 4, finite, bottom row 0 0 0 1) the INVERSE of the transform from B's base frame to the target's:
+ * qx = ((P00 * x + P01 * y) + P02 * z) + P03 and likewise qy, qz, every product and sum rounded once in float64, none fused; then
+ * sx = qx / cs, sy = qy / cs, sz = qz / cs, true float64 divides.  A cell whose quotients are not all below 2^31 in magnitude has
+ * no member.
+ *   mode 0 (nearest): the sole member is the selected row in cell ((int)(gs / 2.0 - (int)sx), (int)(gs / 2.0 - (int)sy), (int)sz),
+ *     upstream's base_pos2grid_id_3d, lambda = 1.
+ *   mode 1 (linear): each axis is bracketed by the centres of B's lattice.  Horizontally the centres are 0, +-1.5, +-2.5, .. (the
+ *     cell k = 0 is two cells wide): with a = |s|, j0 = 0 and u = a / 1.5 where a < 1.5, else j0 = floor(a - 0.5) and u = (a - 0.5)
+ *     - j0; for s >= 0 k0 = j0 and t = u; for s < 0 k0 = -j0 and t = 0 where u == 0, else k0 = -(j0 + 1) and t = 1 - u.  In
+ *     height s = sz - 0.5, h0 = floor(s), t = s - h0.  Corner j = 0 .. 7 has dz = j & 1, dy = j >> 1 & 1, dx = j >> 2 & 1, the
+ *     cell (gs / 2 - (k0x + dx), gs / 2 - (k0y + dy), h0 + dz) and lambda = (lx * ly) * lz with l = t for d = 1 and 1 - t for
+ *     d = 0.  A corner is a member when lambda > 0 and a selected row owns its cell.
+ * The support of c is the sum of its members' lambdas, added in corner order.  The target cell EXISTS when its support is > 0 and
+ * >= min_support (0 < min_support <= 1, compared in float64).  The existing cells are numbered in ascending linear cell order
+ * (row * gs + col) * vh + h, whatever the order of B's rows.
+ *   d_head (8) int32: n_out; the selected rows of B; the error word; rows of B that use or weight unselects; further rows of B
+ *     outside the grid; target cells with a member whose support is below min_support; two zeros.
+ * Scratch: d_index, index_bytes >= avl_cell_index_work_bytes(n_b, gs, vh); d_scratch of scratch_i32 >= 4 * n_b + 2 * W + W / 1024 +
+ * 512 int32 with W = ceil(gs * gs * vh / 32).  Both are read by avl_map_pull_fill and stay untouched until then.  The grid as in
+ * (20), cs > 0 and finite, 0 <= n_b < 2^31 - 1; n_b = 0 gives n_out = 0. */
+AVL_API int avl_map_pull_plan(const int32_t* d_cells_b, const uint8_t* d_use_b, const float* d_w_b, int64_t n_b, const double* h_P,
+                              const int32_t* h_shift, int gs, double cs, int vh, int mode, double min_support, void* d_index,
+                              size_t index_bytes, int32_t* d_scratch, int64_t scratch_i32, int32_t* d_head, void* stream);
+/* Pass 3 of the plan, after the caller has read n_out = d_head[0] back: the same n_b, h_P, h_shift, grid, mode, min_support, d_index,
+ * d_scratch and d_head as in avl_map_pull_plan.  For the v-th existing cell in linear order: d_cells_out (n_out, 3) int32 its cell;
+ * d_members (n_out, 8) int32 the row of B of corner j, -1 where the corner is no member; d_lam (n_out, 8) float64 the member's
+ * lambda, 0 where there is none (nearest mode and h_P = NULL: the sole member in column 0).  d_occupied (gs, gs, vh) int32, NULL =
+ * not wanted: set to -1 and then to v at the cell of voxel v.  d_counts (4) int32: rows of B that use or weight unselects; further
+ * rows outside the grid; target cells below the support; selected rows of B that are a member of no existing cell.  A cell whose
+ * rank is not below n_out is skipped: nothing is written out of bounds.  0 <= n_out <= gs * gs * vh. */
+AVL_API int avl_map_pull_fill(int64_t n_b, const double* h_P, const int32_t* h_shift, int gs, double cs, int vh, int mode, double min_support,
+                              const void* d_index, size_t index_bytes, int32_t* d_scratch, int64_t scratch_i32, const int32_t* d_head,
+                              int64_t n_out, int32_t* d_cells_out, int32_t* d_members, double* d_lam, int32_t* d_occupied,
+                              int32_t* d_counts, void* stream);
+/* The n_out voxels of a plan.  The members of voxel v are the rows m_j = d_members[v, j] in 0 .. n_b - 1, in the order j = 0 .. 7.
+ * In float64: omega_j = d_lam[v, j] * (double)d_w_b[m_j]; Omega = the sum of omega_j and Lambda = the sum of d_lam[v, j] over the
+ * members in that order; per element d, acc = omega_0 * (double)f_0[d] + omega_1 * (double)f_1[d] + .. in that order, every
+ * product and every addition rounded once, none fused, the first product taken as it is (a sole -0.0 stays -0.0).
+ * d_feat_out[v, d] = (float)(acc / Omega); d_weight_out[v] = (float)(Omega / Lambda), the lambda-weighted mean of the members'
+ * weights; d_rgb_out[v, c] = (uint8)(int)(acc_c / Omega) with acc_c the same sum over (double)rgb_j[c], truncated.  A voxel with
+ * one member of lambda 1 comes back bit for bit.  Rows are read and written 16 bytes at a time where D % 4 == 0 and the matrix is
+ * 16-byte aligned and by scalars otherwise, chosen per matrix, same bytes.  A voxel without a member gets zeros.  d_feat_b (n_b, D)
+ * and d_feat_out (n_out, D) float32 contiguous, 1 <= D <= 8192; 0 <= n_out, n_b < 2^31 - 1; n_out = 0 does nothing. */
+AVL_API int avl_map_pull_rows(int64_t n_out, const int32_t* d_members, const double* d_lam, const float* d_feat_b, const float* d_w_b,
+                              const uint8_t* d_rgb_b, int64_t n_b, int D, float* d_feat_out, float* d_weight_out, uint8_t* d_rgb_out,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif
